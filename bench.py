@@ -244,9 +244,11 @@ def smi_clocks():
         return {'error': repr(e)[:120]}
 
 
-def time_steps(loop, steps, warmup, barrier, device, repeats=0, warm_through_graph=True, sample_clocks=False):
+def time_steps(loop, steps, warmup, barrier, device, repeats=0, warm_through_graph=True, sample_clocks=False,
+               after_region=None):
     """EXACTLY `steps` train steps are timed after the untimed warm-up, all through the product's compiled loop
-    (deeptables_amd/compiled.py: k steps per hipGraph replay, k divides `steps`).
+    (deeptables_amd/compiled.py: k steps per hipGraph replay, k divides `steps`).  `after_region()` runs once behind the
+    contract region's synchronize, before the repeats (--dump-outputs: the state of its last step).
 
     Round 6 — what sits between the warm-up and the timed region decides a 2 ms measurement, so that interval is now as short
     as the contract allows (barrier + synchronize) and is itself reported (`pause_before_region_us`):
@@ -302,6 +304,8 @@ def time_steps(loop, steps, warmup, barrier, device, repeats=0, warm_through_gra
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     t_end = time.perf_counter()
+    if after_region is not None:
+        after_region()
     per, prev, units = [], e0, []
     for e, kk in evs:
         per += [prev.elapsed_time(e) * 1e3 / kk] * kk          # us per step (a replay of k steps: its mean)
@@ -353,6 +357,62 @@ def time_steps(loop, steps, warmup, barrier, device, repeats=0, warm_through_gra
         stats['repeat_spread'] = (srt[-1] - srt[0]) / srt[len(srt) // 2]
         stats['steady_step_us'] = srt[len(srt) // 2]
     return wall, gpu_s, stats
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def snapshot_last_step(loop, steps):
+    """--dump-outputs: device copies of what the timed path computed in its last timed step (step `steps` of the contract
+    region), taken before anything else runs on the model:
+      loss [1], logits [B, outputs]   what DeepModel.fit(steps_per_execution=k) collects for that step (CompiledTrainLoop._collect);
+      param.<name>                    every dense parameter after the step's optimizer update;
+      rows.<table>                    the rows of each packed embedding table the step looked up [B, F, D], after its row update
+                                      — a fixed seeded sample of the batch rows when everything would exceed DUMP_MAX_BYTES.
+    -> {name: float32 device tensor}"""
+    from deeptables_amd.models.layers import MultiColumnEmbedding
+    k = loop.k if loop.graph is not None else 1        # the region ends on a whole replay (k divides `steps`) or an eager step
+    assert steps % k == 0
+    B = loop.B
+    got = {'loss': [], 'logit': [], 'y': []}
+    loop._collect(got, k)
+    out = {'loss': got['loss'][0][-1:].float().clone(), 'logits': got['logit'][0][-B:].float()}
+    layers = [(getattr(m, 'name', None) or mname, m) for mname, m in loop.dm.model.named_modules()]   # Keras layer names
+    tables = [(f'{lname}.d{D}', m.tables[f'd{D}'], getattr(m, f'row_offset_d{D}'), cols)
+              for lname, m in layers if isinstance(m, MultiColumnEmbedding) and getattr(m, 'built', False)
+              for D, cols in m.groups]
+    in_tables = {id(t) for _, t, _, _ in tables}
+    for lname, m in layers:
+        for n, p in m.named_parameters(recurse=False):
+            if id(p) not in in_tables:
+                out[f'param.{lname}.{n}'] = p.detach().float().clone()
+    used = sum(t.numel() * 4 for t in out.values())
+    if used > DUMP_MAX_BYTES:
+        raise ValueError(f'--dump-outputs: the dense outputs alone take {used} bytes (> {DUMP_MAX_BYTES})')
+    ids = loop.slots[0][(k - 1) * B:k * B].long()         # make_feed: block 0 = the categorical ids [B, F]
+    row_bytes = sum(len(cols) * t.shape[1] * 4 for _, t, _, cols in tables)
+    keep = None
+    if row_bytes and used + B * row_bytes > DUMP_MAX_BYTES:
+        n_keep = (DUMP_MAX_BYTES - used) // row_bytes
+        keep = torch.randperm(B, generator=torch.Generator().manual_seed(0))[:n_keep].sort().values.to(ids.device)
+    for name, t, offs, cols in tables:
+        rows = ids[:, cols] + offs.view(1, -1)
+        if keep is not None:
+            rows = rows[keep]
+        out[f'rows.{name}'] = t.detach()[rows]
+    return out
+
+
+def write_outputs(snapshot, out_dir):
+    """snapshot_last_step's tensors -> out_dir/<name>.npy (float32) -> (files, bytes)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in snapshot.items():
+        a = t.cpu().numpy().astype(np.float32, copy=False)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+        total += a.nbytes
+    return len(snapshot), total
 
 
 def kernel_split(loop, n_steps=None):
@@ -659,7 +719,13 @@ def main():
     ap.add_argument('--force-dp', action='store_true',
                     help='N=1: run the data-parallel step structure anyway (world size 1: collectives are no-ops)')
     ap.add_argument('--force-sharded', action='store_true', help='N=1: run the sharded-table step anyway (eager)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them computed (loss, logits, dense parameters, the '
+                         'looked-up embedding rows; rank 0) as DIR/<name>.npy, float32, at most 64 MB; the inputs are seeded, '
+                         'so equal arguments give equal inputs on every run')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     world = launch_ranks(args)
     tables_auto = args.tables == 'auto'
@@ -755,8 +821,19 @@ def main():
     loop.set_order(ring_order(feed, args.batch, total_steps, device))
     loop.capture(warm_steps=warm_capture)
     spg = loop.k if loop.graph is not None else 1
+    snapshot = {}
+
+    def take_snapshot():
+        if sharded:         # row-owned tables: every rank's copy is current only for its own fields
+            from deeptables_amd.models.layers import MultiColumnEmbedding
+            for layer in dm.model.modules():
+                if isinstance(layer, MultiColumnEmbedding) and getattr(layer, 'built', False):
+                    strategy.sync_tables(layer)
+        if rank == 0:
+            snapshot.update(snapshot_last_step(loop, args.steps))
     wall, ev_s, step_stats = time_steps(loop, args.steps, args.warmup, barrier, device, repeats=max(0, args.repeats),
-                                        warm_through_graph=not args.legacy_warmup, sample_clocks=(rank == 0))
+                                        warm_through_graph=not args.legacy_warmup, sample_clocks=(rank == 0),
+                                        after_region=take_snapshot if args.dump_outputs else None)
     split = None
     if rank == 0 and world == 1 and strategy is None and not args.no_optimizer and not args.no_extras:
         try:
@@ -988,6 +1065,10 @@ def main():
                                                       'fwd_bwd_only_rows_per_s, not with `value` (fwd + bwd + Adam)')
             except Exception as e:
                 result['cpu_baseline'] = {'error': repr(e)}
+        if args.dump_outputs:
+            n_files, n_bytes = write_outputs(snapshot, args.dump_outputs)
+            result['dump_outputs'] = {'dir': args.dump_outputs, 'files': n_files, 'bytes': n_bytes,
+                                      'step': f'step {args.steps} of the timed region'}
         print(json.dumps(result))
     barrier()
     if dist.is_available() and dist.is_initialized():

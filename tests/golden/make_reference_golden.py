@@ -24,6 +24,7 @@ the same way the oracle does.  tests/test_oracle_reference_code.py compares the 
 every CPU run; this script only runs where /root/reference exists.
 
     python tests/golden/make_reference_golden.py          # regenerates the fixtures (deterministic)
+    python tests/golden/make_reference_golden.py --check  # regenerates into a scratch directory, compares with the committed ones
 """
 import contextlib
 import importlib.util
@@ -1088,5 +1089,32 @@ def main():
     print(f'{len(written)} fixtures written to tests/golden/reference_code_*.npz')
 
 
+def check():
+    """--check: regenerate into a scratch directory and require the committed fixtures to be what the reference code
+    writes now (the stored `meta` strings aside)"""
+    import glob
+    import tempfile
+    global HERE
+    committed = HERE
+    with tempfile.TemporaryDirectory() as tmp:
+        HERE = tmp
+        try:
+            main()
+        finally:
+            HERE = committed
+        assert json.load(open(os.path.join(committed, 'reference_code_api.json'))) == \
+            json.load(open(os.path.join(tmp, 'reference_code_api.json'))), 'reference_code_api.json differs'
+        fixtures = sorted(glob.glob(os.path.join(committed, 'reference_code_*.npz')))
+        assert {os.path.basename(f) for f in fixtures} == \
+            {os.path.basename(f) for f in glob.glob(os.path.join(tmp, 'reference_code_*.npz'))}, 'fixture sets differ'
+        for f in fixtures:
+            a, b = dict(np.load(f)), dict(np.load(os.path.join(tmp, os.path.basename(f))))
+            assert set(a) == set(b), os.path.basename(f)
+            for k in a:
+                if k != 'meta':
+                    assert np.array_equal(a[k], b[k]), (os.path.basename(f), k)
+    print(f'{len(fixtures)} committed fixtures are what the reference code writes')
+
+
 if __name__ == '__main__':
-    main()
+    check() if '--check' in sys.argv else main()
