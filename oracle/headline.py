@@ -162,11 +162,17 @@ def check_train_step(dm, batch, adam=True, lr=1e-3, grad_tol=2e-4):
             return res
         if first is None:
             first = {k: res[k] for k in ('dense_grad_rel_err', 'rows_grad_rel_err', 'min_abs_relu_input') if k in res}
-        with torch.no_grad():
-            for name, layer in dm.model.layers_by_name.items():
-                if (name.startswith('dnn_dense_') or name.startswith('dcn_dense_')) and getattr(layer, 'bias', None) is not None:
-                    layer.bias.add_(2e-5)
+        shift_tower_biases(dm)
         dm.optimizer.zero_grad()
+
+
+def shift_tower_biases(dm, by=2e-5):
+    """moves every relu kink of the Dense tower: +`by` on the bias of each dnn_dense_* / dcn_dense_* layer (the weights
+    both sides then use)"""
+    with torch.no_grad():
+        for name, layer in dm.model.layers_by_name.items():
+            if (name.startswith('dnn_dense_') or name.startswith('dcn_dense_')) and getattr(layer, 'bias', None) is not None:
+                layer.bias.add_(by)
 
 
 def _check_once(dm, batch, adam, lr, accept):

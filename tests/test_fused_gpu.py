@@ -90,14 +90,16 @@ def test_fused_deepfm_matches_oracle_and_generic_path(dev, B, F, Nd, D, idt):
                              1).reshape(B, -1)] + ([dense.double()] if Nd else []), -1)
     assert rel(bn.moving_mean, mm0.double().cpu() * 0.99 + x.mean(0) * 0.01) < 1e-4
     # generic layer-by-layer path gives the same thing
-    import os
-    fused_grads = [a.clone() for a, _ in pairs]
+    grads = lambda: [L['task_output'].kernel.grad, L['dense_logit_dnn_nets'].kernel.grad, L['dnn_dense_2'].kernel.grad,
+                     L['dnn_dense_2'].bias.grad, L['dnn_dense_1'].kernel.grad, L['dnn_dense_1'].bias.grad,
+                     L['bn_concat_emb_dense'].gamma.grad, L['bn_concat_emb_dense'].beta.grad,
+                     L['linear_logit'].kernel.grad, L['task_output'].bias.grad]
+    fused_grads = [a.clone() for a in grads()]
     dm._fused_plan = None
     loss2, logit2 = dm.forward_backward(ins, y.to(dev))
     assert (logit2 - logit).abs().max().item() < 1e-4
-    for i, (a, _) in enumerate(pairs):
-        pass
-    assert rel(L['dnn_dense_1'].kernel.grad, fused_grads[4]) < 2e-4
+    for i, (a, b) in enumerate(zip(grads(), fused_grads)):
+        assert rel(a, b) < 2e-4, f'generic vs fused dense grad {i}: {rel(a, b)}'
 
 
 @pytest.mark.parametrize('B,F,Nd,D,L,idt', [(256, 26, 13, 16, 6, 'int32'), (100, 26, 13, 16, 4, 'float32'),
