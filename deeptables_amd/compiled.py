@@ -334,13 +334,12 @@ class CompiledTrainLoop:
         # fused.preelect) depends on the gathered ids alone: it runs on a forked branch of the graph beside step 1, and the
         # steps behind it skip that work (every captured step has its own rows / segment buffers for this)
         plan = dm.fused_plan()
-        pre = (self.k > 1 and not self.dp and not core_only and plan is not None and hasattr(plan, 'can_preelect') and
-               plan.can_preelect(self.B) and self.feed.kinds[0] == 'cat' and
-               self.slots[0].dtype in (torch.int32, torch.float32))
+        pre = (self.k > 1 and not self.dp and not core_only and plan is not None and plan.can_preelect(self.B) and
+               self.feed.kinds[0] == 'cat' and self.slots[0].dtype in (torch.int32, torch.float32))
         # chained steps: the ids-only and weights-only work of step i + 1 inside step i's launches (no prep launch from the
         # second step of an execution on)
         chain = (not pre and self.k > 1 and not self.dp and not core_only and self.with_optimizer and plan is not None and
-                 hasattr(plan, 'can_chain') and plan.can_chain(self.B) and self.feed.kinds[0] == 'cat' and
+                 plan.can_chain(self.B) and self.feed.kinds[0] == 'cat' and
                  self.slots[0].dtype in (torch.int32, torch.float32) and not self.feed.weighted)
         self.chained = bool(chain)
         self._slots_per_step = bool(pre or chain)

@@ -3080,6 +3080,31 @@ extern "C" int dt_deepfm_train_step(
                             grad_rows_field_major, phases, embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, nullptr, nullptr, 0);
 }
 
+// the optimizer half of dt_deepfm_train_step_adam / dt_dcn_train_step_adam: its argument checks (the messages name the
+// entry point `what`) and the records tower_train_step takes
+struct StepAdam {
+    RowsAdam ad;
+    StepDense sd;
+    StepChain ch;
+};
+static int step_adam_args(const char* what, float* table, int D, void* dedupe_ws, int phases, float* adam_m, float* adam_v,
+                          int slot_stride, void* adam_state, float lr_t, float beta1, float beta2, float eps, float* dense_p,
+                          float* dense_m, float* dense_v, int64_t dense_n, float lr, const void* next_idx,
+                          int64_t* next_rows_out, void* next_dedupe_ws, StepAdam* out) {
+    DT_REQUIRE(table && adam_m && adam_v, "%s: null pointer", what);
+    DT_REQUIRE(dense_n == 0 || (dense_p && dense_m && dense_v && adam_state),
+               "%s: the dense half needs the flat buffers and the device step state", what);
+    DT_REQUIRE((phases & 0xf) == 2 && dedupe_ws, "%s: a backward step (phases 2) with dedupe_ws", what);
+    DT_REQUIRE(slot_stride == D || slot_stride == 2 * D, "%s: slot_stride %d (D or 2 D)", what, slot_stride);
+    DT_REQUIRE(((uintptr_t)table | (uintptr_t)adam_m | (uintptr_t)adam_v) % 16 == 0,
+               "%s: table / slots must be 16-byte aligned", what);
+    out->ad = RowsAdam{table, adam_m, adam_v, slot_stride, adam_state ? adam_state_lr_t(adam_state) : nullptr, lr_t, beta1,
+                       beta2, eps, 0};
+    out->sd = StepDense{dense_p, dense_m, dense_v, dense_n, adam_state, lr};
+    out->ch = StepChain{next_idx, next_rows_out, next_dedupe_ws};
+    return DT_OK;
+}
+
 // the step with the row-sparse Keras-Adam update of the rows looked up ONCE applied inside it (k_wgrad_rows): `table` is
 // updated in place, adam_m / adam_v are its slots (slot_stride floats between consecutive rows' records: D for two
 // [V,D] arrays, 2 D for one [V,2,D] array), adam_state the device-resident step state of dt_adam_state_init (NULL:
@@ -3100,22 +3125,17 @@ extern "C" int dt_deepfm_train_step_adam(
     float* adam_m, float* adam_v, int slot_stride, void* adam_state, float lr_t, float beta1, float beta2,
     float eps, float* dense_p, float* dense_m, float* dense_v, int64_t dense_n, float lr,
     const void* next_idx, int64_t* next_rows_out, void* next_dedupe_ws, void* stream) {
-    DT_REQUIRE(w_lin && table && adam_m && adam_v, "dt_deepfm_train_step_adam: null pointer");
-    DT_REQUIRE(dense_n == 0 || (dense_p && dense_m && dense_v && adam_state),
-               "dt_deepfm_train_step_adam: the dense half needs the flat buffers and the device step state");
-    DT_REQUIRE((phases & 0xf) == 2 && dedupe_ws, "dt_deepfm_train_step_adam: a backward step (phases 2) with dedupe_ws");
-    DT_REQUIRE(slot_stride == D || slot_stride == 2 * D, "dt_deepfm_train_step_adam: slot_stride %d (D or 2 D)", slot_stride);
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)adam_m | (uintptr_t)adam_v) % 16 == 0,
-               "dt_deepfm_train_step_adam: table / slots must be 16-byte aligned");
-    const RowsAdam ad{table, adam_m, adam_v, slot_stride, adam_state ? adam_state_lr_t(adam_state) : nullptr, lr_t, beta1,
-                      beta2, eps, 0};
-    const StepDense sd{dense_p, dense_m, dense_v, dense_n, adam_state, lr};
-    const StepChain ch{next_idx, next_rows_out, next_dedupe_ws};
+    DT_REQUIRE(w_lin, "dt_deepfm_train_step_adam: null pointer");
+    StepAdam a;
+    const int rc = step_adam_args("dt_deepfm_train_step_adam", table, D, dedupe_ws, phases, adam_m, adam_v, slot_stride,
+                                  adam_state, lr_t, beta1, beta2, eps, dense_p, dense_m, dense_v, dense_n, lr, next_idx,
+                                  next_rows_out, next_dedupe_ws, &a);
+    if (rc != DT_OK) return rc;
     return tower_train_step(idx, idx_kind, table, row_offset, vocab, dense, y, B, F, D, Nd, w_lin, bn_gamma, bn_beta,
                             bn_moving_mean, bn_moving_var, bn_eps, bn_momentum, W1, b1, W2, b2, w3, w_out, b_out, logit_out,
                             rows_out, grad_rows, accum, workspace, oob_count, dedupe_ws, dedupe_slots, 1.0f, 0, phases,
-                            embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, nullptr, nullptr, 0, &ad, dense_n > 0 ? &sd : nullptr,
-                            &ch);
+                            embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, nullptr, nullptr, 0, &a.ad,
+                            dense_n > 0 ? &a.sd : nullptr, &a.ch);
 }
 
 // ---- DCN (nets ['dcn_nets'], deepnets.py:194-207): the same step with the Cross network (layers.py:428-436) in place of
@@ -3173,23 +3193,18 @@ extern "C" int dt_dcn_train_step_adam(
     float* adam_m, float* adam_v, int slot_stride, void* adam_state, float lr_t, float beta1, float beta2,
     float eps, float* dense_p, float* dense_m, float* dense_v, int64_t dense_n, float lr,
     const void* next_idx, int64_t* next_rows_out, void* next_dedupe_ws, void* stream) {
-    DT_REQUIRE(cross_w && cross_b && table && adam_m && adam_v, "dt_dcn_train_step_adam: null pointer");
+    DT_REQUIRE(cross_w && cross_b, "dt_dcn_train_step_adam: null pointer");
     DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_train_step_adam: %d cross layers (1..%d)", L, kCrossMax);
-    DT_REQUIRE((phases & 0xf) == 2 && dedupe_ws, "dt_dcn_train_step_adam: a backward step (phases 2) with dedupe_ws");
-    DT_REQUIRE(slot_stride == D || slot_stride == 2 * D, "dt_dcn_train_step_adam: slot_stride %d (D or 2 D)", slot_stride);
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)adam_m | (uintptr_t)adam_v) % 16 == 0,
-               "dt_dcn_train_step_adam: table / slots must be 16-byte aligned");
-    DT_REQUIRE(dense_n == 0 || (dense_p && dense_m && dense_v && adam_state),
-               "dt_dcn_train_step_adam: the dense half needs the flat buffers and the device step state");
-    const RowsAdam ad{table, adam_m, adam_v, slot_stride, adam_state ? adam_state_lr_t(adam_state) : nullptr, lr_t, beta1,
-                      beta2, eps, 0};
-    const StepDense sd{dense_p, dense_m, dense_v, dense_n, adam_state, lr};
-    const StepChain ch{next_idx, next_rows_out, next_dedupe_ws};
+    StepAdam a;
+    const int rc = step_adam_args("dt_dcn_train_step_adam", table, D, dedupe_ws, phases, adam_m, adam_v, slot_stride,
+                                  adam_state, lr_t, beta1, beta2, eps, dense_p, dense_m, dense_v, dense_n, lr, next_idx,
+                                  next_rows_out, next_dedupe_ws, &a);
+    if (rc != DT_OK) return rc;
     return tower_train_step(idx, idx_kind, table, row_offset, vocab, dense, y, B, F, D, Nd, nullptr, bn_gamma, bn_beta,
                             bn_moving_mean, bn_moving_var, bn_eps, bn_momentum, W1, b1, W2, b2, w3, w_out, b_out, logit_out,
                             rows_out, grad_rows, accum, workspace, oob_count, dedupe_ws, dedupe_slots, 1.0f, 0, phases,
-                            embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, cross_w, cross_b, L, &ad, dense_n > 0 ? &sd : nullptr,
-                            &ch);
+                            embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, cross_w, cross_b, L, &a.ad,
+                            dense_n > 0 ? &a.sd : nullptr, &a.ch);
 }
 
 extern "C" int dt_dcn_train_step(

@@ -18,9 +18,6 @@ from ._lib import check, lib, ptr, stream_ptr
 from .ops import SparseRowGrad
 from .utils import consts
 
-_ACC_NAMES = ['dW1', 'dW2', 'db1', 'db2', 'dw3', 'dwo', 'dbo', 'loss', 'dgamma', 'dbeta', 'dwlin']
-
-
 def _step_loss(dm):
     """loss flag of the fused steps: 0 = binary task with BinaryCrossentropy, DT_STEP_LOSS_MSE = regression task with
     'mse' (deepmodel.py:126-141), None = a task / loss the steps do not take"""
@@ -143,49 +140,83 @@ def _row_weights(sample_weight, y):
     return w
 
 
+def _step_dims(dm, net_layers):
+    """(batch hint, F, D, Nd), the leading arguments of dt_*_supported, when the graph passes the checks both fused steps
+    share — fixed-length columns, a loss the steps take, dropout rates in [0, 1), a tower of the compiled tile, the layers
+    `net_layers` besides the embedding / BN / output ones, one embedding group, at most one continuous column —
+    else None"""
+    c = dm.config
+    if dm.var_len_categorical_columns or _step_loss(dm) is None:
+        return None
+    if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
+        return None
+    if _tower_widths(c.dnn_params) is None:
+        return None
+    L = dm.model.layers_by_name
+    if any(n not in L for n in ('emb_categorical_vars_all', 'bn_concat_emb_dense', 'task_output') + tuple(net_layers)):
+        return None
+    emb = L['emb_categorical_vars_all']
+    if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
+        return None
+    Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
+    return max(int(getattr(dm, '_batch_hint', 0) or 0), 1), len(emb.input_dims), emb.groups[0][0], Nd
+
+
 class FusedDeepFM:
-    """Whole-step executor for the DeepFM graph.  Holds the static workspace / gradient buffers."""
+    """Whole-step executor for the DeepFM graph.  Holds the static workspace / gradient buffers.  FusedDCN runs the same
+    executor; the net-specific parts are the declarations and hooks marked 'net:' below."""
 
     NETS = {'linear', 'fm_nets', 'dnn_nets'}
     takes_sample_weight = True                # the loss block scales each row's loss / dlogit (csrc/deepfm.hip DcnArgs.sw)
+    # net: entry points dt_<PREFIX>_accum_floats / _accum_offsets / _workspace_bytes / _train_step / _train_step_adam, the
+    # accumulator entries in dt_<PREFIX>_accum_offsets' order, the tower's two Dense layers
+    PREFIX = 'deepfm'
+    ACC_NAMES = ('dW1', 'dW2', 'db1', 'db2', 'dw3', 'dwo', 'dbo', 'loss', 'dgamma', 'dbeta', 'dwlin')
+    TOWER = ('dnn_dense_1', 'dnn_dense_2')
+    STEP_EXTRA = (1.0, 0)                     # dt_deepfm_train_step's grad_rows_scale, grad_rows_field_major
+    ROW_OWNED = True                          # run() takes parallel.ShardedEmbeddingStrategy's row-owned path
 
     @classmethod
     def eligible(cls, dm):
         c = dm.config
         try:
-            if set(c.nets) != cls.NETS or len(c.nets) != 3 or dm.var_len_categorical_columns:
+            if set(c.nets) != cls.NETS or len(c.nets) != 3 or c.stacking_op != consts.STACKING_OP_ADD:
                 return False
-            if _step_loss(dm) is None:
-                return False
-            if c.stacking_op != consts.STACKING_OP_ADD or not (0 <= float(c.dense_dropout or 0) < 1):
-                return False
-            if not (0 <= float(c.embedding_dropout or 0) < 1):
-                return False
-            if _tower_widths(c.dnn_params) is None:
-                return False
-            L = dm.model.layers_by_name
-            need = ['emb_categorical_vars_all', 'bn_concat_emb_dense', 'linear_logit', 'dnn_dense_1', 'dnn_dense_2',
-                    'dense_logit_dnn_nets', 'task_output', 'fm_layer']
-            if any(n not in L for n in need):
-                return False
-            emb = L['emb_categorical_vars_all']
-            if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
-                return False
-            D = emb.groups[0][0]
-            F = len(emb.input_dims)
-            Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
-            return bool(lib().dt_deepfm_supported(max(int(getattr(dm, '_batch_hint', 0) or 0), 1), F, D, Nd, 128, 64))
+            dims = _step_dims(dm, cls.TOWER + ('linear_logit', 'dense_logit_dnn_nets', 'fm_layer'))
+            return dims is not None and bool(lib().dt_deepfm_supported(*dims, 128, 64))
         except Exception:
             return False
 
+    # -- net: layers, accumulator layout, gradient views and step arguments --------------------------------------------
+    def _net_layers(self, L):
+        self.lin = L['linear_logit']
+        self.dl = L['dense_logit_dnn_nets']
+
+    def _dims(self):
+        return self.F, self.D, self.Nd
+
+    def _net_grad_views(self, H2):
+        """-> ([(parameter, its gradient's view of accum)] of the net's own parameters, floats of the flat group)"""
+        a, o, n = self.accum, self.off, self.F + self.Nd
+        return [(self.dl.kernel, a[o['dw3']:o['dw3'] + H2].view(H2, 1)),
+                (self.out.kernel, a[o['dwo']:o['dwo'] + 1].view(1, 1)),
+                (self.lin.kernel, a[o['dwlin']:o['dwlin'] + n].view(n, 1))], o['dwlin'] + n
+
+    def _net_args(self):
+        """the arguments between Nd and bn_gamma"""
+        return (ptr(self.lin.kernel),)
+
+    def _head_weights(self):
+        """(w3, w_out)"""
+        return ptr(self.dl.kernel), ptr(self.out.kernel)
+
+    # -------------------------------------------------------------------------------------------------------------------
     def __init__(self, dm):
         self.dm = dm
         L = dm.model.layers_by_name
         self.emb = L['emb_categorical_vars_all']
         self.bn = L['bn_concat_emb_dense']
-        self.lin = L['linear_logit']
-        self.d1, self.d2 = L['dnn_dense_1'], L['dnn_dense_2']
-        self.dl = L['dense_logit_dnn_nets']
+        self.d1, self.d2 = L[self.TOWER[0]], L[self.TOWER[1]]
         self.out = L['task_output']
         self.D = self.emb.groups[0][0]
         self.F = len(self.emb.input_dims)
@@ -193,26 +224,25 @@ class FusedDeepFM:
         self.C = self.F * self.D + self.Nd
         self.key = f'd{self.D}'
         self.device = self.emb.tables[self.key].device
-        n_acc = lib().dt_deepfm_accum_floats(self.F, self.D, self.Nd)
-        offs = (ctypes.c_int64 * 11)()
-        check(lib().dt_deepfm_accum_offsets(self.F, self.D, self.Nd, ctypes.cast(offs, ctypes.c_void_p)),
-              'dt_deepfm_accum_offsets')
-        self.off = dict(zip(_ACC_NAMES, [int(v) for v in offs]))
+        self._net_layers(L)
+        n_acc = self._entry('accum_floats')(*self._dims())
+        offs = (ctypes.c_int64 * len(self.ACC_NAMES))()
+        check(self._entry('accum_offsets')(*self._dims(), ctypes.cast(offs, ctypes.c_void_p)),
+              f'dt_{self.PREFIX}_accum_offsets')
+        self.off = dict(zip(self.ACC_NAMES, [int(v) for v in offs]))
         self.accum = torch.zeros(n_acc, dtype=torch.float32, device=self.device)
         self._bufs = {}
         a, o, C = self.accum, self.off, self.C
         H1, H2 = _tower_widths(dm.config.dnn_params)       # <= the compiled tile: the slabs are zero padded
+        net_views, n_flat = self._net_grad_views(H2)
         self.grad_views = [
             (self.d1.kernel, a[o['dW1']:o['dW1'] + C * TILE_H1].view(C, TILE_H1)[:, :H1]),
             (self.d2.kernel, a[o['dW2']:o['dW2'] + TILE_H1 * TILE_H2].view(TILE_H1, TILE_H2)[:H1, :H2]),
             (self.d1.bias, a[o['db1']:o['db1'] + H1]),
             (self.d2.bias, a[o['db2']:o['db2'] + H2]),
-            (self.dl.kernel, a[o['dw3']:o['dw3'] + H2].view(H2, 1)),
-            (self.out.kernel, a[o['dwo']:o['dwo'] + 1].view(1, 1)),
             (self.bn.gamma, a[o['dgamma']:o['dgamma'] + C]),
             (self.bn.beta, a[o['dbeta']:o['dbeta'] + C]),
-            (self.lin.kernel, a[o['dwlin']:o['dwlin'] + self.F + self.Nd].view(self.F + self.Nd, 1)),
-        ]
+        ] + net_views
         if self.out.bias is not None:
             self.grad_views.append((self.out.bias, a[o['dbo']:o['dbo'] + 1]))
         self.loss_view = a[o['loss']:o['loss'] + 1]
@@ -232,29 +262,35 @@ class FusedDeepFM:
         # the model with ONE launch over (flat_params, accum) instead of one launch per tensor.
         self.flat_params = torch.zeros_like(self.accum)
         members = _mirror_in_flat(self.flat_params, a, self.grad_views)
-        n_flat = o['dwlin'] + self.F + self.Nd
         opt = getattr(dm, 'optimizer', None)
         if opt is not None and hasattr(opt, 'register_flat_group'):
             opt.register_flat_group(self.flat_params, self.accum, members, n_flat)
         dm.model._dt_flat_grad = self.accum     # lets DataParallelStrategy all-reduce the gradients in place
 
+    def _entry(self, what):
+        return getattr(lib(), f'dt_{self.PREFIX}_{what}')
+
     def _buffers(self, B):
         b = self._bufs.get(B)
         if b is None:
-            nbytes = lib().dt_deepfm_workspace_bytes(B, self.F, self.D, self.Nd)
+            nbytes = self._entry('workspace_bytes')(B, *self._dims())
             if nbytes < 0:
-                raise _lib.DtHipError('fused DeepFM step: unsupported shape')
+                raise _lib.DtHipError(f'fused {type(self).__name__[len("Fused"):]} step: unsupported shape')
             dev = self.device
             b = {'ws': torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev),   # zero-filled once: the batch-sum accumulators
                  'logit': torch.empty((B, 1), dtype=torch.float32, device=dev),
-                 'rows': torch.empty((B, self.F), dtype=torch.int64, device=dev),
                  'grad_rows': torch.empty((B, self.F, self.D), dtype=torch.float32, device=dev),
-                 # scratch of the in-step dedupe: field-major rows + the segment arrays (csrc/deepfm.hip DedupeWs)
-                 'dedupe': torch.zeros((lib().dt_deepfm_dedupe_bytes(B, self.F) + 7) // 8, dtype=torch.int64,
-                                       device=dev),
-                 'dedupe_slots': lib().dt_deepfm_dedupe_slots(B, self.F)}
+                 **self._id_state(B)}
             self._bufs[B] = b
         return b
+
+    def _id_state(self, B):
+        """the lookups' rows and the in-step dedupe's scratch: field-major rows + the segment arrays (csrc/deepfm.hip
+        DedupeWs)"""
+        return {'rows': torch.empty((B, self.F), dtype=torch.int64, device=self.device),
+                'dedupe': torch.zeros((lib().dt_deepfm_dedupe_bytes(B, self.F) + 7) // 8, dtype=torch.int64,
+                                      device=self.device),
+                'dedupe_slots': lib().dt_deepfm_dedupe_slots(B, self.F)}
 
     # -- per-slot id state: the compiled loop (compiled.CompiledTrainLoop) keeps k steps in one hipGraph and runs the ids-only
     #    work of steps 2..k ahead of them; every captured step then needs its OWN rows / segment buffers --------------------
@@ -263,14 +299,9 @@ class FusedDeepFM:
         if not slot:
             return buf
         slots = buf.setdefault('slots', {})
-        sb = slots.get(slot)
-        if sb is None:
-            dev = self.device
-            sb = {'rows': torch.empty((B, self.F), dtype=torch.int64, device=dev),
-                  'dedupe': torch.zeros((lib().dt_deepfm_dedupe_bytes(B, self.F) + 7) // 8, dtype=torch.int64, device=dev),
-                  'dedupe_slots': buf['dedupe_slots']}
-            slots[slot] = sb
-        return sb
+        if slot not in slots:
+            slots[slot] = self._id_state(B)
+        return slots[slot]
 
     def check_dedupe(self):
         """Host check of the in-step dedupe (reads one word per batch size back: call it outside the step — `DeepModel.fit`
@@ -308,6 +339,30 @@ class FusedDeepFM:
         check(lib().dt_deepfm_preelect(ptr(idx), kind, ptr(getattr(self.emb, f'row_offset_{self.key}')),
                                        ptr(getattr(self.emb, f'vocab_{self.key}')), B, self.F, ptr(sb['rows']),
                                        ptr(sb['dedupe']), sb['dedupe_slots'], stream_ptr()), 'dt_deepfm_preelect')
+
+    # -- the arguments of the step's entry points ------------------------------------------------------------------------
+    def _phases(self, backward=True, part=0, pre=0, diag=True):
+        """the `phases` word: forward (1) or backward (2) step | the split-finish part | the loss | pre-elected / prepared
+        bits | the tower's matrix-core mode and (diag) the phase stamps, for a backward step other than the finish alone"""
+        phases = (2 if backward else 1) | part | _step_loss(self.dm) | pre
+        if backward and part != _lib.DT_STEP_FINISH_ONLY:
+            phases |= self.tower_flag | (self.diag_flag if diag else 0)
+        return phases
+
+    def _head(self, ids, kind, rows_src, dense, y, B, logit, rows, buf, oob, dedupe, dedupe_slots):
+        """the arguments every step entry point starts with, up to dedupe_slots; rows_src = (table, row_offset, vocab)"""
+        training, bn = self.dm.model.training, self.bn
+        return (ptr(ids), kind, *[ptr(t) for t in rows_src], ptr(dense), ptr(y), B, self.F, self.D, self.Nd,
+                *self._net_args(), ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean) if training else None,
+                ptr(bn.moving_variance) if training else None, float(bn.epsilon), float(bn.momentum), ptr(self.d1.kernel),
+                ptr(self.d1.bias), ptr(self.d2.kernel), ptr(self.d2.bias), *self._head_weights(), ptr(self.out.bias),
+                ptr(logit), ptr(rows), ptr(buf['grad_rows']), ptr(self.accum), ptr(buf['ws']), oob, dedupe, dedupe_slots)
+
+    def _tail(self, phases, sw):
+        """phases and the per-step inputs that follow it in every entry point"""
+        training = self.dm.model.training
+        return (phases, self.emb_dropout if training else 0.0, ptr(self.drop_seed),
+                self.dense_dropout if training else 0.0, ptr(sw))
 
     # -- model-parallel tables (parallel.ShardedEmbeddingStrategy) --------------------------------------
     def _sharded_buffers(self, B, st):
@@ -372,24 +427,15 @@ class FusedDeepFM:
 
     def sharded_core(self, B, dense, y, st, sample_weight=None, part=0):
         """the fused step's launches on the received rows (no collective inside: a hipGraph can hold them)"""
-        F, D, W = self.F, self.D, st.world_size
         buf = self._buffers(B)
         sb = self._sharded_buffers(B, st)
         dense = None if dense is None else dense.contiguous()
         y = y.reshape(-1).contiguous()
         sw = _row_weights(sample_weight, y)
-        training = self.dm.model.training
-        check(lib().dt_deepfm_train_step(
-            ptr(sb['iota']), _lib.DT_IDX_I32, ptr(sb['emb_T']), ptr(sb['zero_off']), ptr(sb['fb_vocab']), ptr(dense), ptr(y),
-            B, F, D, self.Nd, ptr(self.lin.kernel), ptr(self.bn.gamma), ptr(self.bn.beta),
-            ptr(self.bn.moving_mean) if training else None, ptr(self.bn.moving_variance) if training else None,
-            float(self.bn.epsilon), float(self.bn.momentum), ptr(self.d1.kernel), ptr(self.d1.bias),
-            ptr(self.d2.kernel), ptr(self.d2.bias), ptr(self.dl.kernel), ptr(self.out.kernel), ptr(self.out.bias),
-            ptr(buf['logit']), ptr(sb['rows_dummy']), ptr(buf['grad_rows']), ptr(self.accum), ptr(buf['ws']),
-            None, None, 0, 1.0 / W, 1, 2 | part | _step_loss(self.dm) | (0 if part == _lib.DT_STEP_FINISH_ONLY else self.tower_flag | self.diag_flag),
-            self.emb_dropout if training else 0.0, ptr(self.drop_seed),
-            self.dense_dropout if training else 0.0, ptr(sw), stream_ptr()),
-            'dt_deepfm_train_step')
+        head = self._head(sb['iota'], _lib.DT_IDX_I32, (sb['emb_T'], sb['zero_off'], sb['fb_vocab']), dense, y, B,
+                          buf['logit'], sb['rows_dummy'], buf, None, None, 0)
+        check(lib().dt_deepfm_train_step(*head, 1.0 / st.world_size, 1, *self._tail(self._phases(part=part), sw),
+                                         stream_ptr()), 'dt_deepfm_train_step')
         for p, g in self.grad_views:
             p.grad = g
         self.dm.model._dt_sharded_step = True
@@ -426,42 +472,13 @@ class FusedDeepFM:
         opt = _rows_in_step(self, B, True, True) if _dedupe_in_step(self, B, True) else None
         if opt is None or not self._whole_in_step(opt):
             return False
-        phases = 2 | _step_loss(self.dm) | self.tower_flag
-        return bool(lib().dt_deepfm_step_chains(B, self.F, self.D, self.Nd, phases))
+        return bool(lib().dt_deepfm_step_chains(B, self.F, self.D, self.Nd, self._phases(diag=False)))
 
-    def run(self, idx, dense, y, backward=True, apply_rows=False, sample_weight=None, logit_out=None, slot=0,
-            preelected=False, next_ids=None, prepared=False):
-        """-> (loss [1] view, logit [B,1]).  slot / preelected: the compiled loop's per-step id buffers (`preelect`).
-        next_ids / prepared (chained steps, `can_chain`): next_ids = (ids of the following step, its slot) — this step prepares
-        it; prepared: this step was prepared by the one before it (slot's buffers hold its rows / segments).  logit_out: a caller-owned [B,1] fp32 buffer the step writes its logits to (the
-        compiled loop keeps one per captured step) instead of the plan's own.  With backward=True fills `.grad` of every dense parameter
-        (views of one static buffer) and registers the embedding table's sparse gradient.  apply_rows=True: the caller
-        runs `optimizer.step()` right after this call, so the step may update the table rows looked up once itself
-        (`_rows_in_step`); the registered sparse gradient then carries `fields = -2` (segments only)."""
-        st = self.dm.config.distribute_strategy
-        if backward and getattr(st, 'sharded_embeddings', False) and st.active and \
-                not self.emb.uses_dense_grad(self.D):
-            return self._run_sharded(idx, dense, y, st, sample_weight)
-        self.dm.model._dt_sharded_step = False
+    def _id_buffers(self, idx, backward, dedupe, opt, slot, preelected, next_ids, prepared):
+        """-> (this step's rows / segment buffers, its pre-elected / prepared bits, the pointers of the next step's ids, rows
+        and segment buffers when this step prepares it)"""
         B = idx.shape[0]
-        buf = self._buffers(B)
-        idx = idx.contiguous()
-        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
-        if idx.dtype not in (torch.float32, torch.int32):
-            idx = idx.to(torch.int32)
-        dense = None if dense is None else dense.contiguous()
-        y = y.reshape(-1).contiguous()
-        sw = _row_weights(sample_weight, y)
-        table = self.emb.tables[self.key]
-        training = self.dm.model.training
-        logit = buf['logit']
-        if logit_out is not None:
-            if logit_out.shape != logit.shape or logit_out.dtype != logit.dtype or not logit_out.is_contiguous():
-                raise ValueError(f'logit_out must be a contiguous float32 {tuple(logit.shape)} tensor')
-            logit = logit_out
-        dedupe = _dedupe_in_step(self, B, backward)
-        opt = _rows_in_step(self, B, backward, apply_rows)
-        ids = self._slot_buffers(B, slot) if (slot and dedupe) else buf        # this step's rows / segment buffers
+        ids = self._slot_buffers(B, slot) if (slot and dedupe) else self._buffers(B)
         pre = _lib.DT_STEP_PREELECTED if (preelected and dedupe and backward) else 0
         if preelected and not pre:
             raise _lib.DtHipError('a pre-elected step needs the in-step dedupe (backward, single process)')
@@ -477,37 +494,61 @@ class FusedDeepFM:
                     raise ValueError('next_ids: (contiguous ids like this step\'s, a slot of their own)')
                 nb = self._slot_buffers(B, nslot)
                 nxt = (ptr(nidx), ptr(nb['rows']), ptr(nb['dedupe']))
-        head = (ptr(idx), kind, ptr(table), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-                ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), ptr(y), B, self.F, self.D, self.Nd,
-                ptr(self.lin.kernel), ptr(self.bn.gamma), ptr(self.bn.beta),
-                ptr(self.bn.moving_mean) if training else None, ptr(self.bn.moving_variance) if training else None,
-                float(self.bn.epsilon), float(self.bn.momentum), ptr(self.d1.kernel), ptr(self.d1.bias),
-                ptr(self.d2.kernel), ptr(self.d2.bias), ptr(self.dl.kernel), ptr(self.out.kernel), ptr(self.out.bias),
-                ptr(logit), ptr(ids['rows']), ptr(buf['grad_rows']), ptr(self.accum), ptr(buf['ws']),
-                ptr(self.emb.oob_count) if self.emb.check_oob else None,
-                ptr(ids['dedupe']) if dedupe else None, buf['dedupe_slots'])
-        whole = False
+        return ids, pre, nxt
+
+    def run(self, idx, dense, y, backward=True, apply_rows=False, sample_weight=None, logit_out=None, slot=0,
+            preelected=False, next_ids=None, prepared=False):
+        """-> (loss [1] view, logit [B,1]).  slot / preelected: the compiled loop's per-step id buffers (`preelect`).
+        next_ids / prepared (chained steps, `can_chain`): next_ids = (ids of the following step, its slot) — this step prepares
+        it; prepared: this step was prepared by the one before it (slot's buffers hold its rows / segments).  logit_out: a caller-owned [B,1] fp32 buffer the step writes its logits to (the
+        compiled loop keeps one per captured step) instead of the plan's own.  With backward=True fills `.grad` of every dense parameter
+        (views of one static buffer) and registers the embedding table's sparse gradient.  apply_rows=True: the caller
+        runs `optimizer.step()` right after this call, so the step may update the table rows looked up once itself
+        (`_rows_in_step`); the registered sparse gradient then carries `fields = -2` (segments only)."""
+        st = self.dm.config.distribute_strategy
+        if self.ROW_OWNED and backward and getattr(st, 'sharded_embeddings', False) and st.active and \
+                not self.emb.uses_dense_grad(self.D):
+            return self._run_sharded(idx, dense, y, st, sample_weight)
+        self.dm.model._dt_sharded_step = False
+        B = idx.shape[0]
+        buf = self._buffers(B)
+        idx = idx.contiguous()
+        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
+        if idx.dtype not in (torch.float32, torch.int32):
+            idx = idx.to(torch.int32)
+        dense = None if dense is None else dense.contiguous()
+        y = y.reshape(-1).contiguous()
+        sw = _row_weights(sample_weight, y)
+        table = self.emb.tables[self.key]
+        logit = buf['logit']
+        if logit_out is not None:
+            if logit_out.shape != logit.shape or logit_out.dtype != logit.dtype or not logit_out.is_contiguous():
+                raise ValueError(f'logit_out must be a contiguous float32 {tuple(logit.shape)} tensor')
+            logit = logit_out
+        dedupe = _dedupe_in_step(self, B, backward)
+        opt = _rows_in_step(self, B, backward, apply_rows)
+        ids, pre, nxt = self._id_buffers(idx, backward, dedupe, opt, slot, preelected, next_ids, prepared)
+        head = self._head(idx, kind, (table, getattr(self.emb, f'row_offset_{self.key}'),
+                                      getattr(self.emb, f'vocab_{self.key}')), dense, y, B, logit, ids['rows'], buf,
+                          ptr(self.emb.oob_count) if self.emb.check_oob else None,
+                          ptr(ids['dedupe']) if dedupe else None, buf['dedupe_slots'])
         if opt is not None:
             # the rows looked up once are updated where their gradient is formed (csrc/deepfm.hip k_wgrad_rows); when the
             # optimizer's flat dense group is this plan's, the step's last launch runs the rest of the optimizer step too
             # (dense elements, segments, the state's advance: k_finish_step) and `optimizer.step()` has nothing left to do
             slots = opt._st(table, rows=True)
-            flat = getattr(opt, '_flat', None)
-            whole = (flat is not None and flat[0] is self.flat_params and flat[1] is self.accum and
-                     os.environ.get('DT_AMD_STEP_IN_STEP', '1') != '0' and
-                     all(id(p) in flat[5] for p in opt.params if p is not table))
+            whole = self._whole_in_step(opt)
+            flat = opt._flat
             dn = (ptr(flat[0]), ptr(flat[2]), ptr(flat[3]), int(flat[4]), float(opt.lr)) if whole else (None, None, None, 0, 0.0)
-            check(lib().dt_deepfm_train_step_adam(
-                *head, 2 | _step_loss(self.dm) | self.tower_flag | self.diag_flag | pre, self.emb_dropout if training else 0.0, ptr(self.drop_seed),
-                self.dense_dropout if training else 0.0, ptr(sw), ptr(slots['m']), ptr(slots['v']), int(slots['m'].stride(0)), ptr(opt._state_tensor(table.device)), 0.0,
-                opt.b1, opt.b2, opt.eps, *dn, *nxt, stream_ptr()), 'dt_deepfm_train_step_adam')
+            check(self._entry('train_step_adam')(
+                *head, *self._tail(self._phases(pre=pre), sw), ptr(slots['m']), ptr(slots['v']), int(slots['m'].stride(0)),
+                ptr(opt._state_tensor(table.device)), 0.0, opt.b1, opt.b2, opt.eps, *dn, *nxt, stream_ptr()),
+                f'dt_{self.PREFIX}_train_step_adam')
             if whole:
                 opt.applied_in_step()
         else:
-            check(lib().dt_deepfm_train_step(
-                *head, 1.0, 0, (2 if backward else 1) | _step_loss(self.dm) | ((self.tower_flag | self.diag_flag) if backward else 0) | pre,
-                self.emb_dropout if training else 0.0,
-                ptr(self.drop_seed), self.dense_dropout if training else 0.0, ptr(sw), stream_ptr()), 'dt_deepfm_train_step')
+            check(self._entry('train_step')(*head, *self.STEP_EXTRA, *self._tail(self._phases(backward, pre=pre), sw),
+                                            stream_ptr()), f'dt_{self.PREFIX}_train_step')
         if backward:
             for p, g in self.grad_views:
                 p.grad = g
@@ -526,202 +567,56 @@ class FusedDeepFM:
         return self.loss_view, logit
 
 
-_DCN_ACC_NAMES = ['dW1', 'dW2', 'db1', 'db2', 'dw3', 'dwo', 'dbo', 'loss', 'dgamma', 'dbeta', 'dcw', 'dcb']
-
-
 class FusedDCN(FusedDeepFM):
     """Whole-step executor for the DCN graph (nets ['dcn_nets'], deepnets.py:194-207): the DeepFM kernel sequence with the
     Cross network (layers.py:428-436) running on the BN'd tile inside the tower kernel -> `dt_dcn_train_step`."""
 
     NETS = {'dcn_nets'}
+    PREFIX = 'dcn'
+    ACC_NAMES = ('dW1', 'dW2', 'db1', 'db2', 'dw3', 'dwo', 'dbo', 'loss', 'dgamma', 'dbeta', 'dcw', 'dcb')
+    TOWER = ('dcn_dense_1', 'dcn_dense_2')
+    STEP_EXTRA = ()
+    ROW_OWNED = False
 
     @classmethod
     def eligible(cls, dm):
         c = dm.config
         try:
-            if list(c.nets) != ['dcn_nets'] or dm.var_len_categorical_columns:
-                return False
-            if _step_loss(dm) is None:
-                return False
-            if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
+            # a single net: Concatenate([cross, dnn]) feeds task_output directly (deepmodel.py:286-301), no dense_logit_*
+            if list(c.nets) != ['dcn_nets'] or 'dense_logit_dcn_nets' in dm.model.layers_by_name:
                 return False
             st = c.distribute_strategy
             if getattr(st, 'sharded_embeddings', False) and getattr(st, 'active', False):
                 return False                      # row-owned tables: the layer-by-layer path
-            if _tower_widths(c.dnn_params) is None:
+            dims = _step_dims(dm, cls.TOWER + ('dcn_cross_layer',))
+            if dims is None:
                 return False
-            L = dm.model.layers_by_name
-            # a single net: Concatenate([cross, dnn]) feeds task_output directly (deepmodel.py:286-301), no dense_logit_*
-            need = ['emb_categorical_vars_all', 'bn_concat_emb_dense', 'dcn_cross_layer', 'dcn_dense_1', 'dcn_dense_2',
-                    'task_output']
-            if 'dense_logit_dcn_nets' in L:
-                return False
-            if any(n not in L for n in need):
-                return False
-            emb = L['emb_categorical_vars_all']
-            if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
-                return False
-            D = emb.groups[0][0]
-            F = len(emb.input_dims)
-            Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
-            nl = int(L['dcn_cross_layer'].num_cross_layer)
-            return bool(lib().dt_dcn_supported(max(int(getattr(dm, '_batch_hint', 0) or 0), 1), F, D, Nd, 128, 64, nl))
+            nl = int(dm.model.layers_by_name['dcn_cross_layer'].num_cross_layer)
+            return bool(lib().dt_dcn_supported(*dims, 128, 64, nl))
         except Exception:
             return False
 
-    def __init__(self, dm):
-        self.dm = dm
-        L = dm.model.layers_by_name
-        self.emb = L['emb_categorical_vars_all']
-        self.bn = L['bn_concat_emb_dense']
+    def _net_layers(self, L):
         self.cross = L['dcn_cross_layer']
         self.nl = int(self.cross.num_cross_layer)
-        self.d1, self.d2 = L['dcn_dense_1'], L['dcn_dense_2']
-        self.out = L['task_output']        # kernel [C + H2, 1]: the step's w3; its w_out is the constant 1
-        self.D = self.emb.groups[0][0]
-        self.F = len(self.emb.input_dims)
-        self.Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
-        self.C = self.F * self.D + self.Nd
-        self.key = f'd{self.D}'
-        self.device = self.emb.tables[self.key].device
-        self.one = torch.ones(4, dtype=torch.float32, device=self.device)
-        n_acc = lib().dt_dcn_accum_floats(self.F, self.D, self.Nd, self.nl)
-        offs = (ctypes.c_int64 * 12)()
-        check(lib().dt_dcn_accum_offsets(self.F, self.D, self.Nd, self.nl, ctypes.cast(offs, ctypes.c_void_p)),
-              'dt_dcn_accum_offsets')
-        self.off = dict(zip(_DCN_ACC_NAMES, [int(v) for v in offs]))
-        self.accum = torch.zeros(n_acc, dtype=torch.float32, device=self.device)
-        self._bufs = {}
+        self.one = torch.ones(4, dtype=torch.float32, device=self.device)     # the step's w_out: task_output is its w3
+
+    def _dims(self):
+        return self.F, self.D, self.Nd, self.nl
+
+    def _net_grad_views(self, H2):
+        # W1 / W2 precede the [C + 64] output kernel in the flat group, so they keep their 16-byte alignment whatever C is
+        # (the kernels read w3 with scalar loads)
         a, o, C, nl = self.accum, self.off, self.C, self.nl
-        H1, H2 = _tower_widths(dm.config.dnn_params)
-        self.grad_views = [
-            (self.d1.kernel, a[o['dW1']:o['dW1'] + C * TILE_H1].view(C, TILE_H1)[:, :H1]),
-            (self.d2.kernel, a[o['dW2']:o['dW2'] + TILE_H1 * TILE_H2].view(TILE_H1, TILE_H2)[:H1, :H2]),
-            (self.d1.bias, a[o['db1']:o['db1'] + H1]),
-            (self.d2.bias, a[o['db2']:o['db2'] + H2]),
-            (self.out.kernel, a[o['dw3']:o['dw3'] + C + H2].view(C + H2, 1)),      # [w3c | w3d], w3d's pad at the end
-            (self.bn.gamma, a[o['dgamma']:o['dgamma'] + C]),
-            (self.bn.beta, a[o['dbeta']:o['dbeta'] + C]),
-            (self.cross.kernel_stack, a[o['dcw']:o['dcw'] + nl * C].view(nl, C)),
-            (self.cross.bias_stack, a[o['dcb']:o['dcb'] + nl * C].view(nl, C)),
-        ]
-        if self.out.bias is not None:
-            self.grad_views.append((self.out.bias, a[o['dbo']:o['dbo'] + 1]))
-        self.loss_view = a[o['loss']:o['loss'] + 1]
-        self.emb_dropout = float(dm.config.embedding_dropout or 0)
-        # dense_dropout (config.py:83): Dropout on the continuous input columns, masked where kernel A packs them
-        self.dense_dropout = float(dm.config.dense_dropout or 0) if self.Nd else 0.0
-        seed = int(torch.randint(1, 2 ** 31 - 1, (1,)).item())
-        self.drop_seed = torch.tensor([seed], dtype=torch.int32, device=self.device)
-        self.dedupe = os.environ.get('DT_AMD_FUSED_DEDUPE', '1') != '0'
-        self.tower_flag = _tower_mfma_flag(dm.config.dnn_params)
-        # diagnostic: s_memtime phase stamps into the workspace (tools/phase_times.py sets DT_AMD_STEP_STAMPS=1)
-        self.diag_flag = _lib.DT_STEP_STAMPS if os.environ.get('DT_AMD_STEP_STAMPS') == '1' else 0
-        # parameters mirror the gradient layout in one flat buffer (one optimizer launch, see FusedDeepFM); W1 / W2 precede
-        # the [C + 64] output kernel, so they keep their 16-byte alignment whatever C is (the kernels read w3 with scalar loads)
-        self.flat_params = torch.zeros_like(self.accum)
-        members = _mirror_in_flat(self.flat_params, a, self.grad_views)
-        n_flat = o['dcb'] + nl * C
-        opt = getattr(dm, 'optimizer', None)
-        if opt is not None and hasattr(opt, 'register_flat_group'):
-            opt.register_flat_group(self.flat_params, self.accum, members, n_flat)
-        dm.model._dt_flat_grad = self.accum
+        return [(self.out.kernel, a[o['dw3']:o['dw3'] + C + H2].view(C + H2, 1)),      # [w3c | w3d], w3d's pad at the end
+                (self.cross.kernel_stack, a[o['dcw']:o['dcw'] + nl * C].view(nl, C)),
+                (self.cross.bias_stack, a[o['dcb']:o['dcb'] + nl * C].view(nl, C))], o['dcb'] + nl * C
 
-    def _buffers(self, B):
-        b = self._bufs.get(B)
-        if b is None:
-            nbytes = lib().dt_dcn_workspace_bytes(B, self.F, self.D, self.Nd, self.nl)
-            if nbytes < 0:
-                raise _lib.DtHipError('fused DCN step: unsupported shape')
-            dev = self.device
-            b = {'ws': torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=dev),   # zero-filled once: the batch-sum accumulators
-                 'logit': torch.empty((B, 1), dtype=torch.float32, device=dev),
-                 'rows': torch.empty((B, self.F), dtype=torch.int64, device=dev),
-                 'grad_rows': torch.empty((B, self.F, self.D), dtype=torch.float32, device=dev),
-                 'dedupe': torch.zeros((lib().dt_deepfm_dedupe_bytes(B, self.F) + 7) // 8, dtype=torch.int64,
-                                       device=dev),
-                 'dedupe_slots': lib().dt_deepfm_dedupe_slots(B, self.F)}
-            self._bufs[B] = b
-        return b
+    def _net_args(self):
+        return ptr(self.cross.kernel_stack), ptr(self.cross.bias_stack), self.nl
 
-    def run(self, idx, dense, y, backward=True, apply_rows=False, sample_weight=None, logit_out=None, slot=0,
-            preelected=False, next_ids=None, prepared=False):
-        self.dm.model._dt_sharded_step = False
-        B = idx.shape[0]
-        buf = self._buffers(B)
-        idx = idx.contiguous()
-        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
-        if idx.dtype not in (torch.float32, torch.int32):
-            idx = idx.to(torch.int32)
-        dense = None if dense is None else dense.contiguous()
-        y = y.reshape(-1).contiguous()
-        sw = _row_weights(sample_weight, y)
-        table = self.emb.tables[self.key]
-        training = self.dm.model.training
-        logit = buf['logit']
-        if logit_out is not None:
-            if logit_out.shape != logit.shape or logit_out.dtype != logit.dtype or not logit_out.is_contiguous():
-                raise ValueError(f'logit_out must be a contiguous float32 {tuple(logit.shape)} tensor')
-            logit = logit_out
-        dedupe = _dedupe_in_step(self, B, backward)
-        opt = _rows_in_step(self, B, backward, apply_rows)
-        ids = self._slot_buffers(B, slot) if (slot and dedupe) else buf        # this step's rows / segment buffers
-        pre = _lib.DT_STEP_PREELECTED if (preelected and dedupe and backward) else 0
-        if preelected and not pre:
-            raise _lib.DtHipError('a pre-elected step needs the in-step dedupe (backward, single process)')
-        nxt = (None, None, None)
-        if prepared or next_ids is not None:
-            if opt is None or not dedupe:
-                raise _lib.DtHipError('chained steps need the in-step dedupe and optimizer (can_chain)')
-            if prepared:
-                pre |= _lib.DT_STEP_PREPARED
-            if next_ids is not None:
-                nidx, nslot = next_ids
-                if nidx.dtype != idx.dtype or nidx.shape != idx.shape or not nidx.is_contiguous() or not nslot or nslot == slot:
-                    raise ValueError('next_ids: (contiguous ids like this step\'s, a slot of their own)')
-                nb = self._slot_buffers(B, nslot)
-                nxt = (ptr(nidx), ptr(nb['rows']), ptr(nb['dedupe']))
-        head = (ptr(idx), kind, ptr(table), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-                ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), ptr(y), B, self.F, self.D, self.Nd,
-                ptr(self.cross.kernel_stack), ptr(self.cross.bias_stack), self.nl, ptr(self.bn.gamma), ptr(self.bn.beta),
-                ptr(self.bn.moving_mean) if training else None, ptr(self.bn.moving_variance) if training else None,
-                float(self.bn.epsilon), float(self.bn.momentum), ptr(self.d1.kernel), ptr(self.d1.bias),
-                ptr(self.d2.kernel), ptr(self.d2.bias), ptr(self.out.kernel), ptr(self.one), ptr(self.out.bias),
-                ptr(logit), ptr(ids['rows']), ptr(buf['grad_rows']), ptr(self.accum), ptr(buf['ws']),
-                ptr(self.emb.oob_count) if self.emb.check_oob else None,
-                ptr(ids['dedupe']) if dedupe else None, buf['dedupe_slots'])
-        if opt is not None:      # the whole optimizer step inside the train step (see FusedDeepFM.run)
-            slots = opt._st(table, rows=True)
-            flat = getattr(opt, '_flat', None)
-            whole = (flat is not None and flat[0] is self.flat_params and flat[1] is self.accum and
-                     os.environ.get('DT_AMD_STEP_IN_STEP', '1') != '0' and
-                     all(id(p) in flat[5] for p in opt.params if p is not table))
-            dn = (ptr(flat[0]), ptr(flat[2]), ptr(flat[3]), int(flat[4]), float(opt.lr)) if whole else (None, None, None, 0, 0.0)
-            check(lib().dt_dcn_train_step_adam(
-                *head, 2 | _step_loss(self.dm) | self.tower_flag | self.diag_flag | pre, self.emb_dropout if training else 0.0, ptr(self.drop_seed),
-                self.dense_dropout if training else 0.0, ptr(sw), ptr(slots['m']), ptr(slots['v']), int(slots['m'].stride(0)), ptr(opt._state_tensor(table.device)), 0.0,
-                opt.b1, opt.b2, opt.eps, *dn, *nxt, stream_ptr()), 'dt_dcn_train_step_adam')
-            if whole:
-                opt.applied_in_step()
-        else:
-            check(lib().dt_dcn_train_step(
-                *head, (2 if backward else 1) | _step_loss(self.dm) | ((self.tower_flag | self.diag_flag) if backward else 0) | pre,
-                self.emb_dropout if training else 0.0,
-                ptr(self.drop_seed), self.dense_dropout if training else 0.0, ptr(sw), stream_ptr()), 'dt_dcn_train_step')
-        if backward:
-            for p, g in self.grad_views:
-                p.grad = g
-            self.emb.sparse_grads[self.key] = [SparseRowGrad(ids['rows'].view(-1), buf['grad_rows'].view(-1, self.D),
-                                                             fields=(-2 if opt is not None else -1) if dedupe else None,
-                                                             segments=_segments(ids, B, self.F) if dedupe else None)]
-            if self.emb.uses_dense_grad(self.D):
-                # small tables keep exact dense-Adam semantics: densify the row gradients
-                g = torch.zeros_like(table)
-                check(lib().dt_embedding_bwd_dense(ptr(ids['rows']), ptr(buf['grad_rows']), B * self.F, self.D,
-                                                   ptr(g), stream_ptr()), 'dt_embedding_bwd_dense')
-                table.grad = g
-                self.emb.sparse_grads.pop(self.key, None)
-        return self.loss_view, logit
+    def _head_weights(self):
+        return ptr(self.out.kernel), ptr(self.one)
 
 
 def make_fused_plan(dm):

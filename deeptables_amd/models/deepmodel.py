@@ -284,14 +284,8 @@ class DeepModel:
         if plan is not None:
             cat = inputs[0]
             dense = inputs[1] if len(inputs) > 1 else None
-            kw = {} if sample_weight is None else {'sample_weight': sample_weight}
-            if logit_out is not None:
-                kw['logit_out'] = logit_out
-            if slot or preelected:
-                kw['slot'], kw['preelected'] = slot, preelected
-            if next_ids is not None or prepared:
-                kw['next_ids'], kw['prepared'], kw['slot'] = next_ids, prepared, slot
-            loss, logit = plan.run(cat, dense, y, apply_rows=apply_rows, **kw)
+            loss, logit = plan.run(cat, dense, y, apply_rows=apply_rows, sample_weight=sample_weight, logit_out=logit_out,
+                                   slot=slot, preelected=preelected, next_ids=next_ids, prepared=prepared)
             self.model._dt_flat_grad = plan.accum
             return loss[0], logit
         # generic path: the dense gradients accumulate in the model-wide flat buffer (None without one)

@@ -94,12 +94,12 @@ def test_balanced_class_weights():
     assert cw == {0: 10 / (3 * 6), 1: 10 / (3 * 3), 2: 10 / (3 * 1)}      # sklearn 'balanced': n / (classes * count)
 
 
-def _cpu_model(nets, hidden, **extra):
+def _cpu_model(nets, hidden, task='binary', **extra):
     from deeptables_amd.models import ModelConfig, DeepModel
     from deeptables_amd.models.metainfo import CategoricalColumn, ContinuousColumn
-    conf = ModelConfig(nets=nets, fixed_embedding_dim=True, embeddings_output_dim=8, embedding_dropout=0,
-                       dnn_params={'hidden_units': hidden, 'activation': 'relu'}, **extra)
-    dm = DeepModel('binary', 2, conf, [CategoricalColumn(f'C{i}', 20 + i, 8) for i in range(6)],
+    conf = ModelConfig(nets=nets, fixed_embedding_dim=True, embeddings_output_dim=8,
+                       dnn_params={'hidden_units': hidden, 'activation': 'relu'}, **{'embedding_dropout': 0, **extra})
+    dm = DeepModel(task, 2, conf, [CategoricalColumn(f'C{i}', 20 + i, 8) for i in range(6)],
                    [ContinuousColumn('input_continuous_all', ['a', 'b', 'c'])])
     dm.build('cpu')
     return dm
@@ -258,3 +258,303 @@ def test_model_peephole_defers_the_interacting_layers_normalisation_only_for_con
     assert deferred(K.Model(inputs=[inp], outputs=out)) == ['att_b']                       # att_a's output has two consumers
     inp, a, b, out = stack(lambda a, b: b)
     assert deferred(K.Model(inputs=[inp], outputs=out)) == ['att_a']                       # a model output stays normalised
+
+
+_STEP_ENTRIES = ('dt_deepfm_train_step', 'dt_deepfm_train_step_adam', 'dt_dcn_train_step', 'dt_dcn_train_step_adam',
+                 'dt_deepfm_preelect', 'dt_embedding_bwd_dense')
+
+
+class _StepRecorder:
+    """stand-in for fused.lib(): the step's launches are recorded as (name, args) and return 0; every host-side query goes
+    to the real library (dt_deepfm_step_chains is recorded as well, and answered by the library)"""
+
+    def __init__(self, real):
+        self.real, self.calls = real, []
+
+    def __getattr__(self, name):
+        if name in _STEP_ENTRIES:
+            return lambda *args: self.calls.append((name, args)) or 0
+        fn = getattr(self.real, name)
+        if name == 'dt_deepfm_step_chains':
+            return lambda *args: self.calls.append((name, args)) or fn(*args)
+        return fn
+
+
+def _tensor_names(plan, dm, inputs):
+    """data_ptr -> 'name' ('a|b' when several named tensors start at the same address)"""
+    import ctypes  # noqa: F401
+    L = dm.model.layers_by_name
+    emb, opt = plan.emb, dm.optimizer
+    table = emb.tables[plan.key]
+    named = dict(inputs)
+    named.update({'table': table, 'row_offset': getattr(emb, f'row_offset_{plan.key}'),
+                  'vocab': getattr(emb, f'vocab_{plan.key}'), 'oob': emb.oob_count,
+                  'gamma': plan.bn.gamma, 'beta': plan.bn.beta, 'mean': plan.bn.moving_mean,
+                  'var': plan.bn.moving_variance, 'W1': plan.d1.kernel, 'b1': plan.d1.bias, 'W2': plan.d2.kernel,
+                  'b2': plan.d2.bias, 'out.kernel': L['task_output'].kernel, 'out.bias': L['task_output'].bias,
+                  'accum': plan.accum, 'flat_params': plan.flat_params, 'drop_seed': plan.drop_seed})
+    if 'linear_logit' in L:
+        named.update({'w_lin': L['linear_logit'].kernel, 'dense_logit.kernel': L['dense_logit_dnn_nets'].kernel})
+    else:
+        named.update({'cross.kernel': L['dcn_cross_layer'].kernel_stack, 'cross.bias': L['dcn_cross_layer'].bias_stack,
+                      'one': plan.one})
+    if table.grad is not None:
+        named['table.grad'] = table.grad
+    if id(table) in opt.state:
+        named.update({'adam.m': opt.state[id(table)]['m'], 'adam.v': opt.state[id(table)]['v']})
+    if opt._dev_state is not None:
+        named['adam.state'] = opt._dev_state
+    if opt._flat is not None:
+        named.update({'flat.m': opt._flat[2], 'flat.v': opt._flat[3]})
+    for key, buf in plan._bufs.items():
+        for k, v in buf.items():
+            if isinstance(v, torch.Tensor):
+                named[k if isinstance(key, int) else f'sharded.{k}'] = v
+        for s, sb in buf.get('slots', {}).items():
+            for k, v in sb.items():
+                if isinstance(v, torch.Tensor):
+                    named[f'slot{s}.{k}'] = v
+    by_ptr = {}
+    for n, t in named.items():
+        by_ptr.setdefault(t.data_ptr(), []).append(n)
+    return {p: '|'.join(sorted(ns)) for p, ns in by_ptr.items()}
+
+
+def _decoded(rec, plan, dm, inputs):
+    """the recorded calls with every pointer argument replaced by the name of the tensor it points to"""
+    import ctypes
+    names = _tensor_names(plan, dm, inputs)
+    out = []
+    for name, args in rec.calls:
+        dec = []
+        for a in args:
+            if isinstance(a, ctypes.c_void_p):
+                assert a.value in names, (name, len(dec), a.value)
+                a = names[a.value]
+            dec.append(a)
+        out.append((name, dec))
+    rec.calls.clear()
+    return out
+
+
+def test_fused_plans_hand_the_step_entry_points_the_same_arguments(monkeypatch):
+    """pins what FusedDeepFM / FusedDCN hand the library in every step mode: the entry point, the argument count, the
+    `phases` word, the scalars and which tensor every pointer points to.  The launches are recorded (not run), so the
+    plans run on CPU tensors; the sharded split (sharded_core) runs with a one-rank stand-in for the strategy."""
+    import pytest
+    from deeptables_amd import _lib, fused
+    from deeptables_amd.models import layers
+    rec = _StepRecorder(_lib.lib())
+    monkeypatch.setattr(fused, 'lib', lambda: rec)
+    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
+    X3, BF16, MSE = _lib.DT_STEP_TOWER_X3, _lib.DT_STEP_TOWER_BF16, _lib.DT_STEP_LOSS_MSE
+    PRE, PREP, STAMPS = _lib.DT_STEP_PREELECTED, _lib.DT_STEP_PREPARED, _lib.DT_STEP_STAMPS
+    B, F, D, Nd = 16, 6, 8, 3
+    slots_n = _lib.lib().dt_deepfm_dedupe_slots(B, F)
+    DEEPFM = ['linear', 'fm_nets', 'dnn_nets']
+    DCN = ['dcn_nets']
+
+    def make(nets, task='binary', env=None, **extra):
+        for k in ('DT_AMD_FUSED_DEDUPE', 'DT_AMD_TOWER_DTYPE', 'DT_AMD_STEP_STAMPS'):      # read when the plan is built
+            monkeypatch.delenv(k, raising=False)
+        for k, v in (env or {}).items():
+            monkeypatch.setenv(k, v)
+        extra = dict(extra)
+        if nets == DCN:
+            extra.setdefault('cross_params', {'num_cross_layer': 2})
+        dm = _cpu_model(nets, ((100, 0, False), (40, 0, False)), task=task, **extra)
+        dm.optimizer._dev_state = torch.zeros(68, dtype=torch.int32)     # _state_tensor launches nothing
+        plan = dm.fused_plan()
+        assert type(plan).__name__ == ('FusedDeepFM' if nets == DEEPFM else 'FusedDCN')
+        for k in (env or {}):
+            monkeypatch.delenv(k)
+        return dm, plan
+
+    g = torch.Generator().manual_seed(0)
+    idx = torch.randint(0, 20, (B, F), generator=g, dtype=torch.int32)
+    idx2 = torch.randint(0, 20, (B, F), generator=g, dtype=torch.int32)
+    dense = torch.randn(B, Nd, generator=g)
+    y = (torch.rand(B, 1, generator=g) < 0.5).float()
+    sw = torch.rand(B, generator=g)
+    logit_out = torch.empty(B, 1)
+    idx_f = idx.float()
+    inputs = {'idx': idx, 'idx_f': idx_f, 'idx2': idx2, 'dense': dense, 'y': y, 'sw': sw, 'logit_out': logit_out}
+
+    def head(dm, net, ids='idx', rows='rows', dedupe='dedupe', training=True, logit='logit', oob=None,
+             kind=_lib.DT_IDX_I32):
+        bn = dm.model.layers_by_name['bn_concat_emb_dense']
+        common = [ids, kind, 'table', 'row_offset', 'vocab', 'dense', 'y', B, F, D, Nd]
+        mid = ['gamma', 'beta', 'mean' if training else None, 'var' if training else None, float(bn.epsilon),
+               float(bn.momentum), 'W1|flat_params', 'b1', 'W2', 'b2']
+        tail = [logit, rows, 'grad_rows', 'accum', 'ws', oob, dedupe, slots_n]
+        if net == DEEPFM:
+            return common + ['w_lin'] + mid + ['dense_logit.kernel', 'out.kernel', 'out.bias'] + tail
+        return common + ['cross.kernel', 'cross.bias', 2] + mid + ['out.kernel', 'one', 'out.bias'] + tail
+
+    def plain_tail(net, phases, emb_drop=0.0, dense_drop=0.0, w=None):
+        return ([1.0, 0] if net == DEEPFM else []) + [phases, emb_drop, 'drop_seed', dense_drop, w, None]
+
+    def adam_tail(dm, plan, phases, whole=True, nxt=(None, None, None), w=None):
+        opt = dm.optimizer
+        dn = ['W1|flat_params', 'flat.m', 'flat.v', opt._flat[4], float(opt.lr)] if whole else [None, None, None, 0, 0.0]
+        return [phases, 0.0, 'drop_seed', 0.0, w, 'adam.m', 'adam.v', 2 * D, 'adam.state', 0.0, opt.b1, opt.b2, opt.eps,
+                *dn, *nxt, None]
+
+    def entry(net, adam=False):
+        return ('dt_deepfm' if net == DEEPFM else 'dt_dcn') + ('_train_step_adam' if adam else '_train_step')
+
+    def one_call(dm, plan, **kw):
+        loss, logit = plan.run(kw.pop('ids', idx), dense, y, **kw)
+        calls = _decoded(rec, plan, dm, inputs)
+        assert len(calls) == 1, [c[0] for c in calls]
+        return calls[0], logit
+
+    def check_call(got, name, want):
+        assert got[0] == name
+        assert len(got[1]) == len(want), (name, len(got[1]), len(want))
+        for i, (a, b) in enumerate(zip(got[1], want)):
+            if isinstance(b, float):
+                assert a == pytest.approx(b), (name, i, a, b)
+            else:
+                assert a == b, (name, i, a, b)
+
+    for net in (DEEPFM, DCN):
+        # -- dense-gradient tables (the small tables' default): no dedupe, the row gradients densified ---------------
+        dm, plan = make(net)
+        assert plan.emb.uses_dense_grad(D)
+        plan.run(idx, dense, y)
+        calls = _decoded(rec, plan, dm, inputs)
+        assert [c[0] for c in calls] == [entry(net), 'dt_embedding_bwd_dense']
+        check_call(calls[0], entry(net), head(dm, net, dedupe=None) + plain_tail(net, 2 | X3))
+        check_call(calls[1], 'dt_embedding_bwd_dense', ['rows', 'grad_rows', B * F, D, 'table.grad', None])
+        assert plan.key not in plan.emb.sparse_grads
+
+        monkeypatch.setattr(layers, 'DENSE_GRAD_MAX_ELEMS', 0)          # row-sparse tables: the dedupe paths
+        dm, plan = make(net)
+        # forward only: no tower / diagnostic bits, no dedupe
+        got, logit = one_call(dm, plan, backward=False)
+        check_call(got, entry(net), head(dm, net, dedupe=None) + plain_tail(net, 1))
+        assert logit is plan._bufs[B]['logit']
+        # backward without the optimizer
+        got, _ = one_call(dm, plan)
+        check_call(got, entry(net), head(dm, net) + plain_tail(net, 2 | X3))
+        sg = plan.emb.sparse_grads[plan.key][0]
+        assert sg.fields == -1 and sg.segments is not None and sg.rows.data_ptr() == plan._bufs[B]['rows'].data_ptr()
+        for p, gv in plan.grad_views:
+            assert p.grad is gv
+        # the whole optimizer step inside the step
+        got, _ = one_call(dm, plan, apply_rows=True)
+        check_call(got, entry(net, True), head(dm, net) + adam_tail(dm, plan, 2 | X3))
+        assert plan.emb.sparse_grads[plan.key][0].fields == -2 and dm.optimizer._applied_in_step
+        dm.optimizer._applied_in_step = False
+        monkeypatch.setenv('DT_AMD_STEP_IN_STEP', '0')
+        got, _ = one_call(dm, plan, apply_rows=True)
+        check_call(got, entry(net, True), head(dm, net) + adam_tail(dm, plan, 2 | X3, whole=False))
+        assert not dm.optimizer._applied_in_step
+        monkeypatch.delenv('DT_AMD_STEP_IN_STEP')
+        monkeypatch.setenv('DT_AMD_ROWS_IN_STEP', '0')
+        got, _ = one_call(dm, plan, apply_rows=True)
+        check_call(got, entry(net), head(dm, net) + plain_tail(net, 2 | X3))
+        assert plan.emb.sparse_grads[plan.key][0].fields == -1
+        monkeypatch.delenv('DT_AMD_ROWS_IN_STEP')
+        # sample weights, float ids, a caller-owned logit buffer, an out-of-range counter
+        plan.emb.check_oob = True
+        got, logit = one_call(dm, plan, ids=idx_f, sample_weight=sw, logit_out=logit_out)
+        check_call(got, entry(net), head(dm, net, ids='idx_f', logit='logit_out', oob='oob', kind=_lib.DT_IDX_F32) +
+                   plain_tail(net, 2 | X3, w='sw'))
+        assert logit is logit_out
+        plan.emb.check_oob = False
+        with pytest.raises(ValueError, match='logit_out must be a contiguous float32'):
+            plan.run(idx, dense, y, logit_out=torch.empty(B, 2))
+        # pre-elected steps: the ids-only half ran ahead into slot 1's buffers
+        plan.preelect(idx, 1)
+        check_call(_decoded(rec, plan, dm, inputs)[0], 'dt_deepfm_preelect',
+                   ['idx', _lib.DT_IDX_I32, 'row_offset', 'vocab', B, F, 'slot1.rows', 'slot1.dedupe', slots_n, None])
+        got, _ = one_call(dm, plan, apply_rows=True, slot=1, preelected=True)
+        check_call(got, entry(net, True), head(dm, net, rows='slot1.rows', dedupe='slot1.dedupe') +
+                   adam_tail(dm, plan, 2 | X3 | PRE))
+        assert plan.emb.sparse_grads[plan.key][0].rows.data_ptr() == plan._bufs[B]['slots'][1]['rows'].data_ptr()
+        got, _ = one_call(dm, plan, slot=1, preelected=True)
+        check_call(got, entry(net), head(dm, net, rows='slot1.rows', dedupe='slot1.dedupe') + plain_tail(net, 2 | X3 | PRE))
+        with pytest.raises(_lib.DtHipError, match='a pre-elected step needs the in-step dedupe'):
+            plan.run(idx, dense, y, backward=False, slot=1, preelected=True)
+        # chained steps: this step prepares the next one (slot 2) and was prepared by the one before it (slot 1)
+        assert plan.can_chain(B)
+        got = _decoded(rec, plan, dm, inputs)
+        check_call(got[0], 'dt_deepfm_step_chains', [B, F, D, Nd, 2 | X3])
+        got, _ = one_call(dm, plan, apply_rows=True, slot=1, next_ids=(idx2, 2), prepared=True)
+        check_call(got, entry(net, True), head(dm, net, rows='slot1.rows', dedupe='slot1.dedupe') +
+                   adam_tail(dm, plan, 2 | X3 | PREP, nxt=('idx2', 'slot2.rows', 'slot2.dedupe')))
+        got, _ = one_call(dm, plan, apply_rows=True, next_ids=(idx2, 2))
+        check_call(got, entry(net, True), head(dm, net) +
+                   adam_tail(dm, plan, 2 | X3, nxt=('idx2', 'slot2.rows', 'slot2.dedupe')))
+        with pytest.raises(_lib.DtHipError, match=r'chained steps need the in-step dedupe and optimizer \(can_chain\)'):
+            plan.run(idx, dense, y, slot=1, prepared=True)
+        with pytest.raises(_lib.DtHipError, match=r'chained steps need the in-step dedupe and optimizer \(can_chain\)'):
+            plan.run(idx, dense, y, next_ids=(idx2, 2))
+        for bad in ((idx2, 1), (idx2, 0), (idx2.float(), 2), (idx2[:8], 2), (idx2.t(), 2)):
+            with pytest.raises(ValueError, match="next_ids: \\(contiguous ids like this step's, a slot of their own\\)"):
+                plan.run(idx, dense, y, apply_rows=True, slot=1, next_ids=bad)
+        assert not rec.calls
+        # evaluation mode: no running statistics, no dropout
+        dm.model.eval()
+        got, _ = one_call(dm, plan, backward=False)
+        check_call(got, entry(net), head(dm, net, dedupe=None, training=False) + plain_tail(net, 1))
+        dm.model.train()
+
+        # DT_AMD_FUSED_DEDUPE=0: no dedupe, so no in-step optimizer and no pre-election
+        dm, plan = make(net, env={'DT_AMD_FUSED_DEDUPE': '0'})
+        got, _ = one_call(dm, plan, apply_rows=True)
+        check_call(got, entry(net), head(dm, net, dedupe=None) + plain_tail(net, 2 | X3))
+        assert plan.emb.sparse_grads[plan.key][0].fields is None
+        assert not plan.can_chain(B)
+        with pytest.raises(_lib.DtHipError, match='a pre-elected step needs the in-step dedupe'):
+            plan.run(idx, dense, y, slot=1, preelected=True)
+        # the tower's matrix-core mode and the phase stamps
+        for mode, bit in (('f32', 0), ('bf16x3', X3), ('bf16', BF16)):
+            dm, plan = make(net, env={'DT_AMD_TOWER_DTYPE': mode, 'DT_AMD_STEP_STAMPS': '1'})
+            got, _ = one_call(dm, plan)
+            check_call(got, entry(net), head(dm, net) + plain_tail(net, 2 | bit | STAMPS))
+            got, _ = one_call(dm, plan, apply_rows=True)
+            check_call(got, entry(net, True), head(dm, net) + adam_tail(dm, plan, 2 | bit | STAMPS))
+            got, _ = one_call(dm, plan, backward=False)
+            check_call(got, entry(net), head(dm, net, dedupe=None) + plain_tail(net, 1))
+            plan.can_chain(B)
+            check_call(_decoded(rec, plan, dm, inputs)[0], 'dt_deepfm_step_chains', [B, F, D, Nd, 2 | bit])
+        # dropouts
+        dm, plan = make(net, embedding_dropout=0.25, dense_dropout=0.5)
+        got, _ = one_call(dm, plan, sample_weight=sw)
+        check_call(got, entry(net), head(dm, net) + plain_tail(net, 2 | X3, 0.25, 0.5, w='sw'))
+        dm.model.eval()
+        got, _ = one_call(dm, plan, backward=False)
+        check_call(got, entry(net), head(dm, net, dedupe=None, training=False) + plain_tail(net, 1))
+        # regression: the mse loss bit
+        dm, plan = make(net, task='regression')
+        got, _ = one_call(dm, plan, backward=False)
+        check_call(got, entry(net), head(dm, net, dedupe=None) + plain_tail(net, 1 | MSE))
+        got, _ = one_call(dm, plan, apply_rows=True)
+        check_call(got, entry(net, True), head(dm, net) + adam_tail(dm, plan, 2 | MSE | X3))
+        monkeypatch.setattr(layers, 'DENSE_GRAD_MAX_ELEMS', 1 << 22)
+
+    # the sharded split (DeepFM only): the step's kernels on the received rows, one rank
+    class OneRank:
+        world_size, rank = 1, 0
+
+        @staticmethod
+        def field_bounds(F):
+            return [(0, F)]
+    monkeypatch.setattr(layers, 'DENSE_GRAD_MAX_ELEMS', 0)
+    dm, plan = make(DEEPFM, env={'DT_AMD_STEP_STAMPS': '1'})
+    bn = plan.bn
+    for part, phases in ((0, 2 | X3 | STAMPS), (_lib.DT_STEP_SKIP_FINISH, 2 | _lib.DT_STEP_SKIP_FINISH | X3 | STAMPS),
+                         (_lib.DT_STEP_FINISH_ONLY, 2 | _lib.DT_STEP_FINISH_ONLY)):
+        plan.sharded_core(B, dense, y, OneRank, sample_weight=sw, part=part)
+        got = _decoded(rec, plan, dm, inputs)
+        assert len(got) == 1
+        check_call(got[0], 'dt_deepfm_train_step',
+                   ['sharded.iota', _lib.DT_IDX_I32, 'sharded.emb_T', 'sharded.zero_off', 'sharded.fb_vocab', 'dense', 'y',
+                    B, F, D, Nd, 'w_lin', 'gamma', 'beta', 'mean', 'var', float(bn.epsilon), float(bn.momentum),
+                    'W1|flat_params', 'b1', 'W2', 'b2', 'dense_logit.kernel', 'out.kernel', 'out.bias', 'logit',
+                    'sharded.rows_dummy', 'grad_rows', 'accum', 'ws', None, None, 0, 1.0, 1, phases, 0.0, 'drop_seed', 0.0,
+                    'sw', None])
+        assert dm.model._dt_sharded_step
