@@ -756,10 +756,16 @@ def test_chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_
     `FusedDeepFM.run(next_ids=..., prepared=...)` (eager: no graph) must leave the tables, slots and dense parameters of
     four plain `train_step`s — with duplicate ids (vocab 40: almost every lookup is a segment member), out-of-range ids and a
     ragged last tile (B = 1000)."""
+    chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_mode, 26, 13, 16)
+
+
+def chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_mode, F, Nd, D):
+    """the body of test_chained_steps_equal_plain_steps at any (F, Nd, D) the chain takes (tests/test_fused_domain_gpu.py runs
+    it at the corners of the step's domain)"""
     from deeptables_amd.models import layers as L, deepnets
     monkeypatch.setattr(L, 'DENSE_GRAD_MAX_ELEMS', 0)
     extra = dict(nets=deepnets.DCN, cross_params={'num_cross_layer': 5}) if net == 'DCN' else {}
-    F, Nd, D = 26, 13, 16
+    key = f'd{D}'
     plain, cats = build(F, Nd, D, vocab=vocab, **extra)
     chained, _ = build(F, Nd, D, vocab=vocab, **extra)
     plan = chained.fused_plan()
@@ -773,10 +779,10 @@ def test_chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_
         idx, dense, y = batch(cats, Nd, B, seed=70 + s)
         if s == 2:
             idx[::13, 4] = vocab + 999                       # out-of-range ids: zero row, no update
-        steps.append((idx.to(torch.int32).to(dev), dense.to(dev), y.to(dev)))
+        steps.append((idx.to(torch.int32).to(dev), dense.to(dev) if Nd else None, y.to(dev)))
     plain.model.train(); chained.model.train()
     for idx, dense, y in steps:
-        plain.train_step([idx, dense], y)
+        plain.train_step([idx, dense] if Nd else [idx], y)
     opt = chained.optimizer
     for s, (idx, dense, y) in enumerate(steps):
         nxt = (steps[s + 1][0], s + 1) if s + 1 < len(steps) else None
@@ -787,7 +793,7 @@ def test_chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_
     assert plain.optimizer.t == chained.optimizer.t == 4
     for (n0, p0), (n1, p1) in zip(plain.model.named_parameters(), chained.model.named_parameters()):
         assert n0 == n1 and (p0 - p1).abs().max().item() <= 2e-6, (n0, (p0 - p1).abs().max().item())
-    ta, tb = plain.optimizer._st(plain.fused_plan().emb.tables['d16'], rows=True), opt._st(plan.emb.tables['d16'], rows=True)
+    ta, tb = plain.optimizer._st(plain.fused_plan().emb.tables[key], rows=True), opt._st(plan.emb.tables[key], rows=True)
     assert (ta['m'] - tb['m']).abs().max().item() <= 1e-6 * max(1.0, ta['m'].abs().max().item())
     # a step that cannot be chained says so instead of running prepared on nothing
     from deeptables_amd import _lib

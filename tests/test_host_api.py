@@ -526,3 +526,41 @@ def test_dedupe_layout_and_chain_queries_need_no_gpu():
     assert lib.dt_deepfm_step_chains(8192, F, 16, 13, 2 | x3 | _lib.DT_STEP_SKIP_FINISH) == 0
     assert lib.dt_deepfm_step_chains(8193, F, 16, 13, 2 | x3) == 0                  # beyond the register-resident election
     assert lib.dt_deepfm_step_chains(8192, F, 8, 13, 2 | x3) == 1 and lib.dt_deepfm_step_chains(8192, 200, 16, 13, 2 | x3) == 0
+
+
+def test_fused_domain_corners_are_what_the_library_accepts():
+    """the corner table of tests/test_fused_domain_gpu.py against the library's own predicates (no launch): every corner runs
+    the fused step rather than the layer path, the first shape past each limit is refused, and the chain (split-bf16 tile,
+    CP <= 512, B <= 8192) is offered exactly where it should be"""
+    from deeptables_amd import _lib
+    from tests import test_fused_domain_gpu as T
+    lib = _lib.lib()
+    H1, H2 = T.H1, T.H2
+    for F, D, Nd in T.DEEPFM_CORNERS:
+        assert lib.dt_deepfm_supported(1, F, D, Nd, H1, H2) == 1, (F, D, Nd)
+        assert lib.dt_deepfm_supported(8193, F, D, Nd, H1, H2) == 1, (F, D, Nd)
+    for F, D, Nd, L in T.DCN_CORNERS:
+        assert lib.dt_dcn_supported(1, F, D, Nd, H1, H2, L) == 1, (F, D, Nd, L)
+        for L_past in T.DCN_PAST_L:
+            assert lib.dt_dcn_supported(1, F, D, Nd, H1, H2, L_past) == 0, (F, D, Nd, L_past)
+    for F, D, Nd in T.DCN_REFUSED:
+        assert lib.dt_deepfm_supported(1, F, D, Nd, H1, H2) == 1
+        assert not any(lib.dt_dcn_supported(1, F, D, Nd, H1, H2, L) for L in range(1, 9)), (F, D, Nd)
+    for what, (F, D, Nd) in T.DEEPFM_PAST.items():
+        assert lib.dt_deepfm_supported(1, F, D, Nd, H1, H2) == 0, what
+        assert lib.dt_dcn_supported(1, F, D, Nd, H1, H2, 1) == 0, what
+    # each past-the-limit shape is one step beyond an accepted one
+    assert lib.dt_deepfm_supported(1, 1, 64, 0, H1, H2) == lib.dt_deepfm_supported(1, 1, 16, 0, H1, H2) == 1
+    assert lib.dt_deepfm_supported(1, 128, 4, 0, H1, H2) == lib.dt_deepfm_supported(1, 1, 4, 64, H1, H2) == 1
+    assert lib.dt_deepfm_supported(1, 32, 16, 32, H1, H2) == 1
+    # the corners the GPU tests hold to the fp32 class in bf16x3 mode are exactly those past the split tile's CP = 512
+    wide = [c for c in T.DEEPFM_CORNERS if T.cp_of(*c) > 512]
+    assert wide and all(T.cp_of(*c) == 576 for c in wide) and (32, 16, 32) in wide
+    x3, bf16 = _lib.DT_STEP_TOWER_X3, _lib.DT_STEP_TOWER_BF16
+    for F, D, Nd in T.DEEPFM_CORNERS + [c[:3] for c in T.DCN_CORNERS]:
+        narrow = T.cp_of(F, D, Nd) <= 512
+        for flag in (x3, bf16):
+            assert lib.dt_deepfm_step_chains(8192, F, D, Nd, 2 | flag) == int(narrow), (F, D, Nd, flag)
+            assert lib.dt_deepfm_step_chains(1, F, D, Nd, 2 | flag) == int(narrow), (F, D, Nd, flag)
+            assert lib.dt_deepfm_step_chains(8193, F, D, Nd, 2 | flag) == 0, (F, D, Nd, flag)
+        assert lib.dt_deepfm_step_chains(8192, F, D, Nd, 2) == 0                  # exact-fp32 tower
