@@ -160,6 +160,21 @@ SIGNATURES = {
                                         _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr, _c_f32, _ptr,
                                         _ptr, _ptr, _c_int, _ptr, _c_f32, _c_f32, _c_f32, _c_f32,
                                         _ptr, _ptr, _ptr, _c_i64, _c_f32, _ptr, _ptr, _ptr, _ptr]),
+    # fused DeepFM / DCN inference (csrc/infer_x3.h)
+    'dt_deepfm_infer_supported': (_c_int, [_c_int] * 6),
+    'dt_dcn_infer_supported': (_c_int, [_c_int] * 7),
+    'dt_deepfm_infer_workspace_bytes': (_c_i64, [_c_int] * 3),
+    'dt_dcn_infer_workspace_bytes': (_c_i64, [_c_int] * 4),
+    'dt_deepfm_infer_prepare': (_c_int, [_c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _c_int, _c_int,
+                                         _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr,
+                                         _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_dcn_infer_prepare': (_c_int, [_c_int, _c_int, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _c_int,
+                                      _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr,
+                                      _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_deepfm_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr,
+                                 _c_int, _ptr]),
+    'dt_dcn_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr,
+                              _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -171,6 +186,7 @@ DT_STEP_PREELECTED = 0x100
 DT_STEP_TOWER_BF16 = 0x200
 DT_STEP_STAMPS = 0x400
 DT_STEP_PREPARED = 0x800
+DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)

@@ -1641,6 +1641,7 @@ __global__ __launch_bounds__(256) void k_mlp_fwd3(const float* __restrict__ X, M
 }
 
 #include "tower_x3.h"
+#include "infer_x3.h"
 
 // E: weight gradients on 64x128 macro tiles = 2x4 MFMA tiles whose rows / columns INTERLEAVE (tile (t,u) holds outputs
 // (2i+t, 4j+u)), so ONE 8-byte load per lane feeds two tiles' worth of A and ONE 16-byte load four tiles' worth of B:
@@ -3222,4 +3223,134 @@ extern "C" int dt_dcn_train_step(
                             bn_moving_mean, bn_moving_var, bn_eps, bn_momentum, W1, b1, W2, b2, w3, w_out, b_out, logit_out,
                             rows_out, grad_rows, accum, workspace, oob_count, dedupe_ws, dedupe_slots, 1.0f, 0, phases,
                             embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, cross_w, cross_b, L);
+}
+
+// ---- DeepFM / DCN inference (infer_x3.h): one k_infer launch per batch over the layouts one k_infer_prep launch wrote ----
+static bool infer_tower_ok(int H1, int H2, int cells) {
+    return H1 >= 1 && H1 <= kH1 && H2 >= 1 && H2 <= kH2 && (cells & ~3) == 0;
+}
+
+extern "C" int dt_deepfm_infer_supported(int F, int D, int Nd, int H1, int H2, int cells) {
+    DeepFmDims dm; int lpr;
+    return (infer_tower_ok(H1, H2, cells) && deepfm_dims(1, F, D, Nd, &dm, &lpr) &&
+            infer_lds_bytes(dm.CP, false) <= 160 * 1024) ? 1 : 0;
+}
+
+extern "C" int dt_dcn_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int L) {
+    DeepFmDims dm; int lpr;
+    return (infer_tower_ok(H1, H2, cells) && L >= 1 && L <= kCrossMax && deepfm_dims(1, F, D, Nd, &dm, &lpr) &&
+            infer_lds_bytes(dm.CP, true) <= 160 * 1024) ? 1 : 0;
+}
+
+extern "C" int64_t dt_deepfm_infer_workspace_bytes(int F, int D, int Nd) {
+    DeepFmDims dm; int lpr;
+    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr)) return -1;
+    return infer_ws_layout(dm.CP, 0).total * (int64_t)sizeof(float);
+}
+
+extern "C" int64_t dt_dcn_infer_workspace_bytes(int F, int D, int Nd, int L) {
+    DeepFmDims dm; int lpr;
+    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr) || L < 1 || L > kCrossMax) return -1;
+    return infer_ws_layout(dm.CP, L).total * (int64_t)sizeof(float);
+}
+
+static int infer_prepare(const char* what, int F, int D, int Nd, InferPrepArgs a, int cells, void* workspace, void* stream) {
+    DeepFmDims dm; int lpr;
+    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
+    DT_UNSUPPORTED(!infer_tower_ok(a.H1, a.H2, cells), "%s: tower %d x %d, cells %d (H1 <= %d, H2 <= %d, cells: BN bits 0 / 1)",
+                   what, a.H1, a.H2, cells, kH1, kH2);
+    DT_REQUIRE(a.ld1 >= a.H1 && a.ld2 >= a.H2, "%s: leading dimensions ld1=%d ld2=%d below the widths", what, a.ld1, a.ld2);
+    DT_REQUIRE(a.mm && a.mv && a.W1 && a.W2 && a.w3 && workspace && (a.L > 0 || (a.wlin && a.wout)), "%s: null pointer", what);
+    DT_REQUIRE(a.L == 0 || (a.cw && a.cb_), "%s: null cross weights", what);
+    for (int i = 0; i < 2; ++i) {
+        if (cells & (1 << i)) {
+            DT_REQUIRE(a.cm[i] && a.cv[i], "%s: tower cell %d has batch norm but no moving statistics", what, i + 1);
+        } else {
+            a.cm[i] = nullptr;
+        }
+    }
+    DT_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", what);
+    const int items = max((dm.CP >> 5) * 512, (2 * a.L + 1) * dm.CP);
+    hipLaunchKernelGGL(k_infer_prep, dim3(ceil_div(items, 256)), dim3(256), 0, as_stream(stream), dm, a,
+                       reinterpret_cast<float*>(workspace));
+    return launch_status(what);
+}
+
+extern "C" int dt_deepfm_infer_prepare(int F, int D, int Nd, const float* w_lin, const float* bn_gamma, const float* bn_beta,
+                                       const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1,
+                                       int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                                       const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
+                                       float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
+                                       const float* c2_var, float c2_eps, const float* w3, const float* w_out,
+                                       const float* b_out, void* workspace, void* stream) {
+    const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
+                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
+                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0};
+    return infer_prepare("dt_deepfm_infer_prepare", F, D, Nd, a, cells, workspace, stream);
+}
+
+extern "C" int dt_dcn_infer_prepare(int F, int D, int Nd, const float* cross_w, const float* cross_b, int L,
+                                    const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
+                                    float bn_eps, const float* W1, int ld1, int H1, const float* b1, const float* W2, int ld2,
+                                    int H2, const float* b2, int cells, const float* c1_gamma, const float* c1_beta,
+                                    const float* c1_mean, const float* c1_var, float c1_eps, const float* c2_gamma,
+                                    const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
+                                    const float* w3, const float* w_out, const float* b_out, void* workspace, void* stream) {
+    DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer_prepare: %d cross layers (1..%d)", L, kCrossMax);
+    const InferPrepArgs a{nullptr, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
+                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
+                          {c1_eps, c2_eps}, w3, w_out, b_out, cross_w, cross_b, L};
+    return infer_prepare("dt_dcn_infer_prepare", F, D, Nd, a, cells, workspace, stream);
+}
+
+static int infer_run(const char* what, const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                     const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int L, const void* workspace,
+                     float* logit_out, float* out, int* oob_count, int flags, void* stream) {
+    DT_REQUIRE(B >= 0, "%s: B=%d", what, B);
+    DeepFmDims dm; int lpr;
+    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
+    DT_REQUIRE((flags & ~(DT_INFER_SIGMOID | DT_INFER_TOWER_BF16)) == 0, "%s: flags 0x%x", what, flags);
+    DT_REQUIRE(idx_kind == DT_IDX_F32 || idx_kind == DT_IDX_I32, "%s: idx_kind %d", what, idx_kind);
+    if (B == 0) return DT_OK;
+    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "%s: null pointer", what);
+    DT_REQUIRE(Nd == 0 || dense, "%s: dense is null", what);
+    DT_REQUIRE(((uintptr_t)table | (uintptr_t)workspace) % 16 == 0, "%s: table / workspace must be 16-byte aligned", what);
+    dm.B = B;
+    const bool dcn = L > 0, one = (flags & DT_INFER_TOWER_BF16) != 0;
+    const InferIo io{idx, idx_kind, reinterpret_cast<const float4*>(table), row_offset, vocab, dense, logit_out, out, oob_count,
+                     (flags & DT_INFER_SIGMOID) ? 1 : 0};
+    const size_t lds = infer_lds_bytes(dm.CP, dcn);
+    DT_UNSUPPORTED(lds > 160 * 1024, "%s: the tile needs %zu B of LDS", what, lds);
+    const float* ws = reinterpret_cast<const float*>(workspace);
+    hipStream_t st = as_stream(stream);
+    const int tiles = ceil_div(B, kTM);
+#define DT_IL(N, LCV, ONEV)                                                                                          \
+    do {                                                                                                             \
+        hipFuncSetAttribute((const void*)k_infer<N, LCV, ONEV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_infer<N, LCV, ONEV>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);        \
+    } while (0)
+#define DT_IN(N)                                                                                                     \
+    case N:                                                                                                          \
+        if (dcn) { if (one) DT_IL(N, kCrossMax, true); else DT_IL(N, kCrossMax, false); }                            \
+        else { if (one) DT_IL(N, 0, true); else DT_IL(N, 0, false); }                                                \
+        break;
+    switch (dm.CP >> 6) { DT_IN(1) DT_IN(2) DT_IN(3) DT_IN(4) DT_IN(5) DT_IN(6) DT_IN(7) DT_IN(8) DT_IN(9) }
+#undef DT_IN
+#undef DT_IL
+    return launch_status(what);
+}
+
+extern "C" int dt_deepfm_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                               const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, const void* workspace,
+                               float* logit_out, float* out, int* oob_count, int flags, void* stream) {
+    return infer_run("dt_deepfm_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, 0, workspace, logit_out,
+                     out, oob_count, flags, stream);
+}
+
+extern "C" int dt_dcn_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                            const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int L,
+                            const void* workspace, float* logit_out, float* out, int* oob_count, int flags, void* stream) {
+    DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer: %d cross layers (1..%d)", L, kCrossMax);
+    return infer_run("dt_dcn_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, L, workspace, logit_out,
+                     out, oob_count, flags, stream);
 }

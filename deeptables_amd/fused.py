@@ -140,17 +140,17 @@ def _row_weights(sample_weight, y):
     return w
 
 
-def _step_dims(dm, net_layers):
+def _step_dims(dm, net_layers, tower=_tower_widths):
     """(batch hint, F, D, Nd), the leading arguments of dt_*_supported, when the graph passes the checks both fused steps
-    share — fixed-length columns, a loss the steps take, dropout rates in [0, 1), a tower of the compiled tile, the layers
-    `net_layers` besides the embedding / BN / output ones, one embedding group, at most one continuous column —
-    else None"""
+    share — fixed-length columns, a loss the steps take, dropout rates in [0, 1), a tower of the compiled tile (`tower`:
+    the predicate of the steps or, for the inference plans, _infer_tower), the layers `net_layers` besides the embedding /
+    BN / output ones, one embedding group, at most one continuous column — else None"""
     c = dm.config
     if dm.var_len_categorical_columns or _step_loss(dm) is None:
         return None
     if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
         return None
-    if _tower_widths(c.dnn_params) is None:
+    if tower(c.dnn_params) is None:
         return None
     L = dm.model.layers_by_name
     if any(n not in L for n in ('emb_categorical_vars_all', 'bn_concat_emb_dense', 'task_output') + tuple(net_layers)):
@@ -626,4 +626,208 @@ def make_fused_plan(dm):
         return FusedDeepFM(dm)
     if FusedDCN.eligible(dm):
         return FusedDCN(dm)
+    return None
+
+
+# ---- inference -----------------------------------------------------------------------------------------------------------
+def predict_enabled():
+    """the inference plans are on unless DT_AMD_FUSED=0 or DT_AMD_FUSED_PREDICT=0"""
+    return fused_enabled() and os.environ.get('DT_AMD_FUSED_PREDICT', '1') != '0'
+
+
+def _infer_tower(dnn_params):
+    """(H1, H2, cells) when the tower is one the inference kernels take — two relu cells whose widths fit the compiled
+    128 x 64 tile, as for the steps, but with any dropout rate (the identity at inference) and with or without batch norm
+    (Dense without bias -> BatchNormalization -> relu, deepnets.py:401-427; at inference a per-column affine map):
+    cells = bit i set when cell i + 1 has one — else None"""
+    hu = tuple(tuple(h) for h in dnn_params.get('hidden_units', ()))
+    if len(hu) != 2 or any(len(h) != 3 for h in hu):
+        return None
+    (h1, d1, bn1), (h2, d2, bn2) = hu
+    if not (0 <= float(d1 or 0) < 1 and 0 <= float(d2 or 0) < 1) or not (1 <= int(h1) <= TILE_H1 and 1 <= int(h2) <= TILE_H2):
+        return None
+    if dnn_params.get('activation', 'relu') != 'relu' or dnn_params.get('custom_dnn_fn') is not None:
+        return None
+    return int(h1), int(h2), (1 if bn1 else 0) | (2 if bn2 else 0)
+
+
+def _infer_flags(dm):
+    """dt_*_infer's flags: the output activation (sigmoid for the binary task) and the tower's precision mode
+    (`_tower_mfma_flag`: 'bf16' -> DT_INFER_TOWER_BF16; 'bf16x3' and 'f32' both run the six-product forward, which is in the
+    fp32 class)"""
+    mode = _tower_mfma_flag(dm.config.dnn_params)
+    return (_lib.DT_INFER_SIGMOID if dm.output_activation == 'sigmoid' else 0) | \
+        (_lib.DT_INFER_TOWER_BF16 if mode == _lib.DT_STEP_TOWER_BF16 else 0)
+
+
+class InferDeepFM:
+    """Inference plan for the DeepFM graph: `prepare` writes the weight layouts (one launch, csrc/infer_x3.h k_infer_prep)
+    from the parameters as they are at that moment, `infer` scores one batch (one launch, k_infer).  Needs nothing of the
+    training plan: it builds no FusedDeepFM, re-homes no parameter and touches no optimizer state; every pointer, leading
+    dimension, moving statistic and epsilon is read in `prepare`, so it follows a training plan that re-homes the tower
+    afterwards.  InferDCN runs the same code; the net-specific parts are marked 'net:'."""
+
+    # net: entry points dt_<PREFIX>_infer*, the tower's layer prefix, the layers besides embedding / BN / output
+    NETS = FusedDeepFM.NETS
+    PREFIX = 'deepfm'
+    CELL = 'dnn'
+    NET_LAYERS = ('linear_logit', 'dense_logit_dnn_nets', 'fm_layer')
+
+    @classmethod
+    def _graph_ok(cls, dm):
+        c = dm.config
+        return set(c.nets) == cls.NETS and len(c.nets) == 3 and c.stacking_op == consts.STACKING_OP_ADD
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            if not cls._graph_ok(dm) or getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            tower = _infer_tower(c.dnn_params)
+            dims = _step_dims(dm, (f'{cls.CELL}_dense_1', f'{cls.CELL}_dense_2') + cls.NET_LAYERS, _infer_tower)
+            return dims is not None and bool(cls._supported(dm, dims[1:], tower))
+        except Exception:
+            return False
+
+    @classmethod
+    def _supported(cls, dm, dims, tower):
+        return lib().dt_deepfm_infer_supported(*dims, *tower)
+
+    def _net_layers(self, L):
+        self.lin = L['linear_logit']
+        self.dl = L['dense_logit_dnn_nets']
+
+    def _dims(self):
+        return self.F, self.D, self.Nd
+
+    def _net_args(self):
+        """dt_*_infer_prepare's arguments between Nd and bn_gamma"""
+        return (ptr(self.lin.kernel),)
+
+    def _head_weights(self):
+        """(w3, w_out) of dt_*_infer_prepare"""
+        return ptr(self.dl.kernel), ptr(self.out.kernel)
+
+    # -------------------------------------------------------------------------------------------------------------------
+    def __init__(self, dm):
+        self.dm = dm
+        L = dm.model.layers_by_name
+        self.emb = L['emb_categorical_vars_all']
+        self.bn = L['bn_concat_emb_dense']
+        self.cells = [(L[f'{self.CELL}_dense_{i}'], L.get(f'{self.CELL}_bn_{i}')) for i in (1, 2)]
+        self.out = L['task_output']
+        self.D = self.emb.groups[0][0]
+        self.F = len(self.emb.input_dims)
+        self.Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
+        self.key = f'd{self.D}'
+        self.device = self.emb.tables[self.key].device
+        self._net_layers(L)
+        nbytes = self._entry('infer_workspace_bytes')(*self._dims())
+        if nbytes < 0:
+            raise _lib.DtHipError(f'{type(self).__name__}: unsupported shape')
+        self.ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        self.flags = 0
+
+    def _entry(self, what):
+        return getattr(lib(), f'dt_{self.PREFIX}_{what}')
+
+    def prepare(self):
+        """the current weights and moving statistics -> the workspace layouts, one launch on the current stream; also reads
+        the precision mode and the output activation (the flags of the `infer` calls that follow)"""
+        self.flags = _infer_flags(self.dm)
+        bn = self.bn
+
+        def ld(w):
+            if w.dim() != 2 or w.stride(1) != 1:
+                raise _lib.DtHipError(f'inference plan: tower kernel with strides {tuple(w.stride())}')
+            return int(w.stride(0))
+
+        def cell_bn(b):
+            if b is None:
+                return None, None, None, None, 0.0
+            return ptr(b.gamma), ptr(b.beta), ptr(b.moving_mean), ptr(b.moving_variance), float(b.epsilon)
+
+        (d1, bn1), (d2, bn2) = self.cells
+        cells = (1 if bn1 is not None else 0) | (2 if bn2 is not None else 0)
+        check(self._entry('infer_prepare')(
+            self.F, self.D, self.Nd, *self._net_args(), ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean),
+            ptr(bn.moving_variance), float(bn.epsilon), ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
+            ptr(d2.kernel), ld(d2.kernel), int(d2.kernel.shape[1]), ptr(d2.bias), cells, *cell_bn(bn1), *cell_bn(bn2),
+            *self._head_weights(), ptr(self.out.bias), ptr(self.ws), stream_ptr()), f'dt_{self.PREFIX}_infer_prepare')
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch: ids [B, F], dense [B, Nd] or None -> logit [B, 1] and, if given, out [B, 1] = the activated output
+        (contiguous float32 device buffers, e.g. row slices of one buffer for the whole call).  After `prepare`."""
+        B = idx.shape[0]
+        idx = idx.contiguous()
+        if idx.dtype not in (torch.float32, torch.int32):
+            idx = idx.to(torch.int32)
+        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
+        dense = None if dense is None else dense.to(torch.float32).contiguous()
+        for t in (logit, out):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B):
+                raise ValueError(f'infer: outputs must be contiguous float32 buffers of {B} rows')
+        check(self._entry('infer')(
+            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
+            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *self._dims(), ptr(self.ws), ptr(logit), ptr(out),
+            ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, stream_ptr()), f'dt_{self.PREFIX}_infer')
+
+    def run_batches(self, data, batch_size, activate=True, each=None):
+        """`prepare` once, then one `infer` per batch of `data` (training.TableBatches, in order) into ONE device buffer ->
+        (logits [n, 1], activated outputs [n, 1] or None).  each(logit, out, y) is called with every batch's slices."""
+        n = data.n
+        logit = torch.empty((n, 1), dtype=torch.float32, device=self.device)
+        out = torch.empty_like(logit) if activate else None
+        self.prepare()
+        r = 0
+        for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
+            b = int(ins[0].shape[0])
+            lg, o = logit[r:r + b], None if out is None else out[r:r + b]
+            self.infer(ins[0], ins[1] if len(ins) > 1 else None, lg, o)
+            if each is not None:
+                each(lg, o, yb)
+            r += b
+        return logit, out
+
+
+class InferDCN(InferDeepFM):
+    """Inference plan for the DCN graph (nets ['dcn_nets'] alone, deepnets.py:194-207): the Cross network runs on the
+    normalised tile inside the same launch."""
+
+    NETS = {'dcn_nets'}
+    PREFIX = 'dcn'
+    CELL = 'dcn'
+    NET_LAYERS = ('dcn_cross_layer',)
+
+    @classmethod
+    def _graph_ok(cls, dm):
+        return list(dm.config.nets) == ['dcn_nets'] and 'dense_logit_dcn_nets' not in dm.model.layers_by_name
+
+    @classmethod
+    def _supported(cls, dm, dims, tower):
+        nl = int(dm.model.layers_by_name['dcn_cross_layer'].num_cross_layer)
+        return lib().dt_dcn_infer_supported(*dims, *tower, nl)
+
+    def _net_layers(self, L):
+        self.cross = L['dcn_cross_layer']
+        self.nl = int(self.cross.num_cross_layer)
+
+    def _dims(self):
+        return self.F, self.D, self.Nd, self.nl
+
+    def _net_args(self):
+        return ptr(self.cross.kernel_stack), ptr(self.cross.bias_stack), self.nl
+
+    def _head_weights(self):
+        return ptr(self.out.kernel), None
+
+
+def make_inference_plan(dm):
+    if not predict_enabled() or dm.model is None:
+        return None
+    if InferDeepFM.eligible(dm):
+        return InferDeepFM(dm)
+    if InferDCN.eligible(dm):
+        return InferDCN(dm)
     return None

@@ -54,8 +54,9 @@ class DeepModel:
     def build(self, device=None):
         self.device = device or default_device()
         self.compiled_loop = None            # a captured loop holds pointers into the model / optimizer it was built on
-        if hasattr(self, '_fused_plan'):
-            del self._fused_plan
+        for plan in ('_fused_plan', '_inference_plan'):
+            if hasattr(self, plan):
+                delattr(self, plan)
         self.model = self._build_model(self.task, self.num_classes, self.config.nets, self.categorical_columns,
                                        self.continuous_columns, self.config,
                                        self.var_len_categorical_columns).to(self.device)
@@ -259,6 +260,17 @@ class DeepModel:
             from ..fused import make_fused_plan
             self._fused_plan = make_fused_plan(self)
         return self._fused_plan
+
+    def inference_plan(self):
+        """One-launch-per-batch inference plan for this graph, if the library has one (fused.make_inference_plan): what
+        `predict` and `evaluate` (and fit's validation pass) run instead of the layer-by-layer forward.  None with
+        DT_AMD_FUSED=0 or DT_AMD_FUSED_PREDICT=0."""
+        from ..fused import make_inference_plan, predict_enabled
+        if not predict_enabled() or self.model is None:
+            return None
+        if not hasattr(self, '_inference_plan'):
+            self._inference_plan = make_inference_plan(self)
+        return self._inference_plan
 
     def forward_backward(self, inputs, y, sample_weight=None, logit_out=None):
         """forward -> loss -> backward; gradients land in `.grad` / MultiColumnEmbedding.sparse_grads and stay there until
@@ -497,12 +509,20 @@ class DeepModel:
     def _evaluate_batches(self, data, batch_size, metrics):
         self.model.eval()
         losses, weights, probs = [], [], []
+        plan = self.inference_plan()
         with torch.no_grad():
-            for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
-                logit = self.model(ins)
-                losses.append(self._loss(logit, yb))
-                weights.append(yb.shape[0])
-                probs.append(self._activate(logit))
+            if plan is not None:
+                # one launch per batch into one device buffer; the loss of every batch from its slice of the logits
+                def each(logit, prob, yb):
+                    losses.append(self._loss(logit, yb))
+                    weights.append(yb.shape[0])
+                probs.append(plan.run_batches(data, batch_size, each=each)[1])
+            else:
+                for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
+                    logit = self.model(ins)
+                    losses.append(self._loss(logit, yb))
+                    weights.append(yb.shape[0])
+                    probs.append(self._activate(logit))
         w = torch.tensor(weights, dtype=torch.float32, device=self.device)
         logs = {'loss': float((torch.stack(losses) * w).sum().item() / w.sum().item())}
         yp, yt = torch.cat(probs).cpu().numpy(), data.y.cpu().numpy()
@@ -517,6 +537,11 @@ class DeepModel:
         data = training.TableBatches(X, None, self.categorical_columns, self.continuous_columns, self.device,
                                      var_len_categorical_columns=self.var_len_categorical_columns)
         model.eval()
+        plan = self.inference_plan() if model is self.model else None     # (apply()'s proxy models: the layer path)
+        if plan is not None:
+            with torch.no_grad():
+                logit, out = plan.run_batches(data, batch_size, activate=activate)
+            return (out if activate else logit).cpu().numpy()
         outs = []
         with torch.no_grad():
             for ins, _ in data.iterate(batch_size, False, drop_remainder=False):

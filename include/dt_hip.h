@@ -654,6 +654,54 @@ int dt_deepfm_train_step_adam(const void* idx, int idx_kind, float* table, const
  * SUM_OVER_BATCH_SIZE reduction of the weighted per-sample losses). */
 unsigned dt_deepfm_dropout_hash(unsigned seed, unsigned b, unsigned col);
 
+/* ---- fused DeepFM / DCN inference: ONE launch per predict batch (replaces, for the graphs dt_*_infer_supported takes, the
+ * layer-by-layer forward that the reference's DeepModel.predict / evaluate run through keras Model.predict / evaluate,
+ * deepmodel.py:134-175).  At inference BatchNormalization normalises with its moving statistics (Keras BN inference:
+ * (x - moving_mean) / sqrt(moving_variance + eps) * gamma + beta), Dropout is the identity and every row's logit depends
+ * on that row only, so a 32-row tile runs gather, linear + FM (DeepFM) or the Cross network (DCN, dcn_nets), the input BN,
+ * the two-cell tower of deepnets.py:401-427 on matrix cores, the output unit and its activation in one block.
+ *   dt_*_infer_supported: the step's field / width domain (as dt_deepfm_supported: D in {4, .., 64} a power of two,
+ *     F D / 4 <= 128, Nd <= 64, C = F D + Nd <= 544; DCN: L in 1..8) at any batch size; H1 <= 128, H2 <= 64 relu cells;
+ *     cells = the tower cells with batch norm (bit 0: cell 1, bit 1: cell 2; Dense without bias -> BN -> relu).
+ *   dt_*_infer_prepare: the weights -> workspace (dt_*_infer_workspace_bytes bytes, 16-byte aligned), one launch on
+ *     `stream`; call it again whenever a weight or moving statistic changed.  W1 [C][ld1] / W2 [H1][ld2] with leading
+ *     dimensions (contiguous, or views into wider zero-padded slabs); per cell its Dense bias (NULL: none) and, with its bit
+ *     in `cells`, its BatchNormalization's gamma / beta (NULL: 1 / 0), moving mean / variance and eps.  DeepFM: w_lin
+ *     [F + Nd] = linear_logit's kernel, w3 [H2] = dense_logit_dnn_nets' kernel, w_out / b_out = task_output's (b_out NULL:
+ *     no bias).  DCN (dcn_nets alone): cross_w / cross_b [L][C], w3 [C + H2] = task_output's kernel (cross part first),
+ *     w_out NULL (= 1), b_out = task_output's bias or NULL.
+ *   dt_*_infer: one batch of B >= 0 rows (ids as in dt_deepfm_train_step, out-of-range ids read a zero row and are counted
+ *     into *oob_count when it is given) -> logit_out [B] and, if out != NULL, out [B] = sigmoid(logit) with DT_INFER_SIGMOID
+ *     (binary task) or the logit (regression).  flags | DT_INFER_TOWER_BF16: the tower's products on plain bf16 operands
+ *     (the 1e-2 class); default: split-bf16 with six products per operand pair, the fp32 class (it also serves the 'f32'
+ *     mode).  The Cross network's scalars keep six products in both modes. */
+#define DT_INFER_SIGMOID 0x1
+#define DT_INFER_TOWER_BF16 0x2
+int dt_deepfm_infer_supported(int F, int D, int Nd, int H1, int H2, int cells);
+int dt_dcn_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int L);
+int64_t dt_deepfm_infer_workspace_bytes(int F, int D, int Nd);
+int64_t dt_dcn_infer_workspace_bytes(int F, int D, int Nd, int L);
+int dt_deepfm_infer_prepare(int F, int D, int Nd, const float* w_lin, const float* bn_gamma, const float* bn_beta,
+                            const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1, int H1,
+                            const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                            const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
+                            float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
+                            const float* c2_var, float c2_eps, const float* w3, const float* w_out, const float* b_out,
+                            void* workspace, void* stream);
+int dt_dcn_infer_prepare(int F, int D, int Nd, const float* cross_w, const float* cross_b, int L, const float* bn_gamma,
+                         const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, const float* W1,
+                         int ld1, int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                         const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
+                         float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
+                         const float* c2_var, float c2_eps, const float* w3, const float* w_out, const float* b_out,
+                         void* workspace, void* stream);
+int dt_deepfm_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                    const float* dense, int B, int F, int D, int Nd, const void* workspace, float* logit_out, float* out,
+                    int* oob_count, int flags, void* stream);
+int dt_dcn_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                 const float* dense, int B, int F, int D, int Nd, int L, const void* workspace, float* logit_out,
+                 float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

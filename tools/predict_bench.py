@@ -1,0 +1,129 @@
+# -*- coding:utf-8 -*-
+"""Times DeepModel inference on the benchmark's Criteo shape (26 categorical fields x 1 M ids, 13 continuous columns,
+D = 16, the default 128 x 64 tower) for the fused inference plan (fused.InferDeepFM: one k_infer_prep launch per call, one
+k_infer launch per batch) and for the layer-by-layer forward (DT_AMD_FUSED_PREDICT=0), at batch sizes 128 (DeepTable's
+default), 8192 and 65536.  Prints one JSON line.
+
+Both paths score the same device-resident rows (training.TableBatches) and write every batch's output into device memory;
+the timed region is what `DeepModel.predict` does after its feed is built, up to the outputs of the last batch (the host copy
+of the result is left out: it is the same for both paths).  Device events around each call, warm-up calls first, the
+median of the repeats reported (run-to-run spread as min / max).
+
+    python tools/predict_bench.py [--rows N] [--batches 128,8192,65536] [--repeats R] [--warmup W] [--paths fused,layer]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+F, VOCAB, ND, D = 26, 1_000_000, 13, 16
+
+
+def build_model(seed=0):
+    from deeptables_amd import functional
+    from deeptables_amd.models import DeepModel, ModelConfig, deepnets
+    from deeptables_amd.models.metainfo import CategoricalColumn, ContinuousColumn
+    functional.set_seed(seed)
+    conf = ModelConfig(nets=deepnets.DeepFM, fixed_embedding_dim=True, embeddings_output_dim=D, embedding_dropout=0,
+                       metrics=[])
+    cats = [CategoricalColumn(f'C{i}', VOCAB, D) for i in range(F)]
+    conts = [ContinuousColumn('input_continuous_all', [f'I{j}' for j in range(ND)])]
+    dm = DeepModel('binary', 2, conf, cats, conts)
+    dm.build()
+    return dm
+
+
+def make_feed(dm, n, seed=1):
+    from deeptables_amd import training
+
+    class _Frame:                       # training.TableBatches reads X['cat'] / X[column name] of a non-DataFrame
+        def __init__(self, d):
+            self.d = d
+
+        def __len__(self):
+            return n
+
+        def __getitem__(self, k):
+            return self.d[k]
+    g = np.random.default_rng(seed)
+    X = _Frame({'cat': g.integers(0, VOCAB, (n, F)), 'input_continuous_all': g.standard_normal((n, ND)).astype(np.float32)})
+    return training.TableBatches(X, None, dm.categorical_columns, dm.continuous_columns, dm.device, resident=True)
+
+
+def fused_call(dm, data, B):
+    plan = dm.inference_plan()
+    return lambda: plan.run_batches(data, B)[1]
+
+
+def layer_call(dm, data, B):
+    out = torch.empty((data.n, 1), dtype=torch.float32, device=dm.device)
+
+    def run():
+        r = 0
+        with torch.no_grad():
+            for ins, _ in data.iterate(B, False, drop_remainder=False):
+                o = torch.sigmoid(dm.model(ins))
+                out[r:r + o.shape[0]].copy_(o)
+                r += o.shape[0]
+        return out
+    return run
+
+
+def time_call(fn, warmup, repeats):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(repeats):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rows', type=int, default=262144)
+    ap.add_argument('--batches', default='128,8192,65536')
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--paths', default='fused,layer')
+    a = ap.parse_args()
+    dm = build_model()
+    dm.model.eval()
+    if dm.inference_plan() is None:
+        raise SystemExit('the benchmark graph has no inference plan')
+    data = make_feed(dm, a.rows)
+    res = {'metric': 'predict_rows_per_s', 'shape': {'fields': F, 'vocab': VOCAB, 'dense': ND, 'D': D, 'tower': [128, 64]},
+           'rows': a.rows, 'repeats': a.repeats, 'warmup': a.warmup}
+    outs = {}
+    for path in a.paths.split(','):
+        res[path] = {}
+        for B in [int(b) for b in a.batches.split(',')]:
+            os.environ['DT_AMD_FUSED_PREDICT'] = '1' if path == 'fused' else '0'
+            fn = fused_call(dm, data, B) if path == 'fused' else layer_call(dm, data, B)
+            ms = time_call(fn, a.warmup, a.repeats)
+            med = statistics.median(ms)
+            res[path][str(B)] = {'rows_per_s': a.rows / (med * 1e-3), 'ms_median': med, 'ms_min': min(ms), 'ms_max': max(ms)}
+            outs[(path, B)] = fn().clone()
+    os.environ.pop('DT_AMD_FUSED_PREDICT', None)
+    if 'fused' in res and 'layer' in res:
+        res['speedup'] = {b: res['fused'][b]['rows_per_s'] / res['layer'][b]['rows_per_s'] for b in res['fused'] if b in res['layer']}
+        res['max_abs_diff'] = max(float((outs[('fused', B)] - outs[('layer', B)]).abs().max())
+                                  for (p, B) in outs if p == 'fused' and ('layer', B) in outs)
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
