@@ -175,6 +175,14 @@ SIGNATURES = {
                                  _c_int, _ptr]),
     'dt_dcn_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr,
                               _ptr, _c_int, _ptr]),
+    # ... for every subset of {linear, fm_nets, dnn_nets}: dt_deepfm_infer*'s arguments with the DT_NET_* mask after Nd
+    'dt_stack_infer_supported': (_c_int, [_c_int] * 7),
+    'dt_stack_infer_workspace_bytes': (_c_i64, [_c_int] * 4),
+    'dt_stack_infer_prepare': (_c_int, [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _c_int,
+                                        _c_int, _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr,
+                                        _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_stack_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr,
+                                _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -187,6 +195,7 @@ DT_STEP_TOWER_BF16 = 0x200
 DT_STEP_STAMPS = 0x400
 DT_STEP_PREPARED = 0x800
 DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
+DT_NET_LINEAR, DT_NET_FM, DT_NET_DNN = 0x1, 0x2, 0x4
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)

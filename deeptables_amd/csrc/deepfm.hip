@@ -3225,7 +3225,8 @@ extern "C" int dt_dcn_train_step(
                             embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, cross_w, cross_b, L);
 }
 
-// ---- DeepFM / DCN inference (infer_x3.h): one k_infer launch per batch over the layouts one k_infer_prep launch wrote ----
+// ---- DeepFM / DCN / net-stack inference (infer_x3.h): one k_infer (or, without a tower, k_infer_sparse) launch per batch
+//      over the layouts one k_infer_prep launch wrote ----
 static bool infer_tower_ok(int H1, int H2, int cells) {
     return H1 >= 1 && H1 <= kH1 && H2 >= 1 && H2 <= kH2 && (cells & ~3) == 0;
 }
@@ -3245,24 +3246,29 @@ extern "C" int dt_dcn_infer_supported(int F, int D, int Nd, int H1, int H2, int 
 extern "C" int64_t dt_deepfm_infer_workspace_bytes(int F, int D, int Nd) {
     DeepFmDims dm; int lpr;
     if (!deepfm_dims(1, F, D, Nd, &dm, &lpr)) return -1;
-    return infer_ws_layout(dm.CP, 0).total * (int64_t)sizeof(float);
+    return infer_ws_layout(dm.CP, 0, kNetAll).total * (int64_t)sizeof(float);
 }
 
 extern "C" int64_t dt_dcn_infer_workspace_bytes(int F, int D, int Nd, int L) {
     DeepFmDims dm; int lpr;
     if (!deepfm_dims(1, F, D, Nd, &dm, &lpr) || L < 1 || L > kCrossMax) return -1;
-    return infer_ws_layout(dm.CP, L).total * (int64_t)sizeof(float);
+    return infer_ws_layout(dm.CP, L, DT_NET_DNN).total * (int64_t)sizeof(float);
 }
 
 static int infer_prepare(const char* what, int F, int D, int Nd, InferPrepArgs a, int cells, void* workspace, void* stream) {
     DeepFmDims dm; int lpr;
     DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
-    DT_UNSUPPORTED(!infer_tower_ok(a.H1, a.H2, cells), "%s: tower %d x %d, cells %d (H1 <= %d, H2 <= %d, cells: BN bits 0 / 1)",
-                   what, a.H1, a.H2, cells, kH1, kH2);
-    DT_REQUIRE(a.ld1 >= a.H1 && a.ld2 >= a.H2, "%s: leading dimensions ld1=%d ld2=%d below the widths", what, a.ld1, a.ld2);
-    DT_REQUIRE(a.mm && a.mv && a.W1 && a.W2 && a.w3 && workspace && (a.L > 0 || (a.wlin && a.wout)), "%s: null pointer", what);
+    const bool tower = (a.nets & DT_NET_DNN) != 0, lin = (a.nets & DT_NET_LINEAR) != 0;
+    if (tower) {
+        DT_UNSUPPORTED(!infer_tower_ok(a.H1, a.H2, cells), "%s: tower %d x %d, cells %d (H1 <= %d, H2 <= %d, cells: BN bits 0 / 1)",
+                       what, a.H1, a.H2, cells, kH1, kH2);
+        DT_REQUIRE(a.ld1 >= a.H1 && a.ld2 >= a.H2, "%s: leading dimensions ld1=%d ld2=%d below the widths", what, a.ld1, a.ld2);
+    }
+    // w_out may be missing (= 1) only where the tower's vector is task_output's own kernel: DCN and the tower alone
+    DT_REQUIRE(workspace && (!tower || (a.mm && a.mv && a.W1 && a.W2 && a.w3)) && (!lin || a.wlin) &&
+               (a.L > 0 || a.nets == DT_NET_DNN || a.wout), "%s: null pointer", what);
     DT_REQUIRE(a.L == 0 || (a.cw && a.cb_), "%s: null cross weights", what);
-    for (int i = 0; i < 2; ++i) {
+    for (int i = 0; tower && i < 2; ++i) {
         if (cells & (1 << i)) {
             DT_REQUIRE(a.cm[i] && a.cv[i], "%s: tower cell %d has batch norm but no moving statistics", what, i + 1);
         } else {
@@ -3270,7 +3276,7 @@ static int infer_prepare(const char* what, int F, int D, int Nd, InferPrepArgs a
         }
     }
     DT_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", what);
-    const int items = max((dm.CP >> 5) * 512, (2 * a.L + 1) * dm.CP);
+    const int items = tower ? max((dm.CP >> 5) * 512, (2 * a.L + 1) * dm.CP) : dm.CP;
     hipLaunchKernelGGL(k_infer_prep, dim3(ceil_div(items, 256)), dim3(256), 0, as_stream(stream), dm, a,
                        reinterpret_cast<float*>(workspace));
     return launch_status(what);
@@ -3285,7 +3291,7 @@ extern "C" int dt_deepfm_infer_prepare(int F, int D, int Nd, const float* w_lin,
                                        const float* b_out, void* workspace, void* stream) {
     const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
                           {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0};
+                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0, kNetAll};
     return infer_prepare("dt_deepfm_infer_prepare", F, D, Nd, a, cells, workspace, stream);
 }
 
@@ -3299,13 +3305,13 @@ extern "C" int dt_dcn_infer_prepare(int F, int D, int Nd, const float* cross_w, 
     DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer_prepare: %d cross layers (1..%d)", L, kCrossMax);
     const InferPrepArgs a{nullptr, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
                           {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, cross_w, cross_b, L};
+                          {c1_eps, c2_eps}, w3, w_out, b_out, cross_w, cross_b, L, DT_NET_DNN};
     return infer_prepare("dt_dcn_infer_prepare", F, D, Nd, a, cells, workspace, stream);
 }
 
 static int infer_run(const char* what, const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
                      const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int L, const void* workspace,
-                     float* logit_out, float* out, int* oob_count, int flags, void* stream) {
+                     float* logit_out, float* out, int* oob_count, int flags, void* stream, int nets = kNetAll) {
     DT_REQUIRE(B >= 0, "%s: B=%d", what, B);
     DeepFmDims dm; int lpr;
     DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
@@ -3319,23 +3325,39 @@ static int infer_run(const char* what, const void* idx, int idx_kind, const floa
     const bool dcn = L > 0, one = (flags & DT_INFER_TOWER_BF16) != 0;
     const InferIo io{idx, idx_kind, reinterpret_cast<const float4*>(table), row_offset, vocab, dense, logit_out, out, oob_count,
                      (flags & DT_INFER_SIGMOID) ? 1 : 0};
-    const size_t lds = infer_lds_bytes(dm.CP, dcn);
-    DT_UNSUPPORTED(lds > 160 * 1024, "%s: the tile needs %zu B of LDS", what, lds);
     const float* ws = reinterpret_cast<const float*>(workspace);
     hipStream_t st = as_stream(stream);
+    if (!(nets & DT_NET_DNN)) {     // no tower: one wave per row, no LDS (the precision flag has nothing to act on)
+        const dim3 grid(ceil_div(B, kInferSparseRows)), block(64 * kInferSparseRows);
+        switch (nets) {
+            case DT_NET_LINEAR: hipLaunchKernelGGL((k_infer_sparse<DT_NET_LINEAR>), grid, block, 0, st, io, dm, ws); break;
+            case DT_NET_FM: hipLaunchKernelGGL((k_infer_sparse<DT_NET_FM>), grid, block, 0, st, io, dm, ws); break;
+            default: hipLaunchKernelGGL((k_infer_sparse<DT_NET_LINEAR | DT_NET_FM>), grid, block, 0, st, io, dm, ws); break;
+        }
+        return launch_status(what);
+    }
+    const size_t lds = infer_lds_bytes(dm.CP, dcn);
+    DT_UNSUPPORTED(lds > 160 * 1024, "%s: the tile needs %zu B of LDS", what, lds);
     const int tiles = ceil_div(B, kTM);
-#define DT_IL(N, LCV, ONEV)                                                                                          \
-    do {                                                                                                             \
-        hipFuncSetAttribute((const void*)k_infer<N, LCV, ONEV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_infer<N, LCV, ONEV>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);        \
+#define DT_IL(N, LCV, ONEV, NETS)                                                                                          \
+    do {                                                                                                                   \
+        hipFuncSetAttribute((const void*)k_infer<N, LCV, ONEV, NETS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_infer<N, LCV, ONEV, NETS>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);        \
     } while (0)
+#define DT_IM(N, NETS)                                                                                               \
+    case NETS:                                                                                                       \
+        if (one) DT_IL(N, 0, true, NETS); else DT_IL(N, 0, false, NETS);                                             \
+        break;
 #define DT_IN(N)                                                                                                     \
     case N:                                                                                                          \
-        if (dcn) { if (one) DT_IL(N, kCrossMax, true); else DT_IL(N, kCrossMax, false); }                            \
-        else { if (one) DT_IL(N, 0, true); else DT_IL(N, 0, false); }                                                \
+        if (dcn) { if (one) DT_IL(N, kCrossMax, true, kNetAll); else DT_IL(N, kCrossMax, false, kNetAll); }          \
+        else switch (nets) {                                                                                         \
+            DT_IM(N, DT_NET_DNN) DT_IM(N, DT_NET_DNN | DT_NET_LINEAR) DT_IM(N, DT_NET_DNN | DT_NET_FM) DT_IM(N, kNetAll) \
+        }                                                                                                            \
         break;
     switch (dm.CP >> 6) { DT_IN(1) DT_IN(2) DT_IN(3) DT_IN(4) DT_IN(5) DT_IN(6) DT_IN(7) DT_IN(8) DT_IN(9) }
 #undef DT_IN
+#undef DT_IM
 #undef DT_IL
     return launch_status(what);
 }
@@ -3353,4 +3375,47 @@ extern "C" int dt_dcn_infer(const void* idx, int idx_kind, const float* table, c
     DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer: %d cross layers (1..%d)", L, kCrossMax);
     return infer_run("dt_dcn_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, L, workspace, logit_out,
                      out, oob_count, flags, stream);
+}
+
+// ---- every Add-stacked subset of {linear, fm_nets, dnn_nets} (reference deepmodel.py:286-301: the nets' logits, Add,
+//      task_output; deepnets.py:43-66 linear, 84-96 fm_nets, 163-169 dnn_nets) through the same launches ----
+static bool stack_nets_ok(int nets) { return nets >= 1 && nets <= kNetAll; }
+
+extern "C" int dt_stack_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int nets) {
+    DeepFmDims dm; int lpr;
+    if (!stack_nets_ok(nets) || !deepfm_dims(1, F, D, Nd, &dm, &lpr)) return 0;
+    if (!(nets & DT_NET_DNN)) return 1;
+    return (infer_tower_ok(H1, H2, cells) && infer_lds_bytes(dm.CP, false) <= 160 * 1024) ? 1 : 0;
+}
+
+extern "C" int64_t dt_stack_infer_workspace_bytes(int F, int D, int Nd, int nets) {
+    DeepFmDims dm; int lpr;
+    if (!stack_nets_ok(nets) || !deepfm_dims(1, F, D, Nd, &dm, &lpr)) return -1;
+    return infer_ws_layout(dm.CP, 0, nets).total * (int64_t)sizeof(float);
+}
+
+extern "C" int dt_stack_infer_prepare(int F, int D, int Nd, int nets, const float* w_lin, const float* bn_gamma,
+                                      const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps,
+                                      const float* W1, int ld1, int H1, const float* b1, const float* W2, int ld2, int H2,
+                                      const float* b2, int cells, const float* c1_gamma, const float* c1_beta,
+                                      const float* c1_mean, const float* c1_var, float c1_eps, const float* c2_gamma,
+                                      const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
+                                      const float* w3, const float* w_out, const float* b_out, void* workspace, void* stream) {
+    DT_REQUIRE(stack_nets_ok(nets), "dt_stack_infer_prepare: nets 0x%x (a non-empty mask of DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN)", nets);
+    DT_REQUIRE(!(nets & DT_NET_LINEAR) || w_lin, "dt_stack_infer_prepare: nets 0x%x has linear but w_lin is null", nets);
+    DT_REQUIRE(!(nets & DT_NET_DNN) || (bn_mean && bn_var && W1 && W2 && w3),
+               "dt_stack_infer_prepare: nets 0x%x has dnn_nets but a tower pointer (bn_mean, bn_var, W1, W2, w3) is null", nets);
+    DT_REQUIRE(nets == DT_NET_DNN || w_out, "dt_stack_infer_prepare: nets 0x%x needs w_out (null only for dnn_nets alone)", nets);
+    const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
+                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
+                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0, nets};
+    return infer_prepare("dt_stack_infer_prepare", F, D, Nd, a, cells, workspace, stream);
+}
+
+extern "C" int dt_stack_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                              const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int nets, const void* workspace,
+                              float* logit_out, float* out, int* oob_count, int flags, void* stream) {
+    DT_REQUIRE(stack_nets_ok(nets), "dt_stack_infer: nets 0x%x (a non-empty mask of DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN)", nets);
+    return infer_run("dt_stack_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, 0, workspace, logit_out,
+                     out, oob_count, flags, stream, nets);
 }

@@ -1,5 +1,7 @@
 // infer_x3.h — DeepFM / DCN inference as ONE launch per batch (dt_deepfm_infer / dt_dcn_infer), plus the launch that writes
 // the weight layouts it reads (dt_*_infer_prepare).  Included by deepfm.hip inside namespace dt, after tower_x3.h.
+// dt_stack_infer runs the same launches for every subset of {linear, fm_nets, dnn_nets}: k_infer with the absent terms
+// compiled out (template NETS) when there is a tower, k_infer_sparse (end of this file; no tile, no LDS) when there is none.
 //
 // At inference nothing in the graph reaches across the batch (reference deepmodel.py predict / evaluate = keras
 // Model.predict): BatchNormalization normalises with its moving statistics (a per-column affine map), Dropout is the
@@ -26,23 +28,28 @@
 #pragma once
 
 constexpr int kInferThreads = 512;
+constexpr int kNetAll = DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN;   // the DeepFM graph; DCN's layouts are those of DT_NET_DNN
 
 // the prepared weights (dt_*_infer_prepare): offsets (floats) inside the inference workspace
 struct InferWsLayout {
     int64_t w1b, w2b, bn, cell1, cell2, w3, head, wlin, cwp, total;
 };
-__host__ __device__ inline InferWsLayout infer_ws_layout(int CP, int L) {
+// nets: the DT_NET_* mask of the graph (DCN, L > 0: a tower and no `linear`, whatever else the mask says) — a region the
+// nets do not need takes no space
+__host__ __device__ inline InferWsLayout infer_ws_layout(int CP, int L, int nets) {
     InferWsLayout w;
     int64_t o = 0;
     auto take = [&](int64_t n) { int64_t r = o; o += (n + 3) & ~(int64_t)3; return r; };
-    w.w1b = take((int64_t)3 * CP * kH1 / 2);       // 3 bf16 parts of [CP][128], lane-major as X3Weights.W1B
-    w.w2b = take((int64_t)3 * kH1 * kH2 / 2);      // 3 bf16 parts of [128][64], lane-major as X3Weights.W2B
-    w.bn = take((int64_t)3 * CP);                  // input BN: mm | gamma / sqrt(mv + eps) | beta, zero beyond C
-    w.cell1 = take((int64_t)3 * kH1);              // tower cell 1: ctr | scl | sft, zero beyond H1
-    w.cell2 = take((int64_t)3 * kH2);              // tower cell 2
-    w.w3 = take(kH2);                              // the tower's output kernel (DeepFM: dense_logit, DCN: task_output's dnn part)
+    const int t = (nets & DT_NET_DNN) ? 1 : 0;     // the tower's regions
+    w.w1b = take(t * (int64_t)3 * CP * kH1 / 2);   // 3 bf16 parts of [CP][128], lane-major as X3Weights.W1B
+    w.w2b = take(t * (int64_t)3 * kH1 * kH2 / 2);  // 3 bf16 parts of [128][64], lane-major as X3Weights.W2B
+    w.bn = take(t * (int64_t)3 * CP);              // input BN: mm | gamma / sqrt(mv + eps) | beta, zero beyond C
+    w.cell1 = take(t * (int64_t)3 * kH1);          // tower cell 1: ctr | scl | sft, zero beyond H1
+    w.cell2 = take(t * (int64_t)3 * kH2);          // tower cell 2
+    w.w3 = take(t * kH2);                          // the tower's output kernel (dense_logit_dnn_nets; task_output's dnn part when
+                                                   // the tower is the only net or DCN's)
     w.head = take(4);                              // w_out, b_out
-    w.wlin = take(L > 0 ? 0 : CP);                 // DeepFM: linear_logit's kernel [F + Nd]
+    w.wlin = take((L == 0 && (nets & DT_NET_LINEAR)) ? CP : 0);    // linear_logit's kernel [F + Nd]
     w.cwp = take(L > 0 ? (int64_t)(2 * L + 1) * CP : 0);   // DCN: cross kernels | cross biases | w3c, [2 L + 1][CP], zero beyond C
     w.total = o;
     return w;
@@ -63,16 +70,24 @@ struct InferPrepArgs {
     const float *w3, *wout, *bout;    // DCN: w3 = task_output's kernel [C + H2] (cross part first), wout NULL (= 1)
     const float *cw, *cb_;            // DCN: cross kernels / biases [L][C]
     int L;
+    int nets;                         // DT_NET_* mask (DCN: DT_NET_DNN): only the regions these nets read are written
 };
 
 // one thread per item of every layout; grid-stride
 __global__ __launch_bounds__(256) void k_infer_prep(DeepFmDims dm, InferPrepArgs a, float* __restrict__ ws) {
-    const InferWsLayout wl = infer_ws_layout(dm.CP, a.L);
+    const InferWsLayout wl = infer_ws_layout(dm.CP, a.L, a.nets);
+    const int stride = (int)(gridDim.x * blockDim.x);
+    const int t0 = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (t0 == 0) {
+        ws[wl.head] = a.wout ? a.wout[0] : 1.f;
+        ws[wl.head + 1] = a.bout ? a.bout[0] : 0.f;
+    }
+    if (a.nets & DT_NET_LINEAR)
+        for (int c = t0; c < dm.CP; c += stride) ws[wl.wlin + c] = c < dm.F + dm.Nd ? a.wlin[c] : 0.f;
+    if (!(a.nets & DT_NET_DNN)) return;      // no tower: the head and the linear kernel are all k_infer_sparse reads
     __bf16* w1b = reinterpret_cast<__bf16*>(ws + wl.w1b);
     __bf16* w2b = reinterpret_cast<__bf16*>(ws + wl.w2b);
     const int64_t n1 = (int64_t)dm.CP * kH1, n2 = (int64_t)kH1 * kH2;     // elements of one part
-    const int stride = (int)(gridDim.x * blockDim.x);
-    const int t0 = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     auto split_store = [](const float (&v)[8], __bf16* dst, int64_t lo) {
         x3_b8 h, m, l;
         x3_split3(v, h, m, l);
@@ -127,13 +142,7 @@ __global__ __launch_bounds__(256) void k_infer_prep(DeepFmDims dm, InferPrepArgs
         dst[n] = ctr; dst[W + n] = scl; dst[2 * W + n] = sft;
     }
     for (int e = t0; e < kH2; e += stride) ws[wl.w3 + e] = e < a.H2 ? a.w3[(a.L > 0 ? dm.C : 0) + e] : 0.f;
-    if (t0 == 0) {
-        ws[wl.head] = a.wout ? a.wout[0] : 1.f;
-        ws[wl.head + 1] = a.bout ? a.bout[0] : 0.f;
-    }
-    if (a.L == 0) {
-        for (int c = t0; c < dm.CP; c += stride) ws[wl.wlin + c] = c < dm.F + dm.Nd ? a.wlin[c] : 0.f;
-    } else {
+    if (a.L > 0) {
         const int nv = (2 * a.L + 1) * dm.CP;
         for (int e = t0; e < nv; e += stride) {
             const int v = e / dm.CP, col = e - v * dm.CP;
@@ -162,11 +171,15 @@ __device__ __forceinline__ float infer_sum_strided(float v, int g) {
     return v;
 }
 
-template <int NCH, int LC = 0, bool ONE = false>   // LC = kCrossMax: DCN
+// NETS: the nets beside the tower (DT_NET_DNN is always in it) — `linear`'s sum and `fm_nets`' sum-square reduction are
+// compiled in per net; a graph without `linear` reads no wlin and runs no wave_sum for it, one without `fm_nets` runs none of
+// the eight infer_sum_strided chains.  The logit is (linear + fm + tower) w_out + b_out over the terms present.
+template <int NCH, int LC = 0, bool ONE = false, int NETS = kNetAll>   // LC = kCrossMax: DCN (NETS unused)
 __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims dm, const float* __restrict__ ws, int L) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int CP = 64 * NCH, NST = CP / 32, XSB = CP + 16, HF = kH1 + 4, XP = kTM * XSB;
-    const InferWsLayout wl = infer_ws_layout(CP, LC ? L : 0);
+    constexpr bool LIN = LC == 0 && (NETS & DT_NET_LINEAR), FM = LC == 0 && (NETS & DT_NET_FM);
+    const InferWsLayout wl = infer_ws_layout(CP, LC ? L : 0, NETS);      // (DCN: L > 0 leaves no room for `linear`)
     char* base = reinterpret_cast<char*>(lds);
     __bf16* xb = reinterpret_cast<__bf16*>(base);                          // [3][32][XSB]
     float* h1f = reinterpret_cast<float*>(base + (size_t)3 * XP * 2);      // [32][HF]
@@ -200,11 +213,13 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                         } else if (c == 0 && io.oob) {
                             atomicAdd(io.oob, 1);
                         }
-                        if (LC == 0) lp += ((v[t].x + v[t].y) + (v[t].z + v[t].w)) * ws[wl.wlin + f];
+                        if (LIN) lp += ((v[t].x + v[t].y) + (v[t].z + v[t].w)) * ws[wl.wlin + f];
                     }
                 }
-                if (LC == 0) {
+                if (LIN) {
                     if (lane < dm.Nd) lp += io.dense[(int64_t)m * dm.Nd + lane] * ws[wl.wlin + dm.F + lane];
+                }
+                if (FM) {
                     float4 S, Q;
                     S.x = infer_sum_strided(v[0].x + v[1].x, LPR); S.y = infer_sum_strided(v[0].y + v[1].y, LPR);
                     S.z = infer_sum_strided(v[0].z + v[1].z, LPR); S.w = infer_sum_strided(v[0].w + v[1].w, LPR);
@@ -214,10 +229,10 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                     Q.w = infer_sum_strided(v[0].w * v[0].w + v[1].w * v[1].w, LPR);
                     ts = lane < LPR ? ((S.x * S.x - Q.x) + (S.y * S.y - Q.y)) + ((S.z * S.z - Q.z) + (S.w * S.w - Q.w)) : 0.f;
                     ts = wave_sum(ts);
-                    lp = wave_sum(lp);
                 }
+                if (LIN) lp = wave_sum(lp);
             }
-            if (LC == 0 && lane == 0) lf[rr] = lp + 0.5f * ts;      // Add([linear, fm, ..]): linear + fm first
+            if ((LIN || FM) && lane == 0) lf[rr] = LIN && FM ? lp + 0.5f * ts : LIN ? lp : 0.5f * ts;   // Add([linear, fm, ..]): linear + fm first
             // the row's CP columns in 4-column pieces: embeddings (this lane's gathered pieces), dense columns, zero padding
             for (int q = lane; q < CP / 4; q += 64) {
                 floatx4 x = {0.f, 0.f, 0.f, 0.f};
@@ -387,11 +402,92 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
         }
         if (s == 0 && m < dm.B) {
             const float pt = (zp[c] + zp[kTM + c]) + (zp[2 * kTM + c] + zp[3 * kTM + c]);
-            const float zz = LC ? zc + pt            // Dense(1)(Concatenate([cross, dnn])) (deepnets.py:194-207)
-                                : lf[c] + pt;        // Add([linear, fm, dnn]) order
+            const float zz = LC ? zc + pt                      // Dense(1)(Concatenate([cross, dnn])) (deepnets.py:194-207)
+                                : (LIN || FM) ? lf[c] + pt     // Add([linear, fm, dnn]) order
+                                              : pt;            // the tower alone
             const float lg = zz * ws[wl.head] + ws[wl.head + 1];
             io.logit[m] = lg;
             if (io.out) io.out[m] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
         }
+    }
+}
+
+// ---- graphs without a tower (`linear` and / or `fm_nets`): neither bn_concat_emb_dense nor a GEMM is in the graph — both
+//      nets read the raw embedding rows — so there is no 32-row tile to build.  One wave = one row, as kernel A
+//      (k_sparse_fwd): the row's <= 128 float4 lookups stay in two registers per lane, the sums run over the wave, lane 0
+//      writes the logit and the activated output.  No LDS, no barrier.  A gather is two dependent round trips (ids / vocabulary
+//      / row offsets, then the table rows) and nothing else happens here, so the kernel lives on occupancy: 256-thread blocks
+//      (four rows, one wave per SIMD) with < 64 VGPRs and <= 80 SGPRs are admitted eight to a CU = the CU's 32 waves; B = 8192
+//      is 8192 waves = one full residency of 256 CUs, and a block that finishes frees its four slots at once (a 1024-thread
+//      block as kernel A's, which needs its 16 rows in LDS for the batch statistics, would hold them until its slowest row).
+//      Every load is unconditional from a clamped address and zeroed afterwards, as in kernel A: guarded loads close each
+//      slot's region with a full wait. ----
+constexpr int kInferSparseRows = 4;
+
+template <int NETS>
+__global__ __launch_bounds__(64 * kInferSparseRows) void k_infer_sparse(InferIo io, DeepFmDims dm, const float* __restrict__ ws) {
+    constexpr bool LIN = (NETS & DT_NET_LINEAR) != 0, FM = (NETS & DT_NET_FM) != 0;
+    const InferWsLayout wl = infer_ws_layout(dm.CP, 0, NETS);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.x * kInferSparseRows + wave;
+    if (m >= dm.B) return;
+    const int LPR = dm.D >> 2, NV = dm.F * LPR, lsh = __ffs(LPR) - 1;
+    const int c = lane & (LPR - 1);
+    const float wout = ws[wl.head], bout = ws[wl.head + 1];
+    int id[2], voc[2], fld[2];
+    int64_t roff[2];
+    bool in[2], ok[2];
+    float wf[2] = {0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int j = lane + 64 * t;
+        in[t] = j < NV;
+        fld[t] = min(j, NV - 1) >> lsh;
+        id[t] = io.kind == DT_IDX_F32 ? load_id<DT_IDX_F32>(io.idx, (int64_t)m * dm.F + fld[t])
+                                      : load_id<DT_IDX_I32>(io.idx, (int64_t)m * dm.F + fld[t]);
+        voc[t] = io.vocab[fld[t]];
+        roff[t] = io.row_offset[fld[t]];
+        if (LIN) wf[t] = ws[wl.wlin + fld[t]];
+    }
+    float dv = 0.f, wd = 0.f;      // the continuous columns' share of `linear`: lane k < Nd takes column k
+    if (LIN && lane < dm.Nd) {
+        dv = io.dense[(int64_t)m * dm.Nd + lane];
+        wd = ws[wl.wlin + dm.F + lane];
+    }
+    float4 v[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        ok[t] = in[t] && (unsigned)id[t] < (unsigned)voc[t];
+        v[t] = io.table[(ok[t] ? roff[t] + id[t] : (int64_t)0) * LPR + c];
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        if (!ok[t]) v[t] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (c == 0 && in[t] && !ok[t] && io.oob) atomicAdd(io.oob, 1);     // counted once per lookup, as in k_infer
+    }
+    float lp = 0.f, ts = 0.f;
+    if (LIN) {          // k_infer's order: the two lookups, then the continuous column
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+            if (in[t]) lp += ((v[t].x + v[t].y) + (v[t].z + v[t].w)) * wf[t];
+        lp += dv * wd;
+        lp = wave_sum(lp);
+    }
+    if (FM) {           // 0.5 sum_d ((sum_f e)^2 - sum_f e^2), k_infer's sums
+        float4 S, Q;
+        S.x = infer_sum_strided(v[0].x + v[1].x, LPR); S.y = infer_sum_strided(v[0].y + v[1].y, LPR);
+        S.z = infer_sum_strided(v[0].z + v[1].z, LPR); S.w = infer_sum_strided(v[0].w + v[1].w, LPR);
+        Q.x = infer_sum_strided(v[0].x * v[0].x + v[1].x * v[1].x, LPR);
+        Q.y = infer_sum_strided(v[0].y * v[0].y + v[1].y * v[1].y, LPR);
+        Q.z = infer_sum_strided(v[0].z * v[0].z + v[1].z * v[1].z, LPR);
+        Q.w = infer_sum_strided(v[0].w * v[0].w + v[1].w * v[1].w, LPR);
+        ts = lane < LPR ? ((S.x * S.x - Q.x) + (S.y * S.y - Q.y)) + ((S.z * S.z - Q.z) + (S.w * S.w - Q.w)) : 0.f;
+        ts = wave_sum(ts);
+    }
+    if (lane == 0) {
+        const float zz = LIN && FM ? lp + 0.5f * ts : LIN ? lp : 0.5f * ts;     // Add([linear, fm]) / the single net
+        const float lg = zz * wout + bout;
+        io.logit[m] = lg;
+        if (io.out) io.out[m] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
     }
 }

@@ -714,14 +714,13 @@ class InferDeepFM:
         self.dm = dm
         L = dm.model.layers_by_name
         self.emb = L['emb_categorical_vars_all']
-        self.bn = L['bn_concat_emb_dense']
-        self.cells = [(L[f'{self.CELL}_dense_{i}'], L.get(f'{self.CELL}_bn_{i}')) for i in (1, 2)]
         self.out = L['task_output']
         self.D = self.emb.groups[0][0]
         self.F = len(self.emb.input_dims)
         self.Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
         self.key = f'd{self.D}'
         self.device = self.emb.tables[self.key].device
+        self._tower_layers(L)
         self._net_layers(L)
         nbytes = self._entry('infer_workspace_bytes')(*self._dims())
         if nbytes < 0:
@@ -732,10 +731,12 @@ class InferDeepFM:
     def _entry(self, what):
         return getattr(lib(), f'dt_{self.PREFIX}_{what}')
 
-    def prepare(self):
-        """the current weights and moving statistics -> the workspace layouts, one launch on the current stream; also reads
-        the precision mode and the output activation (the flags of the `infer` calls that follow)"""
-        self.flags = _infer_flags(self.dm)
+    def _tower_layers(self, L):
+        self.bn = L['bn_concat_emb_dense']
+        self.cells = [(L[f'{self.CELL}_dense_{i}'], L.get(f'{self.CELL}_bn_{i}')) for i in (1, 2)]
+
+    def _tower_args(self):
+        """dt_*_infer_prepare's arguments from bn_gamma to c2_eps: the input BN and the two tower cells as they are now"""
         bn = self.bn
 
         def ld(w):
@@ -750,10 +751,16 @@ class InferDeepFM:
 
         (d1, bn1), (d2, bn2) = self.cells
         cells = (1 if bn1 is not None else 0) | (2 if bn2 is not None else 0)
+        return (ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean),
+                ptr(bn.moving_variance), float(bn.epsilon), ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
+                ptr(d2.kernel), ld(d2.kernel), int(d2.kernel.shape[1]), ptr(d2.bias), cells, *cell_bn(bn1), *cell_bn(bn2))
+
+    def prepare(self):
+        """the current weights and moving statistics -> the workspace layouts, one launch on the current stream; also reads
+        the precision mode and the output activation (the flags of the `infer` calls that follow)"""
+        self.flags = _infer_flags(self.dm)
         check(self._entry('infer_prepare')(
-            self.F, self.D, self.Nd, *self._net_args(), ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean),
-            ptr(bn.moving_variance), float(bn.epsilon), ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
-            ptr(d2.kernel), ld(d2.kernel), int(d2.kernel.shape[1]), ptr(d2.bias), cells, *cell_bn(bn1), *cell_bn(bn2),
+            self.F, self.D, self.Nd, *self._net_args(), *self._tower_args(),
             *self._head_weights(), ptr(self.out.bias), ptr(self.ws), stream_ptr()), f'dt_{self.PREFIX}_infer_prepare')
 
     def infer(self, idx, dense, logit, out=None):
@@ -823,11 +830,106 @@ class InferDCN(InferDeepFM):
         return ptr(self.out.kernel), None
 
 
+class InferStack(InferDeepFM):
+    """Inference plan for every other Add-stacked combination of 'linear', 'fm_nets' and 'dnn_nets', in any order in
+    config.nets — ModelConfig's default ['dnn_nets'], WideDeep, the plain FM model ['linear', 'fm_nets'], ... (the full
+    DeepFM graph stays InferDeepFM's): the same two launches behind the DT_NET_* mask (dt_stack_infer*).  With a tower the
+    tile kernel runs with the absent terms compiled out; without one neither bn_concat_emb_dense nor a GEMM is in the graph
+    and a gather-and-reduce kernel scores one row per wave (csrc/infer_x3.h k_infer_sparse).
+
+    The head follows deepmodel.py:286-301.  Two or more nets: every net is reduced to one logit (dense_logit_dnn_nets,
+    no bias, for the tower), Add, task_output [1, 1].  One net: no dense_logit_* layer and no Add — task_output is applied
+    to the net's output, so for ['dnn_nets'] its [H2, 1] kernel is the tower's vector and the output weight is 1."""
+
+    PREFIX = 'stack'
+    NET_BITS = {'linear': _lib.DT_NET_LINEAR, 'fm_nets': _lib.DT_NET_FM, 'dnn_nets': _lib.DT_NET_DNN}
+    FULL = _lib.DT_NET_LINEAR | _lib.DT_NET_FM | _lib.DT_NET_DNN
+
+    @classmethod
+    def _mask(cls, dm):
+        """the DT_NET_* mask of config.nets; 0 when a net is not one of the three, is named twice, or all three are there"""
+        nets = list(dm.config.nets)
+        if any(not isinstance(n, str) or n not in cls.NET_BITS for n in nets):
+            return 0
+        mask = 0
+        for n in nets:
+            if mask & cls.NET_BITS[n]:
+                return 0
+            mask |= cls.NET_BITS[n]
+        return 0 if mask == cls.FULL else mask
+
+    @classmethod
+    def _net_layer_names(cls, mask, n_nets):
+        names = ('emb_categorical_vars_all', 'task_output')
+        if mask & _lib.DT_NET_LINEAR:
+            names += ('linear_logit',)
+        if mask & _lib.DT_NET_FM:
+            names += ('fm_layer',)
+        if mask & _lib.DT_NET_DNN:
+            # (a last cell of width 1 in a graph of several nets has no dense_logit_dnn_nets: refused, as by InferDeepFM)
+            names += ('bn_concat_emb_dense', 'dnn_dense_1', 'dnn_dense_2') + (('dense_logit_dnn_nets',) if n_nets > 1 else ())
+        return names
+
+    @classmethod
+    def eligible(cls, dm):
+        """the plan's own predicate: _step_dims' checks (the training plans keep theirs as it is) with the tower and its
+        layers asked for only when 'dnn_nets' is among the nets"""
+        c = dm.config
+        try:
+            mask = cls._mask(dm)
+            if not mask or c.stacking_op != consts.STACKING_OP_ADD or getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            if dm.var_len_categorical_columns or _step_loss(dm) is None:
+                return False
+            if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
+                return False
+            tower = _infer_tower(c.dnn_params) if mask & _lib.DT_NET_DNN else (0, 0, 0)
+            if tower is None:
+                return False
+            L = dm.model.layers_by_name
+            if any(n not in L for n in cls._net_layer_names(mask, len(c.nets))):
+                return False
+            emb = L['emb_categorical_vars_all']
+            if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
+                return False
+            if tuple(L['task_output'].kernel.shape) != (tower[1] if mask == _lib.DT_NET_DNN else 1, 1):
+                return False
+            Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
+            return bool(lib().dt_stack_infer_supported(len(emb.input_dims), emb.groups[0][0], Nd, *tower, mask))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.mask = self._mask(self.dm)
+        self.bn = self.cells = None
+        if self.mask & _lib.DT_NET_DNN:
+            super()._tower_layers(L)
+
+    def _net_layers(self, L):
+        self.lin = L['linear_logit'] if self.mask & _lib.DT_NET_LINEAR else None
+        self.dl = L.get('dense_logit_dnn_nets')
+
+    def _dims(self):
+        return self.F, self.D, self.Nd, self.mask
+
+    def _net_args(self):
+        return self.mask, ptr(self.lin.kernel) if self.lin is not None else None
+
+    def _tower_args(self):
+        if self.cells is None:         # no tower: bn_gamma .. c2_eps are not read
+            return (None, None, None, None, 0.0, None, 0, 0, None, None, 0, 0, None, 0) + (None, None, None, None, 0.0) * 2
+        return super()._tower_args()
+
+    def _head_weights(self):
+        if self.mask == _lib.DT_NET_DNN:          # the tower alone: task_output's [H2, 1] kernel is its vector, w_out = 1
+            return ptr(self.out.kernel), None
+        return ptr(self.dl.kernel) if self.mask & _lib.DT_NET_DNN else None, ptr(self.out.kernel)
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    if InferDeepFM.eligible(dm):
-        return InferDeepFM(dm)
-    if InferDCN.eligible(dm):
-        return InferDCN(dm)
+    for plan in (InferDeepFM, InferDCN, InferStack):
+        if plan.eligible(dm):
+            return plan(dm)
     return None

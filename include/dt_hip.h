@@ -702,6 +702,39 @@ int dt_dcn_infer(const void* idx, int idx_kind, const float* table, const int64_
                  const float* dense, int B, int F, int D, int Nd, int L, const void* workspace, float* logit_out,
                  float* out, int* oob_count, int flags, void* stream);
 
+/* ---- fused inference for every Add-stacked subset of {linear, fm_nets, dnn_nets}: the launches of dt_deepfm_infer* with
+ * the graph's nets as a mask (replaces, for the graphs dt_stack_infer_supported takes, the layer-by-layer forward of the
+ * reference's DeepModel.predict / evaluate, deepmodel.py:134-175, over the graph deepmodel.py:286-301 assembles from
+ * deepnets.py:43-66 `linear`, 84-96 `fm_nets`, 163-169 `dnn_nets`).  nets = a non-empty mask of DT_NET_*, the order of
+ * config.nets does not matter: logit = (linear + fm + tower, over the terms present) w_out + b_out.
+ *   With DT_NET_DNN the 32-row tile kernel of dt_deepfm_infer runs with the absent terms compiled out (DT_NET_LINEAR |
+ *   DT_NET_FM | DT_NET_DNN is dt_deepfm_infer's own kernel); without it neither the input BatchNormalization nor a GEMM is
+ *   in the graph and a gather-and-reduce kernel runs, one wave per row, no LDS.  H1 / H2 / cells and every tower argument
+ *   are ignored then, DT_INFER_TOWER_BF16 has nothing to act on.
+ *   The mask sits where dt_dcn_infer* carry L (after Nd; last in _supported); the other arguments of
+ *   dt_stack_infer_prepare are dt_deepfm_infer_prepare's.  w_lin may be NULL when and only when the mask has no
+ *   DT_NET_LINEAR; bn_mean / bn_var / W1 / W2 / w3 may be NULL when and only when it has no DT_NET_DNN.  Two or more nets:
+ *   w3 [H2] = dense_logit_dnn_nets' kernel, w_out = task_output's [1][1] kernel.  One net: there is no dense_logit layer and
+ *   no Add — DT_NET_DNN alone: w3 [H2] = task_output's kernel and w_out NULL (= 1; NULL only in this case); DT_NET_LINEAR or
+ *   DT_NET_FM alone: w_out = task_output's [1][1] kernel.  b_out = task_output's bias or NULL.
+ *   dt_stack_infer's other arguments are dt_deepfm_infer's; the workspace is the one dt_stack_infer_prepare wrote for the same
+ *   mask and dims (dt_stack_infer_workspace_bytes: only the regions the nets read). */
+#define DT_NET_LINEAR 0x1
+#define DT_NET_FM 0x2
+#define DT_NET_DNN 0x4
+int dt_stack_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int nets);
+int64_t dt_stack_infer_workspace_bytes(int F, int D, int Nd, int nets);
+int dt_stack_infer_prepare(int F, int D, int Nd, int nets, const float* w_lin, const float* bn_gamma, const float* bn_beta,
+                           const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1, int H1,
+                           const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                           const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
+                           float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
+                           const float* c2_var, float c2_eps, const float* w3, const float* w_out, const float* b_out,
+                           void* workspace, void* stream);
+int dt_stack_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                   const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int nets, const void* workspace,
+                   float* logit_out, float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

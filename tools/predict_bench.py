@@ -1,15 +1,18 @@
 # -*- coding:utf-8 -*-
 """Times DeepModel inference on the benchmark's Criteo shape (26 categorical fields x 1 M ids, 13 continuous columns,
-D = 16, the default 128 x 64 tower) for the fused inference plan (fused.InferDeepFM: one k_infer_prep launch per call, one
-k_infer launch per batch) and for the layer-by-layer forward (DT_AMD_FUSED_PREDICT=0), at batch sizes 128 (DeepTable's
-default), 8192 and 65536.  Prints one JSON line.
+D = 16, the default 128 x 64 tower) for the fused inference plan (fused.InferDeepFM / InferDCN / InferStack: one
+k_infer_prep launch per call, one k_infer or k_infer_sparse launch per batch) and for the layer-by-layer forward
+(DT_AMD_FUSED_PREDICT=0), at batch sizes 128 (DeepTable's default), 8192 and 65536, for the graphs of CONFIGS: DeepFM, DCN,
+ModelConfig's default ['dnn_nets'], WideDeep ['linear', 'dnn_nets'] and the FM model ['linear', 'fm_nets'].  Both paths of
+a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
 
 Both paths score the same device-resident rows (training.TableBatches) and write every batch's output into device memory;
 the timed region is what `DeepModel.predict` does after its feed is built, up to the outputs of the last batch (the host copy
 of the result is left out: it is the same for both paths).  Device events around each call, warm-up calls first, the
 median of the repeats reported (run-to-run spread as min / max).
 
-    python tools/predict_bench.py [--rows N] [--batches 128,8192,65536] [--repeats R] [--warmup W] [--paths fused,layer]
+    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm] [--rows N] [--batches 128,8192,65536]
+                                  [--repeats R] [--warmup W] [--paths fused,layer]
 """
 import argparse
 import json
@@ -25,14 +28,16 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 F, VOCAB, ND, D = 26, 1_000_000, 13, 16
+CONFIGS = {'deepfm': ['linear', 'fm_nets', 'dnn_nets'], 'dcn': ['dcn_nets'], 'dnn': ['dnn_nets'],
+           'widedeep': ['linear', 'dnn_nets'], 'fm': ['linear', 'fm_nets']}
 
 
-def build_model(seed=0):
+def build_model(nets, seed=0):
     from deeptables_amd import functional
-    from deeptables_amd.models import DeepModel, ModelConfig, deepnets
+    from deeptables_amd.models import DeepModel, ModelConfig
     from deeptables_amd.models.metainfo import CategoricalColumn, ContinuousColumn
     functional.set_seed(seed)
-    conf = ModelConfig(nets=deepnets.DeepFM, fixed_embedding_dim=True, embeddings_output_dim=D, embedding_dropout=0,
+    conf = ModelConfig(nets=list(nets), fixed_embedding_dim=True, embeddings_output_dim=D, embedding_dropout=0,
                        metrics=[])
     cats = [CategoricalColumn(f'C{i}', VOCAB, D) for i in range(F)]
     conts = [ContinuousColumn('input_continuous_all', [f'I{j}' for j in range(ND)])]
@@ -92,22 +97,13 @@ def time_call(fn, warmup, repeats):
     return ms
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--rows', type=int, default=262144)
-    ap.add_argument('--batches', default='128,8192,65536')
-    ap.add_argument('--repeats', type=int, default=5)
-    ap.add_argument('--warmup', type=int, default=2)
-    ap.add_argument('--paths', default='fused,layer')
-    a = ap.parse_args()
-    dm = build_model()
+def run_config(name, a):
+    dm = build_model(CONFIGS[name])
     dm.model.eval()
-    if dm.inference_plan() is None:
-        raise SystemExit('the benchmark graph has no inference plan')
+    if 'fused' in a.paths.split(',') and dm.inference_plan() is None:
+        raise SystemExit(f'the {name} graph has no inference plan')
     data = make_feed(dm, a.rows)
-    res = {'metric': 'predict_rows_per_s', 'shape': {'fields': F, 'vocab': VOCAB, 'dense': ND, 'D': D, 'tower': [128, 64]},
-           'rows': a.rows, 'repeats': a.repeats, 'warmup': a.warmup}
-    outs = {}
+    res, outs = {'nets': CONFIGS[name]}, {}
     for path in a.paths.split(','):
         res[path] = {}
         for B in [int(b) for b in a.batches.split(',')]:
@@ -122,6 +118,23 @@ def main():
         res['speedup'] = {b: res['fused'][b]['rows_per_s'] / res['layer'][b]['rows_per_s'] for b in res['fused'] if b in res['layer']}
         res['max_abs_diff'] = max(float((outs[('fused', B)] - outs[('layer', B)]).abs().max())
                                   for (p, B) in outs if p == 'fused' and ('layer', B) in outs)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--configs', default=','.join(CONFIGS))
+    ap.add_argument('--rows', type=int, default=262144)
+    ap.add_argument('--batches', default='128,8192,65536')
+    ap.add_argument('--repeats', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=2)
+    ap.add_argument('--paths', default='fused,layer')
+    a = ap.parse_args()
+    res = {'metric': 'predict_rows_per_s', 'shape': {'fields': F, 'vocab': VOCAB, 'dense': ND, 'D': D, 'tower': [128, 64]},
+           'rows': a.rows, 'repeats': a.repeats, 'warmup': a.warmup, 'configs': {}}
+    for name in a.configs.split(','):
+        res['configs'][name] = run_config(name, a)
+        torch.cuda.empty_cache()
     print(json.dumps(res))
 
 
