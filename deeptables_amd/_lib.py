@@ -183,6 +183,25 @@ SIGNATURES = {
                                         _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'dt_stack_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr,
                                 _ptr, _c_int, _ptr]),
+    # one CIN layer's forward on a filter packed once (mode = DT_CIN_*)
+    'dt_cin_fwd_supported': (_c_int, [_c_int] * 6),
+    'dt_cin_packed_bytes': (_c_i64, [_c_int] * 4),
+    'dt_cin_pack': (_c_int, [_c_int, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    'dt_cin_layer_fwd_packed': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                         _c_i64, _c_i64, _ptr, _ptr]),
+    # xDeepFM inference: prepare once, then tower / one call per CIN layer / head per batch (layer_sizes, cin_W, y: host arrays)
+    'dt_xdeepfm_infer_supported': (_c_int, [_c_int] * 7 + [_ptr] + [_c_int] * 5),
+    'dt_xdeepfm_infer_workspace_bytes': (_c_i64, [_c_int] * 4 + [_ptr, _c_int, _c_int]),
+    'dt_xdeepfm_infer_prepare': (_c_int, [_c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _c_int, _c_int,
+                                          _ptr, _ptr, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr,
+                                          _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr,
+                                          _ptr, _ptr]),
+    'dt_xdeepfm_infer_tower': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr,
+                                        _ptr, _c_int, _ptr]),
+    'dt_xdeepfm_infer_cin': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int,
+                                      _c_int, _ptr, _ptr, _ptr]),
+    'dt_xdeepfm_infer_head': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr,
+                                       _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -196,6 +215,8 @@ DT_STEP_STAMPS = 0x400
 DT_STEP_PREPARED = 0x800
 DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
 DT_NET_LINEAR, DT_NET_FM, DT_NET_DNN = 0x1, 0x2, 0x4
+DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
+DT_XDEEPFM_MAX_LAYERS = 8
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)

@@ -596,6 +596,12 @@ static int cin_check(const char* who, int B, int F0, int Hk, int L, int D) {
     return DT_OK;
 }
 
+// the shapes dt_cin_layer_fwd launches (its own checks, without a launch): for dt_cin_fwd_supported (cin_bf16.hip)
+bool dt::cin_f32_fwd_ok(int F0, int Hk, int L, int D) {
+    if (F0 <= 0 || Hk <= 0 || L <= 0 || D <= 0 || D > kCinTileM) return false;
+    return ((size_t)kCinTileM * cin_xks(Hk) + 2 * kCinTileN * kCinWS + (size_t)kCinTileM * (F0 | 1)) * sizeof(float) <= 160 * 1024;
+}
+
 extern "C" int dt_cin_layer_fwd(const float* x0, const float* xk, const float* W, const float* bias,
                                 int act, int B, int F0, int Hk, int L, int D, int64_t x0_bstride,
                                 int64_t xk_bstride, float* y, void* stream) {

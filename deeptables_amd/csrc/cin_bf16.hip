@@ -1174,6 +1174,12 @@ static void cinb_pack(const float* W, int F0, int Hk, int L, __bf16* WT, __bf16*
 // (round 4's A/B, profiles/r04_xdeepfm_x3_narrow_kernel_stats.csv: 2.49 ms per step against 3.27 ms with the four-wave kernels)
 static bool cinb_wide(int64_t M) { return M >= 256 * 128; }
 
+// the layer's forward over a filter cinb_pack<NP> wrote to WT: the launch of dt_cin_layer_fwd_bf16 / _bf16x3 behind their
+// weight-pack, and all of dt_cin_layer_fwd_packed (the filter packed once by dt_cin_pack)
+template <int NP>
+static int cinb_fwd_run(const char* who, const float* x0, const float* xk, const __bf16* WT, const float* bias, int act, int B,
+                        int F0, int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y, hipStream_t st);
+
 template <int NP>
 static int cinb_fwd(const char* who, const float* x0, const float* xk, const float* W, const float* bias, int act, int B, int F0,
                     int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y, void* ws, void* stream) {
@@ -1185,6 +1191,12 @@ static int cinb_fwd(const char* who, const float* x0, const float* xk, const flo
     hipStream_t st = as_stream(stream);
     __bf16* WT = reinterpret_cast<__bf16*>(ws);
     cinb_pack<NP>(W, F0, Hk, L, WT, nullptr, st);
+    return cinb_fwd_run<NP>(who, x0, xk, WT, bias, act, B, F0, Hk, L, D, x0_bstride, xk_bstride, y, st);
+}
+
+template <int NP>
+static int cinb_fwd_run(const char* who, const float* x0, const float* xk, const __bf16* WT, const float* bias, int act, int B,
+                        int F0, int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y, hipStream_t st) {
     const int64_t M = (int64_t)B * D;
     dim3 grid((unsigned)((M + kBM - 1) / kBM), (unsigned)ceil_div(L, kBN));
     if (NP == 3) {
@@ -1239,6 +1251,80 @@ extern "C" int dt_cin_layer_fwd_bf16x3(const float* x0, const float* xk, const f
                                        int F0, int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y,
                                        void* ws, void* stream) {
     return cinb_fwd<3>("dt_cin_layer_fwd_bf16x3", x0, xk, W, bias, act, B, F0, Hk, L, D, x0_bstride, xk_bstride, y, ws, stream);
+}
+
+// ---- the forward on a filter packed ONCE (inference: the weights do not change between batches).  dt_cin_pack writes what
+//      the forward of `mode` reads — the bf16 parts of W^T that dt_cin_layer_fwd_bf16 / _bf16x3 re-write on every call, or,
+//      for the exact mode (which reads W as it is), a copy of W — and dt_cin_layer_fwd_packed runs the same kernel launch on
+//      it: the same arithmetic on the same values, so the same bits. ----
+template <int NP>
+static bool cinb_fwd_ok(int F0, int Hk, int L, int D, int act) {
+    if (F0 <= 0 || Hk <= 0 || L <= 0 || D <= 0 || L > 256 || Hk > 128 || F0 > 128) return false;
+    if (NP == 3) {          // cinb_fwd_run's choice: the Z-free kernel (one 128-row block's LDS is the smaller of its two forms)
+        const int ks = cb_hp(Hk) <= 32 ? 2 : cb_hp(Hk) <= 64 ? 4 : 8;
+        const bool any = !(act == DT_ACT_LINEAR || act == DT_ACT_RELU);
+        const size_t wide = (size_t)F0 * 256 * sizeof(float) + (size_t)2 * 3 * kBN * (16 * ks + 8) * 2;
+        if (wide <= 160 * 1024 && !any && ks <= 4) return true;      // (the narrow form needs less)
+    }
+    constexpr int KCH = NP == 1 ? kBK : 16;
+    return ((size_t)kBM * ((F0 | 1) + cb_hp(Hk) + 4)) * sizeof(float) + (size_t)2 * NP * kBN * (KCH + 8) * 2 <= 160 * 1024;
+}
+
+extern "C" int dt_cin_fwd_supported(int mode, int F0, int Hk, int L, int D, int act) {
+    if (act < 0 || act >= DT_ACT_COUNT) return 0;
+    switch (mode) {
+        case DT_CIN_F32: return cin_f32_fwd_ok(F0, Hk, L, D) ? 1 : 0;
+        case DT_CIN_BF16: return cinb_fwd_ok<1>(F0, Hk, L, D, act) ? 1 : 0;
+        case DT_CIN_BF16X3: return cinb_fwd_ok<3>(F0, Hk, L, D, act) ? 1 : 0;
+        default: return 0;
+    }
+}
+
+extern "C" int64_t dt_cin_packed_bytes(int mode, int F0, int Hk, int L) {
+    if (F0 <= 0 || Hk <= 0 || L <= 0) return -1;
+    switch (mode) {
+        case DT_CIN_F32: return ((int64_t)F0 * Hk * L * (int64_t)sizeof(float) + 15) & ~(int64_t)15;
+        case DT_CIN_BF16: return (2 * cinb_nT(F0, Hk, L) + 15) & ~(int64_t)15;
+        case DT_CIN_BF16X3: return (2 * 3 * cinb_nT(F0, Hk, L) + 15) & ~(int64_t)15;
+        default: return -1;
+    }
+}
+
+extern "C" int dt_cin_pack(int mode, const float* W, int F0, int Hk, int L, void* packed, void* stream) {
+    DT_REQUIRE(mode == DT_CIN_F32 || mode == DT_CIN_BF16 || mode == DT_CIN_BF16X3, "dt_cin_pack: mode %d", mode);
+    DT_REQUIRE(F0 > 0 && Hk > 0 && L > 0, "dt_cin_pack: bad sizes F0=%d Hk=%d L=%d", F0, Hk, L);
+    DT_REQUIRE(W && packed && (uintptr_t)packed % 16 == 0, "dt_cin_pack: null / unaligned pointer");
+    hipStream_t st = as_stream(stream);
+    if (mode == DT_CIN_F32) {
+        hipError_t e = hipMemcpyAsync(packed, W, (size_t)F0 * Hk * L * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) {
+            set_error("dt_cin_pack: copy failed: %s", hipGetErrorString(e));
+            return DT_ERR_LAUNCH;
+        }
+        return DT_OK;
+    }
+    if (mode == DT_CIN_BF16) cinb_pack<1>(W, F0, Hk, L, reinterpret_cast<__bf16*>(packed), nullptr, st);
+    else cinb_pack<3>(W, F0, Hk, L, reinterpret_cast<__bf16*>(packed), nullptr, st);
+    return launch_status("dt_cin_pack");
+}
+
+extern "C" int dt_cin_layer_fwd_packed(int mode, const float* x0, const float* xk, const void* packed, const float* bias, int act,
+                                       int B, int F0, int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y,
+                                       void* stream) {
+    const char* who = "dt_cin_layer_fwd_packed";
+    DT_REQUIRE(mode == DT_CIN_F32 || mode == DT_CIN_BF16 || mode == DT_CIN_BF16X3, "%s: mode %d", who, mode);
+    if (mode == DT_CIN_F32)
+        return dt_cin_layer_fwd(x0, xk, reinterpret_cast<const float*>(packed), bias, act, B, F0, Hk, L, D, x0_bstride,
+                                xk_bstride, y, stream);
+    int rc = cinb_check(who, B, F0, Hk, L, D);
+    if (rc) return rc;
+    if (B == 0) return DT_OK;
+    DT_REQUIRE(x0 && xk && packed && y, "%s: null pointer", who);
+    DT_REQUIRE(act >= 0 && act < DT_ACT_COUNT, "%s: act %d", who, act);
+    const __bf16* WT = reinterpret_cast<const __bf16*>(packed);
+    return mode == DT_CIN_BF16
+        ? cinb_fwd_run<1>(who, x0, xk, WT, bias, act, B, F0, Hk, L, D, x0_bstride, xk_bstride, y, as_stream(stream))
+        : cinb_fwd_run<3>(who, x0, xk, WT, bias, act, B, F0, Hk, L, D, x0_bstride, xk_bstride, y, as_stream(stream));
 }
 
 // the eight-wave dgrad exists for L <= 128, Hk <= 64 (G of 256 filters or four j blocks of x_k values per lane spill at

@@ -17,6 +17,9 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 // address of lr_t (the bias-corrected rate the CURRENT step uses) inside the device-resident Adam step state (optim.hip)
 const float* adam_state_lr_t(const void* state);
 
+// dt_cin_layer_fwd's shape domain (cin.hip), asked by dt_cin_fwd_supported (cin_bf16.hip)
+bool cin_f32_fwd_ok(int F0, int Hk, int L, int D);
+
 inline int launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -163,6 +163,10 @@ struct InferIo {
     float* out;              // NULL: logits only
     int* oob;                // NULL: not counted
     int sigmoid;             // out = sigmoid(logit) (binary task), else out = logit (regression)
+    // xDeepFM's tower launch (k_infer<.., XD = true>): the tile's raw embedding rows [B][F D / 4] = the CIN's x0, and
+    // linear + tower . w3 per row, before the output unit
+    float4* x0;
+    float* partial;
 };
 
 // sum over the lanes that share lane % g (g = D / 4, a power of two, runtime): every lane ends with its group's total
@@ -174,7 +178,10 @@ __device__ __forceinline__ float infer_sum_strided(float v, int g) {
 // NETS: the nets beside the tower (DT_NET_DNN is always in it) — `linear`'s sum and `fm_nets`' sum-square reduction are
 // compiled in per net; a graph without `linear` reads no wlin and runs no wave_sum for it, one without `fm_nets` runs none of
 // the eight infer_sum_strided chains.  The logit is (linear + fm + tower) w_out + b_out over the terms present.
-template <int NCH, int LC = 0, bool ONE = false, int NETS = kNetAll>   // LC = kCrossMax: DCN (NETS unused)
+// XD (xDeepFM, NETS = DT_NET_LINEAR | DT_NET_DNN): the launch also stores the rows it gathered (before the input BN: the CIN
+// reads the concatenated embeddings themselves, deepnets.py:69-81) to io.x0, so the table is gathered once per batch, and
+// writes io.partial[m] = linear + tower . w3 instead of running the output unit (k_xdeepfm_head adds the CIN's logit first).
+template <int NCH, int LC = 0, bool ONE = false, int NETS = kNetAll, bool XD = false>   // LC = kCrossMax: DCN (NETS unused)
 __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims dm, const float* __restrict__ ws, int L) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int CP = 64 * NCH, NST = CP / 32, XSB = CP + 16, HF = kH1 + 4, XP = kTM * XSB;
@@ -214,6 +221,7 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                             atomicAdd(io.oob, 1);
                         }
                         if (LIN) lp += ((v[t].x + v[t].y) + (v[t].z + v[t].w)) * ws[wl.wlin + f];
+                        if constexpr (XD) io.x0[(int64_t)m * NV + j] = v[t];      // (an out-of-range id: the zero row)
                     }
                 }
                 if (LIN) {
@@ -400,6 +408,13 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                 else if (l == L) zc = a * pr[l] + q;
             }
         }
+        if constexpr (XD) {
+            if (s == 0 && m < dm.B) {
+                const float pt = (zp[c] + zp[kTM + c]) + (zp[2 * kTM + c] + zp[3 * kTM + c]);
+                io.partial[m] = LIN ? lf[c] + pt : pt;
+            }
+            return;
+        }
         if (s == 0 && m < dm.B) {
             const float pt = (zp[c] + zp[kTM + c]) + (zp[2 * kTM + c] + zp[3 * kTM + c]);
             const float zz = LC ? zc + pt                      // Dense(1)(Concatenate([cross, dnn])) (deepnets.py:194-207)
@@ -490,4 +505,70 @@ __global__ __launch_bounds__(64 * kInferSparseRows) void k_infer_sparse(InferIo 
         io.logit[m] = lg;
         if (io.out) io.out[m] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
     }
+}
+
+// ---- xDeepFM's head (reference layers.py:713-734 + deepmodel.py:286-301): what split-pool, cat, the exFM_out Dense, add_logits,
+//      task_output and the activation do in eight launches.  Of every CIN layer's output y_k [B][L_k][D] only sum_D of the
+//      direct-connect channels [lo_k, L_k) is used (lo_k = 0 with direct=True and for the last layer, else L_k / 2), and that
+//      only through its dot product with exFM_out's kernel: logit_cin = sum_k sum_l wex[off_k + l - lo_k] sum_d y_k[b][l][d] + bex.
+//      Tens of megabytes of y and no flops, so one wave = one row: the row's pooled channels of a layer are one contiguous
+//      run of (L_k - lo_k) D floats that the wave reads as float4s, lane after lane (64 lanes x 16 B = 1 KiB per instruction),
+//      four loads in flight per lane; every lane weighs its piece's four-term sum with the channel's weight, wave_sum ends the
+//      row.  The order of the sums depends on the row alone, not on B.  256-thread blocks (four rows), no LDS. ----
+constexpr int kXdMaxLayers = DT_XDEEPFM_MAX_LAYERS;
+constexpr int kXdHeadRows = 4;
+
+struct XdHeadArgs {
+    const float* y[kXdMaxLayers];
+    int L[kXdMaxLayers], lo[kXdMaxLayers], woff[kXdMaxLayers];     // channels, first pooled channel, its weight's offset in wex
+    int n;
+    const float* wex;            // [sum_k (L_k - lo_k)] exFM_out's kernel | 1 float bias (prepared workspace)
+    const float* bex;
+    const float* head;           // w_out, b_out (InferWsLayout.head)
+    const float* partial;        // [B] linear + tower
+    float* logit;
+    float* out;
+    int sigmoid;
+    int B, D;
+};
+
+__global__ __launch_bounds__(64 * kXdHeadRows) void k_xdeepfm_head(XdHeadArgs a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = blockIdx.x * kXdHeadRows + wave;
+    if (m >= a.B) return;
+    const int lsh = __ffs(a.D >> 2) - 1;                 // float4 pieces per channel = D / 4, a power of two
+    float acc = 0.f;
+    for (int k = 0; k < a.n; ++k) {
+        const int n4 = (a.L[k] - a.lo[k]) << lsh;        // float4 pieces of the pooled run
+        const float4* src = reinterpret_cast<const float4*>(a.y[k] + ((int64_t)m * a.L[k] + a.lo[k]) * a.D);
+        const float* w = a.wex + a.woff[k];
+        int q = lane;
+        for (; q + 192 < n4; q += 256) {
+            const float4 v0 = src[q], v1 = src[q + 64], v2 = src[q + 128], v3 = src[q + 192];
+            const float w0 = w[q >> lsh], w1 = w[(q + 64) >> lsh], w2 = w[(q + 128) >> lsh], w3 = w[(q + 192) >> lsh];
+            acc += ((v0.x + v0.y) + (v0.z + v0.w)) * w0;
+            acc += ((v1.x + v1.y) + (v1.z + v1.w)) * w1;
+            acc += ((v2.x + v2.y) + (v2.z + v2.w)) * w2;
+            acc += ((v3.x + v3.y) + (v3.z + v3.w)) * w3;
+        }
+        for (; q < n4; q += 64) {
+            const float4 v0 = src[q];
+            acc += ((v0.x + v0.y) + (v0.z + v0.w)) * w[q >> lsh];
+        }
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+        const float zz = a.partial[m] + (acc + a.bex[0]);       // Add([linear, cin, dnn]) over the two terms the launches hand over
+        const float lg = zz * a.head[0] + a.head[1];
+        a.logit[m] = lg;
+        if (a.out) a.out[m] = a.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+    }
+}
+
+// one thread per element of exFM_out's kernel and bias -> the workspace (dt_xdeepfm_infer_prepare)
+__global__ __launch_bounds__(256) void k_xdeepfm_prep(const float* __restrict__ wex, const float* __restrict__ bex, int P,
+                                                      float* __restrict__ dst) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e < P) dst[e] = wex[e];
+    else if (e == P) dst[((P + 3) & ~3)] = bex ? bex[0] : 0.f;
 }

@@ -926,10 +926,138 @@ class InferStack(InferDeepFM):
         return ptr(self.dl.kernel) if self.mask & _lib.DT_NET_DNN else None, ptr(self.out.kernel)
 
 
+def _cin_mode(cin):
+    """the CIN layer's precision mode (cin_params['mfma_dtype'] / DT_AMD_CIN_DTYPE, as the layer holds it now) -> DT_CIN_*:
+    the entry point whose kernel the layer path runs in that mode (ops.cin_layer)"""
+    mode = cin.mfma_dtype
+    if mode == 'bf16x3':
+        return _lib.DT_CIN_BF16X3
+    if mode in ('bf16', 'bfloat16'):
+        return _lib.DT_CIN_BF16
+    if mode in ('float32', 'fp32', 'f32'):
+        return _lib.DT_CIN_F32
+    raise ValueError(f'CIN mfma_dtype {mode!r}: expected float32, bf16x3 or bf16')
+
+
+class InferXDeepFM(InferDeepFM):
+    """Inference plan for the xDeepFM graph (nets 'linear', 'cin_nets', 'dnn_nets', each once, in any order, Add-stacked;
+    deepnets.py:21): 2 + len(cross_layer_size) launches per batch (dt_xdeepfm_infer_*, csrc/infer_x3.h) —
+      tower: InferStack's tile launch for linear + dnn_nets, which also stores the embedding rows it gathered (x0, the CIN's
+             input) and hands over linear + tower . w3 instead of the output;
+      cin:   one CIN layer kernel per layer — the layer path's own kernel of the mode in force — on a filter packed in
+             `prepare` (the layer path re-packs it on every call), reading the previous layer's output in place;
+      head:  sum over D of the direct-connect channels, the exFM_out Dense, Add, task_output, the activation.
+    Refused (the layer path runs): what InferStack refuses for a graph with a tower, more than 64 fields, use_residual,
+    reduce_D, a CIN shape outside the layer kernels' domain, any other combination of nets with 'cin_nets'."""
+
+    NETS = {'linear', 'cin_nets', 'dnn_nets'}
+    PREFIX = 'xdeepfm'
+    NET_LAYERS = ('linear_logit', 'dense_logit_dnn_nets')
+
+    @staticmethod
+    def _cin_layer(dm):
+        from .models.layers import CIN
+        found = [l for l in dm.model.layers_by_name.values() if isinstance(l, CIN)]
+        return found[0] if len(found) == 1 else None
+
+    @staticmethod
+    def _cin_shape(cin):
+        """(n_layers, layer sizes as a host int array, direct)"""
+        sizes = [int(v) for v in cin.cross_layer_size]
+        return len(sizes), (ctypes.c_int * len(sizes))(*sizes), 1 if cin.direct else 0
+
+    @classmethod
+    def _supported(cls, dm, dims, tower):
+        cin = cls._cin_layer(dm)
+        if cin is None or tuple(dm.model.layers_by_name['task_output'].kernel.shape) != (1, 1):
+            return False
+        n, sizes, direct = cls._cin_shape(cin)
+        return lib().dt_xdeepfm_infer_supported(*dims, *tower, n, ctypes.cast(sizes, ctypes.c_void_p), direct,
+                                                1 if cin.use_residual else 0, 1 if cin.reduce_D else 0,
+                                                _lib.act_code(cin.activation, 'CIN'), _cin_mode(cin))
+
+    def _net_layers(self, L):
+        super()._net_layers(L)
+        self.cin = self._cin_layer(self.dm)
+        self.n_layers, self.sizes, self.direct = self._cin_shape(self.cin)
+        self.cin_mode = _cin_mode(self.cin)
+        self.cin_act = _lib.act_code(self.cin.activation, 'CIN')
+        self.cin_bias = [None] * self.n_layers
+        self._scratch = None
+
+    def _cin_dims(self):
+        return self.n_layers, ctypes.cast(self.sizes, ctypes.c_void_p), self.direct, self.cin_mode
+
+    def _dims(self):
+        """dt_xdeepfm_infer_workspace_bytes' arguments"""
+        return (self.F, self.D, self.Nd) + self._cin_dims()
+
+    def prepare(self):
+        """the tower's layouts as InferDeepFM.prepare, then the CIN as it is now: its precision mode, every layer's filter
+        (packed for that mode's kernel), the exFM_out Dense's kernel and bias — one call"""
+        self.flags = _infer_flags(self.dm)
+        self.cin_mode = _cin_mode(self.cin)
+        nbytes = self._entry('infer_workspace_bytes')(*self._dims())
+        if nbytes < 0:
+            raise _lib.DtHipError('InferXDeepFM: unsupported shape')
+        if nbytes > self.ws.numel() * 4:           # the mode changed to one with a larger packed filter
+            self.ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        cin, ex = self.cin, self.cin.exFM_out
+        self.cin_bias = [ptr(cin.bias[k]) if cin.use_bias else None for k in range(self.n_layers)]
+        filters = (ctypes.c_void_p * self.n_layers)(*[cin.f_[k].data_ptr() for k in range(self.n_layers)])
+        check(self._entry('infer_prepare')(
+            self.F, self.D, self.Nd, *self._net_args(), *self._tower_args(), *self._head_weights(), ptr(self.out.bias),
+            *self._cin_dims(), ctypes.cast(filters, ctypes.c_void_p), ptr(ex.kernel), ptr(ex.bias), ptr(self.ws),
+            stream_ptr()), 'dt_xdeepfm_infer_prepare')
+
+    def _alloc_scratch(self, rows):
+        """x0 [rows, F, D], partial [rows] and every CIN layer's output [rows, L_k, D] for batches of up to `rows` rows"""
+        dev, f32 = self.device, torch.float32
+        y = [torch.empty((rows, int(l), self.D), dtype=f32, device=dev) for l in self.sizes]
+        return {'rows': rows, 'x0': torch.empty((rows, self.F, self.D), dtype=f32, device=dev),
+                'partial': torch.empty((rows,), dtype=f32, device=dev), 'y': y,
+                'y_ptrs': (ctypes.c_void_p * self.n_layers)(*[t.data_ptr() for t in y])}
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch, as InferDeepFM.infer: the tower launch, one launch per CIN layer, the head.  Inside `run_batches` the
+        scratch is the call's; a lone call allocates its own."""
+        B = idx.shape[0]
+        idx = idx.contiguous()
+        if idx.dtype not in (torch.float32, torch.int32):
+            idx = idx.to(torch.int32)
+        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
+        dense = None if dense is None else dense.to(torch.float32).contiguous()
+        for t in (logit, out):
+            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B):
+                raise ValueError(f'infer: outputs must be contiguous float32 buffers of {B} rows')
+        sc = self._scratch
+        if sc is None or sc['rows'] < B:
+            sc = self._alloc_scratch(B)
+        dims, cin_dims, ws, st = (self.F, self.D, self.Nd), self._cin_dims(), ptr(self.ws), stream_ptr()
+        check(self._entry('infer_tower')(
+            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
+            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *dims, ws, ptr(sc['x0']), ptr(sc['partial']),
+            ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags & _lib.DT_INFER_TOWER_BF16, st),
+            'dt_xdeepfm_infer_tower')
+        for k in range(self.n_layers):
+            check(self._entry('infer_cin')(k, ptr(sc['x0']), ptr(sc['y'][k - 1]) if k else None, self.cin_bias[k],
+                                           self.cin_act, B, *dims, *cin_dims, ws, ptr(sc['y'][k]), st), 'dt_xdeepfm_infer_cin')
+        check(self._entry('infer_head')(ctypes.cast(sc['y_ptrs'], ctypes.c_void_p), ptr(sc['partial']), B, *dims, *cin_dims, ws,
+                                        ptr(logit), ptr(out), self.flags & _lib.DT_INFER_SIGMOID, st), 'dt_xdeepfm_infer_head')
+
+    def run_batches(self, data, batch_size, activate=True, each=None):
+        """InferDeepFM.run_batches with the scratch (x0, partial, the CIN layers' outputs) allocated once for the call"""
+        self._scratch = self._alloc_scratch(max(1, min(int(batch_size), int(data.n))))
+        try:
+            return super().run_batches(data, batch_size, activate=activate, each=each)
+        finally:
+            self._scratch = None
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    for plan in (InferDeepFM, InferDCN, InferStack):
+    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM):
         if plan.eligible(dm):
             return plan(dm)
     return None

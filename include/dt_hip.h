@@ -735,6 +735,72 @@ int dt_stack_infer(const void* idx, int idx_kind, const float* table, const int6
                    const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int nets, const void* workspace,
                    float* logit_out, float* out, int* oob_count, int flags, void* stream);
 
+/* ---- one CIN layer's forward on a filter packed ONCE (inference).  dt_cin_layer_fwd_bf16 / _bf16x3 re-lay W as bf16 parts of
+ * W^T on every call (one extra launch); at inference the filter does not change between batches, so dt_cin_pack writes that
+ * layout once and dt_cin_layer_fwd_packed runs the layer's kernel on it — the same launch on the same values as the entry of
+ * the same mode (reference layers.py:689-710), bit for bit.  mode: DT_CIN_F32 (dt_cin_layer_fwd, which reads W as it is:
+ * `packed` is a copy of W), DT_CIN_BF16 (dt_cin_layer_fwd_bf16), DT_CIN_BF16X3 (dt_cin_layer_fwd_bf16x3).
+ *   dt_cin_fwd_supported: 1 when the forward of `mode` takes the shape at every batch size (bf16 modes: F0 <= 128, Hk <= 128,
+ *     L <= 256 and the tiles fit the LDS; exact mode: D <= 128 and the tiles fit), else 0.
+ *   dt_cin_packed_bytes: size of `packed` (16-byte aligned, a multiple of 16), -1 for bad sizes / mode.
+ *   dt_cin_layer_fwd_packed: dt_cin_layer_fwd's arguments with `packed` for W. */
+#define DT_CIN_F32 0
+#define DT_CIN_BF16 1
+#define DT_CIN_BF16X3 2
+int dt_cin_fwd_supported(int mode, int F0, int Hk, int L, int D, int act);
+int64_t dt_cin_packed_bytes(int mode, int F0, int Hk, int L);
+int dt_cin_pack(int mode, const float* W, int F0, int Hk, int L, void* packed, void* stream);
+int dt_cin_layer_fwd_packed(int mode, const float* x0, const float* xk, const void* packed, const float* bias, int act, int B,
+                            int F0, int Hk, int L, int D, int64_t x0_bstride, int64_t xk_bstride, float* y, void* stream);
+
+/* ---- fused xDeepFM inference: 2 + n_layers launches per predict batch (replaces, for the graph dt_xdeepfm_infer_supported
+ * takes, the layer-by-layer forward of the reference's DeepModel.predict / evaluate, deepmodel.py:134-175, over nets
+ * ['linear', 'cin_nets', 'dnn_nets'] in any order, Add-stacked: deepnets.py:43-66 `linear`, 69-81 `cin_nets`, 163-169
+ * `dnn_nets`, layers.py:638-734 CIN, deepmodel.py:286-301 the head).
+ *   The CIN is n_layers layers of layer_sizes[k] filters (HOST array of ints); direct = cin_params['direct'] (0: the first
+ *   half of every layer but the last feeds the next layer, the second half is pooled; the last layer and, with direct = 1,
+ *   every layer is pooled whole, layers.py:713-721); cin_mode = DT_CIN_* (the layer kernels' precision mode).
+ *   dt_xdeepfm_infer_supported: dt_stack_infer_supported's domain for DT_NET_LINEAR | DT_NET_DNN, F <= 64, 1 ..
+ *     DT_XDEEPFM_MAX_LAYERS layers that dt_cin_fwd_supported takes (F0 = F, Hk = F then the previous layer's share, act =
+ *     cin_params['activation']), even sizes where direct = 0 halves them, use_residual = 0 and reduce_D = 0; else 0.
+ *   dt_xdeepfm_infer_prepare (once per predict / evaluate; replaces nothing of the reference: it writes what the launches
+ *     read): dt_deepfm_infer_prepare's arguments up to b_out — w3 = dense_logit_dnn_nets' kernel, w_out / b_out =
+ *     task_output's (b_out NULL: no bias) — then the CIN: cin_W = HOST array of n_layers device pointers, layer k's filter
+ *     [F Hk][layer_sizes[k]]; w_ex [P] / b_ex (NULL: none) = the exFM_out Dense's kernel and bias, P = the pooled channels.
+ *     workspace: dt_xdeepfm_infer_workspace_bytes bytes, 16-byte aligned.
+ *   Per batch of B >= 0 rows, in this order on one stream:
+ *   dt_xdeepfm_infer_tower (replaces the embedding gather, linear_logit, bn_concat_emb_dense, the two tower cells and
+ *     dense_logit_dnn_nets: deepnets.py:43-66, 163-169, 401-427): dt_stack_infer's launch for DT_NET_LINEAR | DT_NET_DNN that
+ *     also stores the rows it gathered, x0_out [B][F][D] (the CIN's input; an out-of-range id: zeros, counted once into
+ *     *oob_count), and writes partial_out [B] = linear + tower . w3 instead of the output.  flags: DT_INFER_TOWER_BF16 or 0.
+ *   dt_xdeepfm_infer_cin (replaces one pass of the loop of layers.py:689-718): layer `layer` on its packed filter: y
+ *     [B][layer_sizes[layer]][D] = act(conv(outer(x0, xk)) + bias) with xk = x0 for layer 0, else the leading channels of
+ *     y_prev = layer - 1's output (read in place).  bias [layer_sizes[layer]] or NULL.
+ *   dt_xdeepfm_infer_head (replaces layers.py:720-734 — reduce_sum over D, concat, exFM_out — and deepmodel.py:286-301 — Add,
+ *     task_output, the activation): y = HOST array of the n_layers outputs -> logit_out [B] = (partial + (pooled . w_ex +
+ *     b_ex)) w_out + b_out and, if out != NULL, out [B] = sigmoid(logit) with DT_INFER_SIGMOID or the logit. */
+#define DT_XDEEPFM_MAX_LAYERS 8
+int dt_xdeepfm_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int n_layers, const int* layer_sizes,
+                               int direct, int use_residual, int reduce_D, int act, int cin_mode);
+int64_t dt_xdeepfm_infer_workspace_bytes(int F, int D, int Nd, int n_layers, const int* layer_sizes, int direct, int cin_mode);
+int dt_xdeepfm_infer_prepare(int F, int D, int Nd, const float* w_lin, const float* bn_gamma, const float* bn_beta,
+                             const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1, int H1,
+                             const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                             const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
+                             float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
+                             const float* c2_var, float c2_eps, const float* w3, const float* w_out, const float* b_out,
+                             int n_layers, const int* layer_sizes, int direct, int cin_mode, const float* const* cin_W,
+                             const float* w_ex, const float* b_ex, void* workspace, void* stream);
+int dt_xdeepfm_infer_tower(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                           const float* dense, int B, int F, int D, int Nd, const void* workspace, float* x0_out,
+                           float* partial_out, int* oob_count, int flags, void* stream);
+int dt_xdeepfm_infer_cin(int layer, const float* x0, const float* y_prev, const float* bias, int act, int B, int F, int D,
+                         int Nd, int n_layers, const int* layer_sizes, int direct, int cin_mode, const void* workspace,
+                         float* y, void* stream);
+int dt_xdeepfm_infer_head(const float* const* y, const float* partial, int B, int F, int D, int Nd, int n_layers,
+                          const int* layer_sizes, int direct, int cin_mode, const void* workspace, float* logit_out,
+                          float* out, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 D = 16, the default 128 x 64 tower) for the fused inference plan (fused.InferDeepFM / InferDCN / InferStack: one
 k_infer_prep launch per call, one k_infer or k_infer_sparse launch per batch) and for the layer-by-layer forward
 (DT_AMD_FUSED_PREDICT=0), at batch sizes 128 (DeepTable's default), 8192 and 65536, for the graphs of CONFIGS: DeepFM, DCN,
-ModelConfig's default ['dnn_nets'], WideDeep ['linear', 'dnn_nets'] and the FM model ['linear', 'fm_nets'].  Both paths of
+ModelConfig's default ['dnn_nets'], WideDeep ['linear', 'dnn_nets'], the FM model ['linear', 'fm_nets'] and xDeepFM
+['linear', 'cin_nets', 'dnn_nets'] with the default CIN (128, 128) (fused.InferXDeepFM: 2 + 2 launches per batch).  Both paths of
 a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
 
 Both paths score the same device-resident rows (training.TableBatches) and write every batch's output into device memory;
@@ -11,7 +12,7 @@ the timed region is what `DeepModel.predict` does after its feed is built, up to
 of the result is left out: it is the same for both paths).  Device events around each call, warm-up calls first, the
 median of the repeats reported (run-to-run spread as min / max).
 
-    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm] [--rows N] [--batches 128,8192,65536]
+    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm,xdeepfm] [--rows N] [--batches 128,8192,65536]
                                   [--repeats R] [--warmup W] [--paths fused,layer]
 """
 import argparse
@@ -29,7 +30,8 @@ import torch  # noqa: E402
 
 F, VOCAB, ND, D = 26, 1_000_000, 13, 16
 CONFIGS = {'deepfm': ['linear', 'fm_nets', 'dnn_nets'], 'dcn': ['dcn_nets'], 'dnn': ['dnn_nets'],
-           'widedeep': ['linear', 'dnn_nets'], 'fm': ['linear', 'fm_nets']}
+           'widedeep': ['linear', 'dnn_nets'], 'fm': ['linear', 'fm_nets'],
+           'xdeepfm': ['linear', 'cin_nets', 'dnn_nets']}           # cin_params' default: cross_layer_size (128, 128)
 
 
 def build_model(nets, seed=0):
