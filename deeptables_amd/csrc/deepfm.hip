@@ -25,21 +25,13 @@
 // Dense gradients are deterministic: per-slice partials + one pass, and the batch sums are double-precision atomics of fp32
 // addends (exact unless their magnitudes span 2^23: the totals do not depend on the order of arrival).
 #include <stdlib.h>
-#include "common.h"
+#include "tile_common.h"
+#include "tower_x3.h"
 #include "adam_dev.h"
 
 namespace dt {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4_t __attribute__((ext_vector_type(4)));
-
-constexpr int kH1 = 128;  // dnn_params hidden_units[0]
-constexpr int kH2 = 64;   // dnn_params hidden_units[1]
-constexpr int kTM = 32;   // rows per MLP tile
-
-struct DeepFmDims {
-    int B, F, D, Nd, C, CP;  // C = F*D+Nd; CP = C rounded up to 64: row stride of X and the padded GEMM K
-};
 
 // accumulator buffer layout (floats), zeroed once per step by one memset
 struct DeepFmAccum {
@@ -153,33 +145,7 @@ __device__ __forceinline__ unsigned elect_hash(int64_t row) { return ((unsigned)
 // partition of a row among 2^parts_log2: the top bits of the hash (the low 13 bits pick the slot)
 __device__ __forceinline__ int elect_part(unsigned h, int parts_log2) { return (int)((h >> 13) >> (19 - parts_log2)); }
 
-// phase timestamps (s_memtime, shader cycles) of wave 0 of every block: ws region `stamps` [blocks][16] u64,
-// read back by tools/phase_times.py; costs one scalar load + store per phase
-#define DT_STAMP(buf, slot)                                                            \
-    do {                                                                               \
-        if ((buf) && threadIdx.x == 0)                                                 \
-            (buf)[(int64_t)blockIdx.x * 16 + (slot)] = __builtin_amdgcn_s_memtime();    \
-    } while (0)
-
-// ---------------------------------------------------------------------------------------------
-// Batch-wide sums without a reduction launch (round 5).  Two sets of accumulators live in the workspace as DOUBLES, split
-// into shards so that at most 64 blocks meet on one cache line (a wave's atomic covers whole lines: ~55 line requests per
-// block, against the 1.3 K stores + the 5 us reduction launch + its boundary they replace):
-//   bnacc [kBnShards][2][CP]   sum_b x and sum_b x^2 of every column of the concat row X (kernel A adds, kernel C's prologue
-//                              forms mean / variance in double: E[x^2] - mean^2 loses 2 log2(|mean| / sigma) of 53 bits)
-//   racc  [kRecShards][stride] the tile kernel's per-tile record entries (Part3: db1, db2, dw3, d w_out, d b_out, loss, the
-//                              d w_lin column sums, the two BN-backward sums sdx / sdxx, DCN's cross record)
-// racc: every addend is an fp32 value and a shard entry is the double sum of at most 64 of them (B = 8192), which is EXACT
-// unless their magnitudes span more than 2^23 — the totals do not depend on the order the blocks arrive in.  bnacc: the
-// addends are a block's 16-row sums formed in double (x^2 of an fp32 value is exact in double); their order of arrival can
-// move a total by an ulp of a DOUBLE, which survives the rounding to fp32 with probability ~1e-9 per value.  Either way the
-// fp32 results are the same from run to run (what the per-tile records + reduction launch guaranteed before; checked: four
-// runs of a step bit-identical, tools/r5/dbg_elect.py).
-// Life cycle: kernel A zeroes racc (kernel C of the same step adds into it); the launch after kernel C zeroes bnacc for the
-// NEXT step's kernel A — the workspace must be zero-filled once before its first use (dt_deepfm_workspace_bytes).
-constexpr int kBnShards = 8;
-constexpr int kRecShards = 4;
-__device__ __forceinline__ void radd(double* p, float v) { unsafeAtomicAdd(p, (double)v); }
+// the record shards (racc: tile_common.h) as the finishing launches read them
 struct RecSrc {
     const double* racc;          // [kRecShards][stride]
     int stride;
@@ -197,7 +163,6 @@ __device__ __forceinline__ float rec_sum(const RecSrc& r, int e) {
 //    (ids -> table rows) overlap across 32 waves per CU.  The block's 16 rows meet in LDS for the BN statistics.
 // ---------------------------------------------------------------------------------------------
 constexpr int kRowsPerBlockA = 16;
-constexpr int kMaxC = 544;
 
 template <int KIND, int LPR, int RPB>
 __global__ __launch_bounds__(64 * RPB) void k_sparse_fwd(
@@ -823,21 +788,6 @@ __global__ __launch_bounds__(1024) void k_prep(DeepFmDims dm, const float* __res
     }
 }
 
-struct MlpParams {
-    const float *b1, *W2, *b2, *w3, *wo, *bo, *gamma, *mean, *rstd, *sc, *betap;
-    const float *W1, *W1L, *W2L, *W2TL;   // original W1 [C][128]; lane-major operand layouts written by k_prep (see k_mlp_fwd3)
-    // BatchNormalization's statistics inside kernel C: the batch sums kernel A accumulated (bnacc [kBnShards][2][CP] doubles),
-    // the layer's beta, eps / momentum, the moving statistics (updated by block 0, may be NULL) and the padded vectors C
-    // publishes for kernels E and D
-    const double* bnacc;
-    const float* beta;
-    float eps, momentum;
-    float *moving_mean, *moving_var, *mean_w, *rstd_w, *sc_w, *betap_w;
-    float* gammap_w;      // this step's gamma, published like betap: the finishing launch (k_finish_step) reads gamma / beta while
-                          // it UPDATES the parameters themselves in other blocks
-};
-
-
 
 // =============================================================================================
 // Round-2 dense tower.  What round 1's kernels taught (phase stamps, tools/phase_times.py):
@@ -858,48 +808,9 @@ struct MlpParams {
 // the file's header has today's.  k_mlp_fwd3 below is the exact-fp32 tile kernel of `dnn_params['mfma_dtype'] = 'f32'` and of
 // forward-only calls; the default tile kernel is tower_x3.h.)
 // =============================================================================================
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float floatx2 __attribute__((ext_vector_type(2)));
 constexpr int kPad = 4;      // LDS row pad in floats: stride == 4 (mod 64) -> the 16-byte operand reads of 16 rows hit 64 distinct banks
 constexpr int kH2S = kH2 + kPad;
-
-__device__ __forceinline__ floatx4 ld4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
-__device__ __forceinline__ void st4(float* p, floatx4 v) { *reinterpret_cast<floatx4*>(p) = v; }
-// Write-through (sc1) 16-byte store for data the NEXT kernel reads: a plain store leaves the line dirty in this XCD's L2 and
-// the kernel boundary then waits for the write-back of everything the launch dirtied (~1 us per 6 MB: the row update's
-// 41 MB, the tile kernel's 26 MB); written through, the bytes leave while the kernel still computes.  Inline asm: hipcc
-// does not count it (nothing waits on a store) and the trailing s_nop keeps the data registers alive until it has read them.
-__device__ __forceinline__ void st4_wt(float* p, floatx4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void st4_sel(float* p, floatx4 v, bool wt) {
-    if (wt) st4_wt(p, v); else st4(p, v);
-}
-
-// per-tile partial sums written by C and reduced by E (layout of one tile's record, floats; contiguous).  DCN (L > 0
-// cross layers): no slin; G[0..L] (CP floats each: G_l = Xhat^T coeff_l over the tile's rows, see the cross backward of
-// kernel C) and one CP-float block of scalars follow: [l] = sum_r coeff_l, [16 + l] = sum_r A_{l+1}, [31] = sum_r dz.
-// Pipelined step (G3, see k_mlp_fwd3): two more CP-float vectors per tile, sdx = sum_r dXn[r] and sdxx = sum_r dXn[r] xhat[r]
-// over the tile's rows (the two batch sums of BatchNormalization's backward).  Since round 5 every entry is ADDED into the
-// sharded double-precision sums `racc` (radd) instead of being written per tile and reduced by a launch of its own.
-struct Part3 {
-    int slin, db1, db2, dw3, dwo, dbo, loss, cross, sdx, sdxx, n, stride;
-};
-__host__ __device__ inline Part3 part3_layout(int CP, int L = 0, int g3 = 0) {
-    Part3 l;
-    l.slin = 0; l.db1 = L > 0 ? 0 : CP; l.db2 = l.db1 + kH1; l.dw3 = l.db2 + kH2;
-    l.dwo = l.dw3 + kH2; l.dbo = l.dwo + 1; l.loss = l.dbo + 1;
-    l.cross = (l.loss + 1 + 3) & ~3;
-    l.n = L > 0 ? l.cross + (L + 2) * CP : l.loss + 1;
-    l.sdx = l.sdxx = -1;
-    if (g3) {
-        l.sdx = (l.n + 3) & ~3;
-        l.sdxx = l.sdx + CP;
-        l.n = l.sdxx + CP;
-    }
-    l.stride = (l.n + 3) & ~3;
-    return l;
-}
 
 // mean / biased variance of column `col` of the batch from kernel A's sums (double; see bnacc)
 __device__ __forceinline__ void bn_stats_col(const double* __restrict__ bnacc, int CP, int B, int col, float& mean, float& var) {
@@ -916,23 +827,6 @@ __device__ __forceinline__ void bn_stats_col(const double* __restrict__ bnacc, i
     var = v > 0.0 ? (float)v : 0.f;
 }
 
-// DCN arguments of the tile kernels (cw == NULL: DeepFM)
-struct DcnArgs {
-    const float *cw, *cb;        // Cross kernels / biases [L][C] (layers.py:423-426, stacked)
-    const float* w3c;            // cross part [C] of the kernel applied to Concatenate([cross, dnn])
-    int L;
-    float* dXc;                  // [B][CP] d loss / d Xn through the cross network (kernel C -> kernel D)
-    int mse;                     // loss: 0 = BinaryCrossentropy on the sigmoid output, 1 = MeanSquaredError on the linear output
-    int wt;                      // pipelined step: write-through stores of the tile's outputs (st4_wt)
-    const float* sw;             // [B] per-row loss weights (Keras sample_weight x class_weight; loss = sum_b w_b l_b / B), NULL: 1
-    // DCN: the tile's cross vectors G_0 .. G_L [CP each] leave as a per-tile record [tiles][gstride] (plain stores) and are
-    // summed over the tiles where they are finished (the finishing launch's column blocks).  As atomics into the record
-    // shards they made the tile kernel 86 us instead of 35: 3.1 K scattered elements per tile = ~800 line requests per block,
-    // 64 blocks deep on every line.  (The DeepFM record is 1.6 K elements in whole lines: +1.5 us.)
-    float* gpart;
-    int gstride;
-};
-constexpr int kCrossMax = 8;     // cross layers the fused DCN step takes
 constexpr int kCrossScal = 48 * 16;                                  // floats of the P / Gram block (k_mlp_fwd3 crP)
 constexpr int kCrossLds = kTM + kCrossScal + 2 * kTM * 16;          // DCN's LDS next to the layer vectors: zcs | crP | crA | crF
 
@@ -1639,9 +1533,6 @@ __global__ __launch_bounds__(256) void k_mlp_fwd3(const float* __restrict__ X, M
         DT_STAMP(stamps, 15);
     }
 }
-
-#include "tower_x3.h"
-#include "infer_x3.h"
 
 // E: weight gradients on 64x128 macro tiles = 2x4 MFMA tiles whose rows / columns INTERLEAVE (tile (t,u) holds outputs
 // (2i+t, 4j+u)), so ONE 8-byte load per lane feeds two tiles' worth of A and ONE 16-byte load four tiles' worth of B:
@@ -2496,19 +2387,6 @@ __global__ __launch_bounds__(512) void k_wgrad_rows(const float* __restrict__ X,
 
 using namespace dt;
 
-static bool deepfm_dims(int B, int F, int D, int Nd, DeepFmDims* dm, int* lpr) {
-    if (B <= 0 || F <= 0 || D <= 0 || Nd < 0 || D % 4) return false;
-    const int l = D / 4;
-    if (l < 1 || l > 64 || (l & (l - 1))) return false;
-    if (F * l > 128 || Nd > 64) return false;
-    dm->B = B; dm->F = F; dm->D = D; dm->Nd = Nd;
-    dm->C = F * D + Nd;
-    dm->CP = (dm->C + 63) & ~63;
-    if (dm->C > 544 || D > 64) return false;
-    *lpr = l;
-    return true;
-}
-
 extern "C" int dt_deepfm_supported(int B, int F, int D, int Nd, int H1, int H2) {
     DeepFmDims dm; int lpr;
     return (H1 == kH1 && H2 == kH2 && deepfm_dims(B, F, D, Nd, &dm, &lpr)) ? 1 : 0;
@@ -3223,372 +3101,4 @@ extern "C" int dt_dcn_train_step(
                             bn_moving_mean, bn_moving_var, bn_eps, bn_momentum, W1, b1, W2, b2, w3, w_out, b_out, logit_out,
                             rows_out, grad_rows, accum, workspace, oob_count, dedupe_ws, dedupe_slots, 1.0f, 0, phases,
                             embedding_dropout, dropout_seed, dense_input_dropout, sample_weight, stream, cross_w, cross_b, L);
-}
-
-// ---- DeepFM / DCN / net-stack inference (infer_x3.h): one k_infer (or, without a tower, k_infer_sparse) launch per batch
-//      over the layouts one k_infer_prep launch wrote ----
-static bool infer_tower_ok(int H1, int H2, int cells) {
-    return H1 >= 1 && H1 <= kH1 && H2 >= 1 && H2 <= kH2 && (cells & ~3) == 0;
-}
-
-extern "C" int dt_deepfm_infer_supported(int F, int D, int Nd, int H1, int H2, int cells) {
-    DeepFmDims dm; int lpr;
-    return (infer_tower_ok(H1, H2, cells) && deepfm_dims(1, F, D, Nd, &dm, &lpr) &&
-            infer_lds_bytes(dm.CP, false) <= 160 * 1024) ? 1 : 0;
-}
-
-extern "C" int dt_dcn_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int L) {
-    DeepFmDims dm; int lpr;
-    return (infer_tower_ok(H1, H2, cells) && L >= 1 && L <= kCrossMax && deepfm_dims(1, F, D, Nd, &dm, &lpr) &&
-            infer_lds_bytes(dm.CP, true) <= 160 * 1024) ? 1 : 0;
-}
-
-extern "C" int64_t dt_deepfm_infer_workspace_bytes(int F, int D, int Nd) {
-    DeepFmDims dm; int lpr;
-    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr)) return -1;
-    return infer_ws_layout(dm.CP, 0, kNetAll).total * (int64_t)sizeof(float);
-}
-
-extern "C" int64_t dt_dcn_infer_workspace_bytes(int F, int D, int Nd, int L) {
-    DeepFmDims dm; int lpr;
-    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr) || L < 1 || L > kCrossMax) return -1;
-    return infer_ws_layout(dm.CP, L, DT_NET_DNN).total * (int64_t)sizeof(float);
-}
-
-static int infer_prepare(const char* what, int F, int D, int Nd, InferPrepArgs a, int cells, void* workspace, void* stream) {
-    DeepFmDims dm; int lpr;
-    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
-    const bool tower = (a.nets & DT_NET_DNN) != 0, lin = (a.nets & DT_NET_LINEAR) != 0;
-    if (tower) {
-        DT_UNSUPPORTED(!infer_tower_ok(a.H1, a.H2, cells), "%s: tower %d x %d, cells %d (H1 <= %d, H2 <= %d, cells: BN bits 0 / 1)",
-                       what, a.H1, a.H2, cells, kH1, kH2);
-        DT_REQUIRE(a.ld1 >= a.H1 && a.ld2 >= a.H2, "%s: leading dimensions ld1=%d ld2=%d below the widths", what, a.ld1, a.ld2);
-    }
-    // w_out may be missing (= 1) only where the tower's vector is task_output's own kernel: DCN and the tower alone
-    DT_REQUIRE(workspace && (!tower || (a.mm && a.mv && a.W1 && a.W2 && a.w3)) && (!lin || a.wlin) &&
-               (a.L > 0 || a.nets == DT_NET_DNN || a.wout), "%s: null pointer", what);
-    DT_REQUIRE(a.L == 0 || (a.cw && a.cb_), "%s: null cross weights", what);
-    for (int i = 0; tower && i < 2; ++i) {
-        if (cells & (1 << i)) {
-            DT_REQUIRE(a.cm[i] && a.cv[i], "%s: tower cell %d has batch norm but no moving statistics", what, i + 1);
-        } else {
-            a.cm[i] = nullptr;
-        }
-    }
-    DT_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", what);
-    const int items = tower ? max((dm.CP >> 5) * 512, (2 * a.L + 1) * dm.CP) : dm.CP;
-    hipLaunchKernelGGL(k_infer_prep, dim3(ceil_div(items, 256)), dim3(256), 0, as_stream(stream), dm, a,
-                       reinterpret_cast<float*>(workspace));
-    return launch_status(what);
-}
-
-extern "C" int dt_deepfm_infer_prepare(int F, int D, int Nd, const float* w_lin, const float* bn_gamma, const float* bn_beta,
-                                       const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1,
-                                       int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
-                                       const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
-                                       float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
-                                       const float* c2_var, float c2_eps, const float* w3, const float* w_out,
-                                       const float* b_out, void* workspace, void* stream) {
-    const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
-                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0, kNetAll};
-    return infer_prepare("dt_deepfm_infer_prepare", F, D, Nd, a, cells, workspace, stream);
-}
-
-extern "C" int dt_dcn_infer_prepare(int F, int D, int Nd, const float* cross_w, const float* cross_b, int L,
-                                    const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var,
-                                    float bn_eps, const float* W1, int ld1, int H1, const float* b1, const float* W2, int ld2,
-                                    int H2, const float* b2, int cells, const float* c1_gamma, const float* c1_beta,
-                                    const float* c1_mean, const float* c1_var, float c1_eps, const float* c2_gamma,
-                                    const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
-                                    const float* w3, const float* w_out, const float* b_out, void* workspace, void* stream) {
-    DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer_prepare: %d cross layers (1..%d)", L, kCrossMax);
-    const InferPrepArgs a{nullptr, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
-                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, cross_w, cross_b, L, DT_NET_DNN};
-    return infer_prepare("dt_dcn_infer_prepare", F, D, Nd, a, cells, workspace, stream);
-}
-
-static int infer_run(const char* what, const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
-                     const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int L, const void* workspace,
-                     float* logit_out, float* out, int* oob_count, int flags, void* stream, int nets = kNetAll,
-                     float* xd_x0 = nullptr) {
-    // xd_x0 != NULL: xDeepFM's tower launch (nets = DT_NET_LINEAR | DT_NET_DNN) — the gathered rows go to xd_x0 and logit_out
-    // receives linear + tower . w3 (k_infer's XD variant)
-    DT_REQUIRE(B >= 0, "%s: B=%d", what, B);
-    DeepFmDims dm; int lpr;
-    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", what, F, D, Nd);
-    DT_REQUIRE((flags & ~(DT_INFER_SIGMOID | DT_INFER_TOWER_BF16)) == 0, "%s: flags 0x%x", what, flags);
-    DT_REQUIRE(idx_kind == DT_IDX_F32 || idx_kind == DT_IDX_I32, "%s: idx_kind %d", what, idx_kind);
-    if (B == 0) return DT_OK;
-    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "%s: null pointer", what);
-    DT_REQUIRE(Nd == 0 || dense, "%s: dense is null", what);
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)workspace) % 16 == 0, "%s: table / workspace must be 16-byte aligned", what);
-    dm.B = B;
-    const bool dcn = L > 0, one = (flags & DT_INFER_TOWER_BF16) != 0;
-    const bool xd = xd_x0 != nullptr;
-    DT_REQUIRE(!xd || (uintptr_t)xd_x0 % 16 == 0, "%s: x0_out must be 16-byte aligned", what);
-    const InferIo io{idx, idx_kind, reinterpret_cast<const float4*>(table), row_offset, vocab, dense, logit_out, out, oob_count,
-                     (flags & DT_INFER_SIGMOID) ? 1 : 0, reinterpret_cast<float4*>(xd_x0), xd ? logit_out : nullptr};
-    const float* ws = reinterpret_cast<const float*>(workspace);
-    hipStream_t st = as_stream(stream);
-    if (!(nets & DT_NET_DNN)) {     // no tower: one wave per row, no LDS (the precision flag has nothing to act on)
-        const dim3 grid(ceil_div(B, kInferSparseRows)), block(64 * kInferSparseRows);
-        switch (nets) {
-            case DT_NET_LINEAR: hipLaunchKernelGGL((k_infer_sparse<DT_NET_LINEAR>), grid, block, 0, st, io, dm, ws); break;
-            case DT_NET_FM: hipLaunchKernelGGL((k_infer_sparse<DT_NET_FM>), grid, block, 0, st, io, dm, ws); break;
-            default: hipLaunchKernelGGL((k_infer_sparse<DT_NET_LINEAR | DT_NET_FM>), grid, block, 0, st, io, dm, ws); break;
-        }
-        return launch_status(what);
-    }
-    const size_t lds = infer_lds_bytes(dm.CP, dcn);
-    DT_UNSUPPORTED(lds > 160 * 1024, "%s: the tile needs %zu B of LDS", what, lds);
-    const int tiles = ceil_div(B, kTM);
-#define DT_IL(N, LCV, ONEV, NETS)                                                                                          \
-    do {                                                                                                                   \
-        hipFuncSetAttribute((const void*)k_infer<N, LCV, ONEV, NETS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_infer<N, LCV, ONEV, NETS>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);        \
-    } while (0)
-#define DT_IM(N, NETS)                                                                                               \
-    case NETS:                                                                                                       \
-        if (one) DT_IL(N, 0, true, NETS); else DT_IL(N, 0, false, NETS);                                             \
-        break;
-#define DT_IX(N)                                                                                                     \
-    do {                                                                                                             \
-        constexpr int XN = DT_NET_DNN | DT_NET_LINEAR;                                                               \
-        if (one) {                                                                                                   \
-            hipFuncSetAttribute((const void*)k_infer<N, 0, true, XN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_infer<N, 0, true, XN, true>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);        \
-        } else {                                                                                                     \
-            hipFuncSetAttribute((const void*)k_infer<N, 0, false, XN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-            hipLaunchKernelGGL((k_infer<N, 0, false, XN, true>), dim3(tiles), dim3(kInferThreads), lds, st, io, dm, ws, L);       \
-        }                                                                                                            \
-    } while (0)
-#define DT_IN(N)                                                                                                     \
-    case N:                                                                                                          \
-        if (xd) DT_IX(N);                                                                                            \
-        else if (dcn) { if (one) DT_IL(N, kCrossMax, true, kNetAll); else DT_IL(N, kCrossMax, false, kNetAll); }          \
-        else switch (nets) {                                                                                         \
-            DT_IM(N, DT_NET_DNN) DT_IM(N, DT_NET_DNN | DT_NET_LINEAR) DT_IM(N, DT_NET_DNN | DT_NET_FM) DT_IM(N, kNetAll) \
-        }                                                                                                            \
-        break;
-    switch (dm.CP >> 6) { DT_IN(1) DT_IN(2) DT_IN(3) DT_IN(4) DT_IN(5) DT_IN(6) DT_IN(7) DT_IN(8) DT_IN(9) }
-#undef DT_IN
-#undef DT_IX
-#undef DT_IM
-#undef DT_IL
-    return launch_status(what);
-}
-
-extern "C" int dt_deepfm_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
-                               const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, const void* workspace,
-                               float* logit_out, float* out, int* oob_count, int flags, void* stream) {
-    return infer_run("dt_deepfm_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, 0, workspace, logit_out,
-                     out, oob_count, flags, stream);
-}
-
-extern "C" int dt_dcn_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
-                            const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int L,
-                            const void* workspace, float* logit_out, float* out, int* oob_count, int flags, void* stream) {
-    DT_UNSUPPORTED(L < 1 || L > kCrossMax, "dt_dcn_infer: %d cross layers (1..%d)", L, kCrossMax);
-    return infer_run("dt_dcn_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, L, workspace, logit_out,
-                     out, oob_count, flags, stream);
-}
-
-// ---- every Add-stacked subset of {linear, fm_nets, dnn_nets} (reference deepmodel.py:286-301: the nets' logits, Add,
-//      task_output; deepnets.py:43-66 linear, 84-96 fm_nets, 163-169 dnn_nets) through the same launches ----
-static bool stack_nets_ok(int nets) { return nets >= 1 && nets <= kNetAll; }
-
-extern "C" int dt_stack_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int nets) {
-    DeepFmDims dm; int lpr;
-    if (!stack_nets_ok(nets) || !deepfm_dims(1, F, D, Nd, &dm, &lpr)) return 0;
-    if (!(nets & DT_NET_DNN)) return 1;
-    return (infer_tower_ok(H1, H2, cells) && infer_lds_bytes(dm.CP, false) <= 160 * 1024) ? 1 : 0;
-}
-
-extern "C" int64_t dt_stack_infer_workspace_bytes(int F, int D, int Nd, int nets) {
-    DeepFmDims dm; int lpr;
-    if (!stack_nets_ok(nets) || !deepfm_dims(1, F, D, Nd, &dm, &lpr)) return -1;
-    return infer_ws_layout(dm.CP, 0, nets).total * (int64_t)sizeof(float);
-}
-
-extern "C" int dt_stack_infer_prepare(int F, int D, int Nd, int nets, const float* w_lin, const float* bn_gamma,
-                                      const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps,
-                                      const float* W1, int ld1, int H1, const float* b1, const float* W2, int ld2, int H2,
-                                      const float* b2, int cells, const float* c1_gamma, const float* c1_beta,
-                                      const float* c1_mean, const float* c1_var, float c1_eps, const float* c2_gamma,
-                                      const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
-                                      const float* w3, const float* w_out, const float* b_out, void* workspace, void* stream) {
-    DT_REQUIRE(stack_nets_ok(nets), "dt_stack_infer_prepare: nets 0x%x (a non-empty mask of DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN)", nets);
-    DT_REQUIRE(!(nets & DT_NET_LINEAR) || w_lin, "dt_stack_infer_prepare: nets 0x%x has linear but w_lin is null", nets);
-    DT_REQUIRE(!(nets & DT_NET_DNN) || (bn_mean && bn_var && W1 && W2 && w3),
-               "dt_stack_infer_prepare: nets 0x%x has dnn_nets but a tower pointer (bn_mean, bn_var, W1, W2, w3) is null", nets);
-    DT_REQUIRE(nets == DT_NET_DNN || w_out, "dt_stack_infer_prepare: nets 0x%x needs w_out (null only for dnn_nets alone)", nets);
-    const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
-                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0, nets};
-    return infer_prepare("dt_stack_infer_prepare", F, D, Nd, a, cells, workspace, stream);
-}
-
-extern "C" int dt_stack_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
-                              const int32_t* vocab, const float* dense, int B, int F, int D, int Nd, int nets, const void* workspace,
-                              float* logit_out, float* out, int* oob_count, int flags, void* stream) {
-    DT_REQUIRE(stack_nets_ok(nets), "dt_stack_infer: nets 0x%x (a non-empty mask of DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN)", nets);
-    return infer_run("dt_stack_infer", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, 0, workspace, logit_out,
-                     out, oob_count, flags, stream, nets);
-}
-
-// ---- xDeepFM inference (nets 'linear' + 'cin_nets' + 'dnn_nets', Add-stacked; reference deepnets.py:43-81 + 163-169,
-//      layers.py:638-734, deepmodel.py:286-301): 2 + n launches per batch over a workspace written once —
-//      k_infer<XD> (gather once; linear + tower -> partial, the raw rows -> x0), one CIN layer kernel per layer on the
-//      filter dt_cin_pack wrote, k_xdeepfm_head (pool, exFM_out, Add, task_output, activation). ----
-constexpr int kXdNets = DT_NET_LINEAR | DT_NET_DNN;
-
-struct XdLayout {
-    int n;
-    int L[kXdMaxLayers], Hk[kXdMaxLayers], lo[kXdMaxLayers], woff[kXdMaxLayers];
-    int P;                               // pooled channels = exFM_out's inputs
-    int64_t wex;                         // floats: exFM_out's kernel [P rounded up to 4] | its bias [4]
-    int64_t filt[kXdMaxLayers];          // bytes: layer k's packed filter (dt_cin_pack)
-    int64_t total;                       // bytes
-};
-
-// the layers' shapes (layers.py:655-687: direct=False halves every layer but the last) and the workspace behind the tower's
-// layouts; false when the CIN is outside what the launches take
-static bool xd_layout(int F, int CP, int n, const int* sizes, int direct, int mode, XdLayout* x) {
-    if (n < 1 || n > kXdMaxLayers || !sizes || F < 1 || F > 64) return false;
-    if (mode != DT_CIN_F32 && mode != DT_CIN_BF16 && mode != DT_CIN_BF16X3) return false;
-    x->n = n;
-    x->P = 0;
-    int hk = F;
-    for (int k = 0; k < n; ++k) {
-        const int Lk = sizes[k];
-        if (Lk < 1) return false;
-        const bool last = k == n - 1;
-        if (!direct && !last && (Lk & 1)) return false;
-        x->L[k] = Lk; x->Hk[k] = hk;
-        x->lo[k] = (direct || last) ? 0 : Lk / 2;
-        x->woff[k] = x->P;
-        x->P += Lk - x->lo[k];
-        hk = direct ? Lk : Lk / 2;
-    }
-    int64_t o = infer_ws_layout(CP, 0, kXdNets).total * (int64_t)sizeof(float);
-    x->wex = o / (int64_t)sizeof(float);
-    o += (((int64_t)x->P + 3) & ~(int64_t)3) * 4 + 16;
-    for (int k = 0; k < n; ++k) {
-        const int64_t nb = dt_cin_packed_bytes(mode, F, x->Hk[k], x->L[k]);
-        if (nb < 0) return false;
-        x->filt[k] = o;
-        o += nb;
-    }
-    x->total = o;
-    return true;
-}
-
-extern "C" int dt_xdeepfm_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int n_layers, const int* layer_sizes,
-                                          int direct, int use_residual, int reduce_D, int act, int cin_mode) {
-    DeepFmDims dm; int lpr;
-    XdLayout x;
-    if (use_residual || reduce_D || !dt_stack_infer_supported(F, D, Nd, H1, H2, cells, kXdNets)) return 0;
-    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr) || !xd_layout(F, dm.CP, n_layers, layer_sizes, direct, cin_mode, &x)) return 0;
-    for (int k = 0; k < x.n; ++k)
-        if (!dt_cin_fwd_supported(cin_mode, F, x.Hk[k], x.L[k], D, act)) return 0;
-    return 1;
-}
-
-extern "C" int64_t dt_xdeepfm_infer_workspace_bytes(int F, int D, int Nd, int n_layers, const int* layer_sizes, int direct,
-                                                    int cin_mode) {
-    DeepFmDims dm; int lpr;
-    XdLayout x;
-    if (!deepfm_dims(1, F, D, Nd, &dm, &lpr) || !xd_layout(F, dm.CP, n_layers, layer_sizes, direct, cin_mode, &x)) return -1;
-    return x.total;
-}
-
-extern "C" int dt_xdeepfm_infer_prepare(int F, int D, int Nd, const float* w_lin, const float* bn_gamma, const float* bn_beta,
-                                        const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1,
-                                        int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
-                                        const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var,
-                                        float c1_eps, const float* c2_gamma, const float* c2_beta, const float* c2_mean,
-                                        const float* c2_var, float c2_eps, const float* w3, const float* w_out,
-                                        const float* b_out, int n_layers, const int* layer_sizes, int direct, int cin_mode,
-                                        const float* const* cin_W, const float* w_ex, const float* b_ex, void* workspace,
-                                        void* stream) {
-    const char* who = "dt_xdeepfm_infer_prepare";
-    DeepFmDims dm; int lpr;
-    XdLayout x;
-    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", who, F, D, Nd);
-    DT_UNSUPPORTED(!xd_layout(F, dm.CP, n_layers, layer_sizes, direct, cin_mode, &x),
-                   "%s: CIN of %d layers, mode %d, F=%d (1..%d layers of >= 1 filters, even but the last with direct=0; F <= 64)",
-                   who, n_layers, cin_mode, F, kXdMaxLayers);
-    DT_REQUIRE(w_lin && w3 && w_out && cin_W && w_ex, "%s: null pointer (w_lin, w3, w_out, cin_W, w_ex)", who);
-    for (int k = 0; k < x.n; ++k) DT_REQUIRE(cin_W[k], "%s: cin_W[%d] is null", who, k);
-    const InferPrepArgs a{w_lin, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
-                          {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
-                          {c1_eps, c2_eps}, w3, w_out, b_out, nullptr, nullptr, 0, kXdNets};
-    int rc = infer_prepare(who, F, D, Nd, a, cells, workspace, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_xdeepfm_prep, dim3(ceil_div(x.P + 1, 256)), dim3(256), 0, as_stream(stream), w_ex, b_ex, x.P,
-                       reinterpret_cast<float*>(workspace) + x.wex);
-    rc = launch_status(who);
-    for (int k = 0; k < x.n && !rc; ++k)
-        rc = dt_cin_pack(cin_mode, cin_W[k], F, x.Hk[k], x.L[k], reinterpret_cast<char*>(workspace) + x.filt[k], stream);
-    return rc;
-}
-
-extern "C" int dt_xdeepfm_infer_tower(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
-                                      const int32_t* vocab, const float* dense, int B, int F, int D, int Nd,
-                                      const void* workspace, float* x0_out, float* partial_out, int* oob_count, int flags,
-                                      void* stream) {
-    DT_REQUIRE((flags & ~DT_INFER_TOWER_BF16) == 0, "dt_xdeepfm_infer_tower: flags 0x%x", flags);
-    DT_REQUIRE(B == 0 || x0_out, "dt_xdeepfm_infer_tower: x0_out is null");
-    return infer_run("dt_xdeepfm_infer_tower", idx, idx_kind, table, row_offset, vocab, dense, B, F, D, Nd, 0, workspace,
-                     partial_out, nullptr, oob_count, flags, stream, kXdNets, x0_out);
-}
-
-extern "C" int dt_xdeepfm_infer_cin(int layer, const float* x0, const float* y_prev, const float* bias, int act, int B, int F,
-                                    int D, int Nd, int n_layers, const int* layer_sizes, int direct, int cin_mode,
-                                    const void* workspace, float* y, void* stream) {
-    const char* who = "dt_xdeepfm_infer_cin";
-    DeepFmDims dm; int lpr;
-    XdLayout x;
-    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", who, F, D, Nd);
-    DT_UNSUPPORTED(!xd_layout(F, dm.CP, n_layers, layer_sizes, direct, cin_mode, &x), "%s: CIN of %d layers, mode %d, F=%d", who,
-                   n_layers, cin_mode, F);
-    DT_REQUIRE(layer >= 0 && layer < x.n && B >= 0, "%s: layer %d of %d, B=%d", who, layer, x.n, B);
-    if (B == 0) return DT_OK;
-    DT_REQUIRE(x0 && y && workspace && (layer == 0 || y_prev), "%s: null pointer", who);
-    // layer 0 crosses x0 with itself; layer k the leading Hk channels of layer k - 1's output, a view of its [B][L][D] rows
-    const float* xk = layer ? y_prev : x0;
-    const int64_t xk_bs = layer ? (int64_t)x.L[layer - 1] * D : (int64_t)F * D;
-    return dt_cin_layer_fwd_packed(cin_mode, x0, xk, reinterpret_cast<const char*>(workspace) + x.filt[layer], bias, act, B, F,
-                                   x.Hk[layer], x.L[layer], D, (int64_t)F * D, xk_bs, y, stream);
-}
-
-extern "C" int dt_xdeepfm_infer_head(const float* const* y, const float* partial, int B, int F, int D, int Nd, int n_layers,
-                                     const int* layer_sizes, int direct, int cin_mode, const void* workspace, float* logit_out,
-                                     float* out, int flags, void* stream) {
-    const char* who = "dt_xdeepfm_infer_head";
-    DeepFmDims dm; int lpr;
-    XdLayout x;
-    DT_UNSUPPORTED(!deepfm_dims(1, F, D, Nd, &dm, &lpr), "%s: unsupported shape F=%d D=%d Nd=%d", who, F, D, Nd);
-    DT_UNSUPPORTED(!xd_layout(F, dm.CP, n_layers, layer_sizes, direct, cin_mode, &x), "%s: CIN of %d layers, mode %d, F=%d", who,
-                   n_layers, cin_mode, F);
-    DT_REQUIRE(B >= 0 && (flags & ~DT_INFER_SIGMOID) == 0, "%s: B=%d flags 0x%x", who, B, flags);
-    if (B == 0) return DT_OK;
-    DT_REQUIRE(y && partial && workspace && logit_out, "%s: null pointer", who);
-    const float* ws = reinterpret_cast<const float*>(workspace);
-    XdHeadArgs a{};
-    for (int k = 0; k < x.n; ++k) {
-        DT_REQUIRE(y[k] && (uintptr_t)y[k] % 16 == 0, "%s: y[%d] null or not 16-byte aligned", who, k);
-        a.y[k] = y[k]; a.L[k] = x.L[k]; a.lo[k] = x.lo[k]; a.woff[k] = x.woff[k];
-    }
-    a.n = x.n;
-    a.wex = ws + x.wex;
-    a.bex = a.wex + ((x.P + 3) & ~3);
-    a.head = ws + infer_ws_layout(dm.CP, 0, kXdNets).head;
-    a.partial = partial; a.logit = logit_out; a.out = out;
-    a.sigmoid = (flags & DT_INFER_SIGMOID) ? 1 : 0;
-    a.B = B; a.D = D;
-    hipLaunchKernelGGL(k_xdeepfm_head, dim3(ceil_div(B, kXdHeadRows)), dim3(64 * kXdHeadRows), 0, as_stream(stream), a);
-    return launch_status(who);
 }

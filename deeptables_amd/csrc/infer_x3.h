@@ -1,5 +1,5 @@
 // infer_x3.h — DeepFM / DCN inference as ONE launch per batch (dt_deepfm_infer / dt_dcn_infer), plus the launch that writes
-// the weight layouts it reads (dt_*_infer_prepare).  Included by deepfm.hip inside namespace dt, after tower_x3.h.
+// the weight layouts it reads (dt_*_infer_prepare).  Included by infer.hip (the host side).
 // dt_stack_infer runs the same launches for every subset of {linear, fm_nets, dnn_nets}: k_infer with the absent terms
 // compiled out (template NETS) when there is a tower, k_infer_sparse (end of this file; no tile, no LDS) when there is none.
 //
@@ -26,6 +26,9 @@
 //                                 DCN: pb 2 * 48 * 16 * 4       the two K halves of P = [Xn ; b_j] . [w_l, w3c]
 // CP = 576 (C = 544): 131 KB (DeepFM), 140 KB (DCN) — the split tile serves every C the step's dims accept.
 #pragma once
+#include "x3_mfma.h"
+
+namespace dt {
 
 constexpr int kInferThreads = 512;
 constexpr int kNetAll = DT_NET_LINEAR | DT_NET_FM | DT_NET_DNN;   // the DeepFM graph; DCN's layouts are those of DT_NET_DNN
@@ -572,3 +575,5 @@ __global__ __launch_bounds__(256) void k_xdeepfm_prep(const float* __restrict__ 
     if (e < P) dst[e] = wex[e];
     else if (e == P) dst[((P + 3) & ~3)] = bex ? bex[0] : 0.f;
 }
+
+}  // namespace dt

@@ -1,5 +1,5 @@
 // tower_x3.h — kernel C of the pipelined DeepFM step with the Dense tower on SPLIT-bf16 matrix cores ("bf16 x 3").
-// Included by deepfm.hip inside namespace dt, after MlpParams / Part3 / DcnArgs / the k_mlp_fwd3 helpers.
+// Stands on its own: tile_common.h has MlpParams / Part3 / DcnArgs, x3_mfma.h the split-bf16 primitives.
 //
 // Why: gfx950 has no reduced-precision fp32 MFMA (no xf32); v_mfma_f32_32x32x2_f32 runs at 1/16 of the bf16 rate, and the
 // four GEMMs of the tile kernel (Dense128, Dense64, dH1 = dH2 W2^T, dXn = dH1 W1^T: 33 K cycles of fp32-MFMA time per
@@ -27,9 +27,9 @@
 // prep launch writes once per step (X3Weights).  The Xn parts' LDS rows are padded so that the 16 lanes of a ds_read_b128
 // group hit 16 distinct 16-byte bank groups (row stride / 16 B = 2 or 10 mod 16).
 #pragma once
+#include "x3_mfma.h"
 
-typedef __bf16 x3_b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 x3_b4 __attribute__((ext_vector_type(4)));
+namespace dt {
 
 struct X3Weights {
     // bf16 parts of the weights, part p of an array `lo` elements after part p - 1 (written by k_prep once per step):
@@ -39,38 +39,6 @@ struct X3Weights {
     const __bf16* W2R; int64_t w2r_lo;      // 2 parts, [128][64] row-major copy of W2: dH1's B operand
     const float* cwp;                       // DCN: [2 L + 1][CP] fp32, zero beyond C: cross kernels | cross biases | w3c
 };
-
-// a = h + l (16 mantissa bits) / a = h + m + l (all 24: exact)
-__device__ __forceinline__ void x3_split2(const float (&v)[8], x3_b8& h, x3_b8& l) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 a = (__bf16)v[e];
-        h[e] = a;
-        l[e] = (__bf16)(v[e] - (float)a);
-    }
-}
-__device__ __forceinline__ void x3_split3(const float (&v)[8], x3_b8& h, x3_b8& m, x3_b8& l) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const __bf16 a = (__bf16)v[e];
-        const float r1 = v[e] - (float)a;
-        const __bf16 b = (__bf16)r1;
-        h[e] = a; m[e] = b;
-        l[e] = (__bf16)(r1 - (float)b);
-    }
-}
-__device__ __forceinline__ x3_b8 x3_ld8(const __bf16* p) { return *reinterpret_cast<const x3_b8*>(p); }
-__device__ __forceinline__ void x3_ld8f(const float* p, float (&v)[8]) {
-    const floatx4 a = ld4(p), b = ld4(p + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
-}
-#define X3_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0)
-// the lower-order products of a split operand pair: left out in plain-bf16 mode (template ONE, DT_STEP_TOWER_BF16)
-#define X3_LO(acc, a, b)        \
-    do {                        \
-        if constexpr (!ONE) X3_MFMA(acc, a, b); \
-    } while (0)
 
 // LDS plan (bytes), CP = 64 NCH:
 //   xreg  3 * 32 * (CP + 16) * 2      Xn tile as three bf16 parts (GEMM1); afterwards: xhat / dXn fp32 [32][CP + 4], then
@@ -695,3 +663,5 @@ __global__ __launch_bounds__(512) void k_tower_x3(const float* __restrict__ X, M
     }
     DT_STAMP(stamps, 15);
 }
+
+}  // namespace dt

@@ -29,7 +29,7 @@ def _step_loss(dm):
     return None
 
 
-TILE_H1, TILE_H2 = 128, 64         # the tower widths the step's kernels are compiled for (csrc/deepfm.hip kH1 / kH2)
+TILE_H1, TILE_H2 = 128, 64         # the tower widths the step's kernels are compiled for (csrc/tile_common.h kH1 / kH2)
 
 
 def _tower_widths(dnn_params):
@@ -143,17 +143,19 @@ def _row_weights(sample_weight, y):
 def _step_dims(dm, net_layers, tower=_tower_widths):
     """(batch hint, F, D, Nd), the leading arguments of dt_*_supported, when the graph passes the checks both fused steps
     share — fixed-length columns, a loss the steps take, dropout rates in [0, 1), a tower of the compiled tile (`tower`:
-    the predicate of the steps or, for the inference plans, _infer_tower), the layers `net_layers` besides the embedding /
-    BN / output ones, one embedding group, at most one continuous column — else None"""
+    the predicate of the steps or, for the inference plans, _infer_tower; None: a graph without a tower, which has no
+    bn_concat_emb_dense either), the layers `net_layers` besides the embedding / BN / output ones, one embedding group,
+    at most one continuous column — else None"""
     c = dm.config
     if dm.var_len_categorical_columns or _step_loss(dm) is None:
         return None
     if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
         return None
-    if tower(c.dnn_params) is None:
+    if tower is not None and tower(c.dnn_params) is None:
         return None
     L = dm.model.layers_by_name
-    if any(n not in L for n in ('emb_categorical_vars_all', 'bn_concat_emb_dense', 'task_output') + tuple(net_layers)):
+    base = ('emb_categorical_vars_all', 'task_output') + (('bn_concat_emb_dense',) if tower is not None else ())
+    if any(n not in L for n in base + tuple(net_layers)):
         return None
     emb = L['emb_categorical_vars_all']
     if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
@@ -167,7 +169,7 @@ class FusedDeepFM:
     executor; the net-specific parts are the declarations and hooks marked 'net:' below."""
 
     NETS = {'linear', 'fm_nets', 'dnn_nets'}
-    takes_sample_weight = True                # the loss block scales each row's loss / dlogit (csrc/deepfm.hip DcnArgs.sw)
+    takes_sample_weight = True                # the loss block scales each row's loss / dlogit (csrc/tile_common.h DcnArgs.sw)
     # net: entry points dt_<PREFIX>_accum_floats / _accum_offsets / _workspace_bytes / _train_step / _train_step_adam, the
     # accumulator entries in dt_<PREFIX>_accum_offsets' order, the tower's two Dense layers
     PREFIX = 'deepfm'
@@ -763,9 +765,10 @@ class InferDeepFM:
             self.F, self.D, self.Nd, *self._net_args(), *self._tower_args(),
             *self._head_weights(), ptr(self.out.bias), ptr(self.ws), stream_ptr()), f'dt_{self.PREFIX}_infer_prepare')
 
-    def infer(self, idx, dense, logit, out=None):
-        """one batch: ids [B, F], dense [B, Nd] or None -> logit [B, 1] and, if given, out [B, 1] = the activated output
-        (contiguous float32 device buffers, e.g. row slices of one buffer for the whole call).  After `prepare`."""
+    @staticmethod
+    def _batch_args(idx, dense, logit, out):
+        """(B, ids as contiguous float32 / int32, their DT_IDX_* kind, dense as contiguous float32 or None) of one `infer`
+        call; refuses output buffers that are not contiguous float32 of B rows"""
         B = idx.shape[0]
         idx = idx.contiguous()
         if idx.dtype not in (torch.float32, torch.int32):
@@ -775,6 +778,12 @@ class InferDeepFM:
         for t in (logit, out):
             if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B):
                 raise ValueError(f'infer: outputs must be contiguous float32 buffers of {B} rows')
+        return B, idx, kind, dense
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch: ids [B, F], dense [B, Nd] or None -> logit [B, 1] and, if given, out [B, 1] = the activated output
+        (contiguous float32 device buffers, e.g. row slices of one buffer for the whole call).  After `prepare`."""
+        B, idx, kind, dense = self._batch_args(idx, dense, logit, out)
         check(self._entry('infer')(
             ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
             ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *self._dims(), ptr(self.ws), ptr(logit), ptr(out),
@@ -860,42 +869,32 @@ class InferStack(InferDeepFM):
 
     @classmethod
     def _net_layer_names(cls, mask, n_nets):
-        names = ('emb_categorical_vars_all', 'task_output')
+        names = ()
         if mask & _lib.DT_NET_LINEAR:
             names += ('linear_logit',)
         if mask & _lib.DT_NET_FM:
             names += ('fm_layer',)
         if mask & _lib.DT_NET_DNN:
             # (a last cell of width 1 in a graph of several nets has no dense_logit_dnn_nets: refused, as by InferDeepFM)
-            names += ('bn_concat_emb_dense', 'dnn_dense_1', 'dnn_dense_2') + (('dense_logit_dnn_nets',) if n_nets > 1 else ())
+            names += ('dnn_dense_1', 'dnn_dense_2') + (('dense_logit_dnn_nets',) if n_nets > 1 else ())
         return names
 
     @classmethod
     def eligible(cls, dm):
-        """the plan's own predicate: _step_dims' checks (the training plans keep theirs as it is) with the tower and its
-        layers asked for only when 'dnn_nets' is among the nets"""
+        """_step_dims' checks with the tower and its layers asked for only when 'dnn_nets' is among the nets"""
         c = dm.config
         try:
             mask = cls._mask(dm)
             if not mask or c.stacking_op != consts.STACKING_OP_ADD or getattr(c.distribute_strategy, 'sharded_embeddings', False):
                 return False
-            if dm.var_len_categorical_columns or _step_loss(dm) is None:
+            has_tower = bool(mask & _lib.DT_NET_DNN)
+            dims = _step_dims(dm, cls._net_layer_names(mask, len(c.nets)), _infer_tower if has_tower else None)
+            if dims is None:
                 return False
-            if not (0 <= float(c.dense_dropout or 0) < 1) or not (0 <= float(c.embedding_dropout or 0) < 1):
+            tower = _infer_tower(c.dnn_params) if has_tower else (0, 0, 0)
+            if tuple(dm.model.layers_by_name['task_output'].kernel.shape) != (tower[1] if mask == _lib.DT_NET_DNN else 1, 1):
                 return False
-            tower = _infer_tower(c.dnn_params) if mask & _lib.DT_NET_DNN else (0, 0, 0)
-            if tower is None:
-                return False
-            L = dm.model.layers_by_name
-            if any(n not in L for n in cls._net_layer_names(mask, len(c.nets))):
-                return False
-            emb = L['emb_categorical_vars_all']
-            if len(emb.groups) != 1 or len(dm.continuous_columns or []) > 1:
-                return False
-            if tuple(L['task_output'].kernel.shape) != (tower[1] if mask == _lib.DT_NET_DNN else 1, 1):
-                return False
-            Nd = sum(col.input_dim for col in (dm.continuous_columns or []))
-            return bool(lib().dt_stack_infer_supported(len(emb.input_dims), emb.groups[0][0], Nd, *tower, mask))
+            return bool(lib().dt_stack_infer_supported(*dims[1:], *tower, mask))
         except Exception:
             return False
 
@@ -1021,15 +1020,7 @@ class InferXDeepFM(InferDeepFM):
     def infer(self, idx, dense, logit, out=None):
         """one batch, as InferDeepFM.infer: the tower launch, one launch per CIN layer, the head.  Inside `run_batches` the
         scratch is the call's; a lone call allocates its own."""
-        B = idx.shape[0]
-        idx = idx.contiguous()
-        if idx.dtype not in (torch.float32, torch.int32):
-            idx = idx.to(torch.int32)
-        kind = _lib.DT_IDX_F32 if idx.dtype == torch.float32 else _lib.DT_IDX_I32
-        dense = None if dense is None else dense.to(torch.float32).contiguous()
-        for t in (logit, out):
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != B):
-                raise ValueError(f'infer: outputs must be contiguous float32 buffers of {B} rows')
+        B, idx, kind, dense = self._batch_args(idx, dense, logit, out)
         sc = self._scratch
         if sc is None or sc['rows'] < B:
             sc = self._alloc_scratch(B)

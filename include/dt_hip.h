@@ -654,7 +654,8 @@ int dt_deepfm_train_step_adam(const void* idx, int idx_kind, float* table, const
  * SUM_OVER_BATCH_SIZE reduction of the weighted per-sample losses). */
 unsigned dt_deepfm_dropout_hash(unsigned seed, unsigned b, unsigned col);
 
-/* ---- fused DeepFM / DCN inference: ONE launch per predict batch (replaces, for the graphs dt_*_infer_supported takes, the
+/* ---- fused DeepFM / DCN inference (csrc/infer.hip; kernels: csrc/infer_x3.h).
+ * ONE launch per predict batch (replaces, for the graphs dt_*_infer_supported takes, the
  * layer-by-layer forward that the reference's DeepModel.predict / evaluate run through keras Model.predict / evaluate,
  * deepmodel.py:134-175).  At inference BatchNormalization normalises with its moving statistics (Keras BN inference:
  * (x - moving_mean) / sqrt(moving_variance + eps) * gamma + beta), Dropout is the identity and every row's logit depends

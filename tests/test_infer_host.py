@@ -8,7 +8,7 @@ import pytest
 import torch
 
 H1, H2 = 128, 64
-# (F, D, Nd): the corners of the step's field / width domain (csrc/deepfm.hip deepfm_dims)
+# (F, D, Nd): the corners of the step's field / width domain (csrc/tile_common.h deepfm_dims)
 CORNERS = [(8, 64, 0), (7, 64, 64), (1, 4, 0), (1, 4, 64), (127, 4, 0), (128, 4, 32), (16, 16, 0), (32, 16, 32)]
 PAST = {'D = 128': (1, 128, 0), 'D = 12 (3 lanes)': (1, 12, 0), 'D = 0': (1, 0, 0), 'F D / 4 = 129': (129, 4, 0),
         'Nd = 65': (1, 4, 65), 'C = 545': (32, 16, 33), 'F = 0': (0, 4, 4)}
