@@ -202,6 +202,12 @@ SIGNATURES = {
                                       _c_int, _ptr, _ptr, _ptr]),
     'dt_xdeepfm_infer_head': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _c_int, _ptr, _ptr,
                                        _ptr, _c_int, _ptr]),
+    # AutoInt inference: prepare once (per-layer HOST arrays of device pointers), then one launch per batch
+    'dt_autoint_infer_supported': (_c_int, [_c_int] * 6),
+    'dt_autoint_infer_workspace_bytes': (_c_i64, [_c_int] * 3),
+    'dt_autoint_infer_prepare': (_c_int, [_c_int] * 3 + [_ptr] * 12 + [_c_f32, _ptr, _ptr, _ptr, _ptr]),
+    'dt_autoint_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
+                                  _ptr, _ptr, _c_int, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -217,6 +223,7 @@ DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
 DT_NET_LINEAR, DT_NET_FM, DT_NET_DNN = 0x1, 0x2, 0x4
 DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
 DT_XDEEPFM_MAX_LAYERS = 8
+DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)

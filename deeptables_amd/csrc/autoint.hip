@@ -1247,6 +1247,273 @@ __global__ __launch_bounds__(1024) void k_autoint_head_finish(const float* __res
     }
 }
 
+// ---- fused AutoInt inference (dt_autoint_infer*): the table gather, every interacting layer with its inference
+// BatchNormalization, Flatten, the task_output Dense and the activation of nets = ['autoint_nets'] in ONE launch per batch ----
+// At inference BatchNormalization is the per-channel map s a + t over the MOVING statistics, the attention dropout is the
+// identity and a row's logit depends on that row alone, so a wave keeps its row in its LDS slab from the gather to the logit:
+// layer l > 0 reads its A operand back from the slab's first D columns (layer l - 1's output a, over the dead Q columns) and
+// normalises it with layer l - 1's (s, t) while loading (ai_xn_rows), the head reads the top layer's a the same way.  HBM
+// traffic per row: the ids, the F table rows, 4 (8) bytes of output.
+//
+// Every layer's weights sit in the block's LDS (a wave of k_autoint_fwd holds ONE layer's Wcat in D^2 / 16 registers for its
+// whole life; here it needs n_layers of them).  The workspace dt_autoint_infer_prepare writes IS the LDS image, so the
+// prologue is one straight copy and one __syncthreads(), the only barrier of the kernel:
+//   per layer l (ai_inf_layer(D) floats):  Wcat [D][WS = 4 D + 4] (columns >= NP D: zero) | bcat [4 D] | s [D] | t [D]
+//                                          s = gamma / sqrt(moving_variance + eps), t = beta - moving_mean s
+//   head:  w' [32 D] | c0 | 3 floats of padding.  The top layer's normalisation is FOLDED into the head by `prepare`:
+//          w'[i D + c] = s_L[c] w[i D + c] (zero beyond F D) and c0 = sum_{i,c} t_L[c] w[i D + c] + bias (summed in double), so
+//          z = sum_{i < F, c < D} a[i][c] w'[i D + c] + c0.
+// LDS (bytes) = 4 (n_layers ai_inf_layer(D) + 32 D + 4) + W slabs of 32 (4 D + 4) 4, W = the largest of 8 / 6 / 4 waves that
+// fits 160 KiB:            D = 32: layer 17,664, head 4,112, slab 16,896     D = 16: layer 4,736, head 2,064, slab 8,704
+//   n_layers    1        2        3        4        5        6   |   1 .. 8
+//   W           8        6        6        4        4        -   |   8
+//   LDS   156,944  140,816  158,480  142,352  160,016  (> 160 KiB: refused)   |   76,432 .. 109,584
+// The projections are ai_project_lds, the layer kernels' own products operation for operation in all three modes; scores,
+// softmax and P V are k_autoint_fwd's with DROP = false and no lse (restated here: the training kernels' source is untouched).
+constexpr size_t kAiLdsMax = 160 * 1024;
+__host__ __device__ constexpr int ai_inf_layer(int D) { return D * (4 * D + kAiPad) + 6 * D; }
+__host__ __device__ constexpr int ai_inf_consts(int D, int L) { return L * ai_inf_layer(D) + 32 * D + 4; }
+__host__ __device__ constexpr size_t ai_inf_lds(int D, int L, int W) {
+    return ((size_t)ai_inf_consts(D, L) + (size_t)W * 32 * (4 * D + kAiPad)) * sizeof(float);
+}
+// waves per block for (D, n_layers); 0: not even four fit
+inline int ai_inf_waves(int D, int L) {
+    for (int W = 8; W >= 4; W -= 2)
+        if (ai_inf_lds(D, L, W) <= kAiLdsMax) return W;
+    return 0;
+}
+
+struct AiInferIo {
+    const void* idx;
+    int kind;
+    const float* table;
+    const int64_t* row_offset;
+    const int32_t* vocab;
+    float* logit;
+    float* out;              // NULL: logits only
+    int* oob;                // NULL: not counted
+    int sigmoid;
+};
+
+// the per-layer HOST pointer arrays of dt_autoint_infer_prepare, by value
+struct AiInferPrep {
+    const float* W[DT_AUTOINT_INFER_MAX_LAYERS][4];
+    const float* b[DT_AUTOINT_INFER_MAX_LAYERS][4];
+    const float *gamma[DT_AUTOINT_INFER_MAX_LAYERS], *beta[DT_AUTOINT_INFER_MAX_LAYERS];     // entries may be NULL (1 / 0)
+    const float *mm[DT_AUTOINT_INFER_MAX_LAYERS], *mv[DT_AUTOINT_INFER_MAX_LAYERS];
+    float eps;
+    const float *w_out, *b_out;                                                              // b_out may be NULL
+    int F, D, NP, L;
+};
+
+// block l < L: layer l's image; block L: the head.  Every value is read here, at call time.
+__global__ __launch_bounds__(256) void k_autoint_infer_prep(AiInferPrep a, float* __restrict__ ws) {
+    const int D = a.D, WS = 4 * D + kAiPad, M = a.NP * D, t = threadIdx.x, l = blockIdx.x;
+    if (l < a.L) {
+        float* dst = ws + (int64_t)l * ai_inf_layer(D);
+        for (int e = t; e < D * WS; e += 256) {
+            const int k = e / WS, m = e - k * WS;
+            dst[e] = m < M ? a.W[l][m / D][k * D + (m % D)] : 0.f;
+        }
+        for (int m = t; m < 4 * D; m += 256) dst[D * WS + m] = m < M ? a.b[l][m / D][m % D] : 0.f;
+        for (int c = t; c < D; c += 256) {
+            const float sc = (1.0f / sqrtf(a.mv[l][c] + a.eps)) * (a.gamma[l] ? a.gamma[l][c] : 1.f);    // ai_xn_fill's arithmetic
+            dst[D * WS + 4 * D + c] = sc;
+            dst[D * WS + 5 * D + c] = (a.beta[l] ? a.beta[l][c] : 0.f) - a.mm[l][c] * sc;
+        }
+        return;
+    }
+    __shared__ double red[256];
+    float* dst = ws + (int64_t)a.L * ai_inf_layer(D);
+    const int top = a.L - 1;
+    double part = 0.0;
+    for (int k = t; k < 32 * D; k += 256) {
+        float wv = 0.f;
+        if (k < a.F * D) {
+            const int c = k % D;
+            const float sc = (1.0f / sqrtf(a.mv[top][c] + a.eps)) * (a.gamma[top] ? a.gamma[top][c] : 1.f);
+            const float sh = (a.beta[top] ? a.beta[top][c] : 0.f) - a.mm[top][c] * sc;
+            wv = sc * a.w_out[k];
+            part += (double)sh * (double)a.w_out[k];
+        }
+        dst[k] = wv;
+    }
+    red[t] = part;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) red[t] += red[t + o];
+        __syncthreads();
+    }
+    if (t < 4) dst[32 * D + t] = t == 0 ? (float)(red[0] + (a.b_out ? (double)a.b_out[0] : 0.0)) : 0.f;
+}
+
+// the table rows of one batch row as the projections' A operand (ai_load_x's layout: xa[T][t] = x[16T + n][(D/4) q + t], rows >= F
+// repeat row F - 1), straight from the packed table.  Ids as k_infer / k_infer_sparse decode them: the load is unconditional
+// from a clamped address (row 0 for an out-of-range id; the caller zeroes it by `ok` when it consumes xa), the out-of-range
+// lookup is counted once (the q = 0 lane of a real field).
+template <int D>
+__device__ __forceinline__ void ai_gather(const AiInferIo& io, const int (&id)[2], const int (&voc)[2], const int64_t (&roff)[2],
+                                          int F, int n, int q, float (&xa)[2][D / 4], unsigned& ok) {
+    ok = 0;
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+        const bool in = (unsigned)id[T] < (unsigned)voc[T];
+        ok |= (in ? 1u : 0u) << T;
+        const float* p = io.table + (in ? roff[T] + id[T] : (int64_t)0) * D + (D / 4) * q;
+#pragma unroll
+        for (int t = 0; t < D / 4; t += 4) {
+            const ai_f4 v = *reinterpret_cast<const ai_f4*>(p + t);
+            xa[T][t] = v.x; xa[T][t + 1] = v.y; xa[T][t + 2] = v.z; xa[T][t + 3] = v.w;
+        }
+        if (!in && q == 0 && 16 * T + n < F && io.oob) atomicAdd(io.oob, 1);
+    }
+}
+
+template <int D, int DH, int BF>
+__global__ __launch_bounds__(512) void k_autoint_infer(AiInferIo io, int B, int F, int NP, int L, const float* __restrict__ ws) {
+    using C = AiCfg<D, DH>;
+    constexpr int WS = 4 * D + kAiPad, LW = ai_inf_layer(D);
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+    const int n = lane & 15, q = lane >> 4;
+    const int nc = ai_inf_consts(D, L);
+    for (int e = threadIdx.x; e < nc / 4; e += blockDim.x)
+        reinterpret_cast<ai_f4*>(lds)[e] = reinterpret_cast<const ai_f4*>(ws)[e];
+    __syncthreads();                                        // the only barrier: nothing below reads another wave's data
+    float* ys = lds + nc + wave * 32 * C::YS;
+    const float* hw = lds + L * LW;                         // [32 D] w' | c0
+    const float c0 = hw[32 * D];
+    const float scale = 1.0f / sqrtf((float)DH);
+    const int64_t nwaves = (int64_t)gridDim.x * W;
+    // the lane's two fields, their vocabulary sizes and first table rows: the same for every batch row
+    int fld[2], voc[2];
+    int64_t roff[2];
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+        fld[T] = min(16 * T + n, F - 1);
+        voc[T] = io.vocab[fld[T]];
+        roff[T] = io.row_offset[fld[T]];
+    }
+    auto load_ids = [&](int64_t row, int (&id)[2]) {
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+            id[T] = io.kind == DT_IDX_F32 ? load_id<DT_IDX_F32>(io.idx, row * F + fld[T])
+                                          : load_id<DT_IDX_I32>(io.idx, row * F + fld[T]);
+    };
+    // the chain is ids -> table rows -> projection, so two rows are in flight behind the one being attended: the table rows
+    // of b + nwaves (xnx) and the ids of b + 2 nwaves (idn)
+    float xa[2][C::TK], xnx[2][C::TK];
+    int idn[2] = {0, 0};
+    unsigned okc = 0, okn = 0;
+    int64_t b = (int64_t)blockIdx.x * W + wave;
+    if (b < B) {
+        int id0[2];
+        load_ids(b, id0);
+        ai_gather<D>(io, id0, voc, roff, F, n, q, xa, okc);
+    }
+    if (b + nwaves < B) load_ids(b + nwaves, idn);
+    for (; b < B; b += nwaves) {
+        const bool more = b + nwaves < B;
+        if (more) ai_gather<D>(io, idn, voc, roff, F, n, q, xnx, okn);
+        if (b + 2 * nwaves < B) load_ids(b + 2 * nwaves, idn);
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int t = 0; t < C::TK; ++t) xa[T][t] = (okc >> T) & 1u ? xa[T][t] : 0.f;     // an out-of-range id: the zero row
+#pragma unroll 1
+        for (int l = 0; l < L; ++l) {
+            const float* wl = lds + l * LW;
+            if (l > 0) {
+                // layer l - 1's output (un-normalised, in the slab's first D columns) as the A operand, normalised on the way
+#pragma unroll
+                for (int T = 0; T < 2; ++T) {
+                    const float* p = ys + min(16 * T + n, F - 1) * C::YS + C::TK * q;
+#pragma unroll
+                    for (int t = 0; t < C::TK; t += 4) {
+                        const ai_f4 v = *reinterpret_cast<const ai_f4*>(p + t);
+                        xa[T][t] = v.x; xa[T][t + 1] = v.y; xa[T][t + 2] = v.z; xa[T][t + 3] = v.w;
+                    }
+                }
+                ai_xn_rows<D>(wl - LW + D * WS + 4 * D, q, xa);
+                ai_fence();                                 // the reads are done before the projection overwrites the slab
+            }
+            float br[D / 4];
+#pragma unroll
+            for (int ct = 0; ct < D / 4; ++ct) br[ct] = wl[D * WS + 16 * ct + n];
+            ai_project_lds<D, BF>(xa, wl, WS, br, NP, ys, n, q);
+            ai_fence();
+#pragma unroll
+            for (int h = 0; h < C::H; ++h) {
+                ai_f4 st[2][2];
+                ai_tiles<DH>(ys, C::YS, D + DH * h, DH * h, n, q, st);         // A = K_h, B = Q_h
+#pragma unroll
+                for (int I = 0; I < 2; ++I) {               // k_autoint_fwd's lane-local softmax (DROP = false, no lse)
+                    float m = -3.0e38f;
+#pragma unroll
+                    for (int J = 0; J < 2; ++J)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const bool ok = 16 * J + 4 * q + r < F;
+                            st[J][I][r] = ok ? st[J][I][r] * scale : -3.0e38f;
+                            m = fmaxf(m, st[J][I][r]);
+                        }
+                    m = ai_qmax(m);
+                    float lsum = 0.f;
+#pragma unroll
+                    for (int J = 0; J < 2; ++J)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float e = 16 * J + 4 * q + r < F ? __expf(st[J][I][r] - m) : 0.f;
+                            st[J][I][r] = e;
+                            lsum += e;
+                        }
+                    lsum = ai_qsum(lsum);
+                    const float inv = 1.0f / lsum;
+#pragma unroll
+                    for (int J = 0; J < 2; ++J)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) st[J][I][r] *= inv;
+                }
+                ai_f4 o[2];
+                ai_apply<DH>(st, ys, C::YS, 2 * D + DH * h, n, q, o);          // O_h = P V_h
+                if (n < DH) {
+#pragma unroll
+                    for (int I = 0; I < 2; ++I)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int i = 16 * I + 4 * q + r;
+                            const float res = NP == 4 ? ys[i * C::YS + 3 * D + DH * h + n] : 0.f;
+                            ys[i * C::YS + DH * h + n] = fmaxf(o[I][r] + res, 0.f);    // over Q_h, which is dead now
+                        }
+                }
+            }
+            ai_fence();
+        }
+        // Flatten -> task_output over the top layer's rows (its normalisation is folded into w' and c0)
+        float acc = 0.f;
+        for (int e = lane; e < F * (D / 4); e += 64) {
+            const int i = e / (D / 4), c4 = e - i * (D / 4);
+            const ai_f4 v = *reinterpret_cast<const ai_f4*>(ys + i * C::YS + 4 * c4);
+            const ai_f4 w = *reinterpret_cast<const ai_f4*>(hw + 4 * e);
+            acc += (v.x * w.x + v.y * w.y) + (v.z * w.z + v.w * w.w);
+        }
+        acc = wave_sum(acc);
+        if (lane == 0) {
+            const float lg = acc + c0;
+            io.logit[b] = lg;
+            if (io.out) io.out[b] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+        }
+        ai_fence();
+        if (more) {
+#pragma unroll
+            for (int T = 0; T < 2; ++T)
+#pragma unroll
+                for (int t = 0; t < C::TK; ++t) xa[T][t] = xnx[T][t];
+            okc = okn;
+        }
+    }
+}
+
 }  // namespace dt
 
 using namespace dt;
@@ -1530,4 +1797,96 @@ extern "C" int dt_autoint_head_bwd(const float* a, const float* w, const float* 
     const AiXn xn{xn_mean, xn_rstd, xn_gamma, xn_beta};
     hipLaunchKernelGGL(k_autoint_head_finish, dim3((K + 63) / 64), dim3(1024), 0, st, part, blocks, K, D, w, xn, gW, gb, bn_sums);
     return launch_status("dt_autoint_head_bwd");
+}
+
+// ---- fused AutoInt inference: one launch per predict batch (include/dt_hip.h: what it replaces of the reference) ----
+static bool ai_inf_mode_ok(int D, int mfma_mode) {
+    return mfma_mode == DT_AI_F32 || ((mfma_mode == DT_AI_BF16 || mfma_mode == DT_AI_BF16X2) && D == 32);
+}
+
+extern "C" int dt_autoint_infer_supported(int F, int D, int H, int n_layers, int use_residual, int mfma_mode) {
+    if (!dt_autoint_supported(F, D, H) || !ai_inf_mode_ok(D, mfma_mode)) return 0;
+    if (n_layers < 1 || n_layers > DT_AUTOINT_INFER_MAX_LAYERS || (use_residual != 0 && use_residual != 1)) return 0;
+    return ai_inf_waves(D, n_layers) ? 1 : 0;
+}
+
+extern "C" int64_t dt_autoint_infer_workspace_bytes(int F, int D, int n_layers) {
+    if (F < 1 || F > 32 || (D != 16 && D != 32) || n_layers < 1 || n_layers > DT_AUTOINT_INFER_MAX_LAYERS) return -1;
+    if (!ai_inf_waves(D, n_layers)) return -1;
+    return (int64_t)ai_inf_consts(D, n_layers) * (int64_t)sizeof(float);
+}
+
+extern "C" int dt_autoint_infer_prepare(int F, int D, int n_layers, const float* const* Wq, const float* const* Wk,
+                                        const float* const* Wv, const float* const* Wr, const float* const* bq,
+                                        const float* const* bk, const float* const* bv, const float* const* br,
+                                        const float* const* bn_gamma, const float* const* bn_beta,
+                                        const float* const* bn_mean, const float* const* bn_var, float bn_eps,
+                                        const float* w_out, const float* b_out, void* workspace, void* stream) {
+    DT_UNSUPPORTED(dt_autoint_infer_workspace_bytes(F, D, n_layers) < 0, "dt_autoint_infer_prepare: unsupported shape F=%d D=%d n_layers=%d", F, D, n_layers);
+    DT_REQUIRE(Wq && Wk && Wv && bq && bk && bv && bn_mean && bn_var && w_out && workspace, "dt_autoint_infer_prepare: null pointer");
+    DT_REQUIRE(bn_eps >= 0.f, "dt_autoint_infer_prepare: bn_eps %f", bn_eps);
+    // the residual projection is there for every layer or for none (Wr == NULL or NULL entries: none)
+    const bool res = Wr && Wr[0];
+    DT_REQUIRE(!res || br, "dt_autoint_infer_prepare: residual kernels without biases");
+    AiInferPrep a;
+    memset(&a, 0, sizeof(a));
+    for (int l = 0; l < n_layers; ++l) {
+        const float* Ws[4] = {Wq[l], Wk[l], Wv[l], res ? Wr[l] : nullptr};
+        const float* bs[4] = {bq[l], bk[l], bv[l], res ? br[l] : nullptr};
+        for (int p = 0; p < 4; ++p) {
+            DT_REQUIRE((p == 3 && !res) || (Ws[p] && bs[p]), "dt_autoint_infer_prepare: layer %d: null weight pointer", l);
+            a.W[l][p] = Ws[p];
+            a.b[l][p] = bs[p];
+        }
+        DT_REQUIRE(res || !Wr || !Wr[l], "dt_autoint_infer_prepare: layer %d: a residual kernel in a graph without", l);
+        DT_REQUIRE(bn_mean[l] && bn_var[l], "dt_autoint_infer_prepare: layer %d: null moving statistics", l);
+        a.gamma[l] = bn_gamma ? bn_gamma[l] : nullptr;
+        a.beta[l] = bn_beta ? bn_beta[l] : nullptr;
+        a.mm[l] = bn_mean[l];
+        a.mv[l] = bn_var[l];
+    }
+    a.eps = bn_eps;
+    a.w_out = w_out;
+    a.b_out = b_out;
+    a.F = F; a.D = D; a.NP = res ? 4 : 3; a.L = n_layers;
+    hipLaunchKernelGGL(k_autoint_infer_prep, dim3(n_layers + 1), dim3(256), 0, as_stream(stream), a, static_cast<float*>(workspace));
+    return launch_status("dt_autoint_infer_prepare");
+}
+
+#define DT_AI_INFER_LAUNCH(DV, HV, BFV)                                                                                     \
+    do {                                                                                                                    \
+        hipFuncSetAttribute((const void*)k_autoint_infer<DV, HV, BFV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_autoint_infer<DV, HV, BFV>), dim3(blocks), dim3(64 * W), lds, st, io, (int)B, F, NP, n_layers, \
+                           static_cast<const float*>(workspace));                                                           \
+    } while (0)
+#define DT_AI_INFER_MODES(DV, HV)                                        \
+    do {                                                                 \
+        if (mfma_mode == DT_AI_BF16X2) DT_AI_INFER_LAUNCH(DV, HV, 2);    \
+        else if (mfma_mode == DT_AI_BF16) DT_AI_INFER_LAUNCH(DV, HV, 1); \
+        else DT_AI_INFER_LAUNCH(DV, HV, 0);                              \
+    } while (0)
+
+extern "C" int dt_autoint_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                                const int32_t* vocab, int64_t B, int F, int D, int H, int n_layers, int NP,
+                                const void* workspace, float* logit_out, float* out, int* oob_count, int flags,
+                                int mfma_mode, void* stream) {
+    DT_UNSUPPORTED(NP != 3 && NP != 4, "dt_autoint_infer: NP=%d (3: q | k | v, 4: with the residual projection)", NP);
+    DT_UNSUPPORTED(!dt_autoint_infer_supported(F, D, H, n_layers, NP == 4, mfma_mode), "dt_autoint_infer: unsupported F=%d D=%d H=%d n_layers=%d mfma_mode=%d", F, D, H, n_layers, mfma_mode);
+    DT_REQUIRE(idx_kind == DT_IDX_F32 || idx_kind == DT_IDX_I32, "dt_autoint_infer: idx_kind %d", idx_kind);
+    DT_REQUIRE((flags & ~DT_INFER_SIGMOID) == 0, "dt_autoint_infer: flags %#x (DT_INFER_SIGMOID or 0)", flags);
+    if (B == 0) return DT_OK;
+    DT_REQUIRE(B > 0 && B < (1LL << 31), "dt_autoint_infer: bad batch");
+    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "dt_autoint_infer: null pointer");
+    const int W = ai_inf_waves(D, n_layers), dh = D / H;
+    const size_t lds = ai_inf_lds(D, n_layers, W);
+    int blocks = (int)((B + W - 1) / W);
+    if (blocks > DT_AUTOINT_INFER_MAX_BLOCKS) blocks = DT_AUTOINT_INFER_MAX_BLOCKS;
+    hipStream_t st = as_stream(stream);
+    const AiInferIo io{idx, idx_kind, table, row_offset, vocab, logit_out, out, oob_count, (flags & DT_INFER_SIGMOID) ? 1 : 0};
+    if (D == 32 && dh == 8) DT_AI_INFER_MODES(32, 8);
+    else if (D == 32) DT_AI_INFER_MODES(32, 16);
+    else if (dh == 4) DT_AI_INFER_LAUNCH(16, 4, 0);
+    else if (dh == 8) DT_AI_INFER_LAUNCH(16, 8, 0);
+    else DT_AI_INFER_LAUNCH(16, 16, 0);
+    return launch_status("dt_autoint_infer");
 }

@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
-from .ops import SparseRowGrad
+from .ops import SparseRowGrad, autoint_mfma_mode
 from .utils import consts
 
 def _step_loss(dm):
@@ -1045,10 +1045,103 @@ class InferXDeepFM(InferDeepFM):
             self._scratch = None
 
 
+class InferAutoInt(InferDeepFM):
+    """Inference plan for the AutoInt graph (nets ['autoint_nets'] alone, deepnets.py:210-224): ONE launch per batch
+    (dt_autoint_infer, csrc/autoint.hip k_autoint_infer) — the table gather, every interacting layer with its inference
+    BatchNormalization, Flatten, task_output and the activation; a wave keeps its batch row in LDS from the gather to the
+    logit.  `prepare` hands the layers' tensors over as they are at that moment (host arrays of device pointers, one launch):
+    the plan holds no copy of any parameter between calls.  The net does not read the continuous columns, so `dense` is
+    ignored (never dereferenced).
+    Refused (the layer path runs): multiclass, 'autoint_nets' beside any other net, concat stacking, var-len columns, several
+    embedding groups, sharded embeddings, interacting layers that differ in their parameters, shapes outside
+    dt_autoint_supported (F <= 32, embedding size 16 / 32, d_h in {4, 8, 16}), more layers than the LDS holds, a precision mode
+    the embedding size does not take, DT_AMD_FUSED=0 / DT_AMD_FUSED_PREDICT=0."""
+
+    PREFIX = 'autoint'
+
+    @staticmethod
+    def _mha_layers(dm):
+        from .models.layers import MultiheadAttention
+        return [l for l in dm.model.layers_by_name.values() if isinstance(l, MultiheadAttention)]
+
+    @staticmethod
+    def _mode(mha, D):
+        """the layers' precision mode as the layer path reads it (raises for a request the embedding size does not take)"""
+        return autoint_mfma_mode(mha[0].params.get('mfma_dtype'), D)
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            if list(c.nets) != ['autoint_nets'] or c.stacking_op != consts.STACKING_OP_ADD or \
+                    getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            dims = _step_dims(dm, (), tower=None)
+            mha = cls._mha_layers(dm)
+            if dims is None or not mha:
+                return False
+            _, F, D, _ = dims
+            first = mha[0]
+            same = all(l.params == first.params and l.num_heads == first.num_heads and l.num_units == D and
+                       bool(l.use_residual) == bool(first.use_residual) and
+                       float(l.batch_normalize.epsilon) == float(first.batch_normalize.epsilon) for l in mha)
+            if not same or len(mha) != int(c.autoint_params['num_attention']):
+                return False
+            if tuple(dm.model.layers_by_name['task_output'].kernel.shape) != (F * D, 1):
+                return False
+            return bool(lib().dt_autoint_infer_supported(F, D, int(first.num_heads), len(mha), 1 if first.use_residual else 0,
+                                                         cls._mode(mha, D)))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.bn = self.cells = None
+
+    def _net_layers(self, L):
+        self.mha = self._mha_layers(self.dm)
+        self.n_layers = len(self.mha)
+        self.H = int(self.mha[0].num_heads)
+        self.NP, self.mode = 4 if self.mha[0].use_residual else 3, _lib.DT_AI_F32
+
+    def _dims(self):
+        """dt_autoint_infer_workspace_bytes' arguments"""
+        return self.F, self.D, self.n_layers
+
+    def prepare(self):
+        """the layers' tensors as they are now -> the workspace (= the kernel's LDS image), one launch; also reads the
+        precision mode, the residual switch and the output activation (the arguments of the `infer` calls that follow)"""
+        n = self.n_layers
+        self.flags = _lib.DT_INFER_SIGMOID if self.dm.output_activation == 'sigmoid' else 0
+        self.mode = self._mode(self.mha, self.D)
+        res = bool(self.mha[0].use_residual)
+        self.NP = 4 if res else 3
+
+        def arr(tensors):
+            return ctypes.cast((ctypes.c_void_p * n)(*[None if t is None else t.data_ptr() for t in tensors]), ctypes.c_void_p)
+
+        projs = [[l.dense_Q, l.dense_K, l.dense_V, l.dense_residual if res else None] for l in self.mha]
+        kernels = [arr([None if p[k] is None else p[k].kernel for p in projs]) for k in range(4)]
+        biases = [arr([None if p[k] is None else p[k].bias for p in projs]) for k in range(4)]
+        bns = [l.batch_normalize for l in self.mha]
+        stats = [arr([getattr(b, a) for b in bns]) for a in ('gamma', 'beta', 'moving_mean', 'moving_variance')]
+        check(self._entry('infer_prepare')(self.F, self.D, n, *kernels, *biases, *stats, float(bns[0].epsilon),
+                                           ptr(self.out.kernel), ptr(self.out.bias), ptr(self.ws), stream_ptr()),
+              'dt_autoint_infer_prepare')
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch, as InferDeepFM.infer: ids [B, F] -> logit [B, 1] and, if given, out [B, 1]; `dense` is not read"""
+        B, idx, kind, _ = self._batch_args(idx, None, logit, out)
+        check(self._entry('infer')(
+            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
+            ptr(getattr(self.emb, f'vocab_{self.key}')), B, self.F, self.D, self.H, self.n_layers, self.NP, ptr(self.ws),
+            ptr(logit), ptr(out), ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, self.mode,
+            stream_ptr()), 'dt_autoint_infer')
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM):
+    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt):
         if plan.eligible(dm):
             return plan(dm)
     return None

@@ -802,6 +802,44 @@ int dt_xdeepfm_infer_head(const float* const* y, const float* partial, int B, in
                           const int* layer_sizes, int direct, int cin_mode, const void* workspace, float* logit_out,
                           float* out, int flags, void* stream);
 
+/* ---- fused AutoInt inference: ONE launch per predict batch (csrc/autoint.hip k_autoint_infer; replaces, for nets =
+ * ['autoint_nets'] alone, the layer-by-layer forward of the reference's DeepModel.predict / evaluate, deepmodel.py:134-175:
+ * the embedding gather (layers.py:889-904), deepnets.py:210-224 `autoint_nets` — per interacting layer MultiheadAttention.call,
+ * layers.py:119-153, with its BatchNormalization :151 on the moving statistics and its Dropout :141 as the identity — Flatten,
+ * and the head deepmodel.py:131-143 / 286-301: task_output over [F D] and the activation).
+ *   A wave keeps one batch row in its LDS slab from the gather to the logit; every layer's weights sit in the block's LDS.
+ *   All n_layers layers share F, D, H, NP and mfma_mode (DT_AI_*: the projections are the layer kernel's own products).
+ *   dt_autoint_infer_supported: 1 iff dt_autoint_supported(F, D, H), mfma_mode is valid for D (the bf16 modes: D = 32), 1 <=
+ *     n_layers <= DT_AUTOINT_INFER_MAX_LAYERS, use_residual in {0, 1}, and four waves' slabs plus all layers' weights fit the
+ *     160 KiB of LDS: D = 32 takes up to 5 layers (6 do not fit), D = 16 all DT_AUTOINT_INFER_MAX_LAYERS.
+ *   dt_autoint_infer_workspace_bytes: size of `workspace` (16-byte aligned), -1 outside that domain.
+ *   dt_autoint_infer_prepare (once per predict / evaluate, one launch; replaces nothing of the reference: it writes what the
+ *     batch launches read, from the values the tensors hold at call time): Wq / Wk / Wv / Wr, bq / bk / bv / br = HOST arrays
+ *     of n_layers device pointers, layer l's dense_Q / dense_K / dense_V / dense_residual kernel [D][D] and bias [D]
+ *     (use_residual = False: Wr / br NULL or arrays of NULLs -> NP = 3); bn_gamma / bn_beta / bn_mean / bn_var = HOST arrays of
+ *     the layers' BatchNormalization gamma, beta (arrays or entries may be NULL: 1 / 0), moving_mean, moving_variance [D];
+ *     bn_eps their epsilon; w_out [F D] / b_out (NULL: none) = task_output's kernel and bias.  The TOP layer's
+ *     normalisation is folded into the head here: w'[i D + c] = s[c] w_out[i D + c], c0 = sum t[c] w_out[i D + c] + b_out
+ *     (s = gamma / sqrt(var + eps), t = beta - mean s); the layers below keep (s, t) and are normalised when the next
+ *     layer loads them.
+ *   dt_autoint_infer (per batch of B >= 0 rows, B < 2^31; B = 0: no launch): ids [B][F] (idx_kind = DT_IDX_*; an id outside
+ *     [0, vocab[f]) reads a zero row and is counted once into *oob_count when it is given) -> logit_out [B] and, if out !=
+ *     NULL, out [B] = sigmoid(logit) with flags = DT_INFER_SIGMOID or the logit with flags = 0.  NP = 4 with the residual
+ *     projection, else 3, as prepared.  The grid is at most DT_AUTOINT_INFER_MAX_BLOCKS blocks of 8 / 6 / 4 waves (the most
+ *     that fit the LDS); a wave strides over the batch rows. */
+#define DT_AUTOINT_INFER_MAX_LAYERS 8
+#define DT_AUTOINT_INFER_MAX_BLOCKS 256
+int dt_autoint_infer_supported(int F, int D, int H, int n_layers, int use_residual, int mfma_mode);
+int64_t dt_autoint_infer_workspace_bytes(int F, int D, int n_layers);
+int dt_autoint_infer_prepare(int F, int D, int n_layers, const float* const* Wq, const float* const* Wk,
+                             const float* const* Wv, const float* const* Wr, const float* const* bq, const float* const* bk,
+                             const float* const* bv, const float* const* br, const float* const* bn_gamma,
+                             const float* const* bn_beta, const float* const* bn_mean, const float* const* bn_var,
+                             float bn_eps, const float* w_out, const float* b_out, void* workspace, void* stream);
+int dt_autoint_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                     int64_t B, int F, int D, int H, int n_layers, int NP, const void* workspace, float* logit_out, float* out,
+                     int* oob_count, int flags, int mfma_mode, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

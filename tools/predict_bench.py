@@ -4,15 +4,16 @@ D = 16, the default 128 x 64 tower) for the fused inference plan (fused.InferDee
 k_infer_prep launch per call, one k_infer or k_infer_sparse launch per batch) and for the layer-by-layer forward
 (DT_AMD_FUSED_PREDICT=0), at batch sizes 128 (DeepTable's default), 8192 and 65536, for the graphs of CONFIGS: DeepFM, DCN,
 ModelConfig's default ['dnn_nets'], WideDeep ['linear', 'dnn_nets'], the FM model ['linear', 'fm_nets'] and xDeepFM
-['linear', 'cin_nets', 'dnn_nets'] with the default CIN (128, 128) (fused.InferXDeepFM: 2 + 2 launches per batch).  Both paths of
-a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
+['linear', 'cin_nets', 'dnn_nets'] with the default CIN (128, 128) (fused.InferXDeepFM: 2 + 2 launches per batch), and AutoInt
+['autoint_nets'] as bench.py builds it (embedding size 32, three interacting layers of four heads, residual on;
+fused.InferAutoInt: one launch per batch).  Both paths of a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
 
 Both paths score the same device-resident rows (training.TableBatches) and write every batch's output into device memory;
 the timed region is what `DeepModel.predict` does after its feed is built, up to the outputs of the last batch (the host copy
 of the result is left out: it is the same for both paths).  Device events around each call, warm-up calls first, the
 median of the repeats reported (run-to-run spread as min / max).
 
-    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm,xdeepfm] [--rows N] [--batches 128,8192,65536]
+    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm,xdeepfm,autoint] [--rows N] [--batches 128,8192,65536]
                                   [--repeats R] [--warmup W] [--paths fused,layer]
 """
 import argparse
@@ -31,16 +32,19 @@ import torch  # noqa: E402
 F, VOCAB, ND, D = 26, 1_000_000, 13, 16
 CONFIGS = {'deepfm': ['linear', 'fm_nets', 'dnn_nets'], 'dcn': ['dcn_nets'], 'dnn': ['dnn_nets'],
            'widedeep': ['linear', 'dnn_nets'], 'fm': ['linear', 'fm_nets'],
-           'xdeepfm': ['linear', 'cin_nets', 'dnn_nets']}           # cin_params' default: cross_layer_size (128, 128)
+           'xdeepfm': ['linear', 'cin_nets', 'dnn_nets'],           # cin_params' default: cross_layer_size (128, 128)
+           'autoint': ['autoint_nets']}
+# what a configuration changes of the shape above (bench.py's AutoInt graph: MODEL_PARAMS['AutoInt'], embedding size 32)
+EXTRA = {'autoint': {'D': 32, 'autoint_params': {'num_attention': 3, 'num_heads': 4, 'dropout_rate': 0, 'use_residual': True}}}
 
 
-def build_model(nets, seed=0):
+def build_model(nets, seed=0, D=D, **extra):
     from deeptables_amd import functional
     from deeptables_amd.models import DeepModel, ModelConfig
     from deeptables_amd.models.metainfo import CategoricalColumn, ContinuousColumn
     functional.set_seed(seed)
     conf = ModelConfig(nets=list(nets), fixed_embedding_dim=True, embeddings_output_dim=D, embedding_dropout=0,
-                       metrics=[])
+                       metrics=[], **extra)
     cats = [CategoricalColumn(f'C{i}', VOCAB, D) for i in range(F)]
     conts = [ContinuousColumn('input_continuous_all', [f'I{j}' for j in range(ND)])]
     dm = DeepModel('binary', 2, conf, cats, conts)
@@ -100,12 +104,12 @@ def time_call(fn, warmup, repeats):
 
 
 def run_config(name, a):
-    dm = build_model(CONFIGS[name])
+    dm = build_model(CONFIGS[name], **EXTRA.get(name, {}))
     dm.model.eval()
     if 'fused' in a.paths.split(',') and dm.inference_plan() is None:
         raise SystemExit(f'the {name} graph has no inference plan')
     data = make_feed(dm, a.rows)
-    res, outs = {'nets': CONFIGS[name]}, {}
+    res, outs = {'nets': CONFIGS[name], **EXTRA.get(name, {})}, {}
     for path in a.paths.split(','):
         res[path] = {}
         for B in [int(b) for b in a.batches.split(',')]:
