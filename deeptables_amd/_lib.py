@@ -208,6 +208,12 @@ SIGNATURES = {
     'dt_autoint_infer_prepare': (_c_int, [_c_int] * 3 + [_ptr] * 12 + [_c_f32, _ptr, _ptr, _ptr, _ptr]),
     'dt_autoint_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
                                   _ptr, _ptr, _c_int, _c_int, _ptr]),
+    # AFM inference ('afm_nets' alone or with 'linear' / 'fm_nets'): prepare once, then one launch per batch
+    'dt_afm_infer_supported': (_c_int, [_c_int] * 6),
+    'dt_afm_infer_workspace_bytes': (_c_i64, [_c_int] * 5),
+    'dt_afm_infer_prepare': (_c_int, [_c_int] * 5 + [_ptr] * 9),
+    'dt_afm_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                              _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -221,6 +227,8 @@ DT_STEP_STAMPS = 0x400
 DT_STEP_PREPARED = 0x800
 DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
 DT_NET_LINEAR, DT_NET_FM, DT_NET_DNN = 0x1, 0x2, 0x4
+DT_NET_AFM = 0x8
+DT_AFM_INFER_ROWS, DT_AFM_INFER_MAX_BLOCKS = 4, 1024
 DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
 DT_XDEEPFM_MAX_LAYERS = 8
 DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256

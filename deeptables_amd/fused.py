@@ -1138,10 +1138,99 @@ class InferAutoInt(InferDeepFM):
             stream_ptr()), 'dt_autoint_infer')
 
 
+class InferAFM(InferDeepFM):
+    """Inference plan for the AFM graphs: 'afm_nets' alone (deepnets.AFM) or Add-stacked with 'linear' and / or 'fm_nets',
+    each net once, in any order in config.nets — ['linear', 'afm_nets'] is the AFM paper's model.  ONE launch per batch
+    (dt_afm_infer, csrc/afm_infer.hip k_afm_infer): the table gather, `linear` and `fm_nets` from the raw rows, the AFM
+    layer (pair products, attention Dense on the exact-fp32 matrix core, online softmax over the pairs, dense_out), Add,
+    task_output and the activation; one wave per batch row, nothing written but the logit and the output.
+
+    The head follows deepmodel.py:286-301.  The AFM layer's output is [B, 1], so beside other nets it has no dense_logit
+    layer and enters Add as it is; alone, task_output's [1, 1] kernel is applied to it directly.  `prepare` hands the
+    tensors over as they are at that moment: the plan holds no copy of a parameter between calls.  `dense` is dereferenced
+    only when 'linear' is among the nets.
+    Refused (the layer path runs): multiclass, any other net beside these three, a net named twice, concat stacking,
+    var-len columns, several embedding groups, more than one continuous column, sharded embeddings, fewer than two
+    categorical fields (there is no AFM layer then), shapes outside dt_afm_infer_supported (embedding size in {4, 8, 16, 32,
+    64}, F D <= 512, hidden_factor <= 64), an attention activation the AFM kernels do not fuse, a dropout_rate outside
+    [0, 1), DT_AMD_FUSED=0 / DT_AMD_FUSED_PREDICT=0."""
+
+    PREFIX = 'afm'
+    NET_BITS = {'afm_nets': _lib.DT_NET_AFM, 'linear': _lib.DT_NET_LINEAR, 'fm_nets': _lib.DT_NET_FM}
+
+    @classmethod
+    def _mask(cls, dm):
+        """the DT_NET_* mask of config.nets; 0 when a net is not one of the three, is named twice, or 'afm_nets' is absent"""
+        mask = 0
+        for n in list(dm.config.nets):
+            if not isinstance(n, str) or n not in cls.NET_BITS or mask & cls.NET_BITS[n]:
+                return 0
+            mask |= cls.NET_BITS[n]
+        return mask if mask & _lib.DT_NET_AFM else 0
+
+    @staticmethod
+    def _act(afm):
+        """the attention activation as the layer path reads it -> DT_ACT_* (raises for one the kernels do not fuse)"""
+        return _lib.act_code(afm.activation_function, 'AFM')
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            mask = cls._mask(dm)
+            if not mask or c.stacking_op != consts.STACKING_OP_ADD or getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            names = ('afm_layer',) + (('linear_logit',) if mask & _lib.DT_NET_LINEAR else ()) + \
+                (('fm_layer',) if mask & _lib.DT_NET_FM else ())
+            dims = _step_dims(dm, names, tower=None)
+            if dims is None:
+                return False
+            L = dm.model.layers_by_name
+            afm = L['afm_layer']
+            if not 0 <= float(afm.dropout_rate or 0) < 1 or tuple(L['task_output'].kernel.shape) != (1, 1):
+                return False
+            return bool(lib().dt_afm_infer_supported(*dims[1:], int(afm.hidden_factor), cls._act(afm), mask))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.mask = self._mask(self.dm)
+        self.bn = self.cells = None
+
+    def _net_layers(self, L):
+        self.afm = L['afm_layer']
+        self.lin = L['linear_logit'] if self.mask & _lib.DT_NET_LINEAR else None
+        self.H = int(self.afm.hidden_factor)
+        self.act = self._act(self.afm)
+
+    def _dims(self):
+        """dt_afm_infer_workspace_bytes' arguments"""
+        return self.F, self.D, self.Nd, self.H, self.mask
+
+    def prepare(self):
+        """the AFM layer's, linear_logit's and task_output's tensors as they are now -> the workspace, one launch; also reads
+        the attention activation and the output activation (the arguments of the `infer` calls that follow)"""
+        afm, att = self.afm, self.afm.dense_attention
+        self.flags = _lib.DT_INFER_SIGMOID if self.dm.output_activation == 'sigmoid' else 0
+        self.act = self._act(afm)
+        check(self._entry('infer_prepare')(
+            *self._dims(), ptr(att.kernel), ptr(att.bias), ptr(afm.attention_p), ptr(afm.dense_out.kernel),
+            ptr(self.lin.kernel) if self.lin is not None else None, ptr(self.out.kernel), ptr(self.out.bias), ptr(self.ws),
+            stream_ptr()), 'dt_afm_infer_prepare')
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch, as InferDeepFM.infer; `dense` reaches the kernel only when 'linear' is among the nets"""
+        B, idx, kind, dense = self._batch_args(idx, dense if self.lin is not None else None, logit, out)
+        check(self._entry('infer')(
+            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
+            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *self._dims(), self.act, ptr(self.ws), ptr(logit),
+            ptr(out), ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, stream_ptr()), 'dt_afm_infer')
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt):
+    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM):
         if plan.eligible(dm):
             return plan(dm)
     return None

@@ -840,6 +840,46 @@ int dt_autoint_infer(const void* idx, int idx_kind, const float* table, const in
                      int64_t B, int F, int D, int H, int n_layers, int NP, const void* workspace, float* logit_out, float* out,
                      int* oob_count, int flags, int mfma_mode, void* stream);
 
+/* ---- fused AFM inference: ONE launch per predict batch (csrc/afm_infer.hip k_afm_infer; replaces, for nets = 'afm_nets'
+ * alone or Add-stacked with 'linear' and / or 'fm_nets', the layer-by-layer forward of the reference's DeepModel.predict /
+ * evaluate: the embedding gather (layers.py:889-904), deepnets.py:99-108 `afm_nets` = AFM.call layers.py:786-807 — the pair
+ * products, the attention Dense and its activation, projection_h, the softmax over the pairs, the weighted sum, Dropout as the
+ * identity, the Dense(1, no bias) — deepnets.py:43-66 `linear`, deepnets.py:84-96 `fm_nets`, and the head deepmodel.py:286-301:
+ * Add, task_output [1][1], the activation).
+ *   nets = DT_NET_AFM, optionally | DT_NET_LINEAR | DT_NET_FM.  The AFM layer's output is [B, 1]: it enters Add as it is (no
+ *   dense_logit layer), so logit = (linear + fm + afm over the nets present) w_out + b_out.
+ *   One wave scores one batch row: the row's F table rows go to the wave's LDS slab, then for every tile of 16 pairs p = (i, j)
+ *   bi_p = x_i * x_j meets the attention kernel on the exact-fp32 matrix core (v_mfma_f32_16x16x4_f32), l_p = act(bi_p Wa + ba) . h
+ *   and t_p = bi_p . w_do feed an online softmax (running max, sum e^(l - m), sum e^(l - m) t): afm = sum_p softmax(l)_p t_p.
+ *   Nothing but the logit (and the output) is written: no score buffer, no pooled vector.
+ *   dt_afm_infer_supported: 1 iff F >= 2, (F, D, Nd) are dims the fused plans take (D in {4, 8, 16, 32, 64}, F D <= 512,
+ *     Nd <= 64), 1 <= H <= 64 (the attention factor; compiled widths 16 / 32 / 64), act a DT_ACT_* code and nets a mask
+ *     as above.
+ *   dt_afm_infer_workspace_bytes: size of `workspace` (16-byte aligned), -1 outside that domain.
+ *   dt_afm_infer_prepare (once per predict / evaluate, one launch; replaces nothing of the reference: it writes what the batch
+ *     launches read, from the values the tensors hold at call time): Wa [D][H] / ba [H] (NULL: 0) = dense_afm_attention's kernel
+ *     and bias, h [H] = projection_h, w_do [D] = afm_layer_dense_out's kernel — all zero-padded to the compiled width —
+ *     w_lin [F + Nd] = linear_logit's kernel (NULL when and only when nets has no DT_NET_LINEAR), w_out / b_out =
+ *     task_output's [1][1] kernel and bias (b_out NULL: none); also the table of the pairs' (i, j).
+ *   dt_afm_infer (per batch of B >= 0 rows, B < 2^31; B = 0: no launch): ids [B][F] (idx_kind = DT_IDX_*; an id outside
+ *     [0, vocab[f]) reads a zero row and is counted once into *oob_count when it is given), dense [B][Nd] (read only with
+ *     DT_NET_LINEAR and Nd > 0, else it may be NULL) -> logit_out [B] and, if out != NULL, out [B] = sigmoid(logit) with flags
+ *     = DT_INFER_SIGMOID or the logit with flags = 0.  H, nets as prepared; act = the attention activation (DT_ACT_*).  The
+ *     workspace carries the (F, D, Nd, compiled width of H, nets) it was prepared for: a launch with other values reads no
+ *     weight and writes NaN into every logit and output.  The
+ *     grid is at most DT_AFM_INFER_MAX_BLOCKS blocks of DT_AFM_INFER_ROWS waves; a wave strides over the batch rows. */
+#define DT_NET_AFM 0x8
+#define DT_AFM_INFER_ROWS 4
+#define DT_AFM_INFER_MAX_BLOCKS 1024
+int dt_afm_infer_supported(int F, int D, int Nd, int H, int act, int nets);
+int64_t dt_afm_infer_workspace_bytes(int F, int D, int Nd, int H, int nets);
+int dt_afm_infer_prepare(int F, int D, int Nd, int H, int nets, const float* Wa, const float* ba, const float* h,
+                         const float* w_do, const float* w_lin, const float* w_out, const float* b_out, void* workspace,
+                         void* stream);
+int dt_afm_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                 const float* dense, int64_t B, int F, int D, int Nd, int H, int nets, int act, const void* workspace,
+                 float* logit_out, float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
