@@ -214,6 +214,14 @@ SIGNATURES = {
     'dt_afm_infer_prepare': (_c_int, [_c_int] * 5 + [_ptr] * 9),
     'dt_afm_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                               _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
+    # fused PNN inference (csrc/pnn_infer.hip): products = DT_PNN_* mask, kernel_type = DT_OP_KERNEL_*
+    'dt_pnn_infer_supported': (_c_int, [_c_int] * 8),
+    'dt_pnn_infer_workspace_bytes': (_c_i64, [_c_int] * 5),
+    'dt_pnn_infer_prepare': (_c_int, [_c_int] * 5 + [_ptr] * 5 + [_c_f32, _ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int,
+                                      _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr,
+                                      _ptr, _ptr, _ptr]),
+    'dt_pnn_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
+                              _ptr, _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -229,6 +237,8 @@ DT_INFER_SIGMOID, DT_INFER_TOWER_BF16 = 0x1, 0x2
 DT_NET_LINEAR, DT_NET_FM, DT_NET_DNN = 0x1, 0x2, 0x4
 DT_NET_AFM = 0x8
 DT_AFM_INFER_ROWS, DT_AFM_INFER_MAX_BLOCKS = 4, 1024
+DT_PNN_INNER, DT_PNN_OUTER = 0x1, 0x2
+DT_PNN_INFER_MAX_BLOCKS = 512
 DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
 DT_XDEEPFM_MAX_LAYERS = 8
 DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256

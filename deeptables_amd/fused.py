@@ -1227,10 +1227,91 @@ class InferAFM(InferDeepFM):
             ptr(out), ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, stream_ptr()), 'dt_afm_infer')
 
 
+class InferPNN(InferDeepFM):
+    """Inference plan for the product nets: 'pnn_nets' (deepnets.PNN: inner ++ outer ++ xn -> tower), 'ipnn_nets' (inner ++
+    xn) or 'opnn_nets' (outer ++ xn), each alone in config.nets, with every outer_product_kernel_type.  ONE launch per batch
+    (dt_pnn_infer, csrc/pnn_infer.hip k_pnn_infer): the table gather, the product layers from the raw rows ('mat' on the
+    exact-fp32 matrix core), the input BatchNormalization of the embedding and dense columns, the tower, task_output and the
+    activation; neither the field stack, the products nor their concatenation is written.
+
+    The head follows deepmodel.py:286-301 for a single net: no dense_logit layer and no Add, task_output's [H2, 1] kernel is
+    the tower's output vector and the output weight is 1.  `prepare` hands the tensors over as they are at that moment: the
+    plan holds no copy of a parameter between calls.
+    Refused (the layer path runs): multiclass, a product net beside any other net or two of them, concat stacking, fewer than
+    two categorical fields (the net is absent), var-len columns, several embedding groups, sharded embeddings, a tower outside
+    `_infer_tower`, a task_output kernel that is not [H2, 1], shapes outside dt_pnn_infer_supported (2 <= F <= 64, embedding
+    size in {4, 8, 16, 32, 64}, F D <= 512, Nd <= 64), DT_AMD_FUSED=0 / DT_AMD_FUSED_PREDICT=0."""
+
+    PREFIX = 'pnn'
+    # net -> (the tower's layer prefix, inner product layer, outer product layer)
+    PRODUCT_NETS = {'pnn_nets': ('pnn', 'pnn_inner_product_layer', 'pnn_outer_product_layer'),
+                    'ipnn_nets': ('ipnn', 'inner_product_layer', None),
+                    'opnn_nets': ('opnn', None, 'outer_product_layer')}
+
+    @classmethod
+    def _net(cls, dm):
+        """(cell, inner layer name, outer layer name) of the single product net in config.nets, else None"""
+        nets = list(dm.config.nets)
+        if len(nets) != 1 or not isinstance(nets[0], str):
+            return None
+        return cls.PRODUCT_NETS.get(nets[0])
+
+    @staticmethod
+    def _products(L, inner, outer):
+        """(DT_PNN_* mask, DT_OP_KERNEL_* of the outer layer as it is now or 0)"""
+        mask = (_lib.DT_PNN_INNER if inner else 0) | (_lib.DT_PNN_OUTER if outer else 0)
+        return mask, _lib.DT_OP_KERNEL[L[outer].kernel_type] if outer else 0
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            net = cls._net(dm)
+            if net is None or c.stacking_op != consts.STACKING_OP_ADD or \
+                    getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            cell, inner, outer = net
+            names = (f'{cell}_dense_1', f'{cell}_dense_2') + tuple(n for n in (inner, outer) if n)
+            dims = _step_dims(dm, names, _infer_tower)
+            if dims is None:
+                return False
+            L = dm.model.layers_by_name
+            tower = _infer_tower(c.dnn_params)
+            _, F, D, Nd = dims
+            mask, kt = cls._products(L, inner, outer)
+            P = F * (F - 1) // 2
+            rows = P * (bool(inner) + bool(outer)) + F * D + Nd
+            if tuple(L['task_output'].kernel.shape) != (tower[1], 1) or int(L[f'{cell}_dense_1'].kernel.shape[0]) != rows:
+                return False
+            if outer and tuple(L[outer].kernel.shape) != {0: (D, P, D), 1: (P, D), 2: (P, 1)}[kt]:
+                return False
+            return bool(lib().dt_pnn_infer_supported(F, D, Nd, *tower, mask, kt))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.CELL, self.inner_name, self.outer_name = self._net(self.dm)
+        super()._tower_layers(L)
+
+    def _net_layers(self, L):
+        self.op = L[self.outer_name] if self.outer_name else None
+        self.products, self.kt = self._products(L, self.inner_name, self.outer_name)
+
+    def _dims(self):
+        """dt_pnn_infer_workspace_bytes' arguments"""
+        return self.F, self.D, self.Nd, self.products, self.kt
+
+    def _net_args(self):
+        return self.products, self.kt, ptr(self.op.kernel) if self.op is not None else None
+
+    def _head_weights(self):
+        return (ptr(self.out.kernel),)          # w3: the tower alone, the output weight is 1
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM):
+    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM, InferPNN):
         if plan.eligible(dm):
             return plan(dm)
     return None

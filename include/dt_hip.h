@@ -880,6 +880,50 @@ int dt_afm_infer(const void* idx, int idx_kind, const float* table, const int64_
                  const float* dense, int64_t B, int F, int D, int Nd, int H, int nets, int act, const void* workspace,
                  float* logit_out, float* out, int* oob_count, int flags, void* stream);
 
+/* ---- fused PNN inference: ONE launch per predict batch (csrc/pnn_infer.hip k_pnn_infer; replaces, for each of the nets
+ * 'pnn_nets' / 'ipnn_nets' / 'opnn_nets' alone in config.nets, the layer-by-layer forward of the reference's DeepModel.predict /
+ * evaluate: the embedding gather (layers.py:889-904), InnerProduct.call layers.py:473-487, OuterProduct.call layers.py:543-581,
+ * the input BatchNormalization on its moving statistics, deepnets.py:111-160 — Concatenate(products ++ [xn]), the two-cell relu
+ * tower deepnets.py:401-427 with Dropout as the identity — and the head deepmodel.py:286-301: a single net, so no dense_logit
+ * layer and no Add; task_output's [H2][1] kernel is the tower's output vector and the output weight is 1).
+ *   products = a non-empty mask DT_PNN_INNER | DT_PNN_OUTER; kernel_type = DT_OP_KERNEL_* of the outer layer, ignored without
+ *   DT_PNN_OUTER.  P = F (F - 1) / 2 pairs in itertools.combinations order; Cp = P x the number of product layers.  The first
+ *   Dense's rows: the product columns (inner first, then outer), the F D embedding columns, the Nd dense columns.  The
+ *   products are formed from the raw table rows; only the last F D + Nd columns are normalised.
+ *   A block owns a 32-row tile: the rows go to LDS once, the first Dense's K = Cp + F D + Nd runs in chunks of 128 columns
+ *   that are computed into LDS and multiplied at once ('mat': K_p . X_i^T on the exact-fp32 matrix core, then the row-wise
+ *   dot with x_j; the other products and the normalisation elementwise), the accumulators stay in registers over all chunks.
+ *   The product layers are exact fp32 in both tower modes.
+ *   dt_pnn_infer_supported: 1 iff 2 <= F <= 64, D in {4, 8, 16, 32, 64}, F D <= 512, 0 <= Nd <= 64, 1 <= H1 <= 128,
+ *     1 <= H2 <= 64, cells a mask of bits 0 / 1 (as dt_deepfm_infer_supported), products as above and kernel_type valid when
+ *     DT_PNN_OUTER is set.
+ *   dt_pnn_infer_workspace_bytes: size of `workspace` (16-byte aligned), -1 outside that domain.
+ *   dt_pnn_infer_prepare (once per predict / evaluate, one launch; replaces nothing of the reference: it writes what the batch
+ *     launches read, from the values the tensors hold at call time): op_kernel = the outer layer's kernel, 'mat' [D][P][D] |
+ *     'vec' [P][D] | 'num' [P][1] (NULL when and only when products has no DT_PNN_OUTER; 'mat' is re-laid pair-major), the
+ *     input BN over the F D + Nd columns, W1 [Cp + F D + Nd][ld1], W2 and the two cells' bias / BN arguments as
+ *     dt_deepfm_infer_prepare, w3 [H2] = task_output's kernel, b_out = its bias or NULL.
+ *   dt_pnn_infer (per batch of B >= 0 rows, B < 2^31; B = 0: no launch): ids [B][F] (idx_kind = DT_IDX_*; an id outside
+ *     [0, vocab[f]) reads a zero row and is counted once into *oob_count when it is given), dense [B][Nd] (NULL with Nd = 0)
+ *     -> logit_out [B] and, if out != NULL, out [B] = sigmoid(logit) with DT_INFER_SIGMOID or the logit.  flags |
+ *     DT_INFER_TOWER_BF16: the two tower GEMMs on plain bf16 operands.  The workspace carries the (F, D, Nd, products,
+ *     kernel_type) it was prepared for: a launch with other values reads no weight and writes NaN into every logit and
+ *     output.  The grid is at most DT_PNN_INFER_MAX_BLOCKS blocks, strided over the 32-row tiles. */
+#define DT_PNN_INNER 0x1
+#define DT_PNN_OUTER 0x2
+#define DT_PNN_INFER_MAX_BLOCKS 512
+int dt_pnn_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int products, int kernel_type);
+int64_t dt_pnn_infer_workspace_bytes(int F, int D, int Nd, int products, int kernel_type);
+int dt_pnn_infer_prepare(int F, int D, int Nd, int products, int kernel_type, const float* op_kernel, const float* bn_gamma,
+                         const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps, const float* W1, int ld1,
+                         int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                         const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var, float c1_eps,
+                         const float* c2_gamma, const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
+                         const float* w3, const float* b_out, void* workspace, void* stream);
+int dt_pnn_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                 const float* dense, int64_t B, int F, int D, int Nd, int products, int kernel_type, const void* workspace,
+                 float* logit_out, float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
