@@ -29,7 +29,7 @@
 // SIMD holds 4 waves: enough to cover the 40-cycle dependent-accumulator latency of the fp32 MFMA (issue 32) and the gather.
 // A wave strides over the rows with the table rows of its next row and the ids of the one after in flight.
 // LDS (bytes) = 4 (P16 + 4 F (D + 4)): F = 26, D = 16: 9,664; the most, F = 128, D = 4: 48,896.  Registers: DESIGN.md §3.1b.
-#include "tile_common.h"
+#include "infer_common.h"
 
 namespace dt {
 
@@ -120,23 +120,6 @@ struct AfmIo {
 
 __device__ __forceinline__ void afm_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
-// KS consecutive floats of the slab (16-byte aligned for KS >= 4, 8-byte for KS = 2)
-template <int KS>
-__device__ __forceinline__ void afm_chunk(const float* p, float (&o)[KS]) {
-    if constexpr (KS >= 4) {
-#pragma unroll
-        for (int q = 0; q < KS / 4; ++q) {
-            const floatx4 v = ld4(p + 4 * q);
-            o[4 * q] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
-        }
-    } else if constexpr (KS == 2) {
-        const float2 v = *reinterpret_cast<const float2*>(p);
-        o[0] = v.x; o[1] = v.y;
-    } else {
-        o[0] = p[0];
-    }
-}
-
 template <int D, int HT, int NETS>
 __global__ __launch_bounds__(64 * kAfmRows) void k_afm_infer(AfmIo io, int B, int F, int Nd, int act,
                                                             const float* __restrict__ ws) {
@@ -187,15 +170,10 @@ __global__ __launch_bounds__(64 * kAfmRows) void k_afm_infer(AfmIo io, int B, in
     int64_t roff[2];
     bool in[2];
     float wf[2] = {0.f, 0.f};
+    infer_lookup_setup(io.vocab, io.row_offset, lane, NV, LSH, fld, voc, roff, in);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int j = lane + 64 * t;
-        in[t] = j < NV;
-        fld[t] = min(j, NV - 1) >> LSH;
-        voc[t] = io.vocab[fld[t]];
-        roff[t] = io.row_offset[fld[t]];
+    for (int t = 0; t < 2; ++t)
         if (LIN) wf[t] = ws[wl.wlin + fld[t]];
-    }
     const bool has_dense = LIN && lane < Nd;       // the continuous columns' share of `linear`: lane k < Nd takes column k
     const float wd = has_dense ? ws[wl.wlin + F + lane] : 0.f;
     __syncthreads();                               // the pair table; the only barrier: nothing below reads another wave's data
@@ -269,8 +247,8 @@ __global__ __launch_bounds__(64 * kAfmRows) void k_afm_infer(AfmIo io, int B, in
             const int e = tab[p];
             const bool valid = p < wl.P;
             float xi[KS], xj[KS], bi[KS];
-            afm_chunk<KS>(slab + (e & 0xffff) + g * KS, xi);
-            afm_chunk<KS>(slab + (e >> 16) + g * KS, xj);
+            ld_chunk<KS>(slab + (e & 0xffff) + g * KS, xi);
+            ld_chunk<KS>(slab + (e >> 16) + g * KS, xj);
             floatx4 acc[HT];
 #pragma unroll
             for (int t = 0; t < HT; ++t) acc[t] = bav[t];
@@ -318,8 +296,7 @@ __global__ __launch_bounds__(64 * kAfmRows) void k_afm_infer(AfmIo io, int B, in
             if (LIN) zz += lp;
             if (FM) zz += 0.5f * ts;
             const float lgt = zz * wout + bout;
-            io.logit[b] = lgt;
-            if (io.out) io.out[b] = io.sigmoid ? 1.0f / (1.0f + expf(-lgt)) : lgt;
+            infer_store(io.logit, io.out, io.sigmoid, b, lgt);
         }
         if (more) {
             v[0] = vn[0]; v[1] = vn[1];
@@ -385,9 +362,8 @@ extern "C" int dt_afm_infer(const void* idx, int idx_kind, const float* table, c
     DT_REQUIRE((flags & ~DT_INFER_SIGMOID) == 0, "dt_afm_infer: flags %#x (DT_INFER_SIGMOID or 0)", flags);
     if (B == 0) return DT_OK;
     DT_REQUIRE(B > 0 && B < (1LL << 31), "dt_afm_infer: bad batch");
-    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "dt_afm_infer: null pointer");
-    DT_REQUIRE(!(nets & DT_NET_LINEAR) || Nd == 0 || dense, "dt_afm_infer: dense is null");
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)workspace) % 16 == 0, "dt_afm_infer: table / workspace must be 16-byte aligned");
+    if (const int rc = infer_check_io("dt_afm_infer", idx, table, row_offset, vocab, workspace, logit_out,
+                                      !(nets & DT_NET_LINEAR) || Nd == 0 || dense)) return rc;
     const size_t lds = afm_infer_lds(F, D);
     DT_UNSUPPORTED(lds > 64 * 1024, "dt_afm_infer: needs %zu B of LDS", lds);
     const int64_t want = (B + kAfmRows - 1) / kAfmRows;

@@ -20,7 +20,7 @@
 //     the Dense backward (dt_dense_bwd: grad_x = dY Wcat^T, grad_W = x^T dY).
 // Attention-weight dropout (layers.py:141): keep-mask from a counter hash of (seed, row, head, query, key), the
 // same function in both kernels and in deeptables_amd/ops.py (tests rebuild the mask from it).
-#include "common.h"
+#include "infer_common.h"
 
 namespace dt {
 
@@ -1500,8 +1500,7 @@ __global__ __launch_bounds__(512) void k_autoint_infer(AiInferIo io, int B, int 
         acc = wave_sum(acc);
         if (lane == 0) {
             const float lg = acc + c0;
-            io.logit[b] = lg;
-            if (io.out) io.out[b] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+            infer_store(io.logit, io.out, io.sigmoid, b, lg);
         }
         ai_fence();
         if (more) {

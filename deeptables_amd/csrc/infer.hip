@@ -47,12 +47,8 @@ static int infer_prepare(const char* what, int F, int D, int Nd, InferPrepArgs a
     DT_REQUIRE(workspace && (!tower || (a.mm && a.mv && a.W1 && a.W2 && a.w3)) && (!lin || a.wlin) &&
                (a.L > 0 || a.nets == DT_NET_DNN || a.wout), "%s: null pointer", what);
     DT_REQUIRE(a.L == 0 || (a.cw && a.cb_), "%s: null cross weights", what);
-    for (int i = 0; tower && i < 2; ++i) {
-        if (cells & (1 << i)) {
-            DT_REQUIRE(a.cm[i] && a.cv[i], "%s: tower cell %d has batch norm but no moving statistics", what, i + 1);
-        } else {
-            a.cm[i] = nullptr;
-        }
+    if (tower) {
+        if (const int rc = infer_check_cells(what, cells, a.cm, a.cv)) return rc;
     }
     DT_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", what);
     const int items = tower ? max((dm.CP >> 5) * 512, (2 * a.L + 1) * dm.CP) : dm.CP;
@@ -100,9 +96,7 @@ static int infer_run(const char* what, const void* idx, int idx_kind, const floa
     DT_REQUIRE((flags & ~(DT_INFER_SIGMOID | DT_INFER_TOWER_BF16)) == 0, "%s: flags 0x%x", what, flags);
     DT_REQUIRE(idx_kind == DT_IDX_F32 || idx_kind == DT_IDX_I32, "%s: idx_kind %d", what, idx_kind);
     if (B == 0) return DT_OK;
-    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "%s: null pointer", what);
-    DT_REQUIRE(Nd == 0 || dense, "%s: dense is null", what);
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)workspace) % 16 == 0, "%s: table / workspace must be 16-byte aligned", what);
+    if (const int rc = infer_check_io(what, idx, table, row_offset, vocab, workspace, logit_out, Nd == 0 || dense)) return rc;
     dm.B = B;
     const bool dcn = L > 0, one = (flags & DT_INFER_TOWER_BF16) != 0;
     const bool xd = xd_x0 != nullptr;

@@ -26,7 +26,7 @@
 //                                 DCN: pb 2 * 48 * 16 * 4       the two K halves of P = [Xn ; b_j] . [w_l, w3c]
 // CP = 576 (C = 544): 131 KB (DeepFM), 140 KB (DCN) — the split tile serves every C the step's dims accept.
 #pragma once
-#include "x3_mfma.h"
+#include "infer_common.h"
 
 namespace dt {
 
@@ -295,12 +295,7 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                 a[0][q] = x3_ld8(arow0 + q * XP + 32 * s);
                 a[1][q] = x3_ld8(arow1 + q * XP + 32 * s);
             }
-            X3_MFMA(c1[0], a[0][0], b[0]); X3_MFMA(c1[1], a[1][0], b[0]);
-            X3_LO(c2[0], a[0][0], b[1]); X3_LO(c2[1], a[1][0], b[1]);
-            X3_LO(c3[0], a[0][0], b[2]); X3_LO(c3[1], a[1][0], b[2]);
-            X3_LO(c2[0], a[0][1], b[0]); X3_LO(c2[1], a[1][1], b[0]);
-            X3_LO(c3[0], a[0][1], b[1]); X3_LO(c3[1], a[1][1], b[1]);
-            X3_LO(c3[0], a[0][2], b[0]); X3_LO(c3[1], a[1][2], b[0]);
+            infer_mfma6<ONE>(a, b, c1, c2, c3);
         }
         if constexpr (LC > 0) {
             // ---- Cross, part 1 (k_tower_x3's: P = [Xn ; b_0 .. b_{L-1}] . [w_0 .. w_{L-1} w3c], 48 x 16, K = CP, six products in
@@ -339,15 +334,7 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                 for (int r = 0; r < 4; ++r) pb[(kh * 48 + 16 * mt + 4 * kg + r) * 16 + n16] = (q3[r] + q2[r]) + q1[r];
             }
         }
-        // cell 1's epilogue: H1 (C layout: column 16w + n16, rows 16t + 4kg + r) -> fp32 in LDS
-        const float* cv1 = ws + wl.cell1;
-        const int col = 16 * wave + n16;
-        const float ctr = cv1[col], scl = cv1[kH1 + col], sft = cv1[2 * kH1 + col];
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                h1f[(16 * t + 4 * kg + r) * HF + col] = fmaxf((((c3[t][r] + c2[t][r]) + c1[t][r]) - ctr) * scl + sft, 0.f);
+        infer_cell1(c1, c2, c3, ws + wl.cell1, h1f, wave, n16, kg);
     }
     lds_barrier();
 
@@ -424,8 +411,7 @@ __global__ __launch_bounds__(kInferThreads) void k_infer(InferIo io, DeepFmDims 
                                 : (LIN || FM) ? lf[c] + pt     // Add([linear, fm, dnn]) order
                                               : pt;            // the tower alone
             const float lg = zz * ws[wl.head] + ws[wl.head + 1];
-            io.logit[m] = lg;
-            if (io.out) io.out[m] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+            infer_store(io.logit, io.out, io.sigmoid, m, lg);
         }
     }
 }
@@ -505,8 +491,7 @@ __global__ __launch_bounds__(64 * kInferSparseRows) void k_infer_sparse(InferIo 
     if (lane == 0) {
         const float zz = LIN && FM ? lp + 0.5f * ts : LIN ? lp : 0.5f * ts;     // Add([linear, fm]) / the single net
         const float lg = zz * wout + bout;
-        io.logit[m] = lg;
-        if (io.out) io.out[m] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+        infer_store(io.logit, io.out, io.sigmoid, m, lg);
     }
 }
 
@@ -563,8 +548,7 @@ __global__ __launch_bounds__(64 * kXdHeadRows) void k_xdeepfm_head(XdHeadArgs a)
     if (lane == 0) {
         const float zz = a.partial[m] + (acc + a.bex[0]);       // Add([linear, cin, dnn]) over the two terms the launches hand over
         const float lg = zz * a.head[0] + a.head[1];
-        a.logit[m] = lg;
-        if (a.out) a.out[m] = a.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+        infer_store(a.logit, a.out, a.sigmoid, m, lg);
     }
 }
 

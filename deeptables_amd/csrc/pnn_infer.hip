@@ -24,14 +24,15 @@
 //        embedding / dense columns       (x - mm) scale + beta with the centring kept, as k_infer
 //      By default the tower's products are the six split-bf16 products of x3_mfma.h (the fp32 class); ONE
 //      (DT_INFER_TOWER_BF16) keeps the leading product only.  The product layers are exact fp32 in both modes.
-//   3. cell 1's epilogue, GEMM2, cell 2's epilogue, task_output's vector, bias and activation — k_infer's, unchanged (the
-//      fp32 H1 tile takes the chunk buffer's place in LDS).
+//   3. cell 1's epilogue (infer_cell1, as GEMM1's step and the lookup setup from infer_common.h), then GEMM2, cell 2's
+//      epilogue and task_output's vector in k_infer's text (infer_x3.h), the bias and the activation through infer_store.
+//      The fp32 H1 tile takes the chunk buffer's place in LDS.
 // Only the logit (and the activated output) is written.
 //
 // LDS (bytes): slab 128 RS, RS = F D + roundup(Nd, 8) + 4 (4 x odd: 16 rows on 16 distinct bank quads) | input BN 12 (F D + Nd)
 // | pair table 4 P | chunk buffer 27,648 | w3 partial sums 512.  F = 26, D = 16, Nd = 13: 91 KB; the most, F = 64, D = 8,
 // Nd = 64: 117 KB.  One block per CU.
-#include "x3_mfma.h"
+#include "infer_common.h"
 
 namespace dt {
 
@@ -184,23 +185,6 @@ struct PnnIo {
     int sigmoid;
 };
 
-// KS consecutive floats (16-byte aligned for KS >= 4, 8-byte for KS = 2)
-template <int KS>
-__device__ __forceinline__ void pnn_chunk(const float* p, float (&o)[KS]) {
-    if constexpr (KS >= 4) {
-#pragma unroll
-        for (int q = 0; q < KS / 4; ++q) {
-            const floatx4 v = ld4(p + 4 * q);
-            o[4 * q] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
-        }
-    } else if constexpr (KS == 2) {
-        const float2 v = *reinterpret_cast<const float2*>(p);
-        o[0] = v.x; o[1] = v.y;
-    } else {
-        o[0] = p[0];
-    }
-}
-
 // one value -> its three bf16 parts in the chunk buffer (ONE: the leading part is all GEMM1 reads)
 template <bool ONE>
 __device__ __forceinline__ void pnn_put(__bf16* dst, float v) {
@@ -255,14 +239,7 @@ __global__ __launch_bounds__(kPnnThreads) void k_pnn_infer(PnnIo io, int64_t B, 
     int fld[2], voc[2];
     int64_t roff[2];
     bool in[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int j = lane + 64 * t;
-        in[t] = j < NV;
-        fld[t] = min(j, NV - 1) >> LSH;
-        voc[t] = io.vocab[fld[t]];
-        roff[t] = io.row_offset[fld[t]];
-    }
+    infer_lookup_setup(io.vocab, io.row_offset, lane, NV, LSH, fld, voc, roff, in);
 
     const int64_t tiles = (B + kTM - 1) / kTM;
     for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -363,7 +340,7 @@ __global__ __launch_bounds__(kPnnThreads) void k_pnn_infer(PnnIo io, int64_t B, 
 #pragma unroll
                     for (int t = 0; t < AT; ++t) {
                         const int ar = 16 * t + n16;
-                        pnn_chunk<KS>(kpw + ((int64_t)p * D + min(ar, D - 1)) * D + kg * KS, ka[t]);
+                        ld_chunk<KS>(kpw + ((int64_t)p * D + min(ar, D - 1)) * D + kg * KS, ka[t]);
                         if constexpr (D < 16) {
                             if (ar >= D) {
 #pragma unroll
@@ -375,7 +352,7 @@ __global__ __launch_bounds__(kPnnThreads) void k_pnn_infer(PnnIo io, int64_t B, 
                     for (int h = 0; h < 2; ++h) {
                         const float* xr = slab + (16 * h + n16) * RS;
                         float xi[KS];
-                        pnn_chunk<KS>(xr + io_ + kg * KS, xi);
+                        ld_chunk<KS>(xr + io_ + kg * KS, xi);
                         floatx4 acc[AT];
 #pragma unroll
                         for (int t = 0; t < AT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
@@ -412,28 +389,14 @@ __global__ __launch_bounds__(kPnnThreads) void k_pnn_infer(PnnIo io, int64_t B, 
                         a[0][q] = x3_ld8(arow0 + q * kPnnXP + 32 * s);
                         a[1][q] = x3_ld8(arow1 + q * kPnnXP + 32 * s);
                     }
-                    X3_MFMA(c1[0], a[0][0], b[0]); X3_MFMA(c1[1], a[1][0], b[0]);
-                    X3_LO(c2[0], a[0][0], b[1]); X3_LO(c2[1], a[1][0], b[1]);
-                    X3_LO(c3[0], a[0][0], b[2]); X3_LO(c3[1], a[1][0], b[2]);
-                    X3_LO(c2[0], a[0][1], b[0]); X3_LO(c2[1], a[1][1], b[0]);
-                    X3_LO(c3[0], a[0][1], b[1]); X3_LO(c3[1], a[1][1], b[1]);
-                    X3_LO(c3[0], a[0][2], b[0]); X3_LO(c3[1], a[1][2], b[0]);
+                    infer_mfma6<ONE>(a, b, c1, c2, c3);
                 }
             }
             lds_barrier();
         }
 
-        // ---- cell 1's epilogue: H1 (C layout: column 16 w + n16, rows 16 t + 4 kg + r) -> fp32 in LDS ----
-        {
-            const float* cv1 = ws + wl.cell1;
-            const int col = 16 * wave + n16;
-            const float ctr = cv1[col], scl = cv1[kH1 + col], sft = cv1[2 * kH1 + col];
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    h1f[(16 * t + 4 * kg + r) * HF + col] = fmaxf((((c3[t][r] + c2[t][r]) + c1[t][r]) - ctr) * scl + sft, 0.f);
-        }
+        // ---- cell 1's epilogue -> the fp32 H1 tile ----
+        infer_cell1(c1, c2, c3, ws + wl.cell1, h1f, wave, n16, kg);
         lds_barrier();
 
         // ---- GEMM2 (k_infer's): row half mt2, columns [16 nt2, +16); then task_output's vector ----
@@ -474,8 +437,7 @@ __global__ __launch_bounds__(kPnnThreads) void k_pnn_infer(PnnIo io, int64_t B, 
         if (wave == 0 && lane < kTM && m0 + lane < B) {
             const float pt = (zp[lane] + zp[kTM + lane]) + (zp[2 * kTM + lane] + zp[3 * kTM + lane]);
             const float lg = pt * ws[wl.head] + ws[wl.head + 1];
-            io.logit[m0 + lane] = lg;
-            if (io.out) io.out[m0 + lane] = io.sigmoid ? 1.0f / (1.0f + expf(-lg)) : lg;
+            infer_store(io.logit, io.out, io.sigmoid, m0 + lane, lg);
         }
         // (the next tile's gather writes the slab only; zp is read again two barriers from here)
     }
@@ -525,13 +487,7 @@ extern "C" int dt_pnn_infer_prepare(int F, int D, int Nd, int products, int kern
     PnnPrepArgs a{op_kernel, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, W1, ld1, H1, W2, ld2, H2,
                   {b1, b2}, {c1_gamma, c2_gamma}, {c1_beta, c2_beta}, {c1_mean, c2_mean}, {c1_var, c2_var},
                   {c1_eps, c2_eps}, w3, b_out, F, D, Nd, products, pnn_kt(products, kernel_type)};
-    for (int i = 0; i < 2; ++i) {
-        if (cells & (1 << i)) {
-            DT_REQUIRE(a.cm[i] && a.cv[i], "%s: tower cell %d has batch norm but no moving statistics", who, i + 1);
-        } else {
-            a.cm[i] = nullptr;
-        }
-    }
+    if (const int rc = infer_check_cells(who, cells, a.cm, a.cv)) return rc;
     const PnnWsLayout wl = pnn_ws_layout(F, D, Nd, products, a.kt);
     const int64_t items = max((int64_t)(wl.KP >> 5) * 512, (int64_t)wl.P * D * D);
     const int blocks = (int)min((items + 255) / 256, (int64_t)2048);
@@ -562,9 +518,7 @@ extern "C" int dt_pnn_infer(const void* idx, int idx_kind, const float* table, c
     DT_REQUIRE((flags & ~(DT_INFER_SIGMOID | DT_INFER_TOWER_BF16)) == 0, "%s: flags 0x%x", who, flags);
     DT_REQUIRE(B >= 0 && B < (1LL << 31), "%s: bad batch", who);
     if (B == 0) return DT_OK;
-    DT_REQUIRE(idx && table && row_offset && vocab && workspace && logit_out, "%s: null pointer", who);
-    DT_REQUIRE(Nd == 0 || dense, "%s: dense is null", who);
-    DT_REQUIRE(((uintptr_t)table | (uintptr_t)workspace) % 16 == 0, "%s: table / workspace must be 16-byte aligned", who);
+    if (const int rc = infer_check_io(who, idx, table, row_offset, vocab, workspace, logit_out, Nd == 0 || dense)) return rc;
     const size_t lds = pnn_infer_lds(F, D, Nd);
     DT_UNSUPPORTED(lds > 160 * 1024, "%s: the tile needs %zu B of LDS", who, lds);
     const int64_t tiles = (B + kTM - 1) / kTM;

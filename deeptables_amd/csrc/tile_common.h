@@ -21,6 +21,22 @@ constexpr int kCrossMax = 8;    // cross layers the fused DCN step takes
 
 __device__ __forceinline__ floatx4 ld4(const float* p) { return *reinterpret_cast<const floatx4*>(p); }
 __device__ __forceinline__ void st4(float* p, floatx4 v) { *reinterpret_cast<floatx4*>(p) = v; }
+// KS consecutive floats (16-byte aligned for KS >= 4, 8-byte for KS = 2)
+template <int KS>
+__device__ __forceinline__ void ld_chunk(const float* p, float (&o)[KS]) {
+    if constexpr (KS >= 4) {
+#pragma unroll
+        for (int q = 0; q < KS / 4; ++q) {
+            const floatx4 v = ld4(p + 4 * q);
+            o[4 * q] = v.x; o[4 * q + 1] = v.y; o[4 * q + 2] = v.z; o[4 * q + 3] = v.w;
+        }
+    } else if constexpr (KS == 2) {
+        const float2 v = *reinterpret_cast<const float2*>(p);
+        o[0] = v.x; o[1] = v.y;
+    } else {
+        o[0] = p[0];
+    }
+}
 // Write-through (sc1) 16-byte store for data the NEXT kernel reads: a plain store leaves the line dirty in this XCD's L2 and
 // the kernel boundary then waits for the write-back of everything the launch dirtied (~1 us per 6 MB: the row update's
 // 41 MB, the tile kernel's 26 MB); written through, the bytes leave while the kernel still computes.  Inline asm: hipcc

@@ -653,15 +653,6 @@ def _infer_tower(dnn_params):
     return int(h1), int(h2), (1 if bn1 else 0) | (2 if bn2 else 0)
 
 
-def _infer_flags(dm):
-    """dt_*_infer's flags: the output activation (sigmoid for the binary task) and the tower's precision mode
-    (`_tower_mfma_flag`: 'bf16' -> DT_INFER_TOWER_BF16; 'bf16x3' and 'f32' both run the six-product forward, which is in the
-    fp32 class)"""
-    mode = _tower_mfma_flag(dm.config.dnn_params)
-    return (_lib.DT_INFER_SIGMOID if dm.output_activation == 'sigmoid' else 0) | \
-        (_lib.DT_INFER_TOWER_BF16 if mode == _lib.DT_STEP_TOWER_BF16 else 0)
-
-
 class InferDeepFM:
     """Inference plan for the DeepFM graph: `prepare` writes the weight layouts (one launch, csrc/infer_x3.h k_infer_prep)
     from the parameters as they are at that moment, `infer` scores one batch (one launch, k_infer).  Needs nothing of the
@@ -757,10 +748,30 @@ class InferDeepFM:
                 ptr(bn.moving_variance), float(bn.epsilon), ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
                 ptr(d2.kernel), ld(d2.kernel), int(d2.kernel.shape[1]), ptr(d2.bias), cells, *cell_bn(bn1), *cell_bn(bn2))
 
+    def _sigmoid(self):
+        """DT_INFER_SIGMOID when the output activation is the sigmoid (the binary task), else 0"""
+        return _lib.DT_INFER_SIGMOID if self.dm.output_activation == 'sigmoid' else 0
+
+    def _tower_flags(self):
+        """dt_*_infer's flags of a plan with a tower: the output activation and the tower's precision mode
+        (`_tower_mfma_flag`: 'bf16' -> DT_INFER_TOWER_BF16; 'bf16x3' and 'f32' both run the six-product forward, which is in
+        the fp32 class)"""
+        mode = _tower_mfma_flag(self.dm.config.dnn_params)
+        return self._sigmoid() | (_lib.DT_INFER_TOWER_BF16 if mode == _lib.DT_STEP_TOWER_BF16 else 0)
+
+    def _gather_args(self, idx, kind):
+        """the five arguments every dt_*_infer starts with: ids, their DT_IDX_* kind, table, row offsets, vocabulary sizes"""
+        return (ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
+                ptr(getattr(self.emb, f'vocab_{self.key}')))
+
+    def _oob(self):
+        """the out-of-range counter, or None when the embedding layer does not count"""
+        return ptr(self.emb.oob_count) if self.emb.check_oob else None
+
     def prepare(self):
         """the current weights and moving statistics -> the workspace layouts, one launch on the current stream; also reads
         the precision mode and the output activation (the flags of the `infer` calls that follow)"""
-        self.flags = _infer_flags(self.dm)
+        self.flags = self._tower_flags()
         check(self._entry('infer_prepare')(
             self.F, self.D, self.Nd, *self._net_args(), *self._tower_args(),
             *self._head_weights(), ptr(self.out.bias), ptr(self.ws), stream_ptr()), f'dt_{self.PREFIX}_infer_prepare')
@@ -785,9 +796,8 @@ class InferDeepFM:
         (contiguous float32 device buffers, e.g. row slices of one buffer for the whole call).  After `prepare`."""
         B, idx, kind, dense = self._batch_args(idx, dense, logit, out)
         check(self._entry('infer')(
-            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *self._dims(), ptr(self.ws), ptr(logit), ptr(out),
-            ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, stream_ptr()), f'dt_{self.PREFIX}_infer')
+            *self._gather_args(idx, kind), ptr(dense), B, *self._dims(), ptr(self.ws), ptr(logit), ptr(out), self._oob(),
+            self.flags, stream_ptr()), f'dt_{self.PREFIX}_infer')
 
     def run_batches(self, data, batch_size, activate=True, each=None):
         """`prepare` once, then one `infer` per batch of `data` (training.TableBatches, in order) into ONE device buffer ->
@@ -994,7 +1004,7 @@ class InferXDeepFM(InferDeepFM):
     def prepare(self):
         """the tower's layouts as InferDeepFM.prepare, then the CIN as it is now: its precision mode, every layer's filter
         (packed for that mode's kernel), the exFM_out Dense's kernel and bias — one call"""
-        self.flags = _infer_flags(self.dm)
+        self.flags = self._tower_flags()
         self.cin_mode = _cin_mode(self.cin)
         nbytes = self._entry('infer_workspace_bytes')(*self._dims())
         if nbytes < 0:
@@ -1026,10 +1036,8 @@ class InferXDeepFM(InferDeepFM):
             sc = self._alloc_scratch(B)
         dims, cin_dims, ws, st = (self.F, self.D, self.Nd), self._cin_dims(), ptr(self.ws), stream_ptr()
         check(self._entry('infer_tower')(
-            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *dims, ws, ptr(sc['x0']), ptr(sc['partial']),
-            ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags & _lib.DT_INFER_TOWER_BF16, st),
-            'dt_xdeepfm_infer_tower')
+            *self._gather_args(idx, kind), ptr(dense), B, *dims, ws, ptr(sc['x0']), ptr(sc['partial']), self._oob(),
+            self.flags & _lib.DT_INFER_TOWER_BF16, st), 'dt_xdeepfm_infer_tower')
         for k in range(self.n_layers):
             check(self._entry('infer_cin')(k, ptr(sc['x0']), ptr(sc['y'][k - 1]) if k else None, self.cin_bias[k],
                                            self.cin_act, B, *dims, *cin_dims, ws, ptr(sc['y'][k]), st), 'dt_xdeepfm_infer_cin')
@@ -1111,7 +1119,7 @@ class InferAutoInt(InferDeepFM):
         """the layers' tensors as they are now -> the workspace (= the kernel's LDS image), one launch; also reads the
         precision mode, the residual switch and the output activation (the arguments of the `infer` calls that follow)"""
         n = self.n_layers
-        self.flags = _lib.DT_INFER_SIGMOID if self.dm.output_activation == 'sigmoid' else 0
+        self.flags = self._sigmoid()
         self.mode = self._mode(self.mha, self.D)
         res = bool(self.mha[0].use_residual)
         self.NP = 4 if res else 3
@@ -1132,10 +1140,8 @@ class InferAutoInt(InferDeepFM):
         """one batch, as InferDeepFM.infer: ids [B, F] -> logit [B, 1] and, if given, out [B, 1]; `dense` is not read"""
         B, idx, kind, _ = self._batch_args(idx, None, logit, out)
         check(self._entry('infer')(
-            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-            ptr(getattr(self.emb, f'vocab_{self.key}')), B, self.F, self.D, self.H, self.n_layers, self.NP, ptr(self.ws),
-            ptr(logit), ptr(out), ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, self.mode,
-            stream_ptr()), 'dt_autoint_infer')
+            *self._gather_args(idx, kind), B, self.F, self.D, self.H, self.n_layers, self.NP, ptr(self.ws), ptr(logit),
+            ptr(out), self._oob(), self.flags, self.mode, stream_ptr()), 'dt_autoint_infer')
 
 
 class InferAFM(InferDeepFM):
@@ -1211,7 +1217,7 @@ class InferAFM(InferDeepFM):
         """the AFM layer's, linear_logit's and task_output's tensors as they are now -> the workspace, one launch; also reads
         the attention activation and the output activation (the arguments of the `infer` calls that follow)"""
         afm, att = self.afm, self.afm.dense_attention
-        self.flags = _lib.DT_INFER_SIGMOID if self.dm.output_activation == 'sigmoid' else 0
+        self.flags = self._sigmoid()
         self.act = self._act(afm)
         check(self._entry('infer_prepare')(
             *self._dims(), ptr(att.kernel), ptr(att.bias), ptr(afm.attention_p), ptr(afm.dense_out.kernel),
@@ -1222,9 +1228,8 @@ class InferAFM(InferDeepFM):
         """one batch, as InferDeepFM.infer; `dense` reaches the kernel only when 'linear' is among the nets"""
         B, idx, kind, dense = self._batch_args(idx, dense if self.lin is not None else None, logit, out)
         check(self._entry('infer')(
-            ptr(idx), kind, ptr(self.emb.tables[self.key]), ptr(getattr(self.emb, f'row_offset_{self.key}')),
-            ptr(getattr(self.emb, f'vocab_{self.key}')), ptr(dense), B, *self._dims(), self.act, ptr(self.ws), ptr(logit),
-            ptr(out), ptr(self.emb.oob_count) if self.emb.check_oob else None, self.flags, stream_ptr()), 'dt_afm_infer')
+            *self._gather_args(idx, kind), ptr(dense), B, *self._dims(), self.act, ptr(self.ws), ptr(logit), ptr(out),
+            self._oob(), self.flags, stream_ptr()), 'dt_afm_infer')
 
 
 class InferPNN(InferDeepFM):

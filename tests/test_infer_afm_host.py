@@ -7,6 +7,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+from tests.infer_support import install_recorder
 from tests.test_infer_host import DEEPFM, DCN, _decode, _names
 from tests.test_infer_host import _model as _other_model
 
@@ -23,31 +24,9 @@ GRAPHS = [(['afm_nets'], AFM), (['afm_nets'], AFM),
           (['linear', 'fm_nets', 'afm_nets'], AFM | LIN | FM), (['afm_nets', 'fm_nets', 'linear'], AFM | LIN | FM)]
 
 
-class _Recorder:
-    """stand-in for fused.lib(): every inference launch is recorded as (name, args) and returns 0; every other call (the
-    predicates, the workspace size) goes to the real library"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in AFM_ENTRIES + OTHER_ENTRIES:
-            return lambda *args: self.calls.append((name, args)) or 0
-        return getattr(self.real, name)
-
-    def names(self):
-        return [n for n, _ in self.calls]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from deeptables_amd import _lib, fused
-    r = _Recorder(_lib.lib())
-    monkeypatch.setattr(fused, 'lib', lambda: r)
-    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
-    for k in ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT'):
-        monkeypatch.delenv(k, raising=False)
-    return r
+    return install_recorder(monkeypatch, AFM_ENTRIES + OTHER_ENTRIES, ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT'))
 
 
 def _model(nets=('linear', 'afm_nets'), task='binary', D=D_, F=F_, afm=None, **extra):

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from tests import precision as P
-from tests.test_infer_gpu import _frame, _ins, _oracle, _train_and_perturb
+from tests.infer_support import _frame, _oracle, _train_and_perturb, run_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -38,16 +38,7 @@ def _mode_name(dm, D):
 
 def _run_plan(dm, idx, dense, dev, kind='int32'):
     from deeptables_amd import fused
-    plan = dm.inference_plan()
-    assert type(plan) is fused.InferAutoInt
-    B = idx.shape[0]
-    ins = _ins(idx, dense, dev, kind)
-    logit = torch.empty((B, 1), dtype=torch.float32, device=dev)
-    out = torch.empty_like(logit)
-    plan.prepare()
-    plan.infer(ins[0], ins[1] if len(ins) > 1 else None, logit, out)
-    torch.cuda.synchronize()
-    return logit, out
+    return run_plan(dm, idx, dense, dev, fused.InferAutoInt, kind)
 
 
 def _check(dm, idx, dense, dev, label, kind='int32', weights=None, ids_oracle=None):

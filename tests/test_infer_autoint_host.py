@@ -9,6 +9,7 @@ import numpy as np
 import pandas as pd
 import pytest
 
+from tests.infer_support import install_recorder
 from tests.test_infer_host import DEEPFM, DCN, _decode, _names
 from tests.test_infer_host import _model as _other_model
 
@@ -21,31 +22,10 @@ F32, BF16, X2 = 0, 1, 2
 AUTOINT = {'num_attention': 2, 'num_heads': 2, 'dropout_rate': 0, 'use_residual': True}
 
 
-class _Recorder:
-    """stand-in for fused.lib(): every inference launch is recorded as (name, args) and returns 0; every other call (the
-    predicates, the workspace size) goes to the real library"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in AI_ENTRIES + OTHER_ENTRIES:
-            return lambda *args: self.calls.append((name, args)) or 0
-        return getattr(self.real, name)
-
-    def names(self):
-        return [n for n, _ in self.calls]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from deeptables_amd import _lib, fused
-    r = _Recorder(_lib.lib())
-    monkeypatch.setattr(fused, 'lib', lambda: r)
-    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
-    for k in ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_AUTOINT_DTYPE'):
-        monkeypatch.delenv(k, raising=False)
-    return r
+    return install_recorder(monkeypatch, AI_ENTRIES + OTHER_ENTRIES,
+                            ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_AUTOINT_DTYPE'))
 
 
 def _model(nets=('autoint_nets',), task='binary', D=D_, conts=True, autoint=AUTOINT, **extra):

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import precision as P
+from tests.infer_support import _frame, _oracle, _train_and_perturb, run_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -30,49 +31,8 @@ def _build(net, F=26, D=16, Nd=13, L=3, vocab=30, hidden=None, **kw):
     return dm, cats
 
 
-def _ins(idx, dense, dev, kind='int32'):
-    ids = idx.to(torch.int32 if kind == 'int32' else torch.float32).to(dev)
-    return [ids] + ([dense.to(dev)] if dense is not None else [])
-
-
-def _train_and_perturb(dm, cats, Nd, dev, steps=3, seed=21):
-    """a few train steps (the weights and moving statistics leave their initial values), then the moving statistics are
-    moved away from (0, 1) so that the inference BN is not the identity"""
-    import tests.test_fused_gpu as T
-    for s in range(steps):
-        idx, dense, y = T.batch(cats, Nd, 64, seed=seed + s)
-        dm.train_step(_ins(idx, dense, dev), y.to(dev))
-    g = torch.Generator().manual_seed(seed)
-    with torch.no_grad():
-        for name, layer in dm.model.layers_by_name.items():
-            if hasattr(layer, 'moving_mean') and layer.moving_mean is not None:
-                mm, mv = layer.moving_mean, layer.moving_variance
-                mm.add_((torch.randn(mm.shape, generator=g) * 0.2).to(mm.device))
-                mv.mul_((torch.rand(mv.shape, generator=g) + 0.5).to(mv.device))
-
-
-def _run_plan(dm, idx, dense, dev, kind='int32'):
-    """-> (logit [B,1], out [B,1]) of one prepare + one infer"""
-    plan = dm.inference_plan()
-    assert plan is not None
-    B = idx.shape[0]
-    ins = _ins(idx, dense, dev, kind)
-    logit = torch.empty((B, 1), dtype=torch.float32, device=dev)
-    out = torch.empty_like(logit)
-    plan.prepare()
-    plan.infer(ins[0], ins[1] if len(ins) > 1 else None, logit, out)
-    torch.cuda.synchronize()
-    return logit, out
-
-
-def _oracle(dm, ids, dense, dtype, weights=None):
-    from oracle import bridge
-    with torch.no_grad():
-        return bridge.oracle_forward(dm, ids, dense, dtype=dtype, training=False, weights=weights)[0]
-
-
 def _check(dm, idx, dense, dev, mode, label, kind='int32', weights=None, ids_oracle=None):
-    logit, out = _run_plan(dm, idx, dense, dev, kind)
+    logit, out = run_plan(dm, idx, dense, dev, None, kind)
     ids_o = idx if ids_oracle is None else ids_oracle
     w64 = weights(torch.float64) if weights else None
     w32 = weights(torch.float32) if weights else None
@@ -190,16 +150,6 @@ def test_head_variants_and_ignored_dropouts(dev, monkeypatch, net, variant):
     _train_and_perturb(dm, cats, 13, dev, steps=2)
     idx, dense, _ = T.batch(cats, 13, 70, seed=8)
     _check(dm, idx, dense, dev, 'bf16x3', f'infer_head[{net},{variant}]')
-
-
-def _frame(cats, Nd, n, seed):
-    import pandas as pd
-    import tests.test_fused_gpu as T
-    idx, dense, y = T.batch(cats, Nd, n, seed=seed)
-    df = pd.DataFrame({c.name: idx[:, i].numpy() for i, c in enumerate(cats)})
-    for j in range(Nd):
-        df[f'I{j}'] = dense[:, j].numpy()
-    return df, y.reshape(-1).numpy()
 
 
 @pytest.mark.parametrize('net', ['DeepFM', 'DCN'])

@@ -7,6 +7,8 @@ import pandas as pd
 import pytest
 import torch
 
+from tests.infer_support import install_recorder
+
 H1, H2 = 128, 64
 # (F, D, Nd): the corners of the step's field / width domain (csrc/tile_common.h deepfm_dims)
 CORNERS = [(8, 64, 0), (7, 64, 64), (1, 4, 0), (1, 4, 64), (127, 4, 0), (128, 4, 32), (16, 16, 0), (32, 16, 32)]
@@ -55,31 +57,9 @@ F_, D_, ND_ = 6, 8, 3
 INFER_ENTRIES = ('dt_deepfm_infer_prepare', 'dt_deepfm_infer', 'dt_dcn_infer_prepare', 'dt_dcn_infer')
 
 
-class _InferRecorder:
-    """stand-in for fused.lib(): the inference launches are recorded as (name, args) and return 0; every other call goes to
-    the real library"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in INFER_ENTRIES:
-            return lambda *args: self.calls.append((name, args)) or 0
-        return getattr(self.real, name)
-
-    def names(self):
-        return [n for n, _ in self.calls]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from deeptables_amd import _lib, fused
-    r = _InferRecorder(_lib.lib())
-    monkeypatch.setattr(fused, 'lib', lambda: r)
-    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
-    for k in ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE'):
-        monkeypatch.delenv(k, raising=False)
-    return r
+    return install_recorder(monkeypatch, INFER_ENTRIES, ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE'))
 
 
 def _model(nets, hidden=((100, 0, False), (40, 0, False)), task='binary', **extra):

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests import precision as P
-from tests.test_infer_gpu import _ins, _oracle, _train_and_perturb
+from tests.infer_support import _ins, _oracle, _train_and_perturb, run_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -61,16 +61,7 @@ def _trained(dm, cats, Nd, dev, steps=2, train=True):
 
 def _run_plan(dm, idx, dense, dev, kind='int32'):
     from deeptables_amd import fused
-    plan = dm.inference_plan()
-    assert type(plan) is fused.InferPNN
-    B = idx.shape[0]
-    ins = _ins(idx, dense, dev, kind)
-    logit = torch.empty((B, 1), dtype=torch.float32, device=dev)
-    out = torch.empty_like(logit)
-    plan.prepare()
-    plan.infer(ins[0], ins[1] if len(ins) > 1 else None, logit, out)
-    torch.cuda.synchronize()
-    return logit, out
+    return run_plan(dm, idx, dense, dev, fused.InferPNN, kind)
 
 
 def _figs(dm, logit, out, r64, r32):

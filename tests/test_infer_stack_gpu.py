@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import tests.test_infer_gpu as I
+from tests.infer_support import _frame, _train_and_perturb
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +42,7 @@ def test_every_net_combination_matches_the_oracle_after_training(dev, monkeypatc
     from deeptables_amd import fused
     monkeypatch.setenv('DT_AMD_TOWER_DTYPE', mode)
     dm, cats = _build(nets)
-    I._train_and_perturb(dm, cats, 13, dev)
+    _train_and_perturb(dm, cats, 13, dev)
     plan = dm.inference_plan()
     assert plan is not None, f'{nets} should take a fused inference plan'
     assert type(plan) is (fused.InferDeepFM if len(nets) == 3 else fused.InferStack)
@@ -62,7 +63,7 @@ def test_inference_at_the_corners(dev, monkeypatch, nets, mode, F, D, Nd, B):
     import tests.test_fused_gpu as T
     monkeypatch.setenv('DT_AMD_TOWER_DTYPE', mode)
     dm, cats = _build(nets, F, D, Nd)
-    I._train_and_perturb(dm, cats, Nd, dev, steps=1)
+    _train_and_perturb(dm, cats, Nd, dev, steps=1)
     idx, dense, _ = T.batch(cats, Nd, B, seed=B)
     I._check(dm, idx, dense, dev, mode, f'infer_stack_corner[{_id(nets)},{mode},{F},{D},{Nd},{B}]')
 
@@ -78,7 +79,7 @@ def test_out_of_range_and_fractional_ids(dev, monkeypatch, nets, kind):
     mode = _mode(nets)
     monkeypatch.setenv('DT_AMD_TOWER_DTYPE', mode)
     dm, cats = _build(nets, 26, 16, 13, vocab=60)
-    I._train_and_perturb(dm, cats, 13, dev, steps=1)
+    _train_and_perturb(dm, cats, 13, dev, steps=1)
     idx, dense, _ = T.batch(cats, 13, 65, seed=17)
     ids, n_oob = _odd_ids(cats, idx, kind)
     trunc = ids.to(torch.int32).to(torch.int64)
@@ -113,7 +114,7 @@ def test_head_variants(dev, monkeypatch, nets, variant):
     kw = {'no_output_bias': dict(use_bias=False), 'regression': dict(task='regression')}[variant]
     dm, cats = _build(nets, **kw)
     assert (dm.model.layers_by_name['task_output'].bias is None) == (variant == 'no_output_bias')
-    I._train_and_perturb(dm, cats, 13, dev, steps=2)
+    _train_and_perturb(dm, cats, 13, dev, steps=2)
     idx, dense, _ = T.batch(cats, 13, 70, seed=8)
     logit, out = I._check(dm, idx, dense, dev, mode, f'infer_stack_head[{_id(nets)},{variant}]')
     if variant == 'regression':
@@ -129,7 +130,7 @@ def test_tower_cells_with_dropout_and_batch_norm(dev, monkeypatch, nets, hidden)
     import tests.test_fused_gpu as T
     monkeypatch.setenv('DT_AMD_TOWER_DTYPE', 'bf16x3')
     dm, cats = _build(nets, hidden=hidden, embedding_dropout=0.3, dense_dropout=0.4)
-    I._train_and_perturb(dm, cats, 13, dev, steps=2)
+    _train_and_perturb(dm, cats, 13, dev, steps=2)
     idx, dense, _ = T.batch(cats, 13, 97, seed=3)
     I._check(dm, idx, dense, dev, 'bf16x3', f'infer_stack_tower[{_id(nets)},{hidden}]')
 
@@ -140,8 +141,8 @@ def test_predictions_are_row_independent_and_match_the_layer_path(dev, monkeypat
     layer path (DT_AMD_FUSED_PREDICT=0) at the bars of tests/test_infer_gpu.py::test_fit_predict_evaluate_against_the_layer_path"""
     monkeypatch.setenv('DT_AMD_TOWER_DTYPE', 'bf16x3')
     dm, cats = _build(nets)
-    I._train_and_perturb(dm, cats, 13, dev)
-    df, y = I._frame(cats, 13, 9000, 4)
+    _train_and_perturb(dm, cats, 13, dev)
+    df, y = _frame(cats, 13, 9000, 4)
     p1 = dm.predict(df, batch_size=128)
     p2 = dm.predict(df, batch_size=128)
     p7 = dm.predict(df, batch_size=7)
@@ -165,7 +166,7 @@ def test_the_layer_path_is_not_run(dev, monkeypatch, nets):
         nets = ModelConfig().nets
         assert nets == [DNN]
     dm, cats = _build(nets)
-    df, y = I._frame(cats, 13, 300, 2)
+    df, y = _frame(cats, 13, 300, 2)
 
     def boom(*a, **k):
         raise AssertionError('the layer-by-layer forward ran')

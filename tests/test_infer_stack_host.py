@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.infer_support import install_recorder
 from tests.test_infer_host import CORNERS, PAST, H1, H2, F_, D_, ND_, DEEPFM, DCN, _frame, _model, _names, _decode
 
 LIN, FM, DNN = 1, 2, 4
@@ -142,31 +143,10 @@ def test_entry_points_check_their_arguments_before_any_launch():
 
 
 # ---- routing ------------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """stand-in for fused.lib(): every inference launch is recorded as (name, args) and returns 0; every other call goes to
-    the real library"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in STACK_ENTRIES + OTHER_ENTRIES:
-            return lambda *args: self.calls.append((name, args)) or 0
-        return getattr(self.real, name)
-
-    def names(self):
-        return [n for n, _ in self.calls]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from deeptables_amd import _lib, fused
-    r = _Recorder(_lib.lib())
-    monkeypatch.setattr(fused, 'lib', lambda: r)
-    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
-    for k in ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE'):
-        monkeypatch.delenv(k, raising=False)
-    return r
+    return install_recorder(monkeypatch, STACK_ENTRIES + OTHER_ENTRIES,
+                            ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE'))
 
 
 def _expected_prepare(dm, nets, ld1=100, ld2=40):

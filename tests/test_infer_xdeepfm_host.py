@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.infer_support import install_recorder
 from tests.test_infer_host import F_, D_, ND_, DEEPFM, DCN, _frame, _model, _names, _decode
 
 XDEEPFM = ['linear', 'cin_nets', 'dnn_nets']
@@ -22,31 +23,10 @@ CIN = {'cross_layer_size': (8, 6), 'direct': False}
 F32, BF16, X3 = 0, 1, 2
 
 
-class _Recorder:
-    """stand-in for fused.lib(): every inference launch is recorded as (name, args) and returns 0; every other call goes to
-    the real library"""
-
-    def __init__(self, real):
-        self.real, self.calls = real, []
-
-    def __getattr__(self, name):
-        if name in XD_ENTRIES + OTHER_ENTRIES:
-            return lambda *args: self.calls.append((name, args)) or 0
-        return getattr(self.real, name)
-
-    def names(self):
-        return [n for n, _ in self.calls]
-
-
 @pytest.fixture
 def rec(monkeypatch):
-    from deeptables_amd import _lib, fused
-    r = _Recorder(_lib.lib())
-    monkeypatch.setattr(fused, 'lib', lambda: r)
-    monkeypatch.setattr(fused, 'stream_ptr', lambda: None)
-    for k in ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE', 'DT_AMD_CIN_DTYPE'):
-        monkeypatch.delenv(k, raising=False)
-    return r
+    return install_recorder(monkeypatch, XD_ENTRIES + OTHER_ENTRIES,
+                            ('DT_AMD_FUSED', 'DT_AMD_FUSED_PREDICT', 'DT_AMD_TOWER_DTYPE', 'DT_AMD_CIN_DTYPE'))
 
 
 def _xd(nets=XDEEPFM, hidden=((100, 0, False), (40, 0, False)), cin=CIN, **kw):
