@@ -222,6 +222,14 @@ SIGNATURES = {
                                       _ptr, _ptr, _ptr]),
     'dt_pnn_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
                               _ptr, _ptr, _c_int, _ptr]),
+    # fused FiBiNet inference (csrc/fibi_infer.hip): bilinear_type = DT_BILINEAR_*, pooling_op = DT_FIBI_POOL_*
+    'dt_fibi_infer_supported': (_c_int, [_c_int] * 9),
+    'dt_fibi_infer_workspace_bytes': (_c_i64, [_c_int] * 5),
+    'dt_fibi_infer_prepare': (_c_int, [_c_int] * 5 + [_ptr] * 6 + [_ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr,
+                                       _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr,
+                                       _ptr, _ptr]),
+    'dt_fibi_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                               _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -239,6 +247,9 @@ DT_NET_AFM = 0x8
 DT_AFM_INFER_ROWS, DT_AFM_INFER_MAX_BLOCKS = 4, 1024
 DT_PNN_INNER, DT_PNN_OUTER = 0x1, 0x2
 DT_PNN_INFER_MAX_BLOCKS = 512
+DT_BILINEAR_FIELD_INTERACTION, DT_BILINEAR_FIELD_EACH, DT_BILINEAR_FIELD_ALL = 0, 1, 2      # ops.BILINEAR_TYPES' codes
+DT_FIBI_POOL_MEAN, DT_FIBI_POOL_MAX = 0, 1
+DT_FIBI_INFER_MAX_BLOCKS = 512
 DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
 DT_XDEEPFM_MAX_LAYERS = 8
 DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256

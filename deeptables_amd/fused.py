@@ -731,7 +731,11 @@ class InferDeepFM:
     def _tower_args(self):
         """dt_*_infer_prepare's arguments from bn_gamma to c2_eps: the input BN and the two tower cells as they are now"""
         bn = self.bn
+        return (ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean), ptr(bn.moving_variance), float(bn.epsilon)) + \
+            self._cell_args()
 
+    def _cell_args(self):
+        """dt_*_infer_prepare's arguments from W1 to c2_eps: the two tower cells as they are now"""
         def ld(w):
             if w.dim() != 2 or w.stride(1) != 1:
                 raise _lib.DtHipError(f'inference plan: tower kernel with strides {tuple(w.stride())}')
@@ -744,8 +748,7 @@ class InferDeepFM:
 
         (d1, bn1), (d2, bn2) = self.cells
         cells = (1 if bn1 is not None else 0) | (2 if bn2 is not None else 0)
-        return (ptr(bn.gamma), ptr(bn.beta), ptr(bn.moving_mean),
-                ptr(bn.moving_variance), float(bn.epsilon), ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
+        return (ptr(d1.kernel), ld(d1.kernel), int(d1.kernel.shape[1]), ptr(d1.bias),
                 ptr(d2.kernel), ld(d2.kernel), int(d2.kernel.shape[1]), ptr(d2.bias), cells, *cell_bn(bn1), *cell_bn(bn2))
 
     def _sigmoid(self):
@@ -1313,10 +1316,128 @@ class InferPNN(InferDeepFM):
         return (ptr(self.out.kernel),)          # w3: the tower alone, the output weight is 1
 
 
+class InferFiBiNet(InferDeepFM):
+    """Inference plan for the FiBiNet graph: 'fibi_dnn_nets' alone in config.nets (deepnets.FiBiNet), with every bilinear_type
+    and both senet_pooling_op values.  ONE launch per batch (dt_fibi_infer, csrc/fibi_infer.hip k_fibi_infer): the table
+    gather, SENET, both bilinear layers from the raw rows (on the exact-fp32 matrix core; the SENET-scaled stack is never
+    formed), the tower on [senet half | raw half | the raw dense values], task_output and the activation; neither the field
+    stack, the bilinear blocks nor their concatenation is written.  The dense values enter the tower raw: bn_concat_emb_dense
+    is not part of this graph, and the plan applies none.
+
+    The head follows deepmodel.py:286-301 for a single net: task_output's [H2, 1] kernel is the tower's output vector and the
+    output weight is 1.  `prepare` hands the tensors over as they are at that moment — the bilinear type, the pooling op, the
+    tower mode and the output activation are read there: the plan holds no copy of a parameter between calls.
+    Refused (the layer path runs): multiclass, 'fibi_dnn_nets' beside any other net, 'fibi_nets', concat stacking, fewer than
+    two categorical fields or no dense input (the net is absent), var-len columns, several embedding groups, sharded
+    embeddings, a tower outside `_infer_tower`, a task_output kernel that is not [H2, 1], more or fewer than one SENET / senet
+    bilinear / embedding bilinear layer, shapes outside dt_fibi_infer_supported (2 <= F <= 64, embedding size in {4, 8, 16, 32,
+    64}, F D <= 512, 1 <= Nd <= 64), DT_AMD_FUSED=0 / DT_AMD_FUSED_PREDICT=0."""
+
+    PREFIX = 'fibi'
+    CELL = 'fibi_dnn'
+
+    @staticmethod
+    def _fibi_layers(dm):
+        """(SENET, senet bilinear, embedding bilinear): the layers carry a counter in their names, so they are found by prefix
+        and type — exactly one of each, else None"""
+        from .models.layers import SENET, BilinearInteraction
+        found = []
+        for prefix, kind in (('senet_layer_', SENET), ('senet_bilinear_layer_', BilinearInteraction),
+                             ('embedding_bilinear_layer_', BilinearInteraction)):
+            hits = [l for n, l in dm.model.layers_by_name.items()
+                    if n.startswith(prefix) and n[len(prefix):].isdigit() and isinstance(l, kind)]
+            if len(hits) != 1:
+                return None
+            found.append(hits[0])
+        return tuple(found)
+
+    @staticmethod
+    def _codes(se, bs, br):
+        """(DT_BILINEAR_* of the two bilinear layers as BilinearInteraction.call reads it, DT_FIBI_POOL_*, R) as they are now"""
+        from .ops import BILINEAR_TYPES
+        kinds = {b.bilinear_type if b.bilinear_type in ('field_all', 'field_each') else 'field_interaction' for b in (bs, br)}
+        if len(kinds) != 1:
+            raise ValueError('the two bilinear layers differ in their bilinear_type')
+        pool = _lib.DT_FIBI_POOL_MAX if se.pooling_op == 'max' else _lib.DT_FIBI_POOL_MEAN
+        return BILINEAR_TYPES[kinds.pop()], pool, int(se.reduction_num)
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            nets = list(c.nets)
+            if len(nets) != 1 or not isinstance(nets[0], str) or nets[0] != 'fibi_dnn_nets':
+                return False
+            if c.stacking_op != consts.STACKING_OP_ADD or getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            # (tower=None: this graph reads no bn_concat_emb_dense, so _step_dims must not ask for one)
+            dims = _step_dims(dm, (f'{cls.CELL}_dense_1', f'{cls.CELL}_dense_2'), tower=None)
+            found = cls._fibi_layers(dm)
+            tower = _infer_tower(c.dnn_params)
+            if dims is None or found is None or tower is None:
+                return False
+            se, bs, br = found
+            L = dm.model.layers_by_name
+            _, F, D, Nd = dims
+            bt, pool, R = cls._codes(se, bs, br)
+            P = F * (F - 1) // 2
+            if tuple(L['task_output'].kernel.shape) != (tower[1], 1) or \
+                    int(L[f'{cls.CELL}_dense_1'].kernel.shape[0]) != 2 * P * D + Nd:
+                return False
+            nw = (P, F - 1, 1)[bt]
+            if tuple(bs.W.shape) != (nw, D, D) or tuple(br.W.shape) != (nw, D, D):
+                return False
+            if tuple(se.dense_att1.kernel.shape) != (F, R) or tuple(se.dense_att2.kernel.shape) != (R, F):
+                return False
+            return bool(lib().dt_fibi_infer_supported(F, D, Nd, *tower, bt, pool, R))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.bn = None                          # (bn_concat_emb_dense is not part of this graph)
+        self.cells = [(L[f'{self.CELL}_dense_{i}'], L.get(f'{self.CELL}_bn_{i}')) for i in (1, 2)]
+
+    def _net_layers(self, L):
+        self.se, self.bs, self.br = self._fibi_layers(self.dm)
+        self.bt, self.pool, self.R = self._codes(self.se, self.bs, self.br)
+
+    def _dims(self):
+        """dt_fibi_infer_workspace_bytes' arguments"""
+        return self.F, self.D, self.Nd, self.bt, self.R
+
+    def prepare(self):
+        """the SENET, bilinear, tower and task_output tensors as they are now -> the workspace, one launch; also reads the
+        bilinear type, the pooling op, R, the tower's precision mode and the output activation (the arguments of the `infer`
+        calls that follow)"""
+        se, bs, br = self.se, self.bs, self.br
+        self.flags = self._tower_flags()
+        self.bt, self.pool, self.R = self._codes(se, bs, br)
+        nbytes = self._entry('infer_workspace_bytes')(*self._dims())
+        if nbytes < 0:
+            raise _lib.DtHipError('InferFiBiNet: unsupported shape')
+        if nbytes > self.ws.numel() * 4:           # the bilinear type changed to one with a larger layout
+            self.ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        for t in (se.dense_att1.kernel, se.dense_att2.kernel, bs.W, br.W):
+            if not t.is_contiguous():
+                raise _lib.DtHipError(f'inference plan: SENET / bilinear weight with strides {tuple(t.stride())}')
+        check(self._entry('infer_prepare')(
+            *self._dims(), ptr(se.dense_att1.kernel), ptr(se.dense_att1.bias), ptr(se.dense_att2.kernel),
+            ptr(se.dense_att2.bias), ptr(bs.W), ptr(br.W), *self._cell_args(), ptr(self.out.kernel), ptr(self.out.bias),
+            ptr(self.ws), stream_ptr()), 'dt_fibi_infer_prepare')
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch, as InferDeepFM.infer"""
+        B, idx, kind, dense = self._batch_args(idx, dense, logit, out)
+        check(self._entry('infer')(
+            *self._gather_args(idx, kind), ptr(dense), B, self.F, self.D, self.Nd, self.bt, self.pool, self.R, ptr(self.ws),
+            ptr(logit), ptr(out), self._oob(), self.flags, stream_ptr()), 'dt_fibi_infer')
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
-    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM, InferPNN):
+    for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM, InferPNN,
+                 InferFiBiNet):
         if plan.eligible(dm):
             return plan(dm)
     return None

@@ -924,6 +924,56 @@ int dt_pnn_infer(const void* idx, int idx_kind, const float* table, const int64_
                  const float* dense, int64_t B, int F, int D, int Nd, int products, int kernel_type, const void* workspace,
                  float* logit_out, float* out, int* oob_count, int flags, void* stream);
 
+/* ---- fused FiBiNet inference: ONE launch per predict batch (csrc/fibi_infer.hip k_fibi_infer; replaces, for the net
+ * 'fibi_dnn_nets' alone in config.nets (deepnets.FiBiNet), the layer-by-layer forward of the reference's DeepModel.predict /
+ * evaluate: the embedding gather (layers.py:889-904), SENET.call layers.py:245-308, the two BilinearInteraction.call
+ * layers.py:311-382, deepnets.py:344-386 — Concatenate of the two [P][D] blocks, Flatten, Concatenate with the RAW dense
+ * values, the two-cell relu tower deepnets.py:401-427 with Dropout as the identity — and the head deepmodel.py:286-301: a
+ * single net, so no dense_logit layer and no Add; task_output's [H2][1] kernel is the tower's output vector and the output
+ * weight is 1).  bn_concat_emb_dense is not part of this graph and is not applied.
+ *   bilinear_type = DT_BILINEAR_* (ops.BILINEAR_TYPES' codes); pooling_op = DT_FIBI_POOL_*; R = SENET's reduction_num =
+ *   max(F / reduction_ratio, 1).  P = F (F - 1) / 2 pairs (i, j), i < j, in itertools.combinations order; a pair's weight is
+ *   W[p] 'field_interaction' | W[i] 'field_each' | W[0] 'field_all'.  The first Dense's rows: the senet half (P D columns,
+ *   pair-major: a2_i a2_j ((x_i . Ws) * x_j)), the raw half (P D columns: (x_i . Wr) * x_j), the Nd dense columns.
+ *   A block owns a 32-row tile: the rows go to LDS once, SENET's a2 [F] per row is computed once per tile in plain fp32, the
+ *   first Dense's K = 2 P D + Nd runs in chunks of 128 columns that are computed into LDS (W^T . X_i^T on the exact-fp32 matrix
+ *   core, then the elementwise products) and multiplied at once; the accumulators stay in registers over all chunks.  SENET
+ *   and the bilinear products are exact fp32 in both tower modes.
+ *   dt_fibi_infer_supported: 1 iff 2 <= F <= 64, D in {4, 8, 16, 32, 64}, F D <= 512, 1 <= Nd <= 64 (the net concatenates the
+ *     dense input unconditionally), 1 <= R <= 64, 1 <= H1 <= 128, 1 <= H2 <= 64, cells a mask of bits 0 / 1 (as
+ *     dt_deepfm_infer_supported), bilinear_type and pooling_op one of their codes.
+ *   dt_fibi_infer_workspace_bytes: size of `workspace` (16-byte aligned; about 8 MB at F = 26, D = 16, 25 MB at F = 64, D = 8),
+ *     -1 outside the shape domain.
+ *   dt_fibi_infer_prepare (once per predict / evaluate, one launch; it writes what the batch launches read, from the values
+ *     the tensors hold at call time): SENET's att1 kernel [F][R] and bias [R], att2 kernel [R][F] and bias [F] (a bias may be
+ *     NULL), the stacked W [nW][D][D] of senet_bilinear_layer and of embedding_bilinear_layer (nW = P | F - 1 | 1; each
+ *     matrix is stored transposed), W1 [2 P D + Nd][ld1], W2 and the two cells' bias / BN arguments as
+ *     dt_deepfm_infer_prepare, w3 [H2] = task_output's kernel, b_out = its bias or NULL.
+ *   dt_fibi_infer (per batch of B >= 0 rows, B < 2^31; B = 0: no launch, no pointer is looked at): ids [B][F] (idx_kind =
+ *     DT_IDX_*; an id outside [0, vocab[f]) reads a zero row and is counted once into *oob_count when it is given), dense
+ *     [B][Nd] -> logit_out [B] and, if out != NULL, out [B] = sigmoid(logit) with DT_INFER_SIGMOID or the logit.  flags |
+ *     DT_INFER_TOWER_BF16: the first tower GEMM on plain bf16 operands.  The workspace carries the (F, D, Nd, bilinear_type, R)
+ *     it was prepared for: a launch with other values reads no weight and writes NaN into every logit and output.  The
+ *     launch is refused when the tile needs more than 160 KB of LDS (no shape of the domain does).  The grid is at most
+ *     DT_FIBI_INFER_MAX_BLOCKS blocks, strided over the 32-row tiles. */
+#define DT_BILINEAR_FIELD_INTERACTION 0
+#define DT_BILINEAR_FIELD_EACH 1
+#define DT_BILINEAR_FIELD_ALL 2
+#define DT_FIBI_POOL_MEAN 0
+#define DT_FIBI_POOL_MAX 1
+#define DT_FIBI_INFER_MAX_BLOCKS 512
+int dt_fibi_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int bilinear_type, int pooling_op, int R);
+int64_t dt_fibi_infer_workspace_bytes(int F, int D, int Nd, int bilinear_type, int R);
+int dt_fibi_infer_prepare(int F, int D, int Nd, int bilinear_type, int R, const float* se_k1, const float* se_b1,
+                          const float* se_k2, const float* se_b2, const float* W_senet, const float* W_raw, const float* W1,
+                          int ld1, int H1, const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells,
+                          const float* c1_gamma, const float* c1_beta, const float* c1_mean, const float* c1_var, float c1_eps,
+                          const float* c2_gamma, const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps,
+                          const float* w3, const float* b_out, void* workspace, void* stream);
+int dt_fibi_infer(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                  const float* dense, int64_t B, int F, int D, int Nd, int bilinear_type, int pooling_op, int R,
+                  const void* workspace, float* logit_out, float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
