@@ -230,6 +230,18 @@ SIGNATURES = {
                                        _ptr, _ptr]),
     'dt_fibi_infer': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
                                _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
+    # fused FGCNN inference (csrc/fgcnn_infer.hip): depth, then the blocks' filters / heights / pools / new_filters as HOST int
+    # arrays; prepare takes HOST arrays of the blocks' device pointers; per batch conv / recomb per block, then tower
+    'dt_fgcnn_infer_supported': (_c_int, [_c_int] * 7 + [_ptr] * 4),
+    'dt_fgcnn_infer_workspace_bytes': (_c_i64, [_c_int] * 4 + [_ptr] * 4),
+    'dt_fgcnn_infer_prepare': (_c_int, [_c_int] * 4 + [_ptr] * 8 + [_ptr, _c_int, _c_int, _ptr, _ptr, _c_int, _c_int, _ptr,
+                                        _c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr,
+                                        _ptr, _ptr]),
+    'dt_fgcnn_infer_conv': (_c_int, [_c_int, _ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int]
+                            + [_ptr] * 4 + [_ptr, _ptr, _ptr]),
+    'dt_fgcnn_infer_recomb': (_c_int, [_c_int, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int] + [_ptr] * 4 + [_ptr, _ptr, _ptr]),
+    'dt_fgcnn_infer_tower': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int]
+                             + [_ptr] * 4 + [_ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -250,6 +262,7 @@ DT_PNN_INFER_MAX_BLOCKS = 512
 DT_BILINEAR_FIELD_INTERACTION, DT_BILINEAR_FIELD_EACH, DT_BILINEAR_FIELD_ALL = 0, 1, 2      # ops.BILINEAR_TYPES' codes
 DT_FIBI_POOL_MEAN, DT_FIBI_POOL_MAX = 0, 1
 DT_FIBI_INFER_MAX_BLOCKS = 512
+DT_FGCNN_INFER_MAX_BLOCKS, DT_FGCNN_INFER_MAX_DEPTH = 512, 3
 DT_CIN_F32, DT_CIN_BF16, DT_CIN_BF16X3 = 0, 1, 2
 DT_XDEEPFM_MAX_LAYERS = 8
 DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256

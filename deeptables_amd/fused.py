@@ -1433,11 +1433,182 @@ class InferFiBiNet(InferDeepFM):
             ptr(logit), ptr(out), self._oob(), self.flags, stream_ptr()), 'dt_fibi_infer')
 
 
+class InferFGCNN(InferDeepFM):
+    """Inference plan for the FGCNN graph: 'fgcnn_dnn_nets' alone in config.nets (deepnets.FGCNN), with any block list of
+    fgcnn_params inside the library's domain.  2 depth + 1 launches per batch (csrc/fgcnn_infer.hip), every one the
+    library's own kernel:
+      conv:   per block, the (h, 1) convolution with its taps read from the map in LDS (block 1 gathers the table rows
+              itself), tanh and the max pooling -> the pooled map [B, Fp D filters];
+      recomb: per block, the recombination Dense on the matrix core (split-bf16, the fp32 class) on a weight packed in
+              `prepare`, tanh -> the block's columns of the generated features [B, sum F_k D nf_k];
+      tower:  the gather again, the tower on [generated features | raw embedding rows | raw dense values] in K chunks,
+              task_output and the activation.
+    The pooled maps and the generated features live in a batch-sized scratch owned by the call (`run_batches`; a lone
+    `infer` allocates its own); neither the taps matrix, a padded map nor the tower's input is written.  The dense values
+    enter the tower raw: bn_concat_emb_dense is not part of this graph.  The head follows deepmodel.py:286-301 for a single
+    net: task_output's [H2, 1] kernel is the tower's output vector.  `prepare` hands every tensor over as it is at that
+    moment; the tower's precision mode acts on the tower only, the blocks stay in the fp32 class.
+    Refused (the layer path runs): multiclass, 'fgcnn_dnn_nets' beside any other net, every other fgcnn_* / fg_nets net,
+    concat stacking, fewer than two categorical fields (the net is absent), var-len columns, several embedding groups,
+    sharded embeddings, a tower outside `_infer_tower`, a block whose activation is not tanh, a layer count or a weight
+    shape that does not follow from (F, D, fgcnn_params), shapes outside dt_fgcnn_infer_supported (2 <= F <= 64, embedding
+    size in {4, 8, 16, 32, 64}, F D <= 512, Nd <= 64, 1 to 3 blocks, filters <= 16, heights <= 9, pool heights <= 3, new
+    filters <= 3), DT_AMD_FUSED=0 / DT_AMD_FUSED_PREDICT=0."""
+
+    PREFIX = 'fgcnn'
+    CELL = 'fgcnn_dnn'
+
+    @staticmethod
+    def _blocks(dm):
+        """the layers.FGCNN layers in creation order"""
+        from .models.layers import FGCNN
+        return [l for l in dm.model.layers_by_name.values() if isinstance(l, FGCNN)]
+
+    @staticmethod
+    def _params(blocks):
+        """(filters, heights, pool heights, new filters) of the blocks as they are now, each a tuple of ints"""
+        return (tuple(int(b.filters) for b in blocks), tuple(int(b.kernel_height) for b in blocks),
+                tuple(int(b.pool_height) for b in blocks), tuple(int(b.new_filters) for b in blocks))
+
+    @staticmethod
+    def _block_dims(F, D, params):
+        """per block (F_k, C_k, Fp_k, K_k = Fp_k D filters_k, N_k = F_k D nf_k)"""
+        dims, C = [], 1
+        for filt, _, pool, nf in zip(*params):
+            Fp = -(-F // pool)
+            dims.append((F, C, Fp, Fp * D * filt, F * D * nf))
+            F, C = Fp, filt
+        return dims
+
+    @staticmethod
+    def _host_arrays(params):
+        """depth and the four HOST int arrays of dt_fgcnn_infer_* (kept alive by the caller)"""
+        depth = len(params[0])
+        arrs = tuple((ctypes.c_int * depth)(*p) for p in params)
+        return arrs, (depth,) + tuple(ctypes.cast(a, ctypes.c_void_p) for a in arrs)
+
+    @classmethod
+    def eligible(cls, dm):
+        c = dm.config
+        try:
+            nets = list(c.nets)
+            if len(nets) != 1 or not isinstance(nets[0], str) or nets[0] != 'fgcnn_dnn_nets':
+                return False
+            if c.stacking_op != consts.STACKING_OP_ADD or getattr(c.distribute_strategy, 'sharded_embeddings', False):
+                return False
+            # (tower=None: this graph reads no bn_concat_emb_dense, so _step_dims must not ask for one)
+            dims = _step_dims(dm, (f'{cls.CELL}_dense_1', f'{cls.CELL}_dense_2'), tower=None)
+            tower = _infer_tower(c.dnn_params)
+            blocks = cls._blocks(dm)
+            if dims is None or tower is None or not blocks:
+                return False
+            from .models.deepnets import _FG_DEFAULTS
+            want = tuple(tuple(int(v) for v in c.fgcnn_params.get(k, d)) for k, d in _FG_DEFAULTS)
+            depth = min(len(w) for w in want)
+            params = cls._params(blocks)
+            if len(blocks) != depth or params != tuple(w[:depth] for w in want):
+                return False
+            if any(b.activation != 'tanh' for b in blocks):
+                return False
+            _, F, D, Nd = dims
+            bd = cls._block_dims(F, D, params)
+            for b, (Fk, Ck, Fp, K, N), filt, h in zip(blocks, bd, params[0], params[1]):
+                if tuple(b.conv_kernel.shape) != (h, 1, Ck, filt) or tuple(b.conv_bias.shape) != (filt,):
+                    return False
+                if tuple(b.dense_output.kernel.shape) != (K, N):
+                    return False
+                if b.dense_output.bias is not None and tuple(b.dense_output.bias.shape) != (N,):
+                    return False
+            L = dm.model.layers_by_name
+            if tuple(L['task_output'].kernel.shape) != (tower[1], 1) or \
+                    int(L[f'{cls.CELL}_dense_1'].kernel.shape[0]) != sum(d[4] for d in bd) + F * D + Nd:
+                return False
+            keep, args = cls._host_arrays(params)
+            return bool(lib().dt_fgcnn_infer_supported(F, D, Nd, *tower, *args))
+        except Exception:
+            return False
+
+    def _tower_layers(self, L):
+        self.bn = None                          # (bn_concat_emb_dense is not part of this graph)
+        self.cells = [(L[f'{self.CELL}_dense_{i}'], L.get(f'{self.CELL}_bn_{i}')) for i in (1, 2)]
+
+    def _net_layers(self, L):
+        self.blocks = self._blocks(self.dm)
+        self._read_params()
+        self._scratch = None
+
+    def _read_params(self):
+        self.params = self._params(self.blocks)
+        self.depth = len(self.blocks)
+        self._arrays, self._shape_args = self._host_arrays(self.params)
+
+    def _dims(self):
+        """dt_fgcnn_infer_workspace_bytes' arguments"""
+        return (self.F, self.D, self.Nd) + self._shape_args
+
+    def prepare(self):
+        """the blocks', the tower's and task_output's tensors as they are now -> the workspace, one launch; also reads the
+        block parameters, the tower's precision mode and the output activation (the arguments of the launches that follow)"""
+        self.flags = self._tower_flags()
+        self._read_params()
+        nbytes = self._entry('infer_workspace_bytes')(*self._dims())
+        if nbytes < 0:
+            raise _lib.DtHipError('InferFGCNN: unsupported shape')
+        if nbytes > self.ws.numel() * 4:           # the block parameters changed to ones with a larger layout
+            self.ws = torch.zeros((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
+        tensors = [(b.conv_kernel, b.conv_bias, b.dense_output.kernel, b.dense_output.bias) for b in self.blocks]
+        for group in tensors:
+            for t in group:
+                if t is not None and not t.is_contiguous():
+                    raise _lib.DtHipError(f'inference plan: FGCNN weight with strides {tuple(t.stride())}')
+        host = [(ctypes.c_void_p * self.depth)(*[None if g[i] is None else g[i].data_ptr() for g in tensors])
+                for i in range(4)]
+        check(self._entry('infer_prepare')(
+            *self._dims(), *[ctypes.cast(h, ctypes.c_void_p) for h in host], *self._cell_args(), ptr(self.out.kernel),
+            ptr(self.out.bias), ptr(self.ws), stream_ptr()), 'dt_fgcnn_infer_prepare')
+
+    def _alloc_scratch(self, rows):
+        """every block's pooled map [rows, Fp D filters] and the generated features [rows, sum N_k] for batches of up to
+        `rows` rows, for the block parameters in force"""
+        bd = self._block_dims(self.F, self.D, self.params)
+        dev, f32 = self.device, torch.float32
+        return {'rows': rows, 'params': self.params,
+                'pooled': [torch.empty((rows, d[3]), dtype=f32, device=dev) for d in bd],
+                'feats': torch.empty((rows, sum(d[4] for d in bd)), dtype=f32, device=dev)}
+
+    def infer(self, idx, dense, logit, out=None):
+        """one batch, as InferDeepFM.infer: conv and recomb per block, then the tower.  Inside `run_batches` the scratch is
+        the call's; a lone call allocates its own."""
+        B, idx, kind, dense = self._batch_args(idx, dense, logit, out)
+        if B == 0:
+            return
+        sc = self._scratch
+        if sc is None or sc['rows'] < B or sc['params'] != self.params:
+            sc = self._alloc_scratch(B)
+        gather, dims, ws, st = self._gather_args(idx, kind), self._dims(), ptr(self.ws), stream_ptr()
+        for k in range(self.depth):
+            check(self._entry('infer_conv')(k, *gather, ptr(sc['pooled'][k - 1]) if k else None, B, *dims, ws,
+                                            ptr(sc['pooled'][k]), st), 'dt_fgcnn_infer_conv')
+            check(self._entry('infer_recomb')(k, ptr(sc['pooled'][k]), B, *dims, ws, ptr(sc['feats']), st),
+                  'dt_fgcnn_infer_recomb')
+        check(self._entry('infer_tower')(*gather, ptr(dense), ptr(sc['feats']), B, *dims, ws, ptr(logit), ptr(out), self._oob(),
+                                         self.flags, st), 'dt_fgcnn_infer_tower')
+
+    def run_batches(self, data, batch_size, activate=True, each=None):
+        """InferDeepFM.run_batches with the scratch (pooled maps, generated features) allocated once for the call"""
+        self._read_params()
+        self._scratch = self._alloc_scratch(max(1, min(int(batch_size), int(data.n))))
+        try:
+            return super().run_batches(data, batch_size, activate=activate, each=each)
+        finally:
+            self._scratch = None
+
+
 def make_inference_plan(dm):
     if not predict_enabled() or dm.model is None:
         return None
     for plan in (InferDeepFM, InferDCN, InferStack, InferXDeepFM, InferAutoInt, InferAFM, InferPNN,
-                 InferFiBiNet):
+                 InferFiBiNet, InferFGCNN):
         if plan.eligible(dm):
             return plan(dm)
     return None

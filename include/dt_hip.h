@@ -974,6 +974,73 @@ int dt_fibi_infer(const void* idx, int idx_kind, const float* table, const int64
                   const float* dense, int64_t B, int F, int D, int Nd, int bilinear_type, int pooling_op, int R,
                   const void* workspace, float* logit_out, float* out, int* oob_count, int flags, void* stream);
 
+/* ---- fused FGCNN inference: 2 depth + 1 launches per predict batch (csrc/fgcnn_infer.hip; replaces, for the net
+ * 'fgcnn_dnn_nets' alone in config.nets (deepnets.FGCNN), the layer-by-layer forward of the reference's DeepModel.predict /
+ * evaluate: the embedding gather (layers.py:889-904), deepnets.py:227-261 — expand_dims, the FGCNN blocks (FGCNN.call
+ * layers.py:161-242: Conv2D((h, 1), 'same', tanh), MaxPooling2D((p, 1), 'same'), Flatten, the recombination Dense with tanh,
+ * the reshape), Concatenate of the generated features and the raw embeddings — deepnets.py:326-341: Flatten, Concatenate with
+ * the RAW dense values, the two-cell relu tower deepnets.py:401-427 with Dropout as the identity — and the head
+ * deepmodel.py:286-301: a single net, so no dense_logit layer and no Add; task_output's [H2][1] kernel is the tower's output
+ * vector and the output weight is 1).  bn_concat_emb_dense is not part of this graph and is not applied.
+ *   depth = the number of FGCNN blocks; filters / heights / pools / new_filters = HOST int arrays of `depth` entries
+ *   (fgcnn_params' fg_filters, fg_heights, fg_pool_heights, fg_new_feat_filters).  F_1 = F, C_1 = 1; block k maps
+ *   [F_k][D][C_k] to the pooled map [Fp_k = ceil(F_k / pool_k)][D][filters_k] and to N_k = F_k D new_filters_k generated
+ *   columns; F_(k+1) = Fp_k, C_(k+1) = filters_k.  'same' padding as the reference splits it: total / 2 before, the rest
+ *   after; the pooling pads with -inf, so a short window takes the maximum of the fields it has.  The first Dense's rows: the
+ *   generated columns of block 1 .. depth, the F D embedding columns, the Nd dense columns.
+ *   Per batch: dt_fgcnn_infer_conv and dt_fgcnn_infer_recomb once per block, in block order, then dt_fgcnn_infer_tower — one
+ *   launch each, every one this library's own kernel.  The convolution reads its taps from the map in LDS (plain fp32 FMAs;
+ *   no taps matrix and no padded map is written), the recombination Dense and the tower's two GEMMs run on the matrix core
+ *   with the six split-bf16 products (the fp32 class), tanh is libm's tanhf.  Between the launches only the pooled maps
+ *   [B][Fp_k D filters_k] and the generated features [B][sum N_k] live in memory, in buffers the caller owns; the tower reads
+ *   its input in chunks from the features and the rows it gathers itself.
+ *   dt_fgcnn_infer_supported: 1 iff 2 <= F <= 64, D in {4, 8, 16, 32, 64}, F D <= 512, 0 <= Nd <= 64, 1 <= depth <= 3, every
+ *     filters in 1 .. 16, height in 1 .. 9 (either parity, also above F_k), pool in 1 .. 3 (also not dividing F_k), new_filters
+ *     in 1 .. 3, 1 <= H1 <= 128, 1 <= H2 <= 64, cells a mask of bits 0 / 1 (as dt_deepfm_infer_supported).
+ *   dt_fgcnn_infer_workspace_bytes: size of `workspace` (16-byte aligned; about 21 MB at F = 26, D = 16 with the default
+ *     blocks: the packed recombination weights), -1 outside the shape domain.
+ *   dt_fgcnn_infer_prepare (once per predict / evaluate, one launch; it writes what the batch launches read, from the values
+ *     the tensors hold at call time): conv_kernels / conv_biases / rec_kernels / rec_biases = HOST arrays of `depth` device
+ *     pointers: conv2d_kernel [h][1][C_k][filters] and conv2d_bias [filters], the recombination Dense's kernel
+ *     [Fp_k D filters][N_k] and bias [N_k], all contiguous (a bias may be NULL); W1 [sum N_k + F D + Nd][ld1], W2 and the two
+ *     cells' bias / BN arguments as dt_deepfm_infer_prepare, w3 [H2] = task_output's kernel, b_out = its bias or NULL.
+ *   dt_fgcnn_infer_conv (block = 0 .. depth - 1): block 0 gathers ids [B][F] (idx_kind = DT_IDX_*; an id outside
+ *     [0, vocab[f]) reads a zero row; it is counted by dt_fgcnn_infer_tower alone) and `prev` is ignored; a later block reads
+ *     `prev` = the pooled map of the block before and ignores the gather arguments -> pooled_out [B][Fp D filters].
+ *   dt_fgcnn_infer_recomb: pooled [B][Fp D filters] of `block` -> that block's N_k columns of feats [B][sum N_k].
+ *   dt_fgcnn_infer_tower: ids, dense [B][Nd] (NULL with Nd = 0), feats -> logit_out [B] and, if out != NULL, out [B] =
+ *     sigmoid(logit) with DT_INFER_SIGMOID or the logit.  flags | DT_INFER_TOWER_BF16: the first tower GEMM on plain bf16
+ *     operands; the blocks stay in the fp32 class.  An out-of-range id is counted once into *oob_count when it is given.
+ *   All three: B >= 0 rows, B < 2^31; B = 0: no launch, no pointer is looked at.  The workspace carries the (F, D, Nd, block
+ *   parameters) it was prepared for: a launch with other values reads no weight; the conv / recomb launches then write
+ *   nothing and the tower launch writes NaN into every logit and output.  Each grid is at most DT_FGCNN_INFER_MAX_BLOCKS
+ *   blocks (times the 128-column chunks of N_k for the recombination), strided over the row tiles (32 rows; 64 for the
+ *   recombination; up to 32 for the convolution of a later block). */
+#define DT_FGCNN_INFER_MAX_BLOCKS 512
+#define DT_FGCNN_INFER_MAX_DEPTH 3
+int dt_fgcnn_infer_supported(int F, int D, int Nd, int H1, int H2, int cells, int depth, const int* filters, const int* heights,
+                             const int* pools, const int* new_filters);
+int64_t dt_fgcnn_infer_workspace_bytes(int F, int D, int Nd, int depth, const int* filters, const int* heights, const int* pools,
+                                       const int* new_filters);
+int dt_fgcnn_infer_prepare(int F, int D, int Nd, int depth, const int* filters, const int* heights, const int* pools,
+                           const int* new_filters, const float* const* conv_kernels, const float* const* conv_biases,
+                           const float* const* rec_kernels, const float* const* rec_biases, const float* W1, int ld1, int H1,
+                           const float* b1, const float* W2, int ld2, int H2, const float* b2, int cells, const float* c1_gamma,
+                           const float* c1_beta, const float* c1_mean, const float* c1_var, float c1_eps, const float* c2_gamma,
+                           const float* c2_beta, const float* c2_mean, const float* c2_var, float c2_eps, const float* w3,
+                           const float* b_out, void* workspace, void* stream);
+int dt_fgcnn_infer_conv(int block, const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                        const int32_t* vocab, const float* prev, int64_t B, int F, int D, int Nd, int depth, const int* filters,
+                        const int* heights, const int* pools, const int* new_filters, const void* workspace, float* pooled_out,
+                        void* stream);
+int dt_fgcnn_infer_recomb(int block, const float* pooled, int64_t B, int F, int D, int Nd, int depth, const int* filters,
+                          const int* heights, const int* pools, const int* new_filters, const void* workspace, float* feats,
+                          void* stream);
+int dt_fgcnn_infer_tower(const void* idx, int idx_kind, const float* table, const int64_t* row_offset, const int32_t* vocab,
+                         const float* dense, const float* feats, int64_t B, int F, int D, int Nd, int depth, const int* filters,
+                         const int* heights, const int* pools, const int* new_filters, const void* workspace, float* logit_out,
+                         float* out, int* oob_count, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

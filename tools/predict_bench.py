@@ -8,14 +8,15 @@ ModelConfig's default ['dnn_nets'], WideDeep ['linear', 'dnn_nets'], the FM mode
 ['autoint_nets'] as bench.py builds it (embedding size 32, three interacting layers of four heads, residual on;
 fused.InferAutoInt: one launch per batch), and AFM ['linear', 'afm_nets'] (the AFM paper's model, hidden_factor 16;
 fused.InferAFM: one launch per batch), and PNN ['pnn_nets'] as bench.py builds it (inner ++ outer 'mat' ++ xn -> tower;
-fused.InferPNN: one launch per batch).  Both paths of a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
+fused.InferPNN: one launch per batch), and FGCNN ['fgcnn_dnn_nets'] with the default blocks (fused.InferFGCNN: 2 x 2 + 1
+launches per batch).  Both paths of a configuration run in the same process on the same model and rows.  Prints one JSON line: {"configs": {name: {...}}}.
 
 Both paths score the same device-resident rows (training.TableBatches) and write every batch's output into device memory;
 the timed region is what `DeepModel.predict` does after its feed is built, up to the outputs of the last batch (the host copy
 of the result is left out: it is the same for both paths).  Device events around each call, warm-up calls first, the
 median of the repeats reported (run-to-run spread as min / max).
 
-    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm,xdeepfm,autoint,afm,pnn] [--rows N] [--batches 128,8192,65536]
+    python tools/predict_bench.py [--configs deepfm,dcn,dnn,widedeep,fm,xdeepfm,autoint,afm,pnn,fgcnn] [--rows N] [--batches 128,8192,65536]
                                   [--repeats R] [--warmup W] [--paths fused,layer]
 """
 import argparse
@@ -36,7 +37,8 @@ CONFIGS = {'deepfm': ['linear', 'fm_nets', 'dnn_nets'], 'dcn': ['dcn_nets'], 'dn
            'widedeep': ['linear', 'dnn_nets'], 'fm': ['linear', 'fm_nets'],
            'xdeepfm': ['linear', 'cin_nets', 'dnn_nets'],           # cin_params' default: cross_layer_size (128, 128)
            'autoint': ['autoint_nets'], 'afm': ['linear', 'afm_nets'],
-           'pnn': ['pnn_nets']}                                     # bench.py --model PNN: deepnets.PNN, every default
+           'pnn': ['pnn_nets'],                                     # bench.py --model PNN: deepnets.PNN, every default
+           'fgcnn': ['fgcnn_dnn_nets']}                             # bench.py --model FGCNN: deepnets.FGCNN, default fgcnn_params
 # what a configuration changes of the shape above (bench.py's AutoInt graph: MODEL_PARAMS['AutoInt'], embedding size 32)
 EXTRA = {'autoint': {'D': 32, 'autoint_params': {'num_attention': 3, 'num_heads': 4, 'dropout_rate': 0, 'use_residual': True}},
          'afm': {'afm_params': {'hidden_factor': 16, 'dropout_rate': 0}}}
