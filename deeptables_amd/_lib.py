@@ -113,6 +113,11 @@ SIGNATURES = {
     'dt_dense_workspace_bytes': (_c_i64, [_c_int] * 3),
     'dt_dense_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_dense_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # the same Dense on K- and M-independent tiles, for the shapes dt_dense_supported refuses (csrc/dense_tiled.hip)
+    'dt_dense_tiled_supported': (_c_int, [_c_int] * 3),
+    'dt_dense_tiled_workspace_bytes': (_c_i64, [_c_int] * 3),
+    'dt_dense_tiled_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    'dt_dense_tiled_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'dt_afm_fwd': (_c_int, [_ptr] * 4 + [_c_int] * 5 + [_ptr] * 3),
     'dt_afm_bwd': (_c_int, [_ptr] * 6 + [_c_int] * 5 + [_ptr] * 5),
     'dt_bilinear_fwd': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

@@ -12,6 +12,9 @@
 //   M == 1 : one wavefront per row (coalesced row read, shuffle reduction): HBM-bound.
 //   grad_W = x^T G: 32x32 tiles, batch split over blocks, operands streamed from global (coalesced along the
 //            tile's 32 columns), partial tiles merged with a few float atomics per address; grad_b rides along.
+// The [rows x K] slab bounds these kernels (dt_dense_supported: 150 KB of LDS, i.e. K <= ~1198 at M >= 97, ~598 at
+// 33 <= M <= 96, ~298 below; the same with K and M swapped for grad_x).  Shapes beyond it run on dense_tiled.hip, whose
+// tiles depend on neither K nor M: ops.dense asks dt_dense_supported first, so every shape accepted here stays here.
 #include "common.h"
 
 namespace dt {

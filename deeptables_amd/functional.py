@@ -248,8 +248,9 @@ _VENDOR_GEMM_NOTED = set()
 
 
 def note_vendor_gemm(who, x_shape, w_shape):
-    """One log line per (layer, weight shape) when a product leaves the hand-written kernels (csrc/dense.hip takes K and N
-    up to its LDS tile; beyond that the GEMM goes to the vendor library through torch): never silent."""
+    """One log line per (layer, weight shape) when a product leaves the hand-written kernels: never silent.  On the GPU no
+    2-D Dense shape does any more (csrc/dense.hip takes K and N up to its LDS slab, csrc/dense_tiled.hip everything beyond it:
+    ops.dense_supported is true for every non-empty input), so this is reached with CPU tensors only."""
     key = (who, tuple(w_shape))
     if key in _VENDOR_GEMM_NOTED:
         return
@@ -304,7 +305,7 @@ class Dense(Layer):
             if activation is not None and fused_act is None:
                 y = activation(y)
             return y
-        lead = x.shape[:-1]                      # shapes outside the kernels' LDS tile: vendor GEMM
+        lead = x.shape[:-1]                      # CPU tensors only (ops.dense_supported takes every GPU shape): torch's GEMM
         note_vendor_gemm(f'Dense {self.name!r}', x.shape, self.kernel.shape)
         x2 = x.reshape(-1, x.shape[-1])
         y = torch.addmm(self.bias, x2, self.kernel) if self.bias is not None else x2 @ self.kernel

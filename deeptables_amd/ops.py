@@ -997,7 +997,13 @@ class _Dense(torch.autograd.Function):
         M = W.shape[1]
         y = torch.empty((N, M), dtype=torch.float32, device=x.device)
         bias_c = None if bias is None else _f32c(bias)
-        check(lib().dt_dense_fwd(ptr(x2), ptr(W), ptr(bias_c), act, N, K, M, ptr(y), stream_ptr()), 'dt_dense_fwd')
+        # the LDS-slab kernels of csrc/dense.hip where they take the shape, csrc/dense_tiled.hip's fixed tiles otherwise
+        ctx.tiled = N > 0 and not lib().dt_dense_supported(N, K, M)
+        if ctx.tiled:
+            check(lib().dt_dense_tiled_fwd(ptr(x2), ptr(W), ptr(bias_c), act, N, K, M, ptr(y), stream_ptr()),
+                  'dt_dense_tiled_fwd')
+        else:
+            check(lib().dt_dense_fwd(ptr(x2), ptr(W), ptr(bias_c), act, N, K, M, ptr(y), stream_ptr()), 'dt_dense_fwd')
         ctx.save_for_backward(x2, W, y)
         ctx.act, ctx.has_bias, ctx.x_shape = act, bias is not None, x.shape
         ctx.W_ref, ctx.b_ref = W, bias_c
@@ -1019,10 +1025,11 @@ class _Dense(torch.autograd.Function):
         else:
             gW, gW_ret = _grad_target(ctx.W_ref)
             gb, gb_ret = _grad_target(ctx.b_ref) if ctx.has_bias else (None, None)
-        nbytes = lib().dt_dense_workspace_bytes(N, K, M)
-        ws = torch.empty((max(nbytes, 4) + 3) // 4, dtype=torch.float32, device=W.device)
-        check(lib().dt_dense_bwd(ptr(x2), ptr(W), ptr(y), ptr(gy2), ctx.act, N, K, M, ptr(gx), ptr(gW), ptr(gb),
-                                 ptr(ws), stream_ptr()), 'dt_dense_bwd')
+        name = 'dt_dense_tiled' if ctx.tiled else 'dt_dense'
+        nbytes = getattr(lib(), name + '_workspace_bytes')(N, K, M)
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=W.device) if nbytes > 0 else None
+        check(getattr(lib(), name + '_bwd')(ptr(x2), ptr(W), ptr(y), ptr(gy2), ctx.act, N, K, M, ptr(gx), ptr(gW), ptr(gb),
+                                            ptr(ws), stream_ptr()), name + '_bwd')
         return (gx.reshape(ctx.x_shape) if need_x else None), gW_ret, gb_ret, None
 
 
@@ -1032,7 +1039,8 @@ def dense_supported(x, W):
     n = 1
     for d in x.shape[:-1]:
         n *= int(d)
-    return n > 0 and bool(lib().dt_dense_supported(n, int(x.shape[-1]), int(W.shape[1])))
+    k, m = int(x.shape[-1]), int(W.shape[1])
+    return n > 0 and bool(lib().dt_dense_supported(n, k, m) or lib().dt_dense_tiled_supported(n, k, m))
 
 
 def dense(x, W, bias=None, activation=None):

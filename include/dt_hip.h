@@ -315,6 +315,20 @@ int dt_dense_fwd(const float* x, const float* W, const float* bias, int act, int
 int dt_dense_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
                  int M, float* grad_x, float* grad_W, float* grad_b, void* ws, void* stream);
 
+/* ---- Keras Dense, tiled: every 2-D shape with M >= 2 (the tower's first Dense deepnets.py:401-427 at K = 1,677; FGCNN's
+ *      recombination Dense layers.py:161-242 at 2,912 -> 832; FiBiNet's tower deepnets.py:374-386 at K = 10,413) ---- *
+ *   The same contract as dt_dense_fwd / dt_dense_bwd (grad_x OVERWRITTEN, may be NULL; grad_W / grad_b ACCUMULATED,
+ *   grad_b may be NULL) for the shapes dt_dense_supported refuses: fixed 128 x 128 / 64 x 64 output tiles on the same
+ *   exact-fp32 MFMA, the contraction walked in steps of 32 through double-buffered LDS panels, so neither K nor M is
+ *   bounded (csrc/dense_tiled.hip).  dt_dense_tiled_supported: 1 for N > 0, K > 0, M >= 2 (M == 1 stays with the GEMV
+ *   kernels of dt_dense_*).  ws: dt_dense_tiled_workspace_bytes(N,K,M) bytes — 0 today, ws may then be NULL.          */
+int dt_dense_tiled_supported(int N, int K, int M);
+int64_t dt_dense_tiled_workspace_bytes(int N, int K, int M);
+int dt_dense_tiled_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M, float* y,
+                       void* stream);
+int dt_dense_tiled_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
+                       int M, float* grad_x, float* grad_W, float* grad_b, void* ws, void* stream);
+
 /* ---- CIN layer, bf16-MFMA mode (opt-in; north_star "logits within 1e-2 bf16") --------------------------------------- *
  * Same contract as dt_cin_layer_fwd / dt_cin_layer_bwd, computed on v_mfma_f32_32x32x16_bf16 (bf16 operands, fp32
  * accumulation): results within 1e-2 of the float64 oracle instead of 1e-4.  ws: dt_cin_bf16_workspace_bytes(F0, Hk, L)
