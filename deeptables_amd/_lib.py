@@ -118,6 +118,12 @@ SIGNATURES = {
     'dt_dense_tiled_workspace_bytes': (_c_i64, [_c_int] * 3),
     'dt_dense_tiled_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_dense_tiled_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # FGCNN block for training: convolution + activation + max pooling, taps read from the map in LDS (csrc/fgcnn_train.hip)
+    'dt_fg_conv_pool_supported': (_c_int, [_c_int] * 7),
+    'dt_fg_conv_pool_workspace_bytes': (_c_i64, [_c_i64] + [_c_int] * 6),
+    'dt_fg_conv_pool_geometry': (_c_int, [_c_int] * 7 + [_ptr, _ptr]),
+    'dt_fg_conv_pool_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_i64] + [_c_int] * 7 + [_ptr, _ptr, _ptr]),
+    'dt_fg_conv_pool_bwd': (_c_int, [_ptr] * 5 + [_c_i64] + [_c_int] * 7 + [_ptr] * 5),
     'dt_afm_fwd': (_c_int, [_ptr] * 4 + [_c_int] * 5 + [_ptr] * 3),
     'dt_afm_bwd': (_c_int, [_ptr] * 6 + [_c_int] * 5 + [_ptr] * 5),
     'dt_bilinear_fwd': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

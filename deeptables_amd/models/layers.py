@@ -616,7 +616,10 @@ class FGCNN(Layer):
     ([B*F*D, h*Cin], a strided view copy) and multiplied by the [h*Cin, filters] kernel on the library's own
     fp32-MFMA Dense kernel (csrc/dense.hip) — no MIOpen/vendor convolution; the pooling is a reshape + max.
     Tensors keep the Keras channels-last layout [B,F,D,C] (the Flatten order feeds the recombination Dense),
-    kernel stored in the Keras layout [h,1,Cin,Cout]."""
+    kernel stored in the Keras layout [h,1,Cin,Cout].
+    On the GPU, for the blocks dt_fg_conv_pool_supported accepts (activation linear / relu / sigmoid / tanh), the
+    convolution, the activation and the pooling are one HIP launch each way that reads the taps from the map in LDS
+    (csrc/fgcnn_train.hip; DT_AMD_FGCNN_CONV=0 keeps the gather + Dense + amax path)."""
 
     def __init__(self, filters, kernel_height, new_filters, pool_height, activation='tanh', **kwargs):
         self.filters = filters
@@ -645,6 +648,14 @@ class FGCNN(Layer):
     def call(self, x, **kwargs):
         _ndim_check(x, 4)
         B, F, D, C = x.shape
+        if ops.fgcnn_conv_enabled(self.activation) and ops.fgcnn_conv_pool_supported(x, self.conv_kernel, self.activation,
+                                                                                    self.pool_height):
+            # convolution + activation + pooling in one HIP launch each way, the taps read from the map in LDS
+            # (csrc/fgcnn_train.hip): no padded map, no taps matrix
+            pooling_output = ops.fgcnn_conv_pool(x, self.conv_kernel, self.conv_bias, self.activation, self.pool_height)
+            new_features = self.dense_output(pooling_output.reshape(B, -1))
+            new_features = new_features.reshape(-1, F * self.new_filters, D)
+            return [pooling_output, new_features]
         h = self.kernel_height
         _, pb, pa = _same_pad(F, h, 1)
         xp = torch.nn.functional.pad(x, (0, 0, 0, 0, pb, pa))             # zero-pad the field axis

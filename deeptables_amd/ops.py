@@ -1050,6 +1050,75 @@ def dense(x, W, bias=None, activation=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# FGCNN block — Conv2D((h,1), 'same') -> activation -> MaxPooling2D((p,1), 'same'), layers.py:220-225
+# ------------------------------------------------------------------------------------------------
+FGCNN_CONV_ACTS = {None: _lib.ACT_CODES[None], 'linear': _lib.ACT_CODES['linear'], 'relu': _lib.ACT_CODES['relu'],
+                   'sigmoid': _lib.ACT_CODES['sigmoid'], 'tanh': _lib.ACT_CODES['tanh']}
+
+
+class _FgcnnConvPool(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, bias, act, pool, need_grad):
+        require_cuda(x, kernel)
+        x, kernel = _f32c(x), _f32c(kernel)
+        bias_c = None if bias is None else _f32c(bias)
+        B, F, D, C = x.shape
+        h, filters = int(kernel.shape[0]), int(kernel.shape[3])
+        Fp = -(-F // pool)
+        pooled = torch.empty((B, Fp, D, filters), dtype=torch.float32, device=x.device)
+        # the selected field of every window is kept only when a backward pass will read it
+        sel = torch.empty((B, Fp, D, filters), dtype=torch.uint8, device=x.device) if need_grad else None
+        check(lib().dt_fg_conv_pool_fwd(ptr(x), ptr(kernel), ptr(bias_c), B, F, D, C, filters, h, pool, act, ptr(pooled),
+                                           ptr(sel), stream_ptr()), 'dt_fg_conv_pool_fwd')
+        if need_grad:
+            ctx.save_for_backward(x, kernel, pooled, sel)
+        ctx.act, ctx.pool, ctx.has_bias = act, pool, bias is not None
+        return pooled
+
+    @staticmethod
+    def backward(ctx, gp):
+        x, kernel, pooled, sel = ctx.saved_tensors
+        B, F, D, C = x.shape
+        h, filters = int(kernel.shape[0]), int(kernel.shape[3])
+        gp = _f32c(gp)
+        gx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        # the kernels overwrite all three: no zero fill
+        gk = torch.empty_like(kernel)
+        gb = torch.empty(filters, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+        nbytes = lib().dt_fg_conv_pool_workspace_bytes(B, F, D, C, filters, h, ctx.pool)
+        ws = torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=x.device)
+        check(lib().dt_fg_conv_pool_bwd(ptr(x), ptr(kernel), ptr(pooled), ptr(sel), ptr(gp), B, F, D, C, filters, h, ctx.pool,
+                                           ctx.act, ptr(gx), ptr(gk), ptr(gb), ptr(ws), stream_ptr()),
+              'dt_fg_conv_pool_bwd')
+        return gx, gk, gb, None, None, None
+
+
+def fgcnn_conv_enabled(activation):
+    """the layer asks this first: DT_AMD_FGCNN_CONV=0 (read per call) and an activation the kernels do not fuse keep the
+    unfold + Dense + amax path"""
+    return os.environ.get('DT_AMD_FGCNN_CONV', '1') != '0' and activation in FGCNN_CONV_ACTS
+
+
+def fgcnn_conv_pool_supported(x, kernel, activation, pool_height):
+    """dt_fg_conv_pool_supported for a GPU map x [B,F,D,C] and a Keras kernel [h,1,C,filters]"""
+    if not x.is_cuda or x.dim() != 4 or kernel.dim() != 4 or activation not in FGCNN_CONV_ACTS:
+        return False
+    B, F, D, C = [int(v) for v in x.shape]
+    h, one, Ck, filters = [int(v) for v in kernel.shape]
+    if B <= 0 or one != 1 or Ck != C:
+        return False
+    return bool(lib().dt_fg_conv_pool_supported(F, D, C, filters, h, int(pool_height), FGCNN_CONV_ACTS[activation]))
+
+
+def fgcnn_conv_pool(x, kernel, bias, activation, pool_height):
+    """pooled [B, ceil(F / p), D, filters] = maxpool_p(act(conv_(h,1)(x) + bias)) on the HIP kernels of csrc/fgcnn_train.hip:
+    the taps are read from the map in LDS — no padded map, no taps matrix, forward or backward"""
+    need_grad = torch.is_grad_enabled() and (x.requires_grad or kernel.requires_grad or
+                                             (bias is not None and bias.requires_grad))
+    return _FgcnnConvPool.apply(x, kernel, bias, FGCNN_CONV_ACTS[activation], int(pool_height), need_grad)
+
+
+# ------------------------------------------------------------------------------------------------
 # AFM attention pooling — AFM.call layers.py:789-807
 # ------------------------------------------------------------------------------------------------
 class _AfmPool(torch.autograd.Function):

@@ -329,6 +329,41 @@ int dt_dense_tiled_fwd(const float* x, const float* W, const float* bias, int ac
 int dt_dense_tiled_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
                        int M, float* grad_x, float* grad_W, float* grad_b, void* ws, void* stream);
 
+/* ---- FGCNN block, training: Conv2D((h,1), 'same') -> activation -> MaxPooling2D((pool,1), 'same') of FGCNN.call
+ *      (layers.py:161-242, the three layers at :220-225) in one launch each way (csrc/fgcnn_train.hip) ------------------ *
+ *   All tensors contiguous fp32, channels-last: x [B][F][D][C], kernel in the Keras layout [h][1][C][filters], bias
+ *   [filters] | NULL, pooled [B][Fp][D][filters] with Fp = ceil(F / pool).
+ *     z[b,f,d,o] = bias[o] + sum_{t<h, c<C} x[b, f+t-pb, d, c] kernel[t][c][o], pb = (h-1)/2, taps beyond the map are zero
+ *     window i = fields [i pool - qb, i pool - qb + pool) inside the map, qb = (Fp pool - F) / 2
+ *     pooled[b,i,d,o] = act(max_f z) (the activations of the domain are non-decreasing: one activation per window); ties
+ *     go to the first field; a NaN pre-activation makes the window's maximum NaN (as torch.amax).  sel [B][Fp][D][filters], one byte each = the offset of the selected field inside its window;
+ *     sel == NULL (no gradient needed): not stored.
+ *   Backward: dz = grad_pooled act'(pooled) at the selected field of each window (act' as listed beside DT_ACT_*), 0
+ *     elsewhere; grad_x[b,g,d,c] = sum_{t,o} dz[b,g-t+pb,d,o] kernel[t][c][o] (NULL: skipped), grad_kernel[t][c][o] =
+ *     sum_{b,f,d} x[b,f+t-pb,d,c] dz[b,f,d,o], grad_bias[o] = sum dz (NULL: skipped) — all three OVERWRITTEN.  The batch
+ *     reduction uses no float atomics: every block stores its partial sums into `workspace`
+ *     (dt_fg_conv_pool_workspace_bytes bytes, -1 outside the domain) and a second launch on the same stream adds them in
+ *     block order, so the result is bit-identical from run to run.  Plain fp32 FMAs with fp32 accumulation (the partials
+ *     are added in double): the exact fp32 class both ways.
+ *   Domain (dt_fg_conv_pool_supported): 1 <= C, filters, h <= 16, 1 <= pool <= 8, F >= 1, D >= 1 (any D), act in
+ *     {DT_ACT_LINEAR, DT_ACT_RELU, DT_ACT_SIGMOID, DT_ACT_TANH}, and one batch row's map plus its dz fit the LDS tile beside
+ *     the padded kernel, in bytes:  64 h CP + 64 + F D (4 (C | 1) + 80) <= 65536 with CP = C rounded up to a multiple of 4.
+ *   B = 0 launches nothing and looks at no pointer; a shape outside the domain is DT_ERR_UNSUPPORTED, a null pointer
+ *   DT_ERR_INVALID_ARG, both before the first launch.  No alignment beyond that of a float is relied on.  (The names
+ *   start with dt_fg_conv_: the dt_fgcnn_ prefix is the inference family's, dt_fgcnn_infer*, alone.)                    */
+int dt_fg_conv_pool_supported(int F, int D, int C, int filters, int h, int pool, int act);
+int64_t dt_fg_conv_pool_workspace_bytes(int64_t B, int F, int D, int C, int filters, int h, int pool);
+/* the launch geometry, for tests and tools that have to reach the grid-stride loops: *tile_rows = the batch rows of one
+ * tile of the forward (backward = 0) or backward (backward != 0) launch, *max_blocks = the cap of either grid (a launch has
+ * min(ceil(B / tile_rows), max_blocks) blocks); HOST pointers, either may be NULL; DT_ERR_UNSUPPORTED outside the domain */
+int dt_fg_conv_pool_geometry(int F, int D, int C, int filters, int h, int pool, int backward, int* tile_rows,
+                             int* max_blocks);
+int dt_fg_conv_pool_fwd(const float* x, const float* kernel, const float* bias, int64_t B, int F, int D, int C,
+                           int filters, int h, int pool, int act, float* pooled, uint8_t* sel, void* stream);
+int dt_fg_conv_pool_bwd(const float* x, const float* kernel, const float* pooled, const uint8_t* sel,
+                           const float* grad_pooled, int64_t B, int F, int D, int C, int filters, int h, int pool, int act,
+                           float* grad_x, float* grad_kernel, float* grad_bias, void* workspace, void* stream);
+
 /* ---- CIN layer, bf16-MFMA mode (opt-in; north_star "logits within 1e-2 bf16") --------------------------------------- *
  * Same contract as dt_cin_layer_fwd / dt_cin_layer_bwd, computed on v_mfma_f32_32x32x16_bf16 (bf16 operands, fp32
  * accumulation): results within 1e-2 of the float64 oracle instead of 1e-4.  ws: dt_cin_bf16_workspace_bytes(F0, Hk, L)
