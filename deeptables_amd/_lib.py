@@ -116,6 +116,7 @@ SIGNATURES = {
     # the same Dense on K- and M-independent tiles, for the shapes dt_dense_supported refuses (csrc/dense_tiled.hip)
     'dt_dense_tiled_supported': (_c_int, [_c_int] * 3),
     'dt_dense_tiled_workspace_bytes': (_c_i64, [_c_int] * 3),
+    'dt_dense_tiled_geometry': (_c_int, [_c_int] * 4 + [_ptr] * 3),
     'dt_dense_tiled_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_dense_tiled_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # FGCNN block for training: convolution + activation + max pooling, taps read from the map in LDS (csrc/fgcnn_train.hip)

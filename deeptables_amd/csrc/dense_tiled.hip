@@ -291,6 +291,22 @@ inline bool vec_ok(const void* p, const void* q, int64_t ld) {
     return ld % 4 == 0 && (((uintptr_t)p | (uintptr_t)q) % 16) == 0;
 }
 
+// grad_W's batch split: until the grid has ~2 blocks per CU, >= 256 rows per split, every split owning at least one step
+struct BatchSplit {
+    int splits, per;   // gridDim.z, contraction steps of kTK per split
+};
+inline BatchSplit tiled_batch_split(int N, int64_t tiles) {
+    const int total_steps = ceil_div(N, kTK);
+    int splits = 1;
+    if (tiles < kFillBlocks) {
+        splits = (int)((2 * kFillBlocks + tiles - 1) / tiles);
+        const int most = ceil_div(N, 256);
+        if (splits > most) splits = most;
+    }
+    const int per = ceil_div(total_steps, splits);
+    return BatchSplit{ceil_div(total_steps, per), per};
+}
+
 template <bool AKC, bool BKC, int MASK, bool ACC>
 void launch_tiled(hipStream_t st, int wt, dim3 grid, const float* A, int64_t lda, const float* B, int64_t ldb,
                   const float* Y, int mask_act, const float* bias, int act, int R, int Cc, int Kc, int steps_per_split,
@@ -323,6 +339,19 @@ extern "C" int64_t dt_dense_tiled_workspace_bytes(int N, int K, int M) {
     return 0;   // W is read transposed by the staging loads; the batch splits merge with atomics
 }
 
+extern "C" int dt_dense_tiled_geometry(int N, int K, int M, int product, int* tile, int* splits, int* steps_per_split) {
+    DT_REQUIRE(product >= 0 && product <= 2, "dt_dense_tiled_geometry: product %d (0 forward, 1 grad_x, 2 grad_W)", product);
+    DT_UNSUPPORTED(!dt_dense_tiled_supported(N, K, M), "dt_dense_tiled_geometry: N=%d K=%d M=%d", N, K, M);
+    const int R = product == 2 ? K : N, Cc = product == 1 ? K : M, Kc = product == 0 ? K : product == 1 ? M : N;
+    const int wt = tiled_wt(R, Cc), bt = 64 * wt;
+    BatchSplit sp{1, ceil_div(Kc, kTK)};
+    if (product == 2) sp = tiled_batch_split(N, (int64_t)ceil_div(K, bt) * ceil_div(M, bt));
+    if (tile) *tile = bt;
+    if (splits) *splits = sp.splits;
+    if (steps_per_split) *steps_per_split = sp.per;
+    return DT_OK;
+}
+
 extern "C" int dt_dense_tiled_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M,
                                   float* y, void* stream) {
     DT_REQUIRE(N >= 0 && K > 0 && M > 0, "dt_dense_tiled_fwd: bad sizes N=%d K=%d M=%d", N, K, M);
@@ -352,20 +381,11 @@ extern "C" int dt_dense_tiled_bwd(const float* x, const float* W, const float* y
                                            nullptr, DT_ACT_LINEAR, N, K, M, ceil_div(M, kTK), vec_ok(grad_y, y, M),
                                            vec_ok(W, W, M), grad_x, K, nullptr, 0);
     }
-    // grad_W [K,M] += x^T [K,N] . G [N,M]; the batch is split until the grid has ~2 blocks per CU, >= 256 rows per split
+    // grad_W [K,M] += x^T [K,N] . G [N,M], the batch split over blockIdx.z (tiled_batch_split)
     const int wt = tiled_wt(K, M), bt = 64 * wt;
-    const int64_t tiles = (int64_t)ceil_div(K, bt) * ceil_div(M, bt);
-    const int total_steps = ceil_div(N, kTK);
-    int splits = 1;
-    if (tiles < kFillBlocks) {
-        splits = (int)((2 * kFillBlocks + tiles - 1) / tiles);
-        const int most = ceil_div(N, 256);
-        if (splits > most) splits = most;
-    }
-    const int per = ceil_div(total_steps, splits);
-    splits = ceil_div(total_steps, per);         // every split owns at least one step
-    launch_tiled<false, false, 2, true>(st, wt, dim3(ceil_div(K, bt), ceil_div(M, bt), splits), x, K, grad_y, M, y, act,
-                                        nullptr, DT_ACT_LINEAR, K, M, N, per, vec_ok(x, x, K), vec_ok(grad_y, y, M),
-                                        grad_W, M, grad_b, splits > 1);
+    const BatchSplit sp = tiled_batch_split(N, (int64_t)ceil_div(K, bt) * ceil_div(M, bt));
+    launch_tiled<false, false, 2, true>(st, wt, dim3(ceil_div(K, bt), ceil_div(M, bt), sp.splits), x, K, grad_y, M, y,
+                                        act, nullptr, DT_ACT_LINEAR, K, M, N, sp.per, vec_ok(x, x, K), vec_ok(grad_y, y, M),
+                                        grad_W, M, grad_b, sp.splits > 1);
     return launch_status("dt_dense_tiled_bwd");
 }

@@ -324,6 +324,11 @@ int dt_dense_bwd(const float* x, const float* W, const float* y, const float* gr
  *   kernels of dt_dense_*).  ws: dt_dense_tiled_workspace_bytes(N,K,M) bytes — 0 today, ws may then be NULL.          */
 int dt_dense_tiled_supported(int N, int K, int M);
 int64_t dt_dense_tiled_workspace_bytes(int N, int K, int M);
+/* the launch geometry, for tests and tools that have to reach one tile size or one batch split: product = 0 forward
+ * (N x M output), 1 grad_x (N x K), 2 grad_W (K x M); *tile = 64 or 128 (the output tile's edge), *splits = gridDim.z (1 for
+ * products 0 and 1; > 1: grad_W's partial tiles merge with float atomics), *steps_per_split = contraction steps of 32 per
+ * split.  HOST pointers, any may be NULL; no launch; DT_ERR_UNSUPPORTED outside dt_dense_tiled_supported */
+int dt_dense_tiled_geometry(int N, int K, int M, int product, int* tile, int* splits, int* steps_per_split);
 int dt_dense_tiled_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M, float* y,
                        void* stream);
 int dt_dense_tiled_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
