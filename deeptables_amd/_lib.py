@@ -119,6 +119,13 @@ SIGNATURES = {
     'dt_dense_tiled_geometry': (_c_int, [_c_int] * 4 + [_ptr] * 3),
     'dt_dense_tiled_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_dense_tiled_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # the tiled Dense on the bf16 matrix cores, operands split while they are staged (csrc/dense_tiled_x3.hip); mode: DT_DENSE_*
+    'dt_dense_x3_supported': (_c_int, [_c_int] * 4),
+    'dt_dense_x3_workspace_bytes': (_c_i64, [_c_int] * 4),
+    'dt_dense_x3_geometry': (_c_int, [_c_int] * 5 + [_ptr] * 4),
+    'dt_dense_x3_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _c_int, _ptr, _ptr]),
+    'dt_dense_x3_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _c_int, _ptr,
+                                 _ptr]),
     # FGCNN block for training: convolution + activation + max pooling, taps read from the map in LDS (csrc/fgcnn_train.hip)
     'dt_fg_conv_pool_supported': (_c_int, [_c_int] * 7),
     'dt_fg_conv_pool_workspace_bytes': (_c_i64, [_c_i64] + [_c_int] * 6),
@@ -280,6 +287,7 @@ DT_XDEEPFM_MAX_LAYERS = 8
 DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
+DT_DENSE_X3, DT_DENSE_BF16 = 1, 2      # dt_dense_x3_*: split-bf16 (fp32 bars forward) / plain bf16
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

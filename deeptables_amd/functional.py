@@ -14,6 +14,7 @@ Flatten, Dropout, Activation) are library-level plumbing: Dense is one torch.add
 (rocBLAS/hipBLASLt); BatchNormalization calls the HIP kernel with Keras semantics.
 """
 import math
+import os
 import re
 from collections import OrderedDict
 
@@ -262,15 +263,20 @@ def note_vendor_gemm(who, x_shape, w_shape):
 
 
 class Dense(Layer):
-    """keras.layers.Dense: y = act(x @ kernel + bias), kernel [in, out] (glorot_uniform, zeros)."""
+    """keras.layers.Dense: y = act(x @ kernel + bias), kernel [in, out] (glorot_uniform, zeros).
+    mfma_dtype (not a Keras argument, not part of get_config): the precision mode of ops.dense for the shapes the tiled
+    kernels serve — 'float32', 'bf16x3' or 'bf16'.  An explicit value wins; otherwise DT_AMD_DENSE_DTYPE is read at every
+    call; otherwise exact fp32."""
 
     @property
     def accepts_pending_norm(self):
         return self.units == 1 and self.activation_name in (None, 'linear')
 
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer='glorot_uniform',
-                 bias_initializer='zeros', kernel_regularizer=None, activity_regularizer=None, **kwargs):
+                 bias_initializer='zeros', kernel_regularizer=None, activity_regularizer=None, mfma_dtype=None, **kwargs):
         super().__init__(**kwargs)
+        ops.dense_mfma_mode(mfma_dtype)            # an unknown mode raises here, not at the first batch
+        self.mfma_dtype = mfma_dtype
         self.units = int(units)
         self.activation_name = activation if not callable(activation) else getattr(activation, '__name__', 'fn')
         self.activation = get_activation(activation)
@@ -301,7 +307,8 @@ class Dense(Layer):
         fused_act = act_name if act_name in (None, 'linear', 'relu') else None
         if x.is_cuda and ops.dense_supported(x, self.kernel):
             # hand-written fp32 MFMA / GEMV kernels (csrc/dense.hip); relu and bias fused
-            y = ops.dense(x, self.kernel, self.bias, fused_act)
+            mfma_dtype = self.mfma_dtype if self.mfma_dtype is not None else (os.environ.get('DT_AMD_DENSE_DTYPE') or None)
+            y = ops.dense(x, self.kernel, self.bias, fused_act, mfma_dtype)
             if activation is not None and fused_act is None:
                 y = activation(y)
             return y

@@ -222,7 +222,8 @@ def _feature_generation(w):
     x = _ExpandDims()(raw)
     generated = []
     for filters, height, pool, new_filters in zip(*(w.config.fgcnn_params.get(k, d) for k, d in _FG_DEFAULTS)):
-        x, feats = layers.FGCNN(filters=filters, kernel_height=height, pool_height=pool, new_filters=new_filters)(x)
+        x, feats = layers.FGCNN(filters=filters, kernel_height=height, pool_height=pool, new_filters=new_filters,
+                                dense_mfma_dtype=w.config.fgcnn_params.get('dense_mfma_dtype'))(x)
         generated.append(feats)
     return w.note('fg', raw, Concatenate(axis=1)(generated + [raw]))
 
@@ -324,7 +325,8 @@ def dnn(x, params, cellname='dnn'):
         return custom(x, params, cellname + '_custom')
     cells, activation, init = _tower_cells(params)
     for i, (units, rate, use_bn) in enumerate(cells, start=1):
-        x = Dense(units, use_bias=not use_bn, name=f'{cellname}_dense_{i}', kernel_initializer=init)(x)
+        x = Dense(units, use_bias=not use_bn, name=f'{cellname}_dense_{i}', kernel_initializer=init,
+                  mfma_dtype=params.get('dense_mfma_dtype'))(x)
         if use_bn:
             x = BatchNormalization(name=f'{cellname}_bn_{i}')(x)
         x = Activation(activation=activation, name=f'{cellname}_activation_{i}')(x)
@@ -337,7 +339,8 @@ def custom_dnn_D_A_D_B(x, params, cellname='dnn_D_A_D_B'):
     """the alternative cell order Dense(activation) -> (Dropout) -> (BN) (deepnets.py:430-452)."""
     cells, activation, init = _tower_cells(params)
     for i, (units, rate, use_bn) in enumerate(cells, start=1):
-        x = Dense(units, activation=activation, kernel_initializer=init, name=f'{cellname}_dense_{i}')(x)
+        x = Dense(units, activation=activation, kernel_initializer=init, name=f'{cellname}_dense_{i}',
+                  mfma_dtype=params.get('dense_mfma_dtype'))(x)
         if rate > 0:
             x = Dropout(rate, name=f'{cellname}_dropout_{i}')(x)
         if use_bn:

@@ -621,7 +621,9 @@ class FGCNN(Layer):
     convolution, the activation and the pooling are one HIP launch each way that reads the taps from the map in LDS
     (csrc/fgcnn_train.hip; DT_AMD_FGCNN_CONV=0 keeps the gather + Dense + amax path)."""
 
-    def __init__(self, filters, kernel_height, new_filters, pool_height, activation='tanh', **kwargs):
+    def __init__(self, filters, kernel_height, new_filters, pool_height, activation='tanh', dense_mfma_dtype=None,
+                 **kwargs):
+        self.dense_mfma_dtype = dense_mfma_dtype     # fgcnn_params['dense_mfma_dtype']: the recombination Dense's mode
         self.filters = filters
         self.kernel_height = kernel_height
         self.new_filters = new_filters
@@ -635,7 +637,8 @@ class FGCNN(Layer):
         self.conv_bias = self.add_weight('conv2d_bias', (self.filters,), 'zeros')
         Fp = _same_pad(F, self.pool_height, self.pool_height)[0]
         self.dense_output = Dense(F * D * self.new_filters, activation=self.activation,
-                                  kernel_initializer='glorot_uniform', name=f'{self.name}_dense_output')
+                                  kernel_initializer='glorot_uniform', name=f'{self.name}_dense_output',
+                                  mfma_dtype=self.dense_mfma_dtype)
         self.dense_output.build((None, Fp * D * self.filters))
         self._act = get_activation(self.activation)
         self.built = True

@@ -989,7 +989,7 @@ def split_cols(y, D):
 # ------------------------------------------------------------------------------------------------
 class _Dense(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, W, bias, act):
+    def forward(ctx, x, W, bias, act, mode):
         require_cuda(x, W)
         x2 = _f32c(x).reshape(-1, x.shape[-1])
         W = _f32c(W)
@@ -999,7 +999,13 @@ class _Dense(torch.autograd.Function):
         bias_c = None if bias is None else _f32c(bias)
         # the LDS-slab kernels of csrc/dense.hip where they take the shape, csrc/dense_tiled.hip's fixed tiles otherwise
         ctx.tiled = N > 0 and not lib().dt_dense_supported(N, K, M)
-        if ctx.tiled:
+        ctx.mode = mode if ctx.tiled else 0        # a bf16 mode: the same tiles on csrc/dense_tiled_x3.hip
+        if ctx.mode:
+            nbytes = lib().dt_dense_x3_workspace_bytes(N, K, M, mode)
+            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=W.device) if nbytes > 0 else None
+            check(lib().dt_dense_x3_fwd(ptr(x2), ptr(W), ptr(bias_c), act, N, K, M, ptr(y), mode, ptr(ws), stream_ptr()),
+                  'dt_dense_x3_fwd')
+        elif ctx.tiled:
             check(lib().dt_dense_tiled_fwd(ptr(x2), ptr(W), ptr(bias_c), act, N, K, M, ptr(y), stream_ptr()),
                   'dt_dense_tiled_fwd')
         else:
@@ -1025,12 +1031,18 @@ class _Dense(torch.autograd.Function):
         else:
             gW, gW_ret = _grad_target(ctx.W_ref)
             gb, gb_ret = _grad_target(ctx.b_ref) if ctx.has_bias else (None, None)
+        if ctx.mode:
+            nbytes = lib().dt_dense_x3_workspace_bytes(N, K, M, ctx.mode)
+            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=W.device) if nbytes > 0 else None
+            check(lib().dt_dense_x3_bwd(ptr(x2), ptr(W), ptr(y), ptr(gy2), ctx.act, N, K, M, ptr(gx), ptr(gW), ptr(gb),
+                                        ctx.mode, ptr(ws), stream_ptr()), 'dt_dense_x3_bwd')
+            return (gx.reshape(ctx.x_shape) if need_x else None), gW_ret, gb_ret, None, None
         name = 'dt_dense_tiled' if ctx.tiled else 'dt_dense'
         nbytes = getattr(lib(), name + '_workspace_bytes')(N, K, M)
         ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=W.device) if nbytes > 0 else None
         check(getattr(lib(), name + '_bwd')(ptr(x2), ptr(W), ptr(y), ptr(gy2), ctx.act, N, K, M, ptr(gx), ptr(gW), ptr(gb),
                                             ptr(ws), stream_ptr()), name + '_bwd')
-        return (gx.reshape(ctx.x_shape) if need_x else None), gW_ret, gb_ret, None
+        return (gx.reshape(ctx.x_shape) if need_x else None), gW_ret, gb_ret, None, None
 
 
 def dense_supported(x, W):
@@ -1043,10 +1055,26 @@ def dense_supported(x, W):
     return n > 0 and bool(lib().dt_dense_supported(n, k, m) or lib().dt_dense_tiled_supported(n, k, m))
 
 
-def dense(x, W, bias=None, activation=None):
-    """y = act(x @ W + bias) with act in {None/'linear', 'relu'} on the HIP Dense kernels."""
+def dense_mfma_mode(mfma_dtype):
+    """dense_mfma_dtype -> dt_dense_x3_*'s mode (0: the exact fp32 kernels); an unknown request raises (no silent fp32)"""
+    if mfma_dtype in (None, 'float32', 'f32', 'fp32'):
+        return 0
+    if mfma_dtype == 'bf16x3':
+        return _lib.DT_DENSE_X3
+    if mfma_dtype in ('bf16', 'bfloat16'):
+        return _lib.DT_DENSE_BF16
+    raise ValueError(f'Dense mfma_dtype {mfma_dtype!r}: expected float32, bf16x3 or bf16')
+
+
+def dense(x, W, bias=None, activation=None, mfma_dtype=None):
+    """y = act(x @ W + bias) with act in {None/'linear', 'relu'} on the HIP Dense kernels.
+    mfma_dtype: None / 'float32' (exact fp32 MFMA), 'bf16x3' (split-bf16 operands on the bf16 matrix cores: three parts and
+    six products forward, at the fp32 bars; two parts and three products backward) or 'bf16' (one bf16 product, the 1e-2
+    mode).  The modes apply to the shapes dt_dense_supported refuses, the ones the tiled kernels serve
+    (csrc/dense_tiled_x3.hip); a shape the LDS-slab kernels of csrc/dense.hip take stays on them in exact fp32 in every
+    mode: those are small and bandwidth-bound."""
     act = {'relu': _lib.DT_ACT_RELU, 'linear': _lib.DT_ACT_LINEAR, None: _lib.DT_ACT_LINEAR}[activation]
-    return _Dense.apply(x, W, bias, act)
+    return _Dense.apply(x, W, bias, act, dense_mfma_mode(mfma_dtype))
 
 
 # ------------------------------------------------------------------------------------------------

@@ -334,6 +334,31 @@ int dt_dense_tiled_fwd(const float* x, const float* W, const float* bias, int ac
 int dt_dense_tiled_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
                        int M, float* grad_x, float* grad_W, float* grad_b, void* ws, void* stream);
 
+/* ---- Keras Dense, tiled, on the bf16 matrix cores (csrc/dense_tiled_x3.hip): the contract, the shape domain and the tile
+ *      rule of dt_dense_tiled_*, with the operands split into bf16 parts while they are staged into LDS (nothing pre-split
+ *      is written to HBM; fp32 tensors, fp32 accumulation).  mode (dnn_params / fgcnn_params['dense_mfma_dtype']):
+ *        DT_DENSE_X3    forward: three parts per operand, six products (fp32 class: 2 x 2^-24 on cond_rms);
+ *                       grad_x / grad_W: two parts, three products (2^-17 per product)
+ *        DT_DENSE_BF16  one bf16 product everywhere (north_star's 1e-2 mode)
+ *      grad_b is an fp32 column sum of G in both modes; the relu mask reads the stored fp32 y.  A non-finite operand
+ *      poisons the row / column the fp32 kernel would poison and nothing else (its low parts are zero, not inf - inf).
+ *   dt_dense_x3_supported: 1 for a known mode and N > 0, K > 0, M >= 2.  ws: dt_dense_x3_workspace_bytes(N,K,M,mode)
+ *   bytes — 0 today, ws may then be NULL.  Validation as dt_dense_tiled_*; an unknown mode is DT_ERR_INVALID_ARG.      */
+#define DT_DENSE_X3 1
+#define DT_DENSE_BF16 2
+int dt_dense_x3_supported(int N, int K, int M, int mode);
+int64_t dt_dense_x3_workspace_bytes(int N, int K, int M, int mode);
+/* the launch geometry: product = 0 forward (N x M output), 1 grad_x (N x K), 2 grad_W (K x M); *tile_rows x *tile_cols =
+ * the output tile (64 x 64 or 128 x 128), *splits = gridDim.z (1 for products 0 and 1; > 1: grad_W's partial tiles merge
+ * with float atomics), *steps_per_split = contraction steps of 32 per split.  HOST pointers, any may be NULL; no launch;
+ * computed by the helper the launches use; DT_ERR_UNSUPPORTED outside dt_dense_x3_supported */
+int dt_dense_x3_geometry(int N, int K, int M, int mode, int product, int* tile_rows, int* tile_cols, int* splits,
+                         int* steps_per_split);
+int dt_dense_x3_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M, float* y, int mode,
+                    void* ws, void* stream);
+int dt_dense_x3_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K, int M,
+                    float* grad_x, float* grad_W, float* grad_b, int mode, void* ws, void* stream);
+
 /* ---- FGCNN block, training: Conv2D((h,1), 'same') -> activation -> MaxPooling2D((pool,1), 'same') of FGCNN.call
  *      (layers.py:161-242, the three layers at :220-225) in one launch each way (csrc/fgcnn_train.hip) ------------------ *
  *   All tensors contiguous fp32, channels-last: x [B][F][D][C], kernel in the Keras layout [h][1][C][filters], bias
