@@ -109,6 +109,16 @@ SIGNATURES = {
     'dt_bce_logits': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
     'dt_sgd_dense_step': (_c_int, [_ptr, _ptr, _c_i64, _c_f32, _ptr]),
     'dt_sgd_rows_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr]),
+    # Adagrad / RMSprop: one slot per element; the rows forms take dt_adam_rows_step's merge arguments (csrc/optim.hip)
+    'dt_adagrad_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
+    'dt_rmsprop_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
+    'dt_adagrad_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
+    'dt_rmsprop_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
+    'dt_adagrad_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32, _c_f32,
+                                      _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr]),
+    'dt_rmsprop_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32,
+                                      _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr]),
+    'dt_rmsprop_rows_materialize': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_f32, _ptr, _ptr]),
     'dt_dense_supported': (_c_int, [_c_int] * 3),
     'dt_dense_workspace_bytes': (_c_i64, [_c_int] * 3),
     'dt_dense_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

@@ -2,7 +2,8 @@
 """Checkpoint format: one safetensors file holding every weight of the model under its
 KERAS name — `<layer name>/<weight name>` exactly as `keras.Model.save_weights` of the reference graph would
 name them (deepmodel.py:205-221 saves an .h5 of that model; deeptable.py:773-804 wraps it) — plus, optionally,
-the optimizer's slots (`optimizer/<weight>/m|v`, step count in the metadata).
+the optimizer's slots (`optimizer/<weight>/<slot>`: m and v for Adam, acc for Adagrad, rms for RMSprop; the optimizer's
+name, step count and hyperparameters in the metadata).
 
 The packed embedding table of `MultiColumnEmbedding` is stored as the reference's per-column variables
 `embeddings_{i}` (layers.py:863-877); Cross / CIN / BilinearInteraction parameter lists get the reference's
@@ -79,14 +80,21 @@ def _slot_piece(slot, off, t):
     return slot.reshape(-1)[off:off + t.numel()].reshape(t.shape)
 
 
+def _slot_names(optimizer):
+    return getattr(optimizer, 'slot_names', ('m', 'v'))
+
+
 def save_model(model, path, optimizer=None, metadata=None):
-    """Write `path` (safetensors).  optimizer: a KerasAdam whose m/v slots are stored next to the weights."""
+    """Write `path` (safetensors).  optimizer: a KerasAdam / Adagrad / RMSprop whose slots are stored next to the weights
+    (an RMSprop first applies the decay pending on its row-sparse tables: the file holds Keras' slots)."""
     from safetensors.torch import save_file
     tensors = OrderedDict()
     for name, t in named_weights(model).items():
         tensors[name] = t.detach().to('cpu').contiguous()
     meta = {'format': FORMAT}
     if optimizer is not None and hasattr(optimizer, 'state'):
+        if hasattr(optimizer, 'materialize'):
+            optimizer.materialize()
         by_id = {id(t): name for name, t in named_weights(model).items()}
         by_ptr = {}
         for name, t in named_weights(model).items():
@@ -100,10 +108,12 @@ def save_model(model, path, optimizer=None, metadata=None):
                      if _inside(t, p)]
             for name, t in views:
                 off = (t.data_ptr() - p.data_ptr()) // 4
-                for slot in ('m', 'v'):          # (a table's slots may be strided views of one [V,2,D] array)
+                for slot in _slot_names(optimizer):      # (a table's slots may be strided views of one slot record)
                     tensors[f'optimizer/{name}/{slot}'] = _slot_piece(st[slot], off, t).detach().to('cpu').contiguous()
         meta['optimizer'] = getattr(optimizer, '_name', optimizer.__class__.__name__)
         meta['optimizer_iterations'] = str(int(getattr(optimizer, 't', 0)))
+        if hasattr(optimizer, 'hyperparameters'):
+            meta['optimizer_hyperparameters'] = json.dumps(optimizer.hyperparameters())
         del by_id
     if metadata:
         meta.update({k: v if isinstance(v, str) else json.dumps(v) for k, v in metadata.items()})
@@ -145,6 +155,16 @@ def load_model(model, path, optimizer=None, strict=True):
                 t.copy_(src.to(t.dtype))
                 seen.add(name)
             if optimizer is not None and meta.get('optimizer') and hasattr(optimizer, 'state'):
+                name_here = getattr(optimizer, '_name', optimizer.__class__.__name__)
+                if meta['optimizer'] != name_here:
+                    raise ValueError(f'{path}: holds the slots of optimizer {meta["optimizer"]!r}, the model was compiled '
+                                     f'with {name_here!r}; load it without the optimizer or compile the model with '
+                                     f'optimizer={meta["optimizer"].lower()!r}')
+                slots = _slot_names(optimizer)
+                if 'optimizer_hyperparameters' in meta and hasattr(optimizer, 'set_hyperparameters'):
+                    optimizer.set_hyperparameters(json.loads(meta['optimizer_hyperparameters']))
+                # the step count first: slots created below start with nothing pending at THAT count
+                optimizer.t = int(meta.get('optimizer_iterations', '0'))
                 by_ptr = {}
                 for name, t in targets.items():
                     by_ptr.setdefault(t.untyped_storage().data_ptr(), []).append((name, t))
@@ -158,13 +178,12 @@ def load_model(model, path, optimizer=None, strict=True):
                     if st is None:
                         st = optimizer._st(p, rows=id(p) in row_sparse)
                     for name, t in by_ptr.get(p.untyped_storage().data_ptr(), []):
-                        if not _inside(t, p) or f'optimizer/{name}/m' not in keys:
+                        if not _inside(t, p) or f'optimizer/{name}/{slots[0]}' not in keys:
                             continue
                         off = (t.data_ptr() - p.data_ptr()) // 4
-                        for slot in ('m', 'v'):
+                        for slot in slots:
                             dst = _slot_piece(st[slot], off, t)
                             dst.copy_(f.get_tensor(f'optimizer/{name}/{slot}').reshape(dst.shape))
-                optimizer.t = int(meta.get('optimizer_iterations', '0'))
     extra = [k for k in keys if not k.startswith('optimizer/') and k not in seen]
     if strict and extra:
         raise KeyError(f'{path}: unexpected weights {extra[:5]}{"..." if len(extra) > 5 else ""}')

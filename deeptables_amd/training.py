@@ -402,14 +402,362 @@ class SGD:
             layer.sparse_grads.clear()
 
 
+class _SlotOptimizer:
+    """What keras.optimizers.Adagrad and RMSprop (momentum 0) share: ONE slot per element and no bias correction.  The
+    protocol is KerasAdam's — `zero_grad(flat=...)`, `step()`, `register_flat_group`, `pre_dense_hook`, `state`, `t` — and so
+    is the launch order of a step: the dense tensors in one multi-tensor launch, then one row launch per packed table with a
+    sparse gradient, the last of which carries one dense update and advances the device-resident step counter.
+    Unlike Adam's, the row-sparse update IS Keras' result (a row that was not looked up has a zero gradient and does not
+    move).  The fused DeepFM / DCN plans run forward + backward and leave the whole update to `step()`, as they do for SGD."""
+
+    supports_row_segments = False     # the row entry points take no segments: the fused plans hand over plain (rows, values)
+    supports_rows_in_step = False
+    slot_names = ()                   # (the slot's name,): its key in `state[id(p)]` and in a checkpoint
+    slot_init = 0.0
+
+    def __init__(self, params, embedding_layers, learning_rate, epsilon):
+        self.lr, self.eps = float(learning_rate), float(epsilon)
+        self.params = [p for p in params if p.requires_grad]
+        self.state = {}
+        self.embedding_layers = list(embedding_layers)
+        self._dev_state = None        # device-resident step state (DT_ADAM_STATE_BYTES; t and the arrival counters)
+        self.pre_dense_hook = None    # as KerasAdam's: run right before the dense updates of a step
+        self._flat = None             # (flat_param, flat_grad, flat slot, None, n, {id(param): offset})
+        self._flat_views = None
+
+    def _state_tensor(self, device):
+        if self._dev_state is None:
+            self._dev_state = torch.zeros(68, dtype=torch.int32, device=device)     # DT_ADAM_STATE_BYTES / 4
+            check(lib().dt_adam_state_init(ptr(self._dev_state), self.lr, 0.0, 0.0, 0, stream_ptr()), 'dt_adam_state_init')
+        return self._dev_state
+
+    @property
+    def t(self):
+        """number of completed steps (keras `optimizer.iterations`)"""
+        return 0 if self._dev_state is None else int(self._dev_state[0].item()) - 1
+
+    @t.setter
+    def t(self, value):
+        if not self.params:
+            return
+        self.materialize()                 # pending decay belongs to the old step count
+        check(lib().dt_adam_state_init(ptr(self._state_tensor(self.params[0].device)), self.lr, 0.0, 0.0, int(value),
+                                       stream_ptr()), 'dt_adam_state_init')
+        self._restamp()
+
+    def materialize(self):
+        """make every slot Keras' slot (RMSprop applies the decay pending on the rows of its row-sparse tables)"""
+
+    def _restamp(self):
+        pass
+
+    def slot(self, p):
+        """the slot of parameter p as Keras holds it (shape of p), or None before p's first update"""
+        self.materialize()
+        s = self.state.get(id(p))
+        return None if s is None else s[self.slot_names[0]]
+
+    def hyperparameters(self):
+        return {'learning_rate': self.lr, 'epsilon': self.eps}
+
+    def set_hyperparameters(self, hp):
+        self.lr, self.eps = float(hp.get('learning_rate', self.lr)), float(hp.get('epsilon', self.eps))
+
+    def _new_slot(self, p, rows):
+        return {self.slot_names[0]: torch.full_like(p, self.slot_init)}
+
+    def _st(self, p, rows=False):
+        """slot of parameter p.  rows=True: the layout of the row-sparse table update (Adagrad: the same [V, D] array)"""
+        s = self.state.get(id(p))
+        if s is None:
+            s = self._new_slot(p, rows and p.dim() == 2)
+            self.state[id(p)] = s
+        return s
+
+    def register_flat_group(self, flat_param, flat_grad, members, n, grad_views=False):
+        """KerasAdam.register_flat_group with one slot: the members' slots become views of one flat slot buffer"""
+        key = self.slot_names[0]
+        flat_slot = torch.full_like(flat_param, self.slot_init)
+
+        def view_of(flat, p, off, cnt, layout):
+            if layout is None:
+                return flat[off:off + cnt].view(p.shape)
+            return torch.as_strided(flat, layout[0], layout[1], off)
+        members = [(mb[0], mb[1], mb[2], mb[3] if len(mb) > 3 else None) for mb in members]
+        for p, off, cnt, layout in members:
+            old = self.state.get(id(p))
+            sv = view_of(flat_slot, p, off, cnt, layout)
+            if old is not None:
+                sv.copy_(old[key].reshape(p.shape))
+            self.state[id(p)] = {key: sv}
+        self._flat = (flat_param, flat_grad, flat_slot, None, int(n), {id(p): off for p, off, _, _ in members})
+        self._flat_views = [(p, view_of(flat_grad, p, off, cnt, layout)) for p, off, cnt, layout in members] \
+            if grad_views else None
+        for p, off, cnt, layout in members:
+            p._dt_grad_view = None
+        if grad_views:
+            for p, view in self._flat_views:
+                p._dt_grad_view = view
+
+    def zero_grad(self, flat=True):
+        for p in self.params:
+            p.grad = None
+        if flat and self._flat is not None and self._flat_views is not None:
+            self._flat[1].zero_()
+            for p, view in self._flat_views:
+                p.grad = view
+        for layer in self.embedding_layers:
+            layer.sparse_grads.clear()
+
+    # the three launches, by optimizer
+    def _dense_call(self, p, g, s, n, sp, advance, st):
+        raise NotImplementedError
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        raise NotImplementedError
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
+        raise NotImplementedError
+
+    def _dense_launch(self, dense, sp, st, advance):
+        """All dense tensors of the step in one launch (chunks of 32 tensors)."""
+        if not dense:
+            return
+        if len(dense) == 1:
+            pp, gg, ss, n = dense[0]
+            self._dense_call(pp, gg, ss, n, sp, 1 if advance else 0, st)
+            return
+        import ctypes
+        T = len(dense)
+        arr = ctypes.c_void_p * T
+        ps, gs, ss = (ctypes.cast(arr(*[t[k].data_ptr() for t in dense]), ctypes.c_void_p) for k in range(3))
+        ns = ctypes.cast((ctypes.c_int64 * T)(*[int(t[3]) for t in dense]), ctypes.c_void_p)
+        self._multi_call(T, ps, gs, ss, ns, sp, 1 if advance else 0, st)
+
+    def step(self):
+        if not self.params:
+            return
+        key = self.slot_names[0]
+        sp = ptr(self._state_tensor(self.params[0].device))
+        st = stream_ptr()
+        dense = []                                        # (param, grad, slot, n)
+        flat_done = set()
+        if self._flat is not None:
+            fp, fg, fs, _, n, members = self._flat
+            with_grad = [p for p in self.params if id(p) in members and p.grad is not None]
+            if len(with_grad) == len(members):
+                # gradients that are not the members' views of the flat gradient buffer (the layer-by-layer path after a
+                # fused plan re-homed the parameters) are scattered into it: members of a plan with a narrow tower are
+                # strided views of zero-padded slabs, which the (pointer, numel) kernels must not see one by one.  Pads
+                # have a zero gradient: they stay exactly zero.
+                in_flat = {id(p) for p in with_grad if p.grad.data_ptr() == fg.data_ptr() + 4 * members[id(p)]}
+                if len(in_flat) != len(members):
+                    if not in_flat:
+                        fg.zero_()
+                    for p in with_grad:
+                        if id(p) not in in_flat:
+                            view = torch.as_strided(fg, tuple(p.data.shape), tuple(p.data.stride()),
+                                                    (p.data.data_ptr() - fp.data_ptr()) // 4)
+                            view.copy_(p.grad.reshape(view.shape))
+                dense.append((fp, fg, fs, n))
+                flat_done = set(members)
+        deferred = []                                     # (param, slot, contiguous copies) of strided tensors
+        for p in self.params:
+            if p.grad is None or id(p) in flat_done:
+                continue
+            s = self._st(p)[key]
+            if p.data.is_contiguous() and s.is_contiguous():
+                dense.append((p.data, p.grad.contiguous(), s, p.numel()))
+            else:
+                pc, sc = p.data.contiguous(), s.contiguous()
+                dense.append((pc, p.grad.contiguous(), sc, p.numel()))
+                deferred.append((p, s, pc, sc))
+        sparse = [(layer, k, grads) for layer in self.embedding_layers for k, grads in layer.sparse_grads.items()]
+        # launch order (KerasAdam.step): dense updates that cannot ride along, then the table updates; the last table
+        # update carries one dense update in its trailing blocks and advances the step counter
+        hook, self.pre_dense_hook = self.pre_dense_hook, None
+        dense_after = hook is not None and bool(sparse)     # table updates first, overlapping the pending reduce
+        tail = dense.pop(0) if (sparse and dense and not dense_after) else None
+        if hook is not None and not dense_after:
+            hook()
+        if not dense_after:
+            self._dense_launch(dense, sp, st, advance=not sparse)
+        if not sparse and not dense:
+            check(lib().dt_adam_advance(sp, self.lr, 0.0, 0.0, st), 'dt_adam_advance')
+        for i, (layer, k, grads) in enumerate(sparse):
+            table = layer.tables[k]
+            s = self._st(table, rows=True)
+            D = table.shape[1]
+            if any(getattr(g, 'segments', None) is not None or getattr(g, 'fields', None) == -2 for g in grads):
+                raise ValueError(f'{self._name}: a sparse gradient with segments or rows applied inside the step')
+            if len(grads) == 1:
+                rows, values = grads[0].rows, grads[0].values
+            else:
+                rows = torch.cat([g.rows.reshape(-1) for g in grads])
+                values = torch.cat([g.values.reshape(-1, D) for g in grads])
+            n = rows.numel()
+            fields = len(dict(layer.groups)[D]) if hasattr(layer, 'groups') else 0
+            hints = {getattr(g, 'fields', None) for g in grads}
+            if hints != {None}:                           # an explicit layout promise overrides the layer default
+                fields = hints.pop() if len(hints) == 1 else 0
+                fields = 0 if fields is None else int(fields)
+            if fields == -1 and len(grads) != 1:
+                fields = 0                                # distinct within each piece only
+            values = values if values.is_contiguous() else values.contiguous()
+            if fields == -1:
+                slots = mark = None
+                n_slots = 0
+            else:
+                n_slots = lib().dt_adam_rows_slots(n)
+                if s.get('n_slots', 0) < n_slots or s['mark'].numel() < n:
+                    s['slots'] = torch.zeros(n_slots, dtype=torch.int64, device=table.device)
+                    s['mark'] = torch.empty(n, dtype=torch.int32, device=table.device)
+                    s['n_slots'] = n_slots
+                slots, mark, n_slots = s['slots'], s['mark'], s['n_slots']
+            is_last = i == len(sparse) - 1 and not (dense_after and dense)
+            tl = tail if (is_last and tail is not None) else (None, None, None, 0)
+            self._rows_call(table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tl, 1 if is_last else 0, st)
+        if dense_after:
+            hook()
+            self._dense_launch(dense, sp, st, advance=True)
+        for p, s, pc, sc in deferred:
+            p.data.copy_(pc)
+            s.copy_(sc)
+        for layer in self.embedding_layers:
+            layer.sparse_grads.clear()
+
+
+class Adagrad(_SlotOptimizer):
+    """keras.optimizers.Adagrad(learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7):
+        acc += g*g;  p -= lr*g/(sqrt(acc)+eps),  acc starts at initial_accumulator_value.
+    Row-sparse tables: duplicate lookups summed (Keras `_deduplicate_indexed_slices`), every looked-up row updated once;
+    the other rows keep p and acc bit for bit."""
+
+    _name = 'Adagrad'
+    slot_names = ('acc',)
+
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7):
+        if initial_accumulator_value < 0:
+            raise ValueError(f'initial_accumulator_value must be non-negative, got {initial_accumulator_value}')
+        super().__init__(params, embedding_layers, learning_rate, epsilon)
+        self.initial_accumulator_value = self.slot_init = float(initial_accumulator_value)
+
+    def hyperparameters(self):
+        return dict(super().hyperparameters(), initial_accumulator_value=self.initial_accumulator_value)
+
+    def _dense_call(self, p, g, s, n, sp, advance, st):
+        check(lib().dt_adagrad_dense_step(ptr(p), ptr(g), ptr(s), n, self.lr, self.eps, sp, advance, st),
+              'dt_adagrad_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_adagrad_multi_step(T, ps, gs, ss, ns, self.lr, self.eps, sp, advance, st), 'dt_adagrad_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
+        acc = s['acc']
+        check(lib().dt_adagrad_rows_step(ptr(table.data), ptr(acc), ptr(rows), ptr(values), n, D, fields, ptr(slots), n_slots,
+                                         ptr(mark), self.lr, self.eps, sp, ptr(tail[0]), ptr(tail[1]), ptr(tail[2]), tail[3],
+                                         advance, int(acc.stride(0)), st), 'dt_adagrad_rows_step')
+
+
+class RMSprop(_SlotOptimizer):
+    """keras.optimizers.RMSprop(learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False):
+        rms = rho*rms + (1-rho)*g*g;  p -= lr*g/(sqrt(rms)+eps),  rms starts at 0.
+    momentum != 0 and centered=True use another formula and are refused.
+    Row-sparse tables: Keras decays rms of EVERY row each step and moves the looked-up rows.  Here a row's decay waits until
+    the row is looked up again: an int32 stamp per row holds the step at which its rms was last written, and the row update
+    first applies rho^(t - stamp - 1).  The looked-up rows' weights are Keras' after every step; `materialize()` applies what
+    is pending on all rows, after which `rms` is Keras' slot (`slot(p)` and checkpoint.save_model call it)."""
+
+    _name = 'RMSprop'
+    slot_names = ('rms',)
+    # where a row-sparse table's stamps live: False: an int32 [V] array of their own (rms rows stay 16 D bytes apart:
+    # one 128-byte line at D = 32); True: the last 16 bytes of a [V, D + 4] slot record.  DESIGN.md §3.6 has the measurement.
+    stamp_in_record = False
+
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False):
+        if momentum != 0 or centered:
+            raise ValueError('RMSprop: momentum != 0 and centered=True are not supported (Keras switches to another '
+                             f'update formula for them); got momentum={momentum!r}, centered={centered!r}')
+        super().__init__(params, embedding_layers, learning_rate, epsilon)
+        self.rho, self.momentum, self.centered = float(rho), 0.0, False
+
+    def hyperparameters(self):
+        return dict(super().hyperparameters(), rho=self.rho, momentum=0.0, centered=False)
+
+    def set_hyperparameters(self, hp):
+        super().set_hyperparameters(hp)
+        self.rho = float(hp.get('rho', self.rho))
+
+    def _new_slot(self, p, rows):
+        if not rows:
+            return {'rms': torch.zeros_like(p)}
+        V, D = p.shape
+        if self.stamp_in_record:
+            rec = torch.zeros((V, D + 4), dtype=p.dtype, device=p.device)
+            s = {'rms': rec[:, :D], 'stamp': rec[:, D].view(torch.int32), 'rec': rec}
+        else:
+            s = {'rms': torch.zeros_like(p), 'stamp': torch.zeros(V, dtype=torch.int32, device=p.device)}
+        s['stamp'].copy_((self._state_tensor(p.device)[:1] - 1).expand(V))       # nothing is pending on a new slot
+        return s
+
+    def _st(self, p, rows=False):
+        s = self.state.get(id(p))
+        if s is not None and not rows and 'stamp' in s:       # a dense update of a table that has row-sparse slots
+            self._materialize_one(p, s)
+            s = {'rms': s['rms'].contiguous()}
+            self.state[id(p)] = s
+        elif s is not None and rows and p.dim() == 2 and 'stamp' not in s:
+            old, s = s, self._new_slot(p, True)
+            s['rms'].copy_(old['rms'].reshape(p.shape))
+            self.state[id(p)] = s
+        return super()._st(p, rows)
+
+    def _materialize_one(self, p, s):
+        rms, stamp = s['rms'], s['stamp']
+        check(lib().dt_rmsprop_rows_materialize(ptr(rms), ptr(stamp), p.shape[0], p.shape[1], int(rms.stride(0)),
+                                                int(stamp.stride(0)), self.rho, ptr(self._state_tensor(p.device)),
+                                                stream_ptr()), 'dt_rmsprop_rows_materialize')
+
+    def materialize(self):
+        for p in self.params:
+            s = self.state.get(id(p))
+            if s is not None and 'stamp' in s:
+                self._materialize_one(p, s)
+
+    def _restamp(self):
+        for p in self.params:
+            s = self.state.get(id(p))
+            if s is not None and 'stamp' in s:
+                s['stamp'].copy_((self._dev_state[:1] - 1).expand(p.shape[0]))
+
+    def _dense_call(self, p, g, s, n, sp, advance, st):
+        check(lib().dt_rmsprop_dense_step(ptr(p), ptr(g), ptr(s), n, self.lr, self.rho, self.eps, sp, advance, st),
+              'dt_rmsprop_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_rmsprop_multi_step(T, ps, gs, ss, ns, self.lr, self.rho, self.eps, sp, advance, st),
+              'dt_rmsprop_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
+        rms, stamp = s['rms'], s['stamp']
+        check(lib().dt_rmsprop_rows_step(ptr(table.data), ptr(rms), ptr(stamp), ptr(rows), ptr(values), n, D, fields,
+                                         ptr(slots), n_slots, ptr(mark), self.lr, self.rho, self.eps, sp, ptr(tail[0]),
+                                         ptr(tail[1]), ptr(tail[2]), tail[3], advance, int(rms.stride(0)),
+                                         int(stamp.stride(0)), st), 'dt_rmsprop_rows_step')
+
+
+OPTIMIZERS = {'adam': KerasAdam, 'sgd': SGD, 'adagrad': Adagrad, 'rmsprop': RMSprop}
+
+
 def make_optimizer(spec, params, embedding_layers):
-    if spec == 'auto' or spec is None or (isinstance(spec, str) and spec.lower() == 'adam'):
+    if spec == 'auto' or spec is None:
         return KerasAdam(params, embedding_layers)
-    if isinstance(spec, str) and spec.lower() == 'sgd':
-        return SGD(params, embedding_layers)
+    if isinstance(spec, str) and spec.lower() in OPTIMIZERS:
+        return OPTIMIZERS[spec.lower()](params, embedding_layers)
     if callable(spec):
         return spec(params, embedding_layers)
-    raise ValueError(f'Unsupported optimizer: {spec!r}')
+    raise ValueError(f"Unsupported optimizer: {spec!r} (accepted: 'auto', {', '.join(repr(k) for k in OPTIMIZERS)}, or a "
+                     f'callable (params, embedding_layers) -> optimizer)')
 
 
 def flatten_dense_parameters(model, optimizer, exclude=()):

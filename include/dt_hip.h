@@ -302,6 +302,46 @@ int dt_sgd_dense_step(float* p, const float* g, int64_t n, float lr, void* strea
 int dt_sgd_rows_step(float* table, const int64_t* rows, const float* values, int64_t n_rows, int D, float lr,
                      void* stream);
 
+/* keras.optimizers.Adagrad(learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7) and
+ * keras.optimizers.RMSprop(learning_rate=1e-3, rho=0.9, momentum=0, epsilon=1e-7, centered=False), selectable through
+ * ModelConfig.optimizer (deepmodel.py:319-345, "str or object"):
+ *     Adagrad: acc += g*g                  ; p -= lr * g / (sqrt(acc) + eps)     (the caller fills acc with its initial value)
+ *     RMSprop: rms = rho*rms + (1-rho)*g*g ; p -= lr * g / (sqrt(rms) + eps)     (rms starts at 0)
+ * One slot per element.  `state`: the device step state of dt_adam_state_init (DT_ADAM_STATE_BYTES; only t and the arrival
+ * counters are used, pass beta1 = beta2 = 0): the LAST launch of a step is called with advance != 0 and its last block
+ * advances t; dt_adam_advance advances a step that launches nothing.
+ * Dense (replaces one keras `_resource_apply_dense` per variable): n contiguous floats, float4 body when p, g and the slot
+ * are 16-byte aligned, the scalar loop otherwise; pointers that are not float aligned are refused.  The multi forms take
+ * `count` tensors (HOST arrays of device pointers / element counts) in launches of 32 tensors.
+ * Rows (replaces `_resource_apply_sparse` behind `_deduplicate_indexed_slices`): rows / values / fields / slots / n_slots /
+ * mark and the dense tail exactly as dt_adam_rows_step (fields >= -1; the same merge of duplicate lookups into `values`);
+ * the owner of every distinct row then updates the table row and its slot record: slot + row * slot_stride, slot_stride >= D
+ * floats.  Any D > 0; with D % 4 == 0 table, slot and values must be 16-byte aligned and slot_stride % 4 == 0.  Rows that
+ * were not looked up keep p and, for Adagrad, acc bit for bit: that IS Keras' result (their gradient is zero).
+ * RMSprop rows decay lazily and exactly: stamp[row * stamp_stride] (int32, 0 at first) is the step at which the row's rms
+ * was last written; a looked-up row first takes rms *= rho^(t - stamp - 1), t read from `state` (required), then the
+ * update, and its stamp becomes t.  The stamp may live in its own [V] array (stamp_stride 1) or inside the slot record
+ * (stamp = (int*)(rms + D), stamp_stride = slot_stride >= D + 1).  dt_rmsprop_rows_materialize applies the decay pending
+ * on every row, rho^(steps done - stamp), and sets every stamp to the steps done: rms then holds Keras' dense slot, and the
+ * next step is unchanged by it.                                                                                          */
+int dt_adagrad_dense_step(float* p, const float* g, float* acc, int64_t n, float lr, float eps, void* state, int advance,
+                          void* stream);
+int dt_rmsprop_dense_step(float* p, const float* g, float* rms, int64_t n, float lr, float rho, float eps, void* state,
+                          int advance, void* stream);
+int dt_adagrad_multi_step(int count, float* const* p, const float* const* g, float* const* acc, const int64_t* n, float lr,
+                          float eps, void* state, int advance, void* stream);
+int dt_rmsprop_multi_step(int count, float* const* p, const float* const* g, float* const* rms, const int64_t* n, float lr,
+                          float rho, float eps, void* state, int advance, void* stream);
+int dt_adagrad_rows_step(float* table, float* acc, const int64_t* rows, float* values, int64_t n_rows, int D, int fields,
+                         void* slots, int64_t n_slots, int* mark, float lr, float eps, void* state, float* dense_p,
+                         const float* dense_g, float* dense_acc, int64_t dense_n, int advance, int slot_stride, void* stream);
+int dt_rmsprop_rows_step(float* table, float* rms, int* stamp, const int64_t* rows, float* values, int64_t n_rows, int D,
+                         int fields, void* slots, int64_t n_slots, int* mark, float lr, float rho, float eps, void* state,
+                         float* dense_p, const float* dense_g, float* dense_rms, int64_t dense_n, int advance,
+                         int slot_stride, int stamp_stride, void* stream);
+int dt_rmsprop_rows_materialize(float* rms, int* stamp, int64_t V, int D, int slot_stride, int stamp_stride, float rho,
+                                const void* state, void* stream);
+
 /* ---- Keras Dense (deepnets.dnn deepnets.py:401-427; Dense(1) logits / task_output deepmodel.py:291-292,455;
  *      Q/K/V/residual projections layers.py:104-108) --------------------------------------------------- *
  *   y [N,M] = act(x [N,K] . W [K,M] + bias [M]|NULL),  act in {DT_ACT_LINEAR, DT_ACT_RELU}.

@@ -1,0 +1,216 @@
+# -*- coding:utf-8 -*-
+"""Adagrad and RMSprop without a GPU: what `make_optimizer` accepts, the C-ABI of the new entry points (csrc/optim.hip)
+and their argument checks, the float64 restatements the GPU tests compare against (tests/optim_reference.py), and a
+DeepModel compiled with one of them."""
+import ctypes
+import os
+import re
+
+import pytest
+import torch
+
+from tests import optim_reference as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ('dt_adagrad_dense_step', 'dt_rmsprop_dense_step', 'dt_adagrad_multi_step', 'dt_rmsprop_multi_step',
+           'dt_adagrad_rows_step', 'dt_rmsprop_rows_step', 'dt_rmsprop_rows_materialize')
+
+
+def test_make_optimizer_takes_adagrad_and_rmsprop_with_keras_defaults():
+    from deeptables_amd import training as T
+    w = torch.nn.Parameter(torch.zeros(3))
+    for name in ('adagrad', 'Adagrad', 'ADAGRAD'):
+        opt = T.make_optimizer(name, [w], [])
+        assert type(opt) is T.Adagrad and opt._name == 'Adagrad'
+        assert (opt.lr, opt.initial_accumulator_value, opt.eps) == (1e-3, 0.1, 1e-7)
+        assert opt.hyperparameters() == R.ADAGRAD_DEFAULTS
+    for name in ('rmsprop', 'RMSprop', 'RMSProp'):
+        opt = T.make_optimizer(name, [w], [])
+        assert type(opt) is T.RMSprop and opt._name == 'RMSprop'
+        assert (opt.lr, opt.rho, opt.momentum, opt.eps, opt.centered) == (1e-3, 0.9, 0.0, 1e-7, False)
+        assert opt.hyperparameters() == R.RMSPROP_DEFAULTS
+    for opt in (T.make_optimizer('adagrad', [w], []), T.make_optimizer('rmsprop', [w], [])):
+        assert opt.t == 0 and opt.state == {} and opt.pre_dense_hook is None
+        assert not opt.supports_rows_in_step and not opt.supports_row_segments      # the fused plans leave them the update
+        assert hasattr(opt, 'register_flat_group')
+    # what was accepted stays, and an unknown name says what is
+    assert type(T.make_optimizer('auto', [w], [])) is T.KerasAdam and type(T.make_optimizer('Adam', [w], [])) is T.KerasAdam
+    assert type(T.make_optimizer(None, [w], [])) is T.KerasAdam and type(T.make_optimizer('SGD', [w], [])) is T.SGD
+    assert T.make_optimizer(lambda p, e: ('mine', p, e), [w], [])[0] == 'mine'
+    with pytest.raises(ValueError, match='Unsupported optimizer') as e:
+        T.make_optimizer('adadelta', [w], [])
+    assert all(repr(n) in str(e.value) for n in ('adam', 'sgd', 'adagrad', 'rmsprop'))
+    with pytest.raises(ValueError, match='momentum'):
+        T.RMSprop([w], [], momentum=0.9)
+    with pytest.raises(ValueError, match='centered'):
+        T.RMSprop([w], [], centered=True)
+    assert T.RMSprop([w], [], rho=0.95, learning_rate=0.01).hyperparameters()['rho'] == 0.95
+
+
+def test_header_exports_and_binding_name_the_same_entry_points():
+    from deeptables_amd import _lib
+    text = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'dt_hip.h')).read(), flags=re.S)
+    declared = set(re.findall(r'\b(dt_(?:adagrad|rmsprop)_[a-z0-9_]+)\s*\(', text))
+    assert declared == set(ENTRIES) == {n for n in _lib.SIGNATURES if n.startswith(('dt_adagrad_', 'dt_rmsprop_'))}
+    handle = ctypes.CDLL(_lib.LIB_PATH)
+    assert all(hasattr(handle, n) for n in ENTRIES)
+
+
+def test_entry_points_check_their_arguments_before_any_launch():
+    """Nothing here may reach a launch (the pointers are made up): every refusal must come from the argument checks, and
+    the message must name the entry point."""
+    from deeptables_amd import _lib
+    lib = _lib.lib()
+    P, Q = 0x10000, 0x10004            # 16-byte aligned / float aligned only
+    ODD = 0x10002                      # not even float aligned
+
+    def refused(name, *args):
+        assert getattr(lib, name)(*args) != 0, (name, args)
+        err = lib.dt_last_error()
+        assert name.encode() in err and b'launch failed' not in err, err
+
+    # dense: (p, g, slot, n, lr, [rho,] eps, state, advance, stream)
+    for name, hp in (('dt_adagrad_dense_step', (1e-3, 1e-7)), ('dt_rmsprop_dense_step', (1e-3, 0.9, 1e-7))):
+        f = getattr(lib, name)
+        assert f(None, None, None, 0, *hp, None, 0, None) == 0          # n = 0: nothing to do, null pointers are fine
+        refused(name, None, None, None, -1, *hp, None, 0, None)
+        refused(name, None, P, P, 8, *hp, None, 0, None)
+        refused(name, P, None, P, 8, *hp, None, 0, None)
+        refused(name, P, P, None, 8, *hp, None, 0, None)
+        refused(name, P, P, P, 8, *hp, None, 1, None)                   # advance without the device state
+        refused(name, None, None, None, 0, *hp, None, 1, None)
+        for k in range(3):                                              # a pointer that is not float aligned
+            refused(name, *[ODD if i == k else P for i in range(3)], 8, *hp, None, 0, None)
+    # multi: (count, p[], g[], slot[], n[], lr, [rho,] eps, state, advance, stream): host arrays
+    arr = (ctypes.c_void_p * 2)(P, P)
+    bad = (ctypes.c_void_p * 2)(P, ODD)
+    nul = (ctypes.c_void_p * 2)(P, None)
+    ns = (ctypes.c_int64 * 2)(4, 4)
+    neg = (ctypes.c_int64 * 2)(4, -4)
+    big = (ctypes.c_int64 * 2)(4, 1 << 31)
+    zero = (ctypes.c_int64 * 2)(0, 0)
+    c = lambda a: ctypes.cast(a, ctypes.c_void_p)
+    for name, hp in (('dt_adagrad_multi_step', (1e-3, 1e-7)), ('dt_rmsprop_multi_step', (1e-3, 0.9, 1e-7))):
+        f = getattr(lib, name)
+        assert f(0, None, None, None, None, *hp, None, 0, None) == 0
+        assert f(2, c(nul), c(nul), c(nul), c(zero), *hp, None, 0, None) == 0   # empty tensors: nothing launched
+        refused(name, -1, None, None, None, None, *hp, None, 0, None)
+        refused(name, 2, None, c(arr), c(arr), c(ns), *hp, None, 0, None)
+        refused(name, 2, c(arr), c(arr), c(arr), None, *hp, None, 0, None)
+        refused(name, 2, c(arr), c(arr), c(arr), c(neg), *hp, None, 0, None)
+        refused(name, 2, c(arr), c(arr), c(arr), c(big), *hp, None, 0, None)
+        refused(name, 2, c(arr), c(nul), c(arr), c(ns), *hp, None, 0, None)
+        refused(name, 2, c(arr), c(arr), c(bad), c(ns), *hp, None, 0, None)     # the SECOND tensor is bad: no launch for the first
+        refused(name, 2, c(arr), c(arr), c(arr), c(ns), *hp, None, 1, None)
+    # rows
+    ada = lambda **kw: _rows_args('adagrad', P, **kw)
+    rms = lambda **kw: _rows_args('rmsprop', P, **kw)
+    for name, mk in (('dt_adagrad_rows_step', ada), ('dt_rmsprop_rows_step', rms)):
+        f = getattr(lib, name)
+        if name == 'dt_adagrad_rows_step':
+            assert f(*mk(n=0, table=None, slot=None, rows=None, values=None, mark=None, slots=None, state=None)) == 0
+        else:
+            refused(name, *mk(state=None))                              # RMSprop reads the step number from the device
+            refused(name, *mk(stamp=None))
+            refused(name, *mk(stamp=ODD))
+            refused(name, *mk(stamp_stride=0))
+        refused(name, *mk(n=-1))
+        refused(name, *mk(D=0))
+        refused(name, *mk(D=-4))
+        refused(name, *mk(fields=-2))                                   # rows applied inside a fused step: Adam only
+        refused(name, *mk(dense_n=-1))
+        refused(name, *mk(dense_n=5))                                   # a dense tail without its arrays
+        refused(name, *mk(slot_stride=8))                               # < D
+        refused(name, *mk(slot_stride=18))                              # D % 4 == 0 needs a 16-byte stride
+        for k in ('table', 'slot', 'rows', 'values'):
+            refused(name, *mk(**{k: None}))
+        for k in ('table', 'slot', 'values'):
+            refused(name, *mk(**{k: Q}))                                # D = 16 reads 16-byte pieces
+            refused(name, *mk(D=6, slot_stride=6, **{k: ODD}))
+        refused(name, *mk(rows=Q))
+        refused(name, *mk(mark=None))
+        refused(name, *mk(slots=None))                                  # fields = 0 merges through the global hash
+        refused(name, *mk(n_slots=100))
+        refused(name, *mk(n_slots=16))                                  # < 2 n
+        refused(name, *mk(advance=1, state=None))
+        refused(name, *mk(n=1 << 31))
+    m = lib.dt_rmsprop_rows_materialize
+    assert m(None, None, 0, 16, 16, 1, 0.9, None, None) == 0
+    for args in ((P, P, -1, 16, 16, 1, 0.9, P, None), (P, P, 8, 0, 16, 1, 0.9, P, None), (P, P, 8, 16, 8, 1, 0.9, P, None),
+                 (P, P, 8, 16, 16, 0, 0.9, P, None), (None, P, 8, 16, 16, 1, 0.9, P, None), (P, None, 8, 16, 16, 1, 0.9, P, None),
+                 (P, P, 8, 16, 16, 1, 0.9, None, None), (ODD, P, 8, 16, 16, 1, 0.9, P, None), (P, ODD, 8, 16, 16, 1, 0.9, P, None)):
+        refused('dt_rmsprop_rows_materialize', *args)
+
+
+def _rows_args(kind, P, n=10, D=16, fields=0, table='P', slot='P', stamp='P', rows='P', values='P', slots='P', n_slots=1024,
+               mark='P', state='P', dense_n=0, advance=0, slot_stride=16, stamp_stride=1):
+    v = lambda x: P if x == 'P' else x
+    head = [v(table), v(slot)] + ([v(stamp)] if kind == 'rmsprop' else []) + [v(rows), v(values), n, D, fields, v(slots), n_slots,
+                                                                                v(mark)]
+    hp = [1e-3, 0.9, 1e-7] if kind == 'rmsprop' else [1e-3, 1e-7]
+    tail = [v(state), None, None, None, dense_n, advance, slot_stride] + ([stamp_stride] if kind == 'rmsprop' else []) + [None]
+    return head + hp + tail
+
+
+def test_float64_references_reproduce_hand_computed_steps():
+    """two steps on one scalar, w0 = 1, gradients 0.5 then -2, Keras' defaults:
+    Adagrad: acc 0.1 -> 0.35 -> 4.35;  w -= 1e-3 * 0.5 / (sqrt(0.35) + 1e-7), then += 1e-3 * 2 / (sqrt(4.35) + 1e-7)
+    RMSprop: rms 0 -> 0.025 -> 0.4225; w -= 1e-3 * 0.5 / (sqrt(0.025) + 1e-7), then += 1e-3 * 2 / (sqrt(0.4225) + 1e-7)"""
+    t = lambda x: torch.tensor([x], dtype=torch.float64)
+    w, acc = R.adagrad_step(t(1.0), t(0.5), t(0.1))
+    assert abs(acc.item() - 0.35) < 1e-15 and abs(w.item() - 0.9991548458881286) < 1e-15
+    w, acc = R.adagrad_step(w, t(-2.0), acc)
+    assert abs(acc.item() - 4.35) < 1e-15 and abs(w.item() - 1.0001137724451223) < 1e-15
+    w, rms = R.rmsprop_step(t(1.0), t(0.5), t(0.0))
+    assert abs(rms.item() - 0.025) < 1e-15 and abs(w.item() - 0.9968377243398303) < 1e-15
+    w, rms = R.rmsprop_step(w, t(-2.0), rms)
+    assert abs(rms.item() - 0.4225) < 1e-15 and abs(w.item() - 0.9999146469433807) < 1e-15
+    # a sparse gradient: duplicates are summed before the update, skipped lookups (-1) contribute nothing
+    p0, a0 = torch.ones(3, 2, dtype=torch.float64), torch.full((3, 2), 0.1, dtype=torch.float64)
+    rows = torch.tensor([2, -1, 2, 0])
+    vals = torch.tensor([[0.25, 0.0], [9.0, 9.0], [0.25, 1.0], [-2.0, 0.0]], dtype=torch.float64)
+    p1, a1 = R.adagrad_rows_step(p0, a0, rows, vals)
+    assert a1.tolist() == [[4.1, 0.1], [0.1, 0.1], [0.35, 1.1]]
+    assert torch.equal(p1[1], p0[1]) and abs(p1[2, 0].item() - 0.9991548458881286) < 1e-15
+
+
+def test_stamped_rmsprop_equals_the_decay_every_row_form():
+    """6 steps on an 8-row table; rows 0-1 looked up at steps {1, 4}, rows 2-3 at {2}, rows 4-5 at every step, rows 6-7
+    never.  The lazy form moves the looked-up rows exactly like Keras' (every row's rms decays every step), and its rms
+    equals Keras' once the pending decays are applied."""
+    g = torch.Generator().manual_seed(0)
+    V, D = 8, 4
+    when = {0: {1, 4}, 1: {1, 4}, 2: {2}, 3: {2}, 4: set(range(1, 7)), 5: set(range(1, 7)), 6: set(), 7: set()}
+    p_d = p_s = torch.randn(V, D, generator=g, dtype=torch.float64)
+    rms_d = rms_s = torch.zeros(V, D, dtype=torch.float64)
+    stamp = torch.zeros(V, dtype=torch.int64)
+    for t in range(1, 7):
+        ids = [r for r in range(V) if t in when[r]]
+        rows = torch.tensor(ids + ids[:1] + [-1])                         # one duplicate, one skipped lookup
+        vals = torch.randn(len(rows), D, generator=g, dtype=torch.float64)
+        p_d, rms_d = R.rmsprop_rows_step(p_d, rms_d, rows, vals)
+        p_s, rms_s, stamp = R.rmsprop_rows_step_stamped(p_s, rms_s, stamp, t, rows, vals)
+        assert torch.equal(p_d, p_s), t
+        assert torch.equal(rms_d[ids], rms_s[ids]), t
+    assert stamp.tolist() == [4, 4, 2, 2, 6, 6, 0, 0]
+    assert not torch.equal(rms_d[:4], rms_s[:4])                          # decay is pending on the rows that sat steps out
+    rms_m, stamp_m = R.rmsprop_materialize(rms_s, stamp, 6)
+    assert torch.equal(rms_m, rms_d) and stamp_m.tolist() == [6] * 8
+    assert torch.equal(rms_m[2], 0.9 ** 0 * rms_s[2] * 0.9 * 0.9 * 0.9 * 0.9) and float(rms_m[6:].abs().max()) == 0.0
+
+
+def test_a_model_compiled_with_adagrad_builds_on_the_cpu():
+    from deeptables_amd import training as T
+    from deeptables_amd.models import ModelConfig, DeepModel
+    from deeptables_amd.models.metainfo import CategoricalColumn, ContinuousColumn
+    for name, cls in (('adagrad', T.Adagrad), ('RMSprop', T.RMSprop)):
+        conf = ModelConfig(nets=['linear', 'fm_nets', 'dnn_nets'], fixed_embedding_dim=True, embeddings_output_dim=8,
+                           optimizer=name)
+        dm = DeepModel('binary', 2, conf, [CategoricalColumn(f'C{i}', 20 + i, 8) for i in range(4)],
+                       [ContinuousColumn('input_continuous_all', ['a', 'b'])])
+        dm.build('cpu')
+        assert type(dm.optimizer) is cls
+        assert dm.model_desc.optimizer_info() == cls._name
+        assert f'optimizer: {cls._name}' in str(dm.model_desc)
+        tables = [t for layer in dm.optimizer.embedding_layers for t in layer.tables.values()]
+        assert tables and all(any(p is t for p in dm.optimizer.params) for t in tables)
