@@ -271,6 +271,14 @@ SIGNATURES = {
     'dt_fgcnn_infer_recomb': (_c_int, [_c_int, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int] + [_ptr] * 4 + [_ptr, _ptr, _ptr]),
     'dt_fgcnn_infer_tower': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_int]
                              + [_ptr] * 4 + [_ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
+    # epoch metrics on the device (csrc/metrics.hip): stable radix sort, exact AUC counts, accuracy / MSE / MAE sums
+    'dt_metric_sort_tile': (_c_int, []),
+    'dt_metric_sort_workspace_bytes': (_c_i64, [_c_i64]),
+    'dt_metric_sort_pairs': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr]),
+    'dt_metric_auc_workspace_bytes': (_c_i64, [_c_i64]),
+    'dt_metric_auc': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
+    'dt_metric_sums': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr]),
+    'dt_metric_argmax_hits': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -298,6 +306,8 @@ DT_AUTOINT_INFER_MAX_LAYERS, DT_AUTOINT_INFER_MAX_BLOCKS = 8, 256
 DT_FEED_CURSOR_WORDS = 528          # 16 (1 + 32 ticket groups), csrc/embedding.hip kFeedGroups
 DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 DT_DENSE_X3, DT_DENSE_BF16 = 1, 2      # dt_dense_x3_*: split-bf16 (fp32 bars forward) / plain bf16
+DT_METRIC_Y_LABELS, DT_METRIC_Y_ONEHOT = 0, 1
+DT_METRIC_SUMS_BLOCKS, DT_METRIC_SUMS_WORDS = 256, 771      # dt_metric_sums' out: 3 result words + 3 per block
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

@@ -470,9 +470,8 @@ class DeepModel:
                 self._fused_plan.check_dedupe()        # batches beyond 8192 rows: an election table that overflowed (fused.py)
             logs = {'loss': float(torch.cat([l.reshape(-1) for l in losses]).mean().item()) if losses else float('nan')}
             if probs:
-                yp, yt = torch.cat(probs).cpu().numpy(), torch.cat(ys).cpu().numpy()
-                for m in metrics:
-                    logs[training.metric_name(m)] = training.compute_metric(m, yt, yp, self.task)
+                # on the device when the HIP metric kernels cover every metric (training.epoch_metrics), else on the host
+                logs.update(training.epoch_metrics(metrics, torch.cat(ys), torch.cat(probs), self.task))
             if val is not None and (epoch + 1) % max(validation_freq, 1) == 0:
                 self._sync_sharded_tables()        # table rows owned by other ranks: fetch their current values
                 vlogs = self._evaluate_batches(val, batch_size, metrics)
@@ -525,9 +524,7 @@ class DeepModel:
                     probs.append(self._activate(logit))
         w = torch.tensor(weights, dtype=torch.float32, device=self.device)
         logs = {'loss': float((torch.stack(losses) * w).sum().item() / w.sum().item())}
-        yp, yt = torch.cat(probs).cpu().numpy(), data.y.cpu().numpy()
-        for m in metrics:
-            logs[training.metric_name(m)] = training.compute_metric(m, yt, yp, self.task)
+        logs.update(training.epoch_metrics(metrics, data.y, torch.cat(probs), self.task))
         return logs
 
     def predict(self, X, batch_size=128, verbose=0):

@@ -3,6 +3,7 @@
 (dense + row-sparse embedding update, HIP kernels), metrics, batching, and the data-parallel
 gradient exchange hook.  This is what `keras.Model.fit` does for the reference
 (deeptables/models/deepmodel.py:114-129, :319-346)."""
+import ctypes
 import math
 
 import numpy as np
@@ -822,6 +823,123 @@ def compute_metric(m, y_true, y_prob, task):
     if key in ('mae', 'mean_absolute_error'):
         return float(np.abs(y_prob.reshape(-1) - y_true.reshape(-1)).mean())
     raise ValueError(f'Unsupported metric: {name}')
+
+
+# ---------------------------------------------------------------------------------------------
+# metrics on the device (csrc/metrics.hip): the same values, computed where the outputs already are
+# ---------------------------------------------------------------------------------------------
+_AUC_KEYS = ('auc',)
+_ACC_KEYS = ('accuracy', 'acc')
+_MSE_KEYS = ('mse', 'mean_squared_error')
+_RMSE_KEYS = ('rmse', 'rootmeansquarederror', 'root_mean_squared_error')
+_MAE_KEYS = ('mae', 'mean_absolute_error')
+_metric_buffers = {}        # device -> {'ws': uint8 workspace (grown on demand), 'out': int64 result words}
+_OUT_AUC, _OUT_SUMS, _OUT_ARGMAX = 0, 8, 8 + _lib.DT_METRIC_SUMS_WORDS         # word offsets inside 'out'
+
+
+def _is_argmax_accuracy(y_prob, task):
+    return task == consts.TASK_MULTICLASS and y_prob.dim() == 2 and y_prob.shape[1] > 1
+
+
+def device_metrics_supported(metrics, y_true, y_prob, task):
+    """True when compute_metrics_device serves every one of `metrics`: float32 tensors on the GPU, metric names it knows
+    (by name only, a callable is the host's), shapes the kernels cover, and DT_AMD_DEVICE_METRICS not '0'."""
+    if os.environ.get('DT_AMD_DEVICE_METRICS', '1') == '0' or not metrics:
+        return False
+    if not (torch.is_tensor(y_true) and torch.is_tensor(y_prob) and y_true.is_cuda and y_prob.is_cuda and
+            y_true.dtype == torch.float32 and y_prob.dtype == torch.float32 and y_prob.numel() > 0):
+        return False
+    flat = y_true.numel() == y_prob.numel()
+    for m in metrics:
+        if not isinstance(m, str):
+            return False
+        key = m.lower()
+        if key in _ACC_KEYS:
+            if _is_argmax_accuracy(y_prob, task):
+                if not (y_true.numel() == y_prob.shape[0] or (y_true.dim() == 2 and y_true.shape == y_prob.shape)):
+                    return False
+            elif not flat:
+                return False
+        elif key in _AUC_KEYS:
+            if not flat or (y_prob.dim() == 2 and y_prob.shape[1] > 1):       # multiclass one-vs-rest AUC: the host's
+                return False
+        elif key in _MSE_KEYS + _RMSE_KEYS + _MAE_KEYS:
+            if not flat:
+                return False
+        else:
+            return False
+    return True
+
+
+def compute_metrics_device(metrics, y_true, y_prob, task):
+    """{name: value} for metrics that device_metrics_supported accepts, from device tensors: one radix sort (AUC) and one
+    reduction (accuracy / mse / rmse / mae) whatever the number of metrics, and one small device-to-host read.  The values
+    are compute_metric's: AUC is the exact ROC AUC U2 / (2 P N) in integers (nan where roc_auc_score raises: one class
+    only, or a NaN / Inf score); labels other than 0 / 1 send AUC to compute_metric on the host."""
+    if not device_metrics_supported(metrics, y_true, y_prob, task):
+        raise ValueError(f'compute_metrics_device does not cover {[metric_name(m) for m in metrics]} for these outputs')
+    h = lib()
+    y_true, y_prob = y_true.detach().contiguous(), y_prob.detach().contiguous()
+    n = y_prob.numel()
+    keys = [m.lower() for m in metrics]
+    want_auc = any(k in _AUC_KEYS for k in keys)
+    argmax_acc = _is_argmax_accuracy(y_prob, task) and any(k in _ACC_KEYS for k in keys)
+    want_sums = any(k in _MSE_KEYS + _RMSE_KEYS + _MAE_KEYS for k in keys) or \
+        (any(k in _ACC_KEYS for k in keys) and not argmax_acc)
+    buf = _metric_buffers.setdefault(y_prob.device, {})
+    if 'out' not in buf:
+        buf['out'] = torch.zeros(_OUT_ARGMAX + 1, dtype=torch.int64, device=y_prob.device)
+    out = buf['out']
+    word = lambda k: ctypes.c_void_p(out.data_ptr() + 8 * k)
+    with torch.cuda.device(y_prob.device):
+        if want_auc:
+            need = h.dt_metric_auc_workspace_bytes(n)
+            if need < 0:
+                check(int(need), 'dt_metric_auc_workspace_bytes')
+            if buf.get('ws') is None or buf['ws'].numel() < need:
+                buf['ws'] = None                                    # (release before the larger one is allocated)
+                buf['ws'] = torch.empty(int(need), dtype=torch.uint8, device=y_prob.device)
+            check(h.dt_metric_auc(ptr(y_prob), ptr(y_true), n, ptr(buf['ws']), word(_OUT_AUC), stream_ptr()), 'dt_metric_auc')
+        if want_sums:
+            check(h.dt_metric_sums(ptr(y_true), ptr(y_prob), n, word(_OUT_SUMS), stream_ptr()), 'dt_metric_sums')
+        if argmax_acc:
+            kind = _lib.DT_METRIC_Y_ONEHOT if y_true.dim() == 2 and y_true.shape == y_prob.shape else _lib.DT_METRIC_Y_LABELS
+            check(h.dt_metric_argmax_hits(ptr(y_prob), ptr(y_true), kind, y_prob.shape[0], y_prob.shape[1],
+                                          word(_OUT_ARGMAX), stream_ptr()), 'dt_metric_argmax_hits')
+        host = out.cpu()                                            # the one read: 6 KB
+    u2, pos, neg, nonfinite, bad_label = (int(v) for v in host[_OUT_AUC:_OUT_AUC + 5])
+    hits = int(host[_OUT_SUMS])
+    sq, ab = (float(v) for v in host[_OUT_SUMS + 1:_OUT_SUMS + 3].view(torch.float64))
+    res = {}
+    for m, key in zip(metrics, keys):
+        if key in _AUC_KEYS:
+            if bad_label > 0:
+                v = compute_metric(m, y_true.cpu().numpy(), y_prob.cpu().numpy(), task)
+            elif pos == 0 or neg == 0 or nonfinite > 0:
+                v = float('nan')
+            else:
+                v = u2 / (2 * pos * neg)
+        elif key in _ACC_KEYS:
+            v = int(host[_OUT_ARGMAX]) / y_prob.shape[0] if argmax_acc else hits / n
+        elif key in _MSE_KEYS:
+            v = sq / n
+        elif key in _RMSE_KEYS:
+            v = math.sqrt(sq / n)
+        else:
+            v = ab / n
+        res[metric_name(m)] = float(v)
+    return res
+
+
+def epoch_metrics(metrics, y_true, y_prob, task):
+    """{name: value} for an epoch's concatenated labels and outputs (tensors): on the device when
+    device_metrics_supported, else exactly the host path — copy both to the host and compute_metric each."""
+    if not metrics:
+        return {}
+    if device_metrics_supported(metrics, y_true, y_prob, task):
+        return compute_metrics_device(metrics, y_true, y_prob, task)
+    yt, yp = y_true.cpu().numpy(), y_prob.cpu().numpy()
+    return {metric_name(m): compute_metric(m, yt, yp, task) for m in metrics}
 
 
 class History:

@@ -1160,6 +1160,46 @@ int dt_fgcnn_infer_tower(const void* idx, int idx_kind, const float* table, cons
                          const int* heights, const int* pools, const int* new_filters, const void* workspace, float* logit_out,
                          float* out, int* oob_count, int flags, void* stream);
 
+/* Epoch metrics on the device (csrc/metrics.hip): what DeepModel.fit / evaluate compute at the end of every epoch from the
+ * concatenated outputs (deepmodel.py:471-475, 526-530; sklearn.metrics.roc_auc_score and numpy on the host before).  All
+ * results are integer or fixed-order sums: the same input gives the same bits.  No block of any launch waits for another
+ * block; what one needs from the others comes from an earlier launch.  Common rules: n == 0 is a no-op that looks at no
+ * pointer; n < 0 and n >= 2^31 are DT_ERR_INVALID_ARG, as are a null pointer, a null workspace, a float / uint32 array that
+ * is not 4-byte aligned, a 64-bit output that is not 8-byte aligned and a workspace that is not 16-byte aligned, all before
+ * the first launch.  The *_workspace_bytes queries return DT_ERR_INVALID_ARG for an n outside [0, 2^31).
+ *
+ * dt_metric_sort_pairs: stable least-significant-digit radix sort of (keys[i], vals[i]) by key, ascending: 8-bit digits, 4
+ *   passes, per pass a histogram per tile of dt_metric_sort_tile() elements, an exclusive scan over (digit-major, tile-minor)
+ *   counts and a stable scatter (13 launches: one memset + 4 x 3 kernels).  Pairs with equal keys keep their input order.
+ *   keys / vals are not written; keys_out / vals_out may be the inputs themselves (in place).  ws: dt_metric_sort_workspace_
+ *   bytes(n) bytes, contents irrelevant before and after.
+ * dt_metric_auc: exact binary ROC AUC counts for score [n] and label [n] (0 / 1).  out5 (int64, written by the call):
+ *     [0] U2 = sum over groups g of equal score of pos_g * (2 * negatives with a lower score + neg_g)
+ *     [1] P = labels equal to 1      [2] N = n - P      [3] scores that are NaN or +-Inf      [4] labels that are neither 0 nor 1
+ *   AUC = U2 / (2 P N): the probability that a positive outscores a negative, ties counting one half — roc_auc_score's
+ *   value.  -0.0 and +0.0 tie.  The caller returns nan for P == 0, N == 0 or out5[3] > 0 (roc_auc_score raises there) and
+ *   takes its host path when out5[4] > 0 (such labels are counted as negatives here).  19 launches: 2 memsets, the key
+ *   transform, the sort's 12, tile sums, their scan, the groups' compaction and one thread per group.
+ * dt_metric_sums: out (DT_METRIC_SUMS_WORDS 8-byte words; the first three are the result, the rest scratch):
+ *     [0] int64  count of (y_prob > 0.5) == (int64)y_true     [1] double sum (y_prob - y_true)^2     [2] double sum |y_prob - y_true|
+ *   differences, squares and sums in float64; per-block partials (at most DT_METRIC_SUMS_BLOCKS, a function of n alone), then
+ *   one block adds them in a fixed order: no float atomics.  2 launches.
+ * dt_metric_argmax_hits: out[0] (int64) = rows r of y_prob [n, C] whose argmax (the first maximum, as numpy.argmax) equals
+ *   the label: y_true [n] holding the class as a float (DT_METRIC_Y_LABELS) or the argmax of row r of a one-hot y_true [n, C]
+ *   (DT_METRIC_Y_ONEHOT).  C >= 2.  2 launches (memset + kernel).                                                       */
+#define DT_METRIC_Y_LABELS 0
+#define DT_METRIC_Y_ONEHOT 1
+#define DT_METRIC_SUMS_BLOCKS 256
+#define DT_METRIC_SUMS_WORDS 771
+int dt_metric_sort_tile(void);
+int64_t dt_metric_sort_workspace_bytes(int64_t n);
+int dt_metric_sort_pairs(const uint32_t* keys, const uint32_t* vals, int64_t n, uint32_t* keys_out, uint32_t* vals_out, void* ws,
+                         void* stream);
+int64_t dt_metric_auc_workspace_bytes(int64_t n);
+int dt_metric_auc(const float* score, const float* label, int64_t n, void* ws, int64_t* out5, void* stream);
+int dt_metric_sums(const float* y_true, const float* y_prob, int64_t n, void* out, void* stream);
+int dt_metric_argmax_hits(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
