@@ -279,6 +279,11 @@ SIGNATURES = {
     'dt_metric_auc': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
     'dt_metric_sums': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr]),
     'dt_metric_argmax_hits': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
+    # keras.regularizers.L1L2 (csrc/regularizer.hip): HOST arrays of device pointers / sizes / coefficients, one per tensor
+    'dt_reg_chunk': (_c_int, []),
+    'dt_reg_penalty_workspace_bytes': (_c_i64, [_c_int, _ptr]),
+    'dt_reg_penalty': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_reg_grad': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, regularizers
 
 # ---------------------------------------------------------------------------------------------
 # naming (keras.backend.get_uid look-alike)
@@ -179,8 +179,13 @@ def shape_of(x):
 # Layer base
 # ---------------------------------------------------------------------------------------------
 class Layer(nn.Module):
+    activity_regularizer = None     # a regularizers.Regularizer on the layer's outputs (Keras' Layer argument)
+    records_own_activity = False    # the layer's `call` hands the penalised tensors to the sink itself (the embeddings)
+    _activity_sink = None           # list the executing Model collects (tensor, (l1, l2)) in during ITS forward, else None
+
     def __init__(self, name=None, trainable=True, dtype=None, **kwargs):
         super().__init__()
+        self._weight_regularizers = []      # (parameter, regularizer) of add_weight(..., regularizer=)
         self._name = name or unique_name(_to_snake(self.__class__.__name__))
         self.built = False
         self.trainable = trainable
@@ -207,10 +212,24 @@ class Layer(nn.Module):
     def get_config(self):
         return {'name': self.name, 'trainable': self.trainable}
 
-    def add_weight(self, name=None, shape=None, initializer=None, trainable=True, dtype=None, **kwargs):
+    def add_weight(self, name=None, shape=None, initializer=None, trainable=True, dtype=None, regularizer=None, **kwargs):
         p = nn.Parameter(initialize(shape, initializer), requires_grad=bool(trainable))
         self.register_parameter(name.replace('.', '_'), p)
+        regularizer = regularizers.get(regularizer, f'{self.name}.add_weight({name!r}, regularizer')
+        if regularizers.active(regularizer) is not None:
+            self._weight_regularizers.append((p, regularizer))
         return p
+
+    def weight_penalties(self):
+        """[(tensor, (l1, l2))]: the layer's own regularised variables, each penalised whole at every step"""
+        return [(p, r.coefficients()) for p, r in self._weight_regularizers]
+
+    def record_activity(self, tensors):
+        """hand output tensors to the executing model's activity-penalty list (Keras 3: activity_regularizer(output) for every
+        output tensor, not divided by the batch size)"""
+        sink, reg = self._activity_sink, regularizers.active(self.activity_regularizer)
+        if sink is not None and reg is not None:
+            sink.extend((t, reg.coefficients()) for t in tensors)
 
     def _maybe_build(self, inputs):
         if not self.built:
@@ -234,7 +253,10 @@ class Layer(nn.Module):
 
     def forward(self, inputs, *args, **kwargs):
         self._maybe_build(inputs)
-        return self.call(inputs, *args, **kwargs)
+        out = self.call(inputs, *args, **kwargs)
+        if self._activity_sink is not None and not self.records_own_activity:
+            self.record_activity(_flatten(out))
+        return out
 
     # weights in Keras order/naming -> {name: ndarray}
     def get_weights_dict(self):
@@ -270,7 +292,8 @@ class Dense(Layer):
 
     @property
     def accepts_pending_norm(self):
-        return self.units == 1 and self.activation_name in (None, 'linear')
+        return self.units == 1 and self.activation_name in (None, 'linear') and \
+            regularizers.active(self.activity_regularizer) is None      # (the penalty needs this layer's output tensor)
 
     def __init__(self, units, activation=None, use_bias=True, kernel_initializer='glorot_uniform',
                  bias_initializer='zeros', kernel_regularizer=None, activity_regularizer=None, mfma_dtype=None, **kwargs):
@@ -283,9 +306,12 @@ class Dense(Layer):
         self.use_bias = use_bias
         self.kernel_initializer = kernel_initializer
         self.bias_initializer = bias_initializer
+        self.kernel_regularizer = regularizers.get(kernel_regularizer, 'kernel_regularizer')
+        self.activity_regularizer = regularizers.get(activity_regularizer, 'activity_regularizer')
 
     def build(self, input_shape):
-        self.kernel = self.add_weight('kernel', (input_shape[-1], self.units), self.kernel_initializer)
+        self.kernel = self.add_weight('kernel', (input_shape[-1], self.units), self.kernel_initializer,
+                                      regularizer=self.kernel_regularizer)
         self.bias = self.add_weight('bias', (self.units,), self.bias_initializer) if self.use_bias else None
         self.built = True
 
@@ -300,7 +326,7 @@ class Dense(Layer):
         if lk is not None and lk.lazy:
             # the flattened output of an interacting layer whose BatchNormalization is pending (Model.__init__'s peephole):
             # a linear Dense(1) takes it as it is (ops.autoint_head), anything else gets the normalised tensor
-            if self.units == 1 and act_name in (None, 'linear') and self.training and \
+            if self.accepts_pending_norm and act_name in (None, 'linear') and self.training and \
                     ops.autoint_head_supported(x, self.kernel, lk):
                 return ops.autoint_head(x, self.kernel, self.bias)
             x = ops.autoint_materialize(x)
@@ -322,7 +348,9 @@ class Dense(Layer):
 
     def get_config(self):
         c = super().get_config()
-        c.update(units=self.units, activation=self.activation_name, use_bias=self.use_bias)
+        c.update(units=self.units, activation=self.activation_name, use_bias=self.use_bias,
+                 kernel_regularizer=regularizers.serialize(self.kernel_regularizer),
+                 activity_regularizer=regularizers.serialize(self.activity_regularizer))
         return c
 
 
@@ -492,6 +520,14 @@ class BatchNormalization(Layer):
 # ---------------------------------------------------------------------------------------------
 # Model: executes the recorded graph
 # ---------------------------------------------------------------------------------------------
+def _fetch(env, x):
+    """the values of a node's (nested) inputs.  A module-level function on purpose: a recursive closure over `env` refers to
+    itself, and that cycle kept every activation of a forward alive until the cyclic collector happened to run."""
+    if isinstance(x, (list, tuple)):
+        return [_fetch(env, e) for e in x]
+    return env[id(x)]
+
+
 class Model(nn.Module):
     def __init__(self, inputs, outputs, name=None):
         super().__init__()
@@ -532,6 +568,7 @@ class Model(nn.Module):
         self._fused_relu, self._passthrough = set(), set()
         for node in order:
             if isinstance(node.layer, Dense) and node.layer.activation_name in (None, 'linear') \
+                    and regularizers.active(node.layer.activity_regularizer) is None \
                     and not isinstance(node.outputs, list) and id(node.outputs) not in outs:
                 cons = consumers.get(id(node.outputs), [])
                 if len(cons) == 1 and isinstance(cons[0].layer, Activation) and cons[0].layer.activation_name == 'relu':
@@ -555,6 +592,34 @@ class Model(nn.Module):
             if len(cons) == 1 and getattr(cons[0].layer, 'accepts_pending_norm', False) and \
                     not isinstance(cons[0].inputs, (list, tuple)) and id(cons[0]) not in self._fused_relu:
                 self._defer_norm.add(id(node))
+        self._activity = None               # [(tensor, (l1, l2))] of the last forward, until regularization_loss() takes it
+        self.collect_eval_activity = False  # evaluate sets it: activity penalties are collected in eval mode too
+
+    # -- regularizers (Keras: model.losses) ----------------------------------------------------------
+    def weight_penalties(self):
+        """[(tensor, (l1, l2))] over every layer of the model, nested ones (AFM's attention Dense) included"""
+        if getattr(self, '_weight_penalties', None) is None:
+            self._weight_penalties = [tc for m in self.modules() if isinstance(m, Layer) for tc in m.weight_penalties()]
+        return self._weight_penalties
+
+    def activity_layers(self):
+        if getattr(self, '_activity_layers', None) is None:
+            self._activity_layers = [m for m in self.modules() if isinstance(m, Layer)
+                                     and regularizers.active(m.activity_regularizer) is not None]
+        return self._activity_layers
+
+    def has_regularizers(self):
+        return bool(self.weight_penalties() or self.activity_layers())
+
+    def regularization_loss(self, weights=True, activity=True):
+        """The penalties of the forward that just ran as one float32 scalar (ONE ops.regularization_penalty call over every
+        regularised weight and every collected activation), or None when there is nothing to penalise.  Takes the collected
+        activations with it: nothing of the step stays referenced by the model."""
+        collected, self._activity = self._activity, None
+        terms = (list(self.weight_penalties()) if weights else []) + (list(collected or ()) if activity else [])
+        if not terms:
+            return None
+        return ops.regularization_penalty([t for t, _ in terms], [c for _, c in terms])
 
     @property
     def input(self):
@@ -580,11 +645,20 @@ class Model(nn.Module):
         if len(vals) != len(self.inputs):
             raise ValueError(f'Model expects {len(self.inputs)} inputs but got {len(vals)}.')
         env = {id(t): v for t, v in zip(self.inputs, vals)}
+        self._activity = None
+        act_layers = self.activity_layers() if (self.training or self.collect_eval_activity) else ()
+        sink = [] if act_layers else None
+        for layer in act_layers:
+            layer._activity_sink = sink
+        try:
+            return self._run_nodes(env, sink)
+        finally:
+            for layer in act_layers:
+                layer._activity_sink = None
 
+    def _run_nodes(self, env, sink):
         def fetch(x):
-            if isinstance(x, (list, tuple)):
-                return [fetch(e) for e in x]
-            return env[id(x)]
+            return _fetch(env, x)
 
         for node in self.nodes:
             if id(node) in self._passthrough:
@@ -600,6 +674,7 @@ class Model(nn.Module):
                     env[id(t)] = v
             else:
                 env[id(node.outputs)] = out
+        self._activity = sink
         res = [env[id(t)] for t in self.output_list]
         return res if isinstance(self.outputs_struct, (list, tuple)) else res[0]
 

@@ -624,6 +624,8 @@ class FusedDCN(FusedDeepFM):
 def make_fused_plan(dm):
     if not fused_enabled() or dm.model is None:
         return None
+    if dm.model.has_regularizers():
+        return None         # the fused DeepFM / DCN steps have no penalty term: a regularised model trains on the layer path
     if FusedDeepFM.eligible(dm):
         return FusedDeepFM(dm)
     if FusedDCN.eligible(dm):

@@ -185,7 +185,9 @@ class DeepModel:
             output_dims = [column.embeddings_output_dim for column in categorical_columns]
             embeddings = MultiColumnEmbedding(input_dims, output_dims, embedding_dropout,
                                               name=consts.LAYER_PREFIX_EMBEDDING + 'categorical_vars_all',
-                                              embeddings_initializer=self.config.embeddings_initializer)(input_layer)
+                                              embeddings_initializer=self.config.embeddings_initializer,
+                                              embeddings_regularizer=self.config.embeddings_regularizer,
+                                              activity_regularizer=self.config.embeddings_activity_regularizer)(input_layer)
             self.model_desc.set_embeddings(input_dims, output_dims, embedding_dropout)
             embeddings = list(embeddings)
         else:
@@ -194,8 +196,9 @@ class DeepModel:
             embeddings.append(VarLenColumnEmbedding(
                 emb_vocab_size=column.vocabulary_size, emb_output_dim=column.embeddings_output_dim,
                 dropout_rate=embedding_dropout, name=consts.LAYER_PREFIX_EMBEDDING + column.name,
-                embeddings_initializer=self.config.embeddings_initializer, embeddings_regularizer=None,
-                activity_regularizer=None)(var_len_inputs[column.name]))
+                embeddings_initializer=self.config.embeddings_initializer,
+                embeddings_regularizer=self.config.embeddings_regularizer,
+                activity_regularizer=self.config.embeddings_activity_regularizer)(var_len_inputs[column.name]))
         return embeddings
 
     def _build_denses(self, continuous_columns, continuous_inputs, dense_dropout, use_batchnormalization=False):
@@ -306,6 +309,11 @@ class DeepModel:
         logit = self.model(inputs)
         loss = self._loss(logit, y) if sample_weight is None else \
             training.weighted_loss(self.loss_name, logit, y, sample_weight)
+        # Keras: the total loss is the (weighted) data loss plus every regularizer's penalty (csrc/regularizer.hip); the
+        # model's list of this forward's penalised activations is taken here, so nothing of the step outlives it
+        penalty = self.model.regularization_loss() if self.model.has_regularizers() else None
+        if penalty is not None:
+            loss = loss + penalty
         if loss.dim() == 0 and loss.dtype == torch.float32:
             loss.backward(training.unit_grad(loss.device))      # no ones-fill launch (and the BCE skips the multiply)
         else:
@@ -508,22 +516,35 @@ class DeepModel:
     def _evaluate_batches(self, data, batch_size, metrics):
         self.model.eval()
         losses, weights, probs = [], [], []
-        plan = self.inference_plan()
-        with torch.no_grad():
-            if plan is not None:
-                # one launch per batch into one device buffer; the loss of every batch from its slice of the logits
-                def each(logit, prob, yb):
-                    losses.append(self._loss(logit, yb))
-                    weights.append(yb.shape[0])
-                probs.append(plan.run_batches(data, batch_size, each=each)[1])
-            else:
-                for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
-                    logit = self.model(ins)
-                    losses.append(self._loss(logit, yb))
-                    weights.append(yb.shape[0])
-                    probs.append(self._activate(logit))
+        # Keras' evaluate loss carries the penalties: the weight penalty is constant over the evaluation and added once below;
+        # activity penalties need the layers' outputs, so such a model evaluates on the layer path (predict keeps its plan)
+        with_activity = bool(self.model.activity_layers())
+        plan = None if with_activity else self.inference_plan()
+        self.model.collect_eval_activity = with_activity
+        try:
+            with torch.no_grad():
+                if plan is not None:
+                    # one launch per batch into one device buffer; the loss of every batch from its slice of the logits
+                    def each(logit, prob, yb):
+                        losses.append(self._loss(logit, yb))
+                        weights.append(yb.shape[0])
+                    probs.append(plan.run_batches(data, batch_size, each=each)[1])
+                else:
+                    for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
+                        logit = self.model(ins)
+                        loss = self._loss(logit, yb)
+                        if with_activity:
+                            loss = loss + self.model.regularization_loss(weights=False)
+                        losses.append(loss)
+                        weights.append(yb.shape[0])
+                        probs.append(self._activate(logit))
+                weight_penalty = self.model.regularization_loss(activity=False) if self.model.has_regularizers() else None
+        finally:
+            self.model.collect_eval_activity = False
         w = torch.tensor(weights, dtype=torch.float32, device=self.device)
         logs = {'loss': float((torch.stack(losses) * w).sum().item() / w.sum().item())}
+        if weight_penalty is not None:
+            logs['loss'] += float(weight_penalty.item())
         logs.update(training.epoch_metrics(metrics, data.y, torch.cat(probs), self.task))
         return logs
 

@@ -326,6 +326,7 @@ def dnn(x, params, cellname='dnn'):
     cells, activation, init = _tower_cells(params)
     for i, (units, rate, use_bn) in enumerate(cells, start=1):
         x = Dense(units, use_bias=not use_bn, name=f'{cellname}_dense_{i}', kernel_initializer=init,
+                  kernel_regularizer=params.get('kernel_regularizer'), activity_regularizer=params.get('activity_regularizer'),
                   mfma_dtype=params.get('dense_mfma_dtype'))(x)
         if use_bn:
             x = BatchNormalization(name=f'{cellname}_bn_{i}')(x)
@@ -340,6 +341,7 @@ def custom_dnn_D_A_D_B(x, params, cellname='dnn_D_A_D_B'):
     cells, activation, init = _tower_cells(params)
     for i, (units, rate, use_bn) in enumerate(cells, start=1):
         x = Dense(units, activation=activation, kernel_initializer=init, name=f'{cellname}_dense_{i}',
+                  kernel_regularizer=params.get('kernel_regularizer'), activity_regularizer=params.get('activity_regularizer'),
                   mfma_dtype=params.get('dense_mfma_dtype'))(x)
         if rate > 0:
             x = Dropout(rate, name=f'{cellname}_dropout_{i}')(x)

@@ -12,7 +12,7 @@ import os
 import torch
 from torch import nn
 
-from .. import ops
+from .. import ops, regularizers
 from ..functional import (Layer, Dense, Dropout, BatchNormalization, Activation, Concatenate, Flatten,  # noqa: F401
                           Input, Lambda, Add, SpatialDropout1D, ReduceSum, initialize, get_activation)
 from ..utils import consts  # noqa: F401
@@ -351,6 +351,8 @@ class MultiColumnEmbedding(Layer):
     names `embeddings_{i}`.  `call` returns the reference's list of F tensors [B,1,D_f]; they are
     views of one [B,F,D] block so the graph's three Concatenate layers over them cost nothing."""
 
+    records_own_activity = True         # `call` records the packed block (or the dropped-out outputs), not F views
+
     def __init__(self, input_dims, output_dims, dropout_rate=0., embeddings_initializer='uniform',
                  embeddings_regularizer=None, activity_regularizer=None, embeddings_constraint=None,
                  mask_zero=False, **kwargs):
@@ -368,6 +370,8 @@ class MultiColumnEmbedding(Layer):
         self.dropout_rate = dropout_rate
         self.embeddings_initializer = embeddings_initializer
         self.mask_zero = mask_zero
+        self.embeddings_regularizer = regularizers.get(embeddings_regularizer, 'embeddings_regularizer')
+        self.activity_regularizer = regularizers.get(activity_regularizer, 'embeddings_activity_regularizer')
         self.sparse_grads = {}      # group key -> list[SparseRowGrad] (filled by backward)
         self.check_oob = False
 
@@ -389,6 +393,15 @@ class MultiColumnEmbedding(Layer):
             for v in vocabs:
                 t[o:o + v] = initialize((v, D), self.embeddings_initializer)
                 o += v
+            if regularizers.active(self.embeddings_regularizer) is not None and rows * D > DENSE_GRAD_MAX_ELEMS:
+                # Keras' weight penalty covers the whole variable: a dense gradient and a dense optimizer sweep over the table
+                # at every step.  Not done quietly, and no lookup-only variant is invented either.
+                raise ValueError(
+                    f'embeddings_regularizer on the packed [{rows}, {D}] embedding table of {self.name!r}: {rows * D} elements '
+                    f'are above DENSE_GRAD_MAX_ELEMS = {DENSE_GRAD_MAX_ELEMS}, the size up to which a table gets a dense '
+                    f'gradient; beyond it the gradient stays row-sparse and a weight penalty over every row would force a '
+                    f'dense sweep of the table each step.  embeddings_activity_regularizer penalises the looked-up rows '
+                    f'only and stays row-sparse.')
             self.tables[f'd{D}'] = nn.Parameter(t)
             offs = np.concatenate([[0], np.cumsum(vocabs)[:-1]]).astype(np.int64)
             self.register_buffer(f'row_offset_d{D}', torch.from_numpy(offs), persistent=False)
@@ -422,6 +435,13 @@ class MultiColumnEmbedding(Layer):
     def add_sparse_grad(self, key, grad):
         self.sparse_grads.setdefault(key, []).append(grad)
 
+    def weight_penalties(self):
+        """each packed table whole: the union of its columns' `embeddings_i` variables, the same sum"""
+        reg = regularizers.active(self.embeddings_regularizer)
+        if reg is None or not hasattr(self, 'tables'):
+            return []
+        return [(self.tables[f'd{D}'], reg.coefficients()) for D, _cols in self.groups]
+
     def uses_dense_grad(self, D):
         return self.tables[f'd{D}'].numel() <= DENSE_GRAD_MAX_ELEMS
 
@@ -454,10 +474,13 @@ class MultiColumnEmbedding(Layer):
         out = [None] * len(self.input_dims)
         for D, cols in self.groups:
             emb, _rows = self.lookup_group(inputs, D, cols)       # [B, len(cols), D]
+            if not self.dropout_rate > 0:
+                self.record_activity([emb])        # the group's outputs in one piece: the same sum as its columns' views
             for k, i in enumerate(cols):
                 v = emb[:, k:k + 1, :]
                 if self.dropout_rate > 0:
                     v = self.dropouts[i](v)
+                    self.record_activity([v])      # Keras penalises the layer's outputs: after their SpatialDropout1D
                 elif len(self.groups) == 1:
                     v._dt_pack = (emb, k)      # lets Concatenate return the packed block for free
                 out[i] = v
@@ -466,7 +489,9 @@ class MultiColumnEmbedding(Layer):
     def get_config(self):
         c = super().get_config()
         c.update(input_dims=self.input_dims, output_dims=self.output_dims, dropout_rate=self.dropout_rate,
-                 embeddings_initializer=self.embeddings_initializer, mask_zero=self.mask_zero)
+                 embeddings_initializer=self.embeddings_initializer, mask_zero=self.mask_zero,
+                 embeddings_regularizer=regularizers.serialize(self.embeddings_regularizer),
+                 activity_regularizer=regularizers.serialize(self.activity_regularizer))
         return c
 
 
@@ -492,7 +517,7 @@ class AFM(Layer):
         self.hidden_factor = params.get('hidden_factor', 16)
         self.dropout_rate = params.get('dropout_rate', 0)
         self.activation_function = params.get('activation', 'relu')
-        self.kernel_regularizer = params.get('kernel_regularizer', None)
+        self.kernel_regularizer = regularizers.get(params.get('kernel_regularizer', None), "afm_params['kernel_regularizer']")
         super().__init__(**kwargs)
 
     def build(self, input_shape):
@@ -500,7 +525,8 @@ class AFM(Layer):
             raise ValueError('A `AttentionalFM` layer should be called on a list of at least 2 inputs')
         D = int(input_shape[0][-1])
         self.dense_attention = Dense(self.hidden_factor, activation=self.activation_function,
-                                     kernel_initializer='glorot_normal', name='dense_afm_attention')
+                                     kernel_initializer='glorot_normal', kernel_regularizer=self.kernel_regularizer,
+                                     name='dense_afm_attention')
         self.dense_attention.build((None, D))
         self.dense_out = Dense(1, use_bias=False, name=f'{self.name}_dense_out')
         self.dense_out.build((None, D))
@@ -695,14 +721,15 @@ class FGCNN(Layer):
 class VarLenColumnEmbedding(Layer):
     """One table shared by the L positions of a multi-valued column: [B,L] ids -> [B,1,L*D].
     The gather is the same HIP kernel as MultiColumnEmbedding with every 'field' pointing at one table."""
+    records_own_activity = True         # `call` records the inner lookup, not the reshaped output
 
     def __init__(self, emb_vocab_size, emb_output_dim, embeddings_initializer='uniform',
                  embeddings_regularizer=None, activity_regularizer=None, dropout_rate=0., **kwargs):
         self.emb_vocab_size = int(emb_vocab_size)
         self.emb_output_dim = int(emb_output_dim)
         self.embeddings_initializer = embeddings_initializer
-        self.embeddings_regularizer = embeddings_regularizer
-        self.activity_regularizer = activity_regularizer
+        self.embeddings_regularizer = regularizers.get(embeddings_regularizer, 'embeddings_regularizer')
+        self.activity_regularizer = regularizers.get(activity_regularizer, 'embeddings_activity_regularizer')
         self.dropout_rate = dropout_rate
         super().__init__(**kwargs)
         self.dropout = None
@@ -714,6 +741,8 @@ class VarLenColumnEmbedding(Layer):
         L = int(input_shape[1])
         self.embeddings = nn.Parameter(initialize((self.emb_vocab_size, self.emb_output_dim),
                                                   self.embeddings_initializer))
+        if regularizers.active(self.embeddings_regularizer) is not None:
+            self._weight_regularizers.append((self.embeddings, self.embeddings_regularizer))
         self.register_buffer('row_offset', torch.zeros(L, dtype=torch.int64))
         self.register_buffer('vocab', torch.full((L,), self.emb_vocab_size, dtype=torch.int32))
         self.dropout = SpatialDropout1D(self.dropout_rate, name='var_len_emb_dropout') \
@@ -722,6 +751,7 @@ class VarLenColumnEmbedding(Layer):
 
     def call(self, inputs, **kwargs):
         out, _rows = ops.embedding_lookup(inputs, self.embeddings, self.row_offset, self.vocab, dense_grad=True)
+        self.record_activity([out])        # the inner Embedding's [B, L, D] output, before the reshape and the dropout
         out = out.reshape(out.shape[0], 1, -1)
         return self.dropout(out) if self.dropout is not None else out
 
@@ -731,7 +761,8 @@ class VarLenColumnEmbedding(Layer):
     def get_config(self):
         c = super().get_config()
         c.update(dropout_rate=self.dropout_rate, embeddings_initializer=self.embeddings_initializer,
-                 embeddings_regularizer=self.embeddings_regularizer, emb_vocab_size=self.emb_vocab_size,
+                 embeddings_regularizer=regularizers.serialize(self.embeddings_regularizer),
+                 activity_regularizer=regularizers.serialize(self.activity_regularizer), emb_vocab_size=self.emb_vocab_size,
                  emb_output_dim=self.emb_output_dim)
         return c
 

@@ -1283,3 +1283,93 @@ class _FieldScale(torch.autograd.Function):
 def field_scale(x, a):
     """x [B,F,D] * a [B,F,1|None]."""
     return _FieldScale.apply(x, a.reshape(x.shape[0], x.shape[1]))
+
+
+# ------------------------------------------------------------------------------------------------
+# keras.regularizers.L1L2 — every regularised weight and activation of a step in one Function (csrc/regularizer.hip)
+# ------------------------------------------------------------------------------------------------
+def _reg_arrays(xs, coeffs, ctype):
+    import ctypes
+    n = len(xs)
+    return ((ctypes.c_void_p * n)(*[x.data_ptr() for x in xs]), (ctypes.c_int64 * n)(*[x.numel() for x in xs]),
+            (ctype * n)(*[float(c[0]) for c in coeffs]), (ctype * n)(*[float(c[1]) for c in coeffs]))
+
+
+class _RegPenalty(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, coeffs, *tensors):
+        import ctypes
+        require_cuda(*tensors)
+        xs = [_f32c(t) for t in tensors]
+        dev = xs[0].device
+        px, pn, l1, l2 = _reg_arrays(xs, coeffs, ctypes.c_double)
+        nbytes = lib().dt_reg_penalty_workspace_bytes(len(xs), pn)
+        if nbytes < 0:
+            check(int(nbytes), 'dt_reg_penalty_workspace_bytes')
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(2, dtype=torch.float64, device=dev)          # [0] the double total, [1] its float32 rounding
+        total_f32 = out.view(torch.float32)[2:3]
+        check(lib().dt_reg_penalty(len(xs), px, pn, l1, l2, ptr(ws), ptr(out), ptr(total_f32), stream_ptr()), 'dt_reg_penalty')
+        ctx.coeffs = [(float(a), float(b)) for a, b in coeffs]
+        ctx.save_for_backward(*xs)
+        return total_f32.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes
+        xs = ctx.saved_tensors
+        go = _f32c(g).reshape(1)
+        need = [i for i in range(len(xs)) if ctx.needs_input_grad[i + 1]]
+        grads = [None] * len(xs)
+        if need:
+            # one flat buffer; every view starts at its input's offset inside a 16-byte line, so aligned inputs get float4
+            offs, cur = [], 0
+            for i in need:
+                cur = (cur + 3) // 4 * 4 + (xs[i].data_ptr() % 16) // 4
+                offs.append(cur)
+                cur += xs[i].numel()
+            flat = torch.empty(max(cur, 1), dtype=torch.float32, device=go.device)
+            outs = [flat[o:o + xs[i].numel()] for i, o in zip(need, offs)]
+            px, pn, l1, l2 = _reg_arrays([xs[i] for i in need], [ctx.coeffs[i] for i in need], ctypes.c_float)
+            po = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+            check(lib().dt_reg_grad(len(outs), px, po, pn, l1, l2, ptr(go), 0, stream_ptr()), 'dt_reg_grad')
+            for i, o in zip(need, outs):
+                grads[i] = o.view(xs[i].shape)
+        return (None, *grads)
+
+
+def regularization_penalty(tensors, coeffs):
+    """sum over i of l1_i * sum|t_i| + l2_i * sum t_i^2 as ONE float32 scalar: every regularised tensor of a step, leaf weights
+    and activations alike, goes through one call — two launches forward (float64 partial sums in a fixed order, then their
+    fixed-order total), one launch backward (go * (l1 sign(t) + 2 l2 t) for all tensors into one flat buffer whose views are
+    the gradients).  coeffs: one (l1, l2) per tensor."""
+    tensors, coeffs = list(tensors), [tuple(c) for c in coeffs]
+    if len(tensors) != len(coeffs) or any(len(c) != 2 for c in coeffs):
+        raise ValueError('regularization_penalty: one (l1, l2) pair per tensor')
+    if not tensors:
+        raise ValueError('regularization_penalty: no tensors')
+    return _RegPenalty.apply(coeffs, *tensors)
+
+
+def reg_penalty_raw(tensors, coeffs):
+    """(float64 total, float32 total) device tensors of dt_reg_penalty for contiguous float32 tensors, no autograd"""
+    import ctypes
+    require_cuda(*tensors)
+    px, pn, l1, l2 = _reg_arrays(tensors, coeffs, ctypes.c_double)
+    nbytes = lib().dt_reg_penalty_workspace_bytes(len(tensors), pn)
+    dev = tensors[0].device
+    ws = torch.empty(max(int(nbytes), 8) // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(2, dtype=torch.float64, device=dev)
+    f32 = out.view(torch.float32)[2:3]
+    check(lib().dt_reg_penalty(len(tensors), px, pn, l1, l2, ptr(ws), ptr(out), ptr(f32), stream_ptr()), 'dt_reg_penalty')
+    return out[0], f32[0]
+
+
+def reg_grad_raw(tensors, outs, coeffs, go, accumulate=False):
+    """dt_reg_grad into caller-owned `outs` (written, or added to with accumulate=True); go: a device float32 scalar"""
+    import ctypes
+    require_cuda(go, *tensors, *outs)
+    px, pn, l1, l2 = _reg_arrays(tensors, coeffs, ctypes.c_float)
+    po = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
+    check(lib().dt_reg_grad(len(tensors), px, po, pn, l1, l2, ptr(go), 1 if accumulate else 0, stream_ptr()), 'dt_reg_grad')
+    return outs

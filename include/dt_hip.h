@@ -1200,6 +1200,32 @@ int dt_metric_auc(const float* score, const float* label, int64_t n, void* ws, i
 int dt_metric_sums(const float* y_true, const float* y_prob, int64_t n, void* out, void* stream);
 int dt_metric_argmax_hits(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int64_t* out, void* stream);
 
+/* keras.regularizers.L1L2 on the device (csrc/regularizer.hip): penalty and gradient of `count` float32 tensors per call, tensor
+ * t being (x[t], n[t] elements, l1[t], l2[t]).  x / out / n / l1 / l2 are HOST arrays (of device pointers, sizes and
+ * coefficients); the descriptors travel as kernel arguments, 32 tensors per launch.  Common rules: a member with n == 0
+ * contributes nothing and its pointer is not looked at; count == 0 is valid; a negative count, a negative n (or one of 2^40
+ * and more), a null pointer with n > 0, a null descriptor array, a null or misaligned output / workspace are
+ * DT_ERR_INVALID_ARG before the first launch.  No alignment beyond that of a float is asked of x / out.  NaN / Inf propagate.
+ *
+ * dt_reg_penalty: total[0] (double) = sum over t of l1[t] * sum|x| + l2[t] * sum x^2, total_f32[0] its float32 rounding.  A
+ *   coefficient equal to zero adds no term (Keras' `if self.l1:`).  Launch 1 (one per 32 tensors): a block sums one chunk of
+ *   dt_reg_chunk() elements in float64 in a fixed order and writes one double into `workspace`
+ *   (dt_reg_penalty_workspace_bytes(count, n) bytes, 8-byte aligned, contents irrelevant before and after); launch 2: one
+ *   block adds the partials in index order with a fixed tree.  No float atomics, no block waits for another: the same
+ *   input gives the same bits, and an unaligned view gives the bits of an aligned copy.
+ * dt_reg_grad: out[t][i] = go * (l1 * sign(x) + 2 * l2 * x) for every element (one launch per 32 tensors), in this fp32 order
+ *   with no contraction: t = fl(fl(2 l2) x); u = +l1, -l1 or 0 (sign(+-0) = 0); r = fl(u + t); fl(go r).  accumulate != 0:
+ *   out[t][i] = fl(out[t][i] + that) instead.  go: DEVICE pointer to the upstream scalar, read by the kernel (no host
+ *   synchronisation; replays inside a captured graph).  float4 where x[t] and out[t] reach 16-byte alignment at the same
+ *   element, scalars before that, for the tail and otherwise: every route gives the same bits.  out[t] must not overlap
+ *   another member's out or any x except in place (out[t] == x[t]).                                                     */
+int dt_reg_chunk(void);
+int64_t dt_reg_penalty_workspace_bytes(int count, const int64_t* n);
+int dt_reg_penalty(int count, const float* const* x, const int64_t* n, const double* l1, const double* l2, void* workspace,
+                   double* total, float* total_f32, void* stream);
+int dt_reg_grad(int count, const float* const* x, float* const* out, const int64_t* n, const float* l1, const float* l2,
+                const float* go, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
