@@ -40,7 +40,7 @@ SIGNATURES = {
     'dt_embed_fm_linear_bwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int,
                                         _ptr, _ptr]),
     'dt_bn_workspace_bytes': (_c_i64, [_c_int, _c_int]),
-    'dt_bn_train_fwd': (_c_int, [_ptr, _c_int, _c_int, _ptr, _ptr, _c_f32, _c_f32, _ptr, _ptr, _ptr,
+    'dt_bn_train_fwd': (_c_int, [_ptr, _c_int, _c_int, _ptr, _ptr, _c_f32, _c_f32, _c_f32, _ptr, _ptr, _ptr,
                                  _ptr, _ptr, _ptr, _ptr]),
     'dt_bn_infer_fwd': (_c_int, [_ptr, _c_int, _c_int, _ptr, _ptr, _c_f32, _ptr, _ptr, _ptr, _ptr]),
     'dt_bn_train_bwd': (_c_int, [_ptr, _ptr, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,

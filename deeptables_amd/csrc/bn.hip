@@ -8,9 +8,18 @@
 //
 // HBM-bound column reduction: a block owns a chunk of rows and all C columns; threads are laid
 // out (row-lane, column) with the column index fastest so every wave reads contiguous row
-// segments.  Per column the block accumulates SHIFTED sums (shift = first row of the chunk) so
-// the M2 it reports does not suffer E[x^2]-E[x]^2 cancellation; chunk results are merged with
-// Chan's parallel formula in a one-thread-per-column finalize kernel.
+// segments.  Per column the block accumulates SHIFTED sums so the M2 it reports does not suffer
+// E[x^2]-E[x]^2 cancellation; chunk results are merged with Chan's parallel formula in a
+// one-wave-per-column finalize kernel.
+//
+// The shift K of a chunk is the median of its first, middle and last row: a lone outlier is never
+// the shift, so the other rows are not summed as x - outlier.  A chunk reports its mean twice: as
+// K + s/n, and relative to the column's reference K0 (the median of rows 0, N/2 and N-1) as
+// (K - K0) + s/n.  Chan's delta^2 term is taken between the K0-relative means, which carry the
+// spread of the column and not the rounding of its magnitude (at mean 1e4, spread 1 the plain
+// means are rounded to 1e-3 and their deltas put 1e-4 into the variance); the batch mean itself is
+// merged from the plain ones, which are the accurate ones where the mean is small against the
+// spread.
 #include <initializer_list>
 #include "common.h"
 
@@ -31,7 +40,15 @@ static int bn_col_width(int C) {  // power of two in [1,256]
     return w;
 }
 
-// partial[chunk][0..2][C] = {count, mean, M2}
+__device__ __forceinline__ float bn_med3(float a, float b, float c) {
+    return fmaxf(fminf(a, b), fminf(fmaxf(a, b), c));
+}
+
+// partial[chunk][0..2][C] = {mean, mean - K0, M2}; the count follows from N and rows_per_chunk (bn_chunk_rows)
+__device__ __forceinline__ int bn_chunk_rows(int N, int rows_per_chunk, int chunk) {
+    return max(min(N, (chunk + 1) * rows_per_chunk) - chunk * rows_per_chunk, 0);
+}
+
 __global__ __launch_bounds__(kBnThreads) void k_bn_stats(const float* __restrict__ x, int N, int C,
                                                          int CW, int rows_per_chunk,
                                                          float* __restrict__ partial) {
@@ -46,7 +63,7 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats(const float* __restrict
         const int col = c0 + tx;
         float s = 0.f, q = 0.f, K = 0.f;
         if (col < C && r0 < r1) {
-            K = x[(int64_t)r0 * C + col];
+            K = bn_med3(x[(int64_t)r0 * C + col], x[(int64_t)((r0 + r1 - 1) >> 1) * C + col], x[(int64_t)(r1 - 1) * C + col]);
             for (int r = r0 + ty; r < r1; r += RS) {
                 const float d = x[(int64_t)r * C + col] - K;
                 s += d;
@@ -61,15 +78,17 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats(const float* __restrict
                 s += ps[k * CW + tx];
                 q += pq[k * CW + tx];
             }
-            const float n = (float)max(r1 - r0, 0);
-            float mean = 0.f, m2 = 0.f;
+            const float n = (float)bn_chunk_rows(N, rows_per_chunk, blockIdx.x);
+            float mean = 0.f, rel = 0.f, m2 = 0.f;
             if (n > 0.f) {
+                const float K0 = bn_med3(x[col], x[(int64_t)(N >> 1) * C + col], x[(int64_t)(N - 1) * C + col]);
                 mean = K + s / n;
+                rel = (K - K0) + s / n;
                 m2 = fmaxf(q - s * s / n, 0.f);
             }
             float* p = partial + (int64_t)blockIdx.x * 3 * C;
-            p[col] = n;
-            p[C + col] = mean;
+            p[col] = mean;
+            p[C + col] = rel;
             p[2 * C + col] = m2;
         }
         __syncthreads();
@@ -77,8 +96,8 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats(const float* __restrict
 }
 
 // one wavefront per column: lanes stride over the chunk partials, then a Chan-merge butterfly
-__global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ partial, int chunks,
-                                                     int C, float eps, float momentum,
+__global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ partial, int chunks, int N,
+                                                     int rows_per_chunk, int C, float eps, float momentum, float decay,
                                                      float* __restrict__ moving_mean,
                                                      float* __restrict__ moving_var,
                                                      float* __restrict__ save_mean,
@@ -86,28 +105,32 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ p
     const int col = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (col >= C) return;  // wave-uniform
     const int lane = threadIdx.x & 63;
-    float n = 0.f, mean = 0.f, m2 = 0.f;
+    float n = 0.f, mean = 0.f, rel = 0.f, m2 = 0.f;  // rel: the mean relative to K0, for the deltas
     for (int k = lane; k < chunks; k += 64) {
-        const float* p = partial + (int64_t)k * 3 * C;
-        const float nb = p[col];
+        const float nb = (float)bn_chunk_rows(N, rows_per_chunk, k);
         if (nb <= 0.f) continue;
-        const float mb = p[C + col], m2b = p[2 * C + col];
+        const float* p = partial + (int64_t)k * 3 * C;
+        const float mb = p[col], rb = p[C + col], m2b = p[2 * C + col];
         const float nt = n + nb;
-        const float delta = mb - mean;
-        mean += delta * (nb / nt);
+        const float delta = rb - rel;
+        mean += (mb - mean) * (nb / nt);
+        rel += delta * (nb / nt);
         m2 += m2b + delta * delta * (n * nb / nt);
         n = nt;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-        const float nb = __shfl_xor(n, o, 64), mb = __shfl_xor(mean, o, 64), m2b = __shfl_xor(m2, o, 64);
+        const float nb = __shfl_xor(n, o, 64), mb = __shfl_xor(mean, o, 64), rb = __shfl_xor(rel, o, 64),
+                    m2b = __shfl_xor(m2, o, 64);
         const float nt = n + nb;
         if (nt > 0.f) {
-            const float delta = mb - mean;
-            // symmetric form so both partners compute the same merged value
-            const float new_mean = (n * mean + nb * mb) / nt;
+            const float delta = rb - rel;
+            // rel and m2 in a symmetric form, so both partners compute the same merged value; the mean in the delta
+            // form, exact for a constant column (partners may differ in its last bit: lane 0's chain is the one written)
+            const float new_rel = (n * rel + nb * rb) / nt;
             m2 = m2 + m2b + delta * delta * (n * nb / nt);
-            mean = new_mean;
+            mean += (mb - mean) * (nb / nt);
+            rel = new_rel;
         }
         n = nt;
     }
@@ -115,8 +138,9 @@ __global__ __launch_bounds__(256) void k_bn_finalize(const float* __restrict__ p
     const float var = n > 0.f ? m2 / n : 0.f;
     save_mean[col] = mean;
     save_rstd[col] = 1.0f / sqrtf(var + eps);
-    if (moving_mean) moving_mean[col] = moving_mean[col] * momentum + mean * (1.f - momentum);
-    if (moving_var) moving_var[col] = moving_var[col] * momentum + var * (1.f - momentum);
+    // decay is 1 - momentum as Keras rounds it, from the double: 1.f - 0.99f is 9.5e-7 off 0.01f
+    if (moving_mean) moving_mean[col] = moving_mean[col] * momentum + mean * decay;
+    if (moving_var) moving_var[col] = moving_var[col] * momentum + var * decay;
 }
 
 // y = (x-mean)*rstd*gamma+beta   (a = rstd*gamma, b = beta-mean*a evaluated per element to keep
@@ -232,6 +256,13 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(
 // index with 32-bit arithmetic (the scalar versions spend most of their time in a 64-bit modulo).
 typedef float bn_f4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ bn_f4 bn_med3(bn_f4 a, bn_f4 b, bn_f4 c) {
+    bn_f4 m;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m[e] = bn_med3(a[e], b[e], c[e]);
+    return m;
+}
+
 __global__ __launch_bounds__(kBnThreads) void k_bn_stats_v4(const float* __restrict__ x, int N, int C, int CW4,
                                                             int rows_per_chunk, float* __restrict__ partial) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [2][RS][CW4] float4
@@ -244,9 +275,9 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats_v4(const float* __restr
     for (int c0 = 0; c0 < C4; c0 += CW4) {
         const int c4 = c0 + tx;
         bn_f4 s = {0.f, 0.f, 0.f, 0.f}, q = s, K = s;
+        const bn_f4* xp = reinterpret_cast<const bn_f4*>(x) + c4;
         if (c4 < C4 && r0 < r1) {
-            const bn_f4* xp = reinterpret_cast<const bn_f4*>(x) + c4;
-            K = xp[(int64_t)r0 * C4];
+            K = bn_med3(xp[(int64_t)r0 * C4], xp[(int64_t)((r0 + r1 - 1) >> 1) * C4], xp[(int64_t)(r1 - 1) * C4]);
             int r = r0 + ty;
             for (; r + 3 * RS < r1; r += 4 * RS) {
                 const bn_f4 v0 = xp[(int64_t)r * C4], v1 = xp[(int64_t)(r + RS) * C4],
@@ -269,17 +300,20 @@ __global__ __launch_bounds__(kBnThreads) void k_bn_stats_v4(const float* __restr
                 s += ps[k * CW4 + tx];
                 q += pq[k * CW4 + tx];
             }
-            const float n = (float)max(r1 - r0, 0);
+            const float n = (float)bn_chunk_rows(N, rows_per_chunk, blockIdx.x);
+            bn_f4 K0 = K;
+            if (n > 0.f) K0 = bn_med3(xp[0], xp[(int64_t)(N >> 1) * C4], xp[(int64_t)(N - 1) * C4]);
             float* p = partial + (int64_t)blockIdx.x * 3 * C + 4 * c4;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                float mean = 0.f, m2 = 0.f;
+                float mean = 0.f, rel = 0.f, m2 = 0.f;
                 if (n > 0.f) {
                     mean = K[e] + s[e] / n;
+                    rel = (K[e] - K0[e]) + s[e] / n;
                     m2 = fmaxf(q[e] - s[e] * s[e] / n, 0.f);
                 }
-                p[e] = n;
-                p[C + e] = mean;
+                p[e] = mean;
+                p[C + e] = rel;
                 p[2 * C + e] = m2;
             }
         }
@@ -394,7 +428,7 @@ extern "C" int64_t dt_bn_workspace_bytes(int N, int C) {
 }
 
 extern "C" int dt_bn_train_fwd(const float* x, int N, int C, const float* gamma, const float* beta,
-                               float eps, float momentum, float* moving_mean, float* moving_var,
+                               float eps, float momentum, float decay, float* moving_mean, float* moving_var,
                                float* y, float* save_mean, float* save_rstd, void* ws,
                                void* stream) {
     DT_REQUIRE(N > 0 && C > 0, "dt_bn_train_fwd: bad sizes N=%d C=%d", N, C);
@@ -413,8 +447,8 @@ extern "C" int dt_bn_train_fwd(const float* x, int N, int C, const float* gamma,
     } else {
         hipLaunchKernelGGL(k_bn_stats, dim3(chunks), dim3(kBnThreads), lds, st, x, N, C, CW, rpc, partial);
     }
-    hipLaunchKernelGGL(k_bn_finalize, dim3(ceil_div(C, 4)), dim3(256), 0, st, partial, chunks, C,
-                       eps, momentum, moving_mean, moving_var, save_mean, save_rstd);
+    hipLaunchKernelGGL(k_bn_finalize, dim3(ceil_div(C, 4)), dim3(256), 0, st, partial, chunks, N, rpc, C,
+                       eps, momentum, decay, moving_mean, moving_var, save_mean, save_rstd);
     const int64_t total = (int64_t)N * C;
     if (v4)
         hipLaunchKernelGGL(k_bn_apply_v4, dim3(elementwise_blocks(total / 4)), dim3(256), 0, st, x, (int)(total / 4), C / 4,

@@ -260,7 +260,7 @@ class _BatchNormTrain(torch.autograd.Function):
         mean = torch.empty((C,), dtype=torch.float32, device=x.device)
         rstd = torch.empty((C,), dtype=torch.float32, device=x.device)
         ws = _bn_ws(N, C, x.device)
-        check(lib().dt_bn_train_fwd(ptr(x2), N, C, ptr(gamma), ptr(beta), eps, momentum,
+        check(lib().dt_bn_train_fwd(ptr(x2), N, C, ptr(gamma), ptr(beta), eps, momentum, 1.0 - momentum,
                                     ptr(moving_mean), ptr(moving_var), ptr(y), ptr(mean), ptr(rstd),
                                     ptr(ws), stream_ptr()), 'dt_bn_train_fwd')
         ctx.save_for_backward(x2, gamma, mean, rstd)
@@ -723,7 +723,8 @@ class _AutoIntLayer(torch.autograd.Function):
         mean = torch.empty((D,), dtype=torch.float32, device=x.device)
         rstd = torch.empty((D,), dtype=torch.float32, device=x.device)
         ws = _bn_ws(N, D, x.device)
-        check(lib().dt_bn_train_fwd(ptr(a), N, D, ptr(gamma), ptr(beta), float(eps), float(momentum), ptr(moving_mean),
+        check(lib().dt_bn_train_fwd(ptr(a), N, D, ptr(gamma), ptr(beta), float(eps), float(momentum), 1.0 - float(momentum),
+                                    ptr(moving_mean),
                                     ptr(moving_var), ptr(y), ptr(mean), ptr(rstd), ptr(ws), stream_ptr()),
               'dt_bn_train_fwd')
         ctx.save_for_backward(x, a, *wb, mean, rstd, *([gamma] if gamma is not None else []))

@@ -129,12 +129,14 @@ int dt_embed_fm_linear_bwd(const float* emb, const float* g_emb, const float* g_
  * Training forward over x [N,C] (N = batch, or batch*fields for MultiheadAttention's BN):
  *   mean/var: biased batch statistics (two-pass-accurate, Chan-merged Welford)
  *   y = gamma*(x-mean)*rsqrt(var+eps)+beta
- *   moving_mean = moving_mean*momentum + mean*(1-momentum)   (same for var; biased var)
+ *   moving_mean = moving_mean*momentum + mean*decay          (same for var; biased var)
+ *   decay = 1-momentum, rounded to float from the DOUBLE as Keras does: (float)(1.0 - 0.99) is 0.01f, where
+ *   1.f - 0.99f is 9.5e-7 off it
  * save_mean/save_rstd [C] are written for the backward.  ws: workspace of
  * dt_bn_workspace_bytes(N,C) bytes.                                                          */
 int64_t dt_bn_workspace_bytes(int N, int C);
 int dt_bn_train_fwd(const float* x, int N, int C, const float* gamma, const float* beta,
-                    float eps, float momentum, float* moving_mean, float* moving_var,
+                    float eps, float momentum, float decay, float* moving_mean, float* moving_var,
                     float* y, float* save_mean, float* save_rstd, void* ws, void* stream);
 int dt_bn_infer_fwd(const float* x, int N, int C, const float* gamma, const float* beta,
                     float eps, const float* moving_mean, const float* moving_var, float* y,

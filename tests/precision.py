@@ -7,6 +7,8 @@ Metrics (kernel result `got` against the float64 reference `ref`):
   row_rel   per row: max |e| / max |ref| of that row, then the max over the rows whose reference is not zero — a table
             row seen once, or one input feature's row of a weight gradient, is measured against itself
   cond_rms  per element: |e| / (|A| |B|) of the same contraction in float64 (`abs_scale`), then the root mean square
+  col_cond  per column of a column sum: |e| / sum_n |term| in float64, then the max over the columns (the BatchNorm backward
+            sums, tests/test_bn_gpu.py)
 
 Yardstick A (one GEMM-shaped product: dense, cin, cin_bf16, one cross layer): cond_rms <= COND_BAR[class].  The units are
 those of tests/test_split_bf16_arithmetic.py, so the classes carry over: ~2^-24 for fp32 arithmetic and for six products of
@@ -52,6 +54,8 @@ CLAIMS = {
     ('bilinear', 'float32'): ('fp32', 'fp32'),  # csrc/interaction.hip
     ('afm', 'float32'): ('fp32', 'fp32'),       # csrc/interaction.hip
     ('bn', 'float32'): ('fp32', 'fp32'),        # csrc/bn.hip
+    ('field_pool', 'float32'): ('fp32', 'fp32'),    # csrc/interaction.hip: SENET squeeze
+    ('field_scale', 'float32'): ('fp32', 'fp32'),   # csrc/interaction.hip: SENET re-weight
 }
 
 # Yardstick A: bar on cond_rms, per class, in units U = 2^-24.  "GPU worst" is the largest figure test_precision_gpu.py
@@ -67,7 +71,8 @@ CLAIMS = {
 COND_BAR = {'fp32': 2.0 * U, 'b17': 128 * U, 'bf16': 65536 * U}
 
 # Yardstick B: factor over the float32 CPU oracle's own error, per class, and the floor of that error.
-#   fp32: GPU worst 3.7x (BN gamma through the timed step's m, exact tower), 2.5x (bilinear dx, outer product dW);   a two-part (16-bit) tower forward: logits
+#   fp32: GPU worst 5.1x (SENET mean pooling, D = 33 summed in order), 4.2x (BN moving mean, mean 0 / std 1 at N = 16385), 3.7x (BN gamma
+#         through the timed step's m, exact tower), 2.5x (bilinear dx, outer product dW);   a two-part (16-bit) tower forward: logits
 #         ~40x (2e-5 against 5.3e-7)
 #   b17:  GPU worst 59x (autoint bf16x2 dx), 52x (timed step BN gamma, wgrad_heavy_bf16);   an 8-bit backward: >= 2e3x
 #   bf16: GPU worst 2.3e4x (autoint bf16 dx), 1.3e4x (plain-bf16 tower logits)
@@ -97,6 +102,17 @@ def row_rel(got, ref):
     if not bool(live.any()):
         return (got - ref).abs().max().item()
     return ((got - ref).abs().amax(1)[live] / top[live]).max().item()
+
+
+def col_cond(got, ref, scale):
+    """per column: |got - ref| / scale, then the max over the columns — for a column sum of N signed terms, with `scale` the
+    sum of the terms' magnitudes in float64 (a sum near zero has no relative error two summation orders agree on).  A
+    column whose scale is zero has only zero terms and the sum zero: its error counts as it is, as row_rel counts the
+    error against a reference that is zero everywhere."""
+    err, scale = (_d(got).reshape(-1) - _d(ref).reshape(-1)).abs(), _d(scale).reshape(-1)
+    live = scale > 0
+    return max((err[live] / scale[live]).max().item() if bool(live.any()) else 0.0,
+               err[~live].max().item() if not bool(live.all()) else 0.0)
 
 
 def cond_rms(got, ref, scale):
