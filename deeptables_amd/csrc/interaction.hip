@@ -706,7 +706,7 @@ extern "C" int dt_afm_fwd(const float* x, const float* Wa, const float* ba, cons
     DT_REQUIRE(x && Wa && pv && out, "dt_afm_fwd: null pointer");
     DT_UNSUPPORTED(H > 64, "dt_afm_fwd: attention factor %d > 64", H);
     const size_t lds = afm_lds_fwd(F, D, H);
-    DT_UNSUPPORTED(lds > 150 * 1024, "dt_afm_fwd: needs %zu B of LDS", lds);
+    DT_UNSUPPORTED(lds > 150 * 1024, "dt_afm_fwd: F=%d D=%d H=%d needs %zu B of LDS (> 150 KiB)", F, D, H, lds);
     int blocks = B < 2048 ? B : 2048;
     hipStream_t st = as_stream(stream);
     const bool simple_act = act == DT_ACT_LINEAR || act == DT_ACT_RELU;
@@ -730,7 +730,7 @@ extern "C" int dt_afm_bwd(const float* x, const float* Wa, const float* ba, cons
     DT_REQUIRE(x && Wa && pv && score && grad_out && grad_x && grad_Wa && grad_pv, "dt_afm_bwd: null pointer");
     DT_UNSUPPORTED(H > 64, "dt_afm_bwd: attention factor %d > 64", H);
     const size_t lds = afm_lds_bwd(F, D, H);
-    DT_UNSUPPORTED(lds > 150 * 1024, "dt_afm_bwd: needs %zu B of LDS", lds);
+    DT_UNSUPPORTED(lds > 150 * 1024, "dt_afm_bwd: F=%d D=%d H=%d needs %zu B of LDS (> 150 KiB)", F, D, H, lds);
     int blocks = B < 512 ? B : 512;
     hipStream_t st = as_stream(stream);
     const bool simple_act = act == DT_ACT_LINEAR || act == DT_ACT_RELU;
@@ -787,7 +787,9 @@ extern "C" int dt_bilinear_bwd(const float* x, const float* W, const float* grad
                            grad_W);
         return launch_status("dt_bilinear_bwd");
     }
-    const size_t lds = ((size_t)D * D + 3 * 64 * (D + 1)) * sizeof(float);
+    const size_t lds = ((size_t)D * D + 3 * 64 * (D + 1)) * sizeof(float);     // 66,304 B at D = 64: past the 64 KiB default
+    DT_UNSUPPORTED(lds > 150 * 1024, "dt_bilinear_bwd: D=%d needs %zu B of LDS (> 150 KiB)", D, lds);
+    hipFuncSetAttribute((const void*)k_bilinear_bwd_x, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_bilinear_bwd_x, dim3(ceil_div(B, 64), F), dim3(64), lds, st, x, W, grad_out, wtype, B, F, D,
                        grad_x);
     int splits = ceil_div(B, 1024);

@@ -7,6 +7,7 @@ Metrics (kernel result `got` against the float64 reference `ref`):
   row_rel   per row: max |e| / max |ref| of that row, then the max over the rows whose reference is not zero — a table
             row seen once, or one input feature's row of a weight gradient, is measured against itself
   cond_rms  per element: |e| / (|A| |B|) of the same contraction in float64 (`abs_scale`), then the root mean square
+  elem_cond per element: |e| / (|A| |B|) of the same contraction, then the max (tests/test_pairwise_kernels_gpu.py)
   col_cond  per column of a column sum: |e| / sum_n |term| in float64, then the max over the columns (the BatchNorm backward
             sums, tests/test_bn_gpu.py)
 
@@ -113,6 +114,14 @@ def col_cond(got, ref, scale):
     live = scale > 0
     return max((err[live] / scale[live]).max().item() if bool(live.any()) else 0.0,
                err[~live].max().item() if not bool(live.all()) else 0.0)
+
+
+def elem_cond(got, ref, scale):
+    """per element: |got - ref| / scale, then the max over the elements — `scale` the |A| |B| of the same contraction
+    (`abs_scale`).  For a tensor whose rows mix magnitudes (fields scaled 1e-3 .. 1e3) or whose terms cancel, where row_rel
+    measures the small entries against the row's largest.  An element whose scale is zero has only zero terms: its error
+    counts as it is."""
+    return col_cond(got, ref, scale)
 
 
 def cond_rms(got, ref, scale):
