@@ -632,7 +632,7 @@ static int launch_dgrad(const float* x0, int64_t x0_bs, const float* xk, int64_t
                         float* gx0, float* gxk, hipStream_t st, int overwrite) {
     const size_t lds = ((size_t)cin_nb(D) * cin_slab(Hk, D) + 2 * 32 * (2 * LH + 4) + 4) * sizeof(float);
     if (lds > 160 * 1024) {
-        set_error("dt_cin_layer_bwd: tiles need %zu B of LDS (> 160 KiB)", lds);
+        set_error("dt_cin_layer_bwd: F0=%d Hk=%d L=%d D=%d: the dgrad tiles need %zu B of LDS (> 160 KiB)", F0, Hk, L, D, lds);
         return DT_ERR_UNSUPPORTED;
     }
     const int64_t M = (int64_t)B * D;

@@ -1342,7 +1342,7 @@ static int launch_dgrad_b(const float* x0, int64_t x0_bs, const float* xk, int64
     constexpr int BM = 32 * WV;
     const size_t lds = dgrad_lds<LSTEPS, NP, WV>(F0);
     if (lds > 160 * 1024) {
-        set_error("dt_cin_layer_bwd_bf16: tiles need %zu B of LDS (> 160 KiB)", lds);
+        set_error("dt_cin_layer_bwd_bf16: F0=%d Hk=%d L=%d D=%d: the dgrad tiles need %zu B of LDS (> 160 KiB)", F0, Hk, L, D, lds);
         return DT_ERR_UNSUPPORTED;
     }
     const int64_t M = (int64_t)B * D;
