@@ -284,6 +284,10 @@ SIGNATURES = {
     'dt_reg_penalty_workspace_bytes': (_c_i64, [_c_int, _ptr]),
     'dt_reg_penalty': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'dt_reg_grad': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr]),
+    # the losses of a train step from the logits (csrc/loss.hip): kind = DT_LOSS_*, z, t, w (or NULL), rows, classes, gamma,
+    # alpha, loss [1], dz (or NULL: value only), workspace, stream
+    'dt_loss_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
+    'dt_loss': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -313,6 +317,8 @@ DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 DT_DENSE_X3, DT_DENSE_BF16 = 1, 2      # dt_dense_x3_*: split-bf16 (fp32 bars forward) / plain bf16
 DT_METRIC_Y_LABELS, DT_METRIC_Y_ONEHOT = 0, 1
 DT_METRIC_SUMS_BLOCKS, DT_METRIC_SUMS_WORDS = 256, 771      # dt_metric_sums' out: 3 result words + 3 per block
+DT_LOSS_BCE, DT_LOSS_CCE, DT_LOSS_MSE, DT_LOSS_MAE, DT_LOSS_BINARY_FOCAL, DT_LOSS_CATEGORICAL_FOCAL = 0, 1, 2, 3, 4, 5
+DT_LOSS_MAX_CLASSES = 4096
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

@@ -13,9 +13,9 @@ import numpy as np
 import torch
 
 from . import deepnets
-from .layers import MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
+from .layers import BinaryFocalLoss, CategoricalFocalLoss, MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
 from .. import functional as F
-from .. import training
+from .. import _lib, training
 from ..functional import Dense, Concatenate, Flatten, Input, Add, BatchNormalization, Dropout, Model
 from ..utils import consts
 
@@ -239,16 +239,35 @@ class DeepModel:
     # ------------------------------------------------------------------------------------------
     # train / predict
     # ------------------------------------------------------------------------------------------
-    def _loss(self, logit, y):
-        if self.loss_name == 'binary_crossentropy':
-            return training.bce_from_logits(logit, y)
-        if self.loss_name == 'categorical_crossentropy':
-            return training.categorical_ce_from_logits(logit, y)
-        if self.loss_name in ('mse', 'mean_squared_error'):
-            return training.mse(logit, y)
-        if hasattr(self, '_custom_loss'):
-            return self._custom_loss(y, self._activate(logit))
-        raise ValueError(f'Unsupported loss: {self.loss_name}')
+    def _loss(self, logit, y, sample_weight=None):
+        """The data loss of a batch from the LOGITS, with Keras' per-row weights (sample_weight x class_weight).  The named
+        losses and the layers module's focal losses (reduction 'auto') run in csrc/loss.hip on the device (training.py);
+        any other callable, and a focal loss with another reduction, gets the activated probabilities."""
+        name = self.loss_name
+        custom = getattr(self, '_custom_loss', None)
+        if custom is None:
+            if name not in training.LOSS_NAMES:
+                raise ValueError(f'Unsupported loss: {name}')
+            if sample_weight is not None:
+                return training.weighted_loss(name, logit, y, sample_weight)
+            if name == 'binary_crossentropy':
+                return training.bce_from_logits(logit, y)
+            if name == 'categorical_crossentropy':
+                return training.categorical_ce_from_logits(logit, y)
+            if name in ('mse', 'mean_squared_error'):
+                return training.mse(logit, y)
+            return training.mae(logit, y)
+        if isinstance(custom, BinaryFocalLoss):
+            if sample_weight is not None:
+                raise ValueError('sample / class weights with loss BinaryFocalLoss: its `call` returns one scalar already '
+                                 'averaged over the batch, so a per-row weight has no defined place in it')
+            if custom.reduction == 'auto':
+                return training.focal_from_logits(_lib.DT_LOSS_BINARY_FOCAL, custom, logit, y, None, self._activate)
+        elif isinstance(custom, CategoricalFocalLoss) and custom.reduction == 'auto':
+            return training.focal_from_logits(_lib.DT_LOSS_CATEGORICAL_FOCAL, custom, logit, y, sample_weight, self._activate)
+        if sample_weight is not None:
+            raise ValueError(f'sample / class weights with loss {name!r}')
+        return custom(y, self._activate(logit))
 
     def _activate(self, logit):
         if self.output_activation == 'sigmoid':
@@ -307,8 +326,7 @@ class DeepModel:
         self.model._dt_flat_grad = getattr(self, '_generic_flat_grad', None)
         self.model._dt_sharded_step = False
         logit = self.model(inputs)
-        loss = self._loss(logit, y) if sample_weight is None else \
-            training.weighted_loss(self.loss_name, logit, y, sample_weight)
+        loss = self._loss(logit, y, sample_weight)
         # Keras: the total loss is the (weighted) data loss plus every regularizer's penalty (csrc/regularizer.hip); the
         # model's list of this forward's penalised activations is taken here, so nothing of the step outlives it
         penalty = self.model.regularization_loss() if self.model.has_regularizers() else None

@@ -768,8 +768,11 @@ class VarLenColumnEmbedding(Layer):
 
 
 # =============================================================================================
-# losses shipped with the layers module — layers.py:983-1163.  Element-wise work on [B, classes]
-# predictions (a few KB per step); expressed with torch ops on the device, no dedicated kernel.
+# losses shipped with the layers module — layers.py:983-1163.  The classes keep Keras' protocol: `call(y_true, y_pred)` on
+# PROBABILITIES, in torch ops.  A train / evaluate step does not go through `call`: DeepModel._loss hands a BinaryFocalLoss or
+# CategoricalFocalLoss (reduction 'auto') to csrc/loss.hip, which evaluates the same loss and its gradient from the logits in
+# at most two launches (dt_loss, DT_LOSS_BINARY_FOCAL / DT_LOSS_CATEGORICAL_FOCAL).  `call` serves CPU tensors, other
+# reductions, DT_AMD_DEVICE_LOSS=0 and direct use.  GHMCLoss is not a keras Loss and stays in torch ops.
 # =============================================================================================
 K_EPSILON = 1e-7   # keras.backend.epsilon()
 

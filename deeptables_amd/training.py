@@ -69,30 +69,157 @@ def bce_from_logits(logit, y):
     return (torch.clamp(z, min=0) - z * y + torch.log1p(torch.exp(-z.abs()))).mean()
 
 
+# ---------------------------------------------------------------------------------------------
+# the losses on the device (csrc/loss.hip): value and gradient from the logits in at most two launches
+# ---------------------------------------------------------------------------------------------
+LOSS_KINDS = {'binary_crossentropy': _lib.DT_LOSS_BCE, 'categorical_crossentropy': _lib.DT_LOSS_CCE,
+              'mse': _lib.DT_LOSS_MSE, 'mean_squared_error': _lib.DT_LOSS_MSE,
+              'mae': _lib.DT_LOSS_MAE, 'mean_absolute_error': _lib.DT_LOSS_MAE}
+LOSS_NAMES = tuple(LOSS_KINDS)            # the loss strings DeepModel compiles
+_CATEGORICAL_KINDS = (_lib.DT_LOSS_CCE, _lib.DT_LOSS_CATEGORICAL_FOCAL)
+
+
+def _on_device(t):
+    return torch.is_tensor(t) and t.is_cuda
+
+
+def device_loss_enabled():
+    """DT_AMD_DEVICE_LOSS=0 restores the torch op chains everywhere (the comparison leg of the tests and of
+    tools/loss_bench.py)"""
+    return os.environ.get('DT_AMD_DEVICE_LOSS', '1') != '0'
+
+
+class _DeviceLoss(torch.autograd.Function):
+    """dt_loss: loss and d loss / d logits together in the forward; dz is written only when the logits ask for a gradient
+    (evaluate runs under no_grad: value only).  backward hands out the saved dz itself when the incoming gradient is
+    `unit_grad`, else one multiply."""
+
+    @staticmethod
+    def forward(ctx, z, t, w, kind, gamma, alpha, want_dz):
+        z, t = z.contiguous(), t.contiguous()
+        w = None if w is None else w.contiguous()
+        rows, classes = z.shape
+        h = lib()
+        need = h.dt_loss_workspace_bytes(rows, classes)
+        if need < 0:
+            check(int(need), 'dt_loss_workspace_bytes')
+        # one allocation: the loss word (8 bytes, so that the partials behind it are 8-byte aligned), then the workspace
+        buf = torch.empty(2 + int(need) // 4, dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z) if want_dz else None
+        check(h.dt_loss(int(kind), ptr(z), ptr(t), ptr(w), rows, classes, float(gamma), float(alpha), ptr(buf), ptr(dz),
+                        ctypes.c_void_p(buf.data_ptr() + 8), stream_ptr()), 'dt_loss')
+        if dz is not None:
+            ctx.save_for_backward(dz)
+        return buf[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return (dz if _is_unit_grad(g) else dz * g), None, None, None, None, None, None
+
+
+def device_loss_supported(kind, z, t, w=None):
+    """True when `device_loss` serves this call: DT_AMD_DEVICE_LOSS not '0', float32 tensors on the GPU, logits [rows, classes]
+    inside dt_loss' domain with as many targets, one weight per row — and none for the binary focal loss"""
+    if not device_loss_enabled():
+        return False
+    if not (_on_device(z) and z.dtype == torch.float32 and z.dim() == 2 and _on_device(t) and t.dtype == torch.float32 and
+            t.shape == z.shape):
+        return False
+    rows, classes = z.shape
+    if not (1 <= rows < (1 << 31) and 1 <= classes <= _lib.DT_LOSS_MAX_CLASSES and rows * classes < (1 << 40)):
+        return False
+    if kind in _CATEGORICAL_KINDS and classes < 2:
+        return False
+    if w is not None:
+        if kind == _lib.DT_LOSS_BINARY_FOCAL:
+            return False
+        if not (_on_device(w) and w.dtype == torch.float32 and w.numel() == rows):
+            return False
+    return True
+
+
+def device_loss(kind, logit, y, w=None, gamma=0.0, alpha=0.0):
+    """The loss `kind` (DT_LOSS_*) of logits [B, ...] against targets y with per-row weights w [B] (None: 1) through
+    csrc/loss.hip, or None when the call is outside `device_loss_supported` — the caller then takes its torch path."""
+    B = logit.shape[0]
+    if B == 0 or y.numel() != logit.numel():
+        return None
+    z = logit.reshape(B, -1)
+    t = y.reshape(z.shape)
+    t = t if t.dtype == z.dtype else t.to(z.dtype)
+    w = None if w is None else w.reshape(-1)
+    if not device_loss_supported(kind, z, t, w):
+        return None
+    return _DeviceLoss.apply(z, t, w, kind, gamma, alpha, torch.is_grad_enabled() and z.requires_grad)
+
+
+def _per_row_loss(loss_name, z, t):
+    if loss_name == 'binary_crossentropy':
+        return (torch.clamp(z, min=0) - z * t + torch.log1p(torch.exp(-z.abs()))).mean(-1)
+    if loss_name == 'categorical_crossentropy':
+        return -(torch.log_softmax(z, dim=-1) * t).sum(-1)
+    if loss_name in ('mse', 'mean_squared_error'):
+        return ((z - t) ** 2).mean(-1)
+    if loss_name in ('mae', 'mean_absolute_error'):
+        return (z - t).abs().mean(-1)
+    raise ValueError(f'sample / class weights with loss {loss_name!r}')
+
+
 def weighted_loss(loss_name, logit, y, w):
     """Keras `sample_weight` / `class_weight` semantics (keras Model.fit -> compile loss with reduction
-    SUM_OVER_BATCH_SIZE): per-sample loss times its weight, summed, divided by the batch size.  Element-wise torch on
-    [B, outputs] — not on the hot path (the fused steps and the one-launch BCE are used only without weights)."""
+    SUM_OVER_BATCH_SIZE): per-sample loss times its weight, summed, divided by the batch size.  On the device one dt_loss
+    call (csrc/loss.hip); element-wise torch on [B, outputs] for CPU tensors and with DT_AMD_DEVICE_LOSS=0."""
+    if loss_name not in LOSS_KINDS:
+        raise ValueError(f'sample / class weights with loss {loss_name!r}')
     B = y.shape[0]
+    if _on_device(logit):
+        loss = device_loss(LOSS_KINDS[loss_name], logit, y, w.to(logit.dtype))
+        if loss is not None:
+            return loss
     z = logit.reshape(B, -1)
     t = y.reshape(B, -1).to(z.dtype)
-    if loss_name == 'binary_crossentropy':
-        per = (torch.clamp(z, min=0) - z * t + torch.log1p(torch.exp(-z.abs()))).mean(-1)
-    elif loss_name == 'categorical_crossentropy':
-        per = -(torch.log_softmax(z, dim=-1) * t).sum(-1)
-    elif loss_name in ('mse', 'mean_squared_error'):
-        per = ((z - t) ** 2).mean(-1)
-    else:
-        raise ValueError(f'sample / class weights with loss {loss_name!r}')
-    return (per * w.reshape(B).to(z.dtype)).sum() / B
+    return (_per_row_loss(loss_name, z, t) * w.reshape(B).to(z.dtype)).sum() / B
 
 
 def categorical_ce_from_logits(logit, y_onehot):
+    if _on_device(logit):
+        loss = device_loss(_lib.DT_LOSS_CCE, logit, y_onehot)
+        if loss is not None:
+            return loss
     return -(torch.log_softmax(logit, dim=-1) * y_onehot).sum(-1).mean()
 
 
 def mse(pred, y):
+    if _on_device(pred):
+        loss = device_loss(_lib.DT_LOSS_MSE, pred, y)
+        if loss is not None:
+            return loss
     return ((pred.reshape(y.shape[0], -1) - y.reshape(y.shape[0], -1).to(pred.dtype)) ** 2).mean()
+
+
+def mae(pred, y):
+    """keras.losses.MeanAbsoluteError ('mae' / 'mean_absolute_error')"""
+    if _on_device(pred):
+        loss = device_loss(_lib.DT_LOSS_MAE, pred, y)
+        if loss is not None:
+            return loss
+    return (pred.reshape(y.shape[0], -1) - y.reshape(y.shape[0], -1).to(pred.dtype)).abs().mean()
+
+
+def focal_from_logits(kind, loss_obj, logit, y, w, activate):
+    """layers.BinaryFocalLoss / CategoricalFocalLoss (reduction 'auto') of a step: from the logits through dt_loss on the
+    device, carrying the object's gamma and alpha; otherwise the object's own `call` on `activate(logit)` — for the
+    categorical loss, whose `call` returns one value per row, with Keras' per-row weights."""
+    if _on_device(logit):
+        loss = device_loss(kind, logit, y, w, loss_obj.gamma, loss_obj.alpha)
+        if loss is not None:
+            return loss
+    if w is None:
+        return loss_obj(y, activate(logit))
+    B = y.shape[0]
+    prob = activate(logit)
+    return (loss_obj.call(y, prob).reshape(B) * w.reshape(B).to(prob.dtype)).sum() / B
 
 
 # ---------------------------------------------------------------------------------------------

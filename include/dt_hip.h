@@ -1228,6 +1228,43 @@ int dt_reg_penalty(int count, const float* const* x, const int64_t* n, const dou
 int dt_reg_grad(int count, const float* const* x, float* const* out, const int64_t* n, const float* l1, const float* l2,
                 const float* go, int accumulate, void* stream);
 
+/* The losses of a train step on the device (csrc/loss.hip), from the LOGITS z [rows, classes] (the `task_output` Dense before
+ * its activation), the float32 target t [rows, classes] and Keras' sample_weight x class_weight per row w [rows] (NULL: 1).
+ * Replaces keras.losses.BinaryCrossentropy / CategoricalCrossentropy / MeanSquaredError / MeanAbsoluteError selected by
+ * deepmodel.py:324-338 and layers.py:1006-1017 (BinaryFocalLoss) / :1062-1076 (CategoricalFocalLoss), with reduction
+ * SUM_OVER_BATCH_SIZE: loss[0] = sum_b w_b l_b / rows and dz = (w_b / rows) dl_b/dz (dz NULL: the value only), eps = 1e-7:
+ *   DT_LOSS_BCE    l_b = mean_c max(z,0) - z t + log1p(exp(-|z|))               dl/dz = (sigmoid(z) - t) / classes
+ *   DT_LOSS_CCE    l_b = -sum_c t_c log p_c, p = softmax(z), log p = z - lse     dl/dz = (sum_k t_k) p_c - t_c
+ *   DT_LOSS_MSE    l_b = mean_c (z - t)^2                                        dl/dz = 2 (z - t) / classes
+ *   DT_LOSS_MAE    l_b = mean_c |z - t|                                          dl/dz = sign(z - t) / classes, sign(0) = 0
+ *   DT_LOSS_CATEGORICAL_FOCAL  l_b = sum_c alpha (1 - ph_c)^gamma (-t_c log ph_c), ph = clamp(softmax(z), eps, 1 - eps);
+ *                  dl/dz_k = p_k (g_k - sum_c g_c p_c), g_c = alpha t_c [gamma (1 - ph_c)^(gamma-1) log ph_c - (1 - ph_c)^gamma / ph_c]
+ *                  and g_c = 0 where the clamp is active; 1 - p is formed as -expm1(log p)
+ *   DT_LOSS_BINARY_FOCAL  not a per-row loss (w must be NULL): with p = sigmoid(z), q = sigmoid(-z) clamped to [eps, 1 - eps],
+ *                  loss = -(1 / (rows classes)) sum [T1 + T0], T1 = alpha qh^gamma log ph where t == 1, else the constant
+ *                  alpha eps^gamma log(1 - eps); T0 = (1 - alpha) ph^gamma log qh where t == 0, else (1 - alpha) eps^gamma
+ *                  log(1 - eps); the constants are added in float64 as count x constant.  dz = -(1 / (rows classes)) p q
+ *                  [(t==1) alpha (-gamma qh^(gamma-1) log ph + qh^gamma / ph) + (t==0)(1 - alpha)(gamma ph^(gamma-1) log qh -
+ *                  ph^gamma / qh)], zero where the clamp is active (|z| > ln((1 - eps) / eps)).
+ * Per-element and per-row math is float32; every sum over classes, elements and rows is float64 in a fixed order (lanes by
+ * halving, waves in order, partials in index order): no float atomics, no block waits for another, the same input gives
+ * the same bits in loss and dz, and dz = NULL gives the bits of loss.  At most two launches: per-block partials into
+ * `workspace` (dt_loss_workspace_bytes(rows, classes) bytes, 8-byte aligned, contents irrelevant before and after), then one
+ * block adds them; one launch when one block covers the problem.  gamma / alpha are read by the focal kinds only.
+ * Domain: 1 <= rows < 2^31, 1 <= classes <= DT_LOSS_MAX_CLASSES, classes >= 2 for the categorical kinds, gamma >= 0; a kind,
+ * shape or gamma outside it, a null z / t / loss / workspace, a misaligned pointer or a w with DT_LOSS_BINARY_FOCAL are
+ * DT_ERR_INVALID_ARG before the first launch (dt_loss_workspace_bytes returns it for a shape outside the domain).        */
+#define DT_LOSS_BCE 0
+#define DT_LOSS_CCE 1
+#define DT_LOSS_MSE 2
+#define DT_LOSS_MAE 3
+#define DT_LOSS_BINARY_FOCAL 4
+#define DT_LOSS_CATEGORICAL_FOCAL 5
+#define DT_LOSS_MAX_CLASSES 4096
+int64_t dt_loss_workspace_bytes(int64_t rows, int classes);
+int dt_loss(int kind, const float* z, const float* t, const float* w, int64_t rows, int classes, float gamma, float alpha,
+            float* loss, float* dz, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
