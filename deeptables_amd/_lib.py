@@ -288,6 +288,14 @@ SIGNATURES = {
     # alpha, loss [1], dz (or NULL: value only), workspace, stream
     'dt_loss_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
     'dt_loss': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr]),
+    # Activation -> (Dropout) of a tower cell in one launch each way (csrc/cell.hip): x, N, C, act (CELL_ACT_CODES), rate, the
+    # DEVICE seed word, salt, out, stream / g, saved, saved_is_input, N, C, act, rate, seed, salt, dx, stream
+    'dt_cell_dropout_hash': (ctypes.c_uint32, [ctypes.c_uint32] * 4),
+    'dt_cell_dropout_threshold': (ctypes.c_uint32, [_c_f32]),
+    'dt_cell_pass_elems': (_c_i64, []),
+    'dt_cell_saves_input': (_c_int, [_c_int]),
+    'dt_cell_fwd': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32, _ptr, _ptr]),
+    'dt_cell_bwd': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -322,6 +330,14 @@ DT_LOSS_MAX_CLASSES = 4096
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}
+
+
+# ... and the names dt_cell_fwd / dt_cell_bwd take (include/dt_hip.h DT_CELL_ACT_*): the table above plus the rest of Keras 3's
+# element-wise set; 'swish' / 'silu' and 'hard_swish' / 'hard_silu' are one function each.  softmax is a row operation: not here.
+DT_CELL_ACT_RELU6, DT_CELL_ACT_LEAKY_RELU, DT_CELL_ACT_SILU, DT_CELL_ACT_GELU = 9, 10, 11, 12
+DT_CELL_ACT_MISH, DT_CELL_ACT_HARD_SIGMOID, DT_CELL_ACT_HARD_SILU, DT_CELL_ACT_COUNT = 13, 14, 15, 16
+CELL_ACT_CODES = dict(ACT_CODES, relu6=9, leaky_relu=10, silu=11, swish=11, gelu=12, mish=13, hard_sigmoid=14, hard_silu=15,
+                      hard_swish=15)
 
 
 def act_code(name, what):

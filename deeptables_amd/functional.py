@@ -108,7 +108,13 @@ def initialize(shape, initializer):
     return torch.as_tensor(np.asarray(a, dtype=np.float32))
 
 
+def _leaky_relu(t):
+    return torch.nn.functional.leaky_relu(t, 0.2)       # keras.activations.leaky_relu's default negative_slope
+
+
 def get_activation(name):
+    """the torch definition of a Keras activation name: what CPU tensors and DT_AMD_CELL=0 run; on the GPU the element-wise
+    names go through ops.cell (csrc/cell.hip) instead"""
     if name is None or name == 'linear':
         return None
     if callable(name):
@@ -116,7 +122,11 @@ def get_activation(name):
     table = {'relu': torch.relu, 'tanh': torch.tanh, 'sigmoid': torch.sigmoid,
              'softmax': lambda t: torch.softmax(t, dim=-1), 'selu': torch.selu, 'elu': torch.nn.functional.elu,
              'softplus': torch.nn.functional.softplus, 'gelu': torch.nn.functional.gelu,
-             'swish': torch.nn.functional.silu, 'softsign': torch.nn.functional.softsign, 'exponential': torch.exp}
+             'swish': torch.nn.functional.silu, 'softsign': torch.nn.functional.softsign, 'exponential': torch.exp,
+             # [ext] the rest of Keras 3's element-wise set (csrc/cell.hip holds the same definitions and kink derivatives)
+             'relu6': torch.nn.functional.relu6, 'leaky_relu': _leaky_relu, 'silu': torch.nn.functional.silu,
+             'mish': torch.nn.functional.mish, 'hard_sigmoid': torch.nn.functional.hardsigmoid,
+             'hard_silu': torch.nn.functional.hardswish, 'hard_swish': torch.nn.functional.hardswish}
     if name not in table:
         raise ValueError(f'Unknown activation: {name}')
     return table[name]
@@ -267,6 +277,35 @@ class Layer(nn.Module):
 # ---------------------------------------------------------------------------------------------
 # built-in Keras layers used by the reference graph
 # ---------------------------------------------------------------------------------------------
+class CellSeed:
+    """the seed word of ONE forward's dropout masks, drawn (ops.draw_cell_seed) when the first cell asks for it and shared by
+    the cells of that forward, which differ by their salts"""
+
+    def __init__(self):
+        self.word = None
+
+    def __call__(self, device):
+        if self.word is None:
+            self.word = ops.draw_cell_seed(device)
+        return self.word
+
+
+def act_drop(y, name, fn, drop=None):
+    """activation `name` (torch definition `fn`, None for linear) followed by the dropout `drop` = (rate, CellSeed, salt) or
+    None: ONE csrc/cell.hip launch where ops.cell_supported, the torch ops otherwise (CPU tensors, DT_AMD_CELL=0, softmax, a
+    callable)"""
+    rate, seeds, salt = drop if drop is not None else (0.0, None, 0)
+    if ops.cell_supported(y, name):
+        if fn is None and rate == 0:
+            return y
+        return ops.cell(y, name, rate, seeds(y.device) if 0.0 < rate < 1.0 else None, salt)
+    if fn is not None:
+        y = fn(y)
+    if rate > 0:
+        y = torch.nn.functional.dropout(y, rate, True)
+    return y
+
+
 _VENDOR_GEMM_NOTED = set()
 
 
@@ -303,6 +342,7 @@ class Dense(Layer):
         self.units = int(units)
         self.activation_name = activation if not callable(activation) else getattr(activation, '__name__', 'fn')
         self.activation = get_activation(activation)
+        self.cell_activation = None if callable(activation) else activation     # the NAME ops.cell may take, never a callable's
         self.use_bias = use_bias
         self.kernel_initializer = kernel_initializer
         self.bias_initializer = bias_initializer
@@ -318,8 +358,9 @@ class Dense(Layer):
     def compute_output_shape(self, input_shape):
         return tuple(input_shape[:-1]) + (self.units,)
 
-    def call(self, x, fused_activation=None, **kwargs):
-        """fused_activation: an activation the model's execution plan folds into this layer (Model.__init__)."""
+    def call(self, x, fused_activation=None, cell_dropout=None, **kwargs):
+        """fused_activation: an activation the model's execution plan folds into this layer (Model.__init__).
+        cell_dropout: (rate, CellSeed, salt) of the Dropout that plan folds into this layer's activation launch."""
         act_name = self.activation_name if self.activation_name not in (None, 'linear') else fused_activation
         activation = self.activation if self.activation is not None else get_activation(fused_activation)
         lk = getattr(x, '_dt_bn_link', None)
@@ -335,15 +376,16 @@ class Dense(Layer):
             # hand-written fp32 MFMA / GEMV kernels (csrc/dense.hip); relu and bias fused
             mfma_dtype = self.mfma_dtype if self.mfma_dtype is not None else (os.environ.get('DT_AMD_DENSE_DTYPE') or None)
             y = ops.dense(x, self.kernel, self.bias, fused_act, mfma_dtype)
-            if activation is not None and fused_act is None:
-                y = activation(y)
-            return y
+            if fused_act is not None or activation is None:
+                return act_drop(y, None, None, cell_dropout)
+            # any other activation: the GEMM as it is, then the cell (activation and a folded dropout in one launch)
+            own_name = self.activation is activation and self.cell_activation is not None
+            return act_drop(y, self.cell_activation if own_name else False, activation, cell_dropout)
         lead = x.shape[:-1]                      # CPU tensors only (ops.dense_supported takes every GPU shape): torch's GEMM
         note_vendor_gemm(f'Dense {self.name!r}', x.shape, self.kernel.shape)
         x2 = x.reshape(-1, x.shape[-1])
         y = torch.addmm(self.bias, x2, self.kernel) if self.bias is not None else x2 @ self.kernel
-        if activation is not None:
-            y = activation(y)
+        y = act_drop(y, False, activation, cell_dropout)
         return y.reshape(*lead, self.units)
 
     def get_config(self):
@@ -360,18 +402,25 @@ class Activation(Layer):
         self.activation_name = activation
         self.fn = get_activation(activation)
 
-    def call(self, x, **kwargs):
-        return x if self.fn is None else self.fn(x)
+    def call(self, x, cell_dropout=None, **kwargs):
+        """cell_dropout: (rate, CellSeed, salt) of the Dropout the model's plan folds into this launch (Model.__init__)"""
+        return act_drop(x, self.activation_name, self.fn, cell_dropout)
 
 
 class Dropout(Layer):
     def __init__(self, rate, **kwargs):
         super().__init__(**kwargs)
         self.rate = float(rate)
+        self.salt = ops.cell_salt(self.name)        # tells this layer's mask from the other cells' of one forward
 
-    def call(self, x, **kwargs):
+    def cell_args(self, seeds):
+        """(rate, CellSeed, salt) while the layer drops, else None"""
+        return (self.rate, seeds, self.salt) if self.training and self.rate > 0 else None
+
+    def call(self, x, cell_seed=None, **kwargs):
+        """cell_seed: the executing model's CellSeed (one draw per forward); a layer called on its own draws its own"""
         if self.training and self.rate > 0:
-            return torch.nn.functional.dropout(x, self.rate, True)
+            return act_drop(x, None, None, self.cell_args(cell_seed if cell_seed is not None else CellSeed()))
         return x
 
 
@@ -520,6 +569,11 @@ class BatchNormalization(Layer):
 # ---------------------------------------------------------------------------------------------
 # Model: executes the recorded graph
 # ---------------------------------------------------------------------------------------------
+def _cell_name(name):
+    """an activation NAME the cell kernels take (ops.cell); a callable, softmax or an unknown name is not"""
+    return (name is None or isinstance(name, str)) and name in ops._lib.CELL_ACT_CODES
+
+
 def _fetch(env, x):
     """the values of a node's (nested) inputs.  A module-level function on purpose: a recursive closure over `env` refers to
     itself, and that cycle kept every activation of a forward alive until the cyclic collector happened to run."""
@@ -592,6 +646,28 @@ class Model(nn.Module):
             if len(cons) == 1 and getattr(cons[0].layer, 'accepts_pending_norm', False) and \
                     not isinstance(cons[0].inputs, (list, tuple)) and id(cons[0]) not in self._fused_relu:
                 self._defer_norm.add(id(node))
+        # third peephole: Activation -> Dropout, and a Dense with an activation of its own -> Dropout (the D_A_D_B cell), run as
+        # ONE launch each way (csrc/cell.hip: keep * act(x), the mask recomputed in the backward) where the intermediate tensor
+        # feeds the Dropout alone, is not one of the model's outputs and carries no activity penalty.  An Activation('relu')
+        # the first peephole folded into its GEMM stays there (its Dropout then runs as a cell of its own), as does a Dense's
+        # own relu.  Layers, names, configs and `apply(output_layers=[...])` proxies are unaffected.
+        self._cell_fused, self._cell_passthrough = {}, set()        # id(head node) -> the Dropout layer folded into it
+        for node in order:
+            layer = node.layer
+            if isinstance(layer, Activation):
+                head = id(node) not in self._passthrough and _cell_name(layer.activation_name)
+            elif isinstance(layer, Dense):
+                head = layer.cell_activation not in (None, 'linear', 'relu') and _cell_name(layer.cell_activation)
+            else:
+                continue
+            if not head or isinstance(node.outputs, list) or id(node.outputs) in outs or isinstance(node.inputs, (list, tuple)) \
+                    or regularizers.active(layer.activity_regularizer) is not None:
+                continue
+            cons = consumers.get(id(node.outputs), [])
+            if len(cons) == 1 and type(cons[0].layer) is Dropout and not isinstance(cons[0].inputs, (list, tuple)) and \
+                    regularizers.active(cons[0].layer.activity_regularizer) is None:
+                self._cell_fused[id(node)] = cons[0].layer
+                self._cell_passthrough.add(id(cons[0]))
         self._activity = None               # [(tensor, (l1, l2))] of the last forward, until regularization_loss() takes it
         self.collect_eval_activity = False  # evaluate sets it: activity penalties are collected in eval mode too
 
@@ -660,9 +736,16 @@ class Model(nn.Module):
         def fetch(x):
             return _fetch(env, x)
 
+        seeds = CellSeed()                                    # one seed word per forward, drawn when a cell first needs it
         for node in self.nodes:
             if id(node) in self._passthrough:
                 out = fetch(node.inputs)                      # its relu already ran inside the producing Dense
+            elif id(node) in self._cell_passthrough:
+                out = fetch(node.inputs)                      # its mask already ran inside the producing activation launch
+            elif id(node) in self._cell_fused:
+                out = node.layer(fetch(node.inputs), cell_dropout=self._cell_fused[id(node)].cell_args(seeds))
+            elif type(node.layer) is Dropout:
+                out = node.layer(fetch(node.inputs), cell_seed=seeds)
             elif id(node) in self._fused_relu:
                 out = node.layer(fetch(node.inputs), fused_activation='relu')
             elif id(node) in self._defer_norm:

@@ -1374,3 +1374,137 @@ def reg_grad_raw(tensors, outs, coeffs, go, accumulate=False):
     po = (ctypes.c_void_p * len(outs))(*[o.data_ptr() for o in outs])
     check(lib().dt_reg_grad(len(tensors), px, po, pn, l1, l2, ptr(go), 1 if accumulate else 0, stream_ptr()), 'dt_reg_grad')
     return outs
+
+
+# ------------------------------------------------------------------------------------------------
+# Activation -> (Dropout) of a tower cell — deepnets.py:401-427, :430-452: one launch each way (csrc/cell.hip), the dropout
+# mask recomputed in the backward from a seed word that lives on the device
+# ------------------------------------------------------------------------------------------------
+def cell_enabled():
+    """DT_AMD_CELL=0 (read at every call) restores the torch ops: elementwise activations and torch.nn.functional.dropout"""
+    return os.environ.get('DT_AMD_CELL', '1') != '0'
+
+
+def cell_supported(x, activation):
+    """True when `cell` serves this call: DT_AMD_CELL not '0', a non-empty float32 GPU tensor and an activation NAME of
+    _lib.CELL_ACT_CODES (a callable, softmax or an unknown name stays with the caller)"""
+    if not (activation is None or isinstance(activation, str)) or activation not in _lib.CELL_ACT_CODES:
+        return False
+    if not cell_enabled() or x.device.type != 'cuda' or x.dtype != torch.float32 or x.numel() == 0:
+        return False
+    C = int(x.shape[-1]) if x.dim() else 1
+    return x.numel() // C < 2 ** 31 and x.numel() < 2 ** 40
+
+
+def cell_salt(name):
+    """the 32-bit word that tells a layer's mask from the other cells' of the same forward: a checksum of the layer's name"""
+    import zlib
+    return zlib.crc32(str(name).encode('utf-8')) & 0xFFFFFFFF
+
+
+def draw_cell_seed(device):
+    """The seed word of one forward's dropout masks: ONE int32 element on `device`, drawn by torch's generator of that device —
+    no host synchronisation, reproducible under torch.manual_seed, and a captured graph (compiled.CompiledTrainLoop) draws a
+    fresh word at every replay, where a host integer would freeze one mask into all of them.  Tests monkeypatch this function."""
+    return torch.randint(-2 ** 31, 2 ** 31, (1,), dtype=torch.int32, device=device)
+
+
+def _cell_seed_ptr(seed, rate):
+    if not 0.0 < rate < 1.0:
+        return None
+    if seed is None or not seed.is_cuda or seed.dtype != torch.int32 or seed.numel() != 1:
+        raise ValueError('cell: 0 < rate < 1 needs the seed word, a one-element int32 tensor on the GPU (ops.draw_cell_seed)')
+    return ptr(seed)
+
+
+def cell_fwd_launch(x2, code, rate, seed, salt, out):
+    """THE call of dt_cell_fwd (tests count the launches here)"""
+    N, C = x2.shape
+    check(lib().dt_cell_fwd(ptr(x2), N, C, code, rate, _cell_seed_ptr(seed, rate), salt, ptr(out), stream_ptr()), 'dt_cell_fwd')
+
+
+def cell_bwd_launch(g2, saved, saved_is_input, code, rate, seed, salt, dx):
+    """THE call of dt_cell_bwd"""
+    N, C = g2.shape
+    check(lib().dt_cell_bwd(ptr(g2), ptr(saved), int(saved_is_input), N, C, code, rate, _cell_seed_ptr(seed, rate), salt, ptr(dx),
+                            stream_ptr()), 'dt_cell_bwd')
+
+
+# silu / swish, gelu, mish, hard_silu / hard_swish: the codes dt_cell_saves_input answers 1 for
+_CELL_INPUT_KINDS = frozenset((_lib.DT_CELL_ACT_SILU, _lib.DT_CELL_ACT_GELU, _lib.DT_CELL_ACT_MISH, _lib.DT_CELL_ACT_HARD_SILU))
+
+
+class _Cell(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, code, rate, seed, salt):
+        require_cuda(x)
+        C = int(x.shape[-1]) if x.dim() else 1
+        x2 = _f32c(x).reshape(-1, C)
+        out = torch.empty_like(x2)
+        cell_fwd_launch(x2, code, rate, seed, salt, out)
+        # ONE saved tensor: the output where the derivative follows from it, the input for gelu / silu / mish / hard_silu and
+        # under a mask (the scaled output does not decide y < 6 exactly; the producing Dense keeps the input anyway)
+        ctx.by_input = code in _CELL_INPUT_KINDS or 0.0 < rate < 1.0
+        ctx.save_for_backward(x2 if ctx.by_input else out, seed if 0.0 < rate < 1.0 else None)
+        ctx.code, ctx.rate, ctx.salt, ctx.shape = code, rate, salt, x.shape
+        return out.reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, g):
+        saved, seed = ctx.saved_tensors
+        g2 = _f32c(g).reshape(saved.shape)
+        dx = torch.empty_like(saved)
+        cell_bwd_launch(g2, saved, ctx.by_input, ctx.code, ctx.rate, seed, ctx.salt, dx)
+        return dx.reshape(ctx.shape), None, None, None, None
+
+
+def cell(x, activation=None, rate=0.0, seed=None, salt=0):
+    """keep * act(x): the Activation and the Dropout of a tower cell in one HIP launch, and one for the backward.
+    activation: a name of _lib.CELL_ACT_CODES (None / 'linear': dropout alone); rate: the dropout rate, 0 for none;
+    seed: the forward's seed word (draw_cell_seed; drawn here when a mask is needed and none is given); salt: the layer's
+    32-bit word (cell_salt).  The mask is cell_dropout_keep(seed, salt, N, C, rate) for x seen as [N, C = last dimension]."""
+    if activation not in _lib.CELL_ACT_CODES:
+        raise ValueError(f'cell activation {activation!r}: the HIP cell takes {sorted(k for k in _lib.CELL_ACT_CODES if k)}')
+    rate = float(rate)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError(f'cell dropout rate {rate} outside [0, 1]')
+    if x.numel() == 0:
+        return x
+    if 0.0 < rate < 1.0 and seed is None:
+        seed = draw_cell_seed(x.device)
+    return _Cell.apply(x, _lib.CELL_ACT_CODES[activation], rate, seed, int(salt) & 0xFFFFFFFF)
+
+
+def cell_dropout_hash(seed, salt, rows, cols):
+    """dt_cell_dropout_hash restated with torch integer ops: int64 tensors `rows`, `cols` (broadcast) -> the 32-bit hashes"""
+    M32 = 0xFFFFFFFF
+
+    def mix(x):
+        x = x ^ (x >> 16); x = (x * 0x7FEB352D) & M32; x = x ^ (x >> 15); x = (x * 0x846CA68B) & M32
+        return x ^ (x >> 16)
+    seed = int(seed.item() if torch.is_tensor(seed) else seed) & M32
+    head = (seed ^ ((int(salt) & M32) * 0x9E3779B1 & M32))
+    head = int(mix(torch.tensor(head, dtype=torch.int64)))
+    r = mix(head ^ (((rows & M32) * 0x85EBCA77) & M32))
+    return mix(r ^ (((cols & M32) * 0xC2B2AE3D) & M32))
+
+
+def cell_dropout_threshold(rate):
+    """dt_cell_dropout_threshold: keep iff hash >= thr, thr = float32(rate) * 2^32 saturated"""
+    t = float(torch.tensor(float(rate), dtype=torch.float32)) * 4294967296.0
+    return 4294967295 if t >= 4294967295.0 else (0 if t <= 0.0 else int(t))
+
+
+def cell_dropout_keep(seed, salt, N, C, rate, device='cpu'):
+    """[N, C] keep-scale (0 or fl(1 / (1 - rate))) of the cell's dropout for the seed word and salt: the counter hash of
+    csrc/cell.hip restated with torch integer ops (tests rebuild the kernel's mask from it).  rate 0: ones; rate 1: zeros."""
+    rate = float(rate)
+    if rate <= 0.0:
+        return torch.ones(N, C, dtype=torch.float32, device=device)
+    if rate >= 1.0:
+        return torch.zeros(N, C, dtype=torch.float32, device=device)
+    rows = torch.arange(N, dtype=torch.int64, device=device).view(N, 1)
+    cols = torch.arange(C, dtype=torch.int64, device=device).view(1, C)
+    one, r32 = torch.tensor(1.0, dtype=torch.float32, device=device), torch.tensor(rate, dtype=torch.float32, device=device)
+    keep = cell_dropout_hash(seed, salt, rows, cols) >= cell_dropout_threshold(rate)
+    return keep.to(torch.float32) * (one / (one - r32))

@@ -1265,6 +1265,40 @@ int64_t dt_loss_workspace_bytes(int64_t rows, int classes);
 int dt_loss(int kind, const float* z, const float* t, const float* w, int64_t rows, int classes, float gamma, float alpha,
             float* loss, float* dz, void* workspace, void* stream);
 
+/* ---- the tail of a DNN tower cell: Activation -> (Dropout) in one launch each way (csrc/cell.hip) ------------------------ *
+ * Over x [N, C] fp32:  out = keep * act(x)  and  dx = g * keep * act'(.), keep = 0 or 1 / (1 - rate) by the counter hash
+ * dt_cell_dropout_hash(seed[0], salt, row, col) >= dt_cell_dropout_threshold(rate) — recomputed by the backward from the same
+ * DEVICE seed word, so no mask tensor exists; salt tells the cells of one forward apart.  rate == 0 runs no hash and reads
+ * no seed (NULL allowed); rate == 1 multiplies by 0, as torch's dropout does.
+ * act: a DT_ACT_* code (0-8, evaluated by the helpers the CIN / AFM kernels use) or one of the cell's own codes below, which
+ * only these two entry points take.  [ext] Keras 3 definitions: relu6 min(max(x,0),6); leaky_relu x > 0 ? x : 0.2 x; silu =
+ * swish x sigmoid(x); gelu the exact erf form; mish x tanh(softplus(x)); hard_sigmoid relu6(x + 3) / 6; hard_silu = hard_swish
+ * x hard_sigmoid(x).
+ * The backward takes act' from ONE saved tensor: the forward's OUTPUT for codes 0-8, relu6, leaky_relu and hard_sigmoid when
+ * rate is 0 or 1 (saved_is_input = 0), the forward's INPUT for silu, gelu, mish and hard_silu (dt_cell_saves_input = 1) and
+ * for every code when 0 < rate < 1 (saved_is_input = 1; anything else is DT_ERR_INVALID_ARG).  At a kink the derivative is
+ * the one torch's autograd takes: relu, relu6 0 at 0 and at 6; leaky_relu 0.2 at 0; hard_sigmoid 0 at +-3; hard_silu 0 at
+ * -3 and 1 at 3.  NaN in gives NaN out both ways; every value and derivative is finite for finite |x| <= 80.
+ * 16-byte loads and stores when N C >= 4 and every tensor is 16-byte aligned, floats otherwise; a grid-stride loop of at most
+ * 2048 blocks: dt_cell_pass_elems() elements per grid pass of the 16-byte path.  Domain: 1 <= N < 2^31, C >= 1, N C < 2^40,
+ * 0 <= rate <= 1; outside it, an unknown code, a null or misaligned pointer: DT_ERR_INVALID_ARG before any launch.          */
+#define DT_CELL_ACT_RELU6 9
+#define DT_CELL_ACT_LEAKY_RELU 10
+#define DT_CELL_ACT_SILU 11
+#define DT_CELL_ACT_GELU 12
+#define DT_CELL_ACT_MISH 13
+#define DT_CELL_ACT_HARD_SIGMOID 14
+#define DT_CELL_ACT_HARD_SILU 15
+#define DT_CELL_ACT_COUNT 16
+unsigned dt_cell_dropout_hash(unsigned seed, unsigned salt, unsigned row, unsigned col);
+unsigned dt_cell_dropout_threshold(float rate);
+int64_t dt_cell_pass_elems(void);
+int dt_cell_saves_input(int act);
+int dt_cell_fwd(const float* x, int64_t N, int C, int act, float rate, const unsigned* seed, unsigned salt, float* out,
+                void* stream);
+int dt_cell_bwd(const float* g, const float* saved, int saved_is_input, int64_t N, int C, int act, float rate,
+                const unsigned* seed, unsigned salt, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
