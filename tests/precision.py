@@ -48,7 +48,7 @@ CLAIMS = {
     ('autoint', 'bf16'): ('b17', 'bf16'),       # DT_AI_BF16: two-part forward projection, plain bf16 backward (autoint.hip:138-144)
     ('dense', 'float32'): ('fp32', 'fp32'),     # csrc/dense.hip
     ('cross', 'float32'): ('fp32', 'fp32'),     # csrc/cross.hip
-    ('fm', 'float32'): ('fp32', 'fp32'),        # csrc/interaction.hip
+    ('fm', 'float32'): ('fp32', 'fp32'),        # csrc/embedding.hip
     ('embed_fm_linear', 'float32'): ('fp32', 'fp32'),   # csrc/embedding.hip
     ('inner', 'float32'): ('fp32', 'fp32'),     # csrc/product.hip
     ('outer', 'float32'): ('fp32', 'fp32'),     # csrc/product.hip
