@@ -223,25 +223,28 @@ def focal_from_logits(kind, loss_obj, logit, y, w, activate):
 
 
 # ---------------------------------------------------------------------------------------------
-# Keras Adam
+# optimizers with slots and a device-resident step state: Adam, Adagrad, RMSprop
 # ---------------------------------------------------------------------------------------------
-class KerasAdam:
-    """keras.optimizers.Adam(learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-7):
-        lr_t = lr*sqrt(1-b2^t)/(1-b1^t);  p -= lr_t*m/(sqrt(v)+eps).
-    Dense parameters: one fused HIP launch each — or ONE launch for a whole registered flat group (the fused
-    train-step plans keep parameters and gradients of all dense layers in two contiguous buffers).
-    Packed embedding tables with a sparse gradient (MultiColumnEmbedding.sparse_grads): duplicate lookups merged
-    through a per-step hash of the row ids, then a row-sparse ("lazy") update of only the rows touched
-    this step — a documented deviation from Keras' dense semantics for tables too large to sweep every step.
-    The step counter and lr_t live on the device (dt_adam_advance), so a captured hipGraph of the step replays
-    with the right bias correction."""
+DT_ADAM_STATE_WORDS = 272 // 4        # DT_ADAM_STATE_BYTES (include/dt_hip.h) in int32 words
 
-    supports_row_segments = True      # takes SparseRowGrad.segments (dt_adam_rows_step_seg)
-    supports_rows_in_step = True      # a fused step may apply the update of the rows looked up once itself (fields = -2)
-    _name = 'Adam'
 
-    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        self.lr, self.b1, self.b2, self.eps = learning_rate, beta_1, beta_2, epsilon
+class _DeviceOptimizer:
+    """The step driver KerasAdam, Adagrad and RMSprop share.  One protocol — `zero_grad(flat=...)`, `step()`,
+    `register_flat_group`, `pre_dense_hook`, `state`, `t` — and one launch order: the dense tensors in one multi-tensor
+    launch (a registered flat group is ONE tensor: the fused train-step plans keep parameters and gradients of all dense
+    layers in two contiguous buffers), then one row launch per packed table with a sparse gradient
+    (MultiColumnEmbedding.sparse_grads), the last of which carries one dense update in its trailing blocks and advances the
+    step state.  The step counter (and Adam's lr_t) live on the device (dt_adam_state_init / dt_adam_advance), so a
+    captured hipGraph of the step replays with the right step.
+    A subclass names its slots (`slot_names`, `slot_init`), spells out its three library calls (`_dense_call`, `_multi_call`,
+    `_rows_call`) and, where a table's slots have a layout of their own, `_new_slot` / `_st`, `materialize` / `_restamp`."""
+
+    supports_row_segments = False     # takes SparseRowGrad.segments
+    supports_rows_in_step = False     # a fused step may apply the update of the rows looked up once itself (fields = -2)
+    slot_names = ()                   # the slots' names: their keys in `state[id(p)]` and in a checkpoint
+    slot_init = 0.0
+
+    def __init__(self, params, embedding_layers):
         self.params = [p for p in params if p.requires_grad]
         self.state = {}
         self.embedding_layers = list(embedding_layers)
@@ -249,15 +252,18 @@ class KerasAdam:
         # optional callable run right before the dense updates of a step (after the table updates were launched):
         # the data-parallel strategy uses it to wait for an all-reduce it started asynchronously
         self.pre_dense_hook = None
-        self._applied_in_step = False  # a fused step ran this step's whole update itself (applied_in_step)
-        self._flat = None             # (flat_param, flat_grad, m, v, n, {id(param): offset})
+        self._flat = None             # (flat_param, flat_grad, slot 0, slot 1 or None, n, {id(param): offset})
         self._flat_views = None       # [(param, grad view)] when gradients may be accumulated straight into flat_grad
+
+    def _betas(self):
+        """(beta_1, beta_2) of the bias correction the device state keeps (lr_t); none: (0, 0)"""
+        return 0.0, 0.0
 
     # -- step counter (device resident: int32 t_next, float lr_t, block-arrival counters) -----------------
     def _state_tensor(self, device):
         if self._dev_state is None:
-            self._dev_state = torch.zeros(68, dtype=torch.int32, device=device)     # DT_ADAM_STATE_BYTES / 4
-            check(lib().dt_adam_state_init(ptr(self._dev_state), self.lr, self.b1, self.b2, 0, stream_ptr()),
+            self._dev_state = torch.zeros(DT_ADAM_STATE_WORDS, dtype=torch.int32, device=device)
+            check(lib().dt_adam_state_init(ptr(self._dev_state), self.lr, *self._betas(), 0, stream_ptr()),
                   'dt_adam_state_init')
         return self._dev_state
 
@@ -268,37 +274,38 @@ class KerasAdam:
 
     @t.setter
     def t(self, value):
-        if self._dev_state is None:
-            if not self.params:
-                return
-            self._state_tensor(self.params[0].device)
-        check(lib().dt_adam_state_init(ptr(self._dev_state), self.lr, self.b1, self.b2, int(value), stream_ptr()),
-              'dt_adam_state_init')
+        if not self.params:
+            return
+        self.materialize()                 # pending decay belongs to the old step count
+        check(lib().dt_adam_state_init(ptr(self._state_tensor(self.params[0].device)), self.lr, *self._betas(), int(value),
+                                       stream_ptr()), 'dt_adam_state_init')
+        self._restamp()
+
+    def materialize(self):
+        """make every slot Keras' slot (RMSprop applies the decay pending on the rows of its row-sparse tables)"""
+
+    def _restamp(self):
+        pass
+
+    # -- slots --------------------------------------------------------------------------------------------
+    def _new_slot(self, p, rows):
+        return {k: torch.full_like(p, self.slot_init) for k in self.slot_names}
 
     def _st(self, p, rows=False):
-        """slots of parameter p.  rows=True (the row-sparse table update): m and v of a row side by side in ONE
-        [V, 2, D] array (a 128-byte line at D = 16), so the update touches two random locations per row instead of
-        three; `m` / `v` are its strided views.  The dense update needs contiguous slots and converts back."""
+        """slots of parameter p.  rows=True: in the layout of the row-sparse table update"""
         s = self.state.get(id(p))
         if s is None:
-            if rows and p.dim() == 2:
-                mv = torch.zeros((p.shape[0], 2, p.shape[1]), dtype=p.dtype, device=p.device)
-                s = {'m': mv[:, 0, :], 'v': mv[:, 1, :], 'mv': mv}
-            else:
-                s = {'m': torch.zeros_like(p), 'v': torch.zeros_like(p)}
-            self.state[id(p)] = s
-        elif not rows and 'mv' in s:
-            s = {'m': s['m'].contiguous(), 'v': s['v'].contiguous()}
+            s = self._new_slot(p, rows and p.dim() == 2)
             self.state[id(p)] = s
         return s
 
     def register_flat_group(self, flat_param, flat_grad, members, n, grad_views=False):
         """members: [(param, offset, numel[, (shape, strides)])] whose .data are views of flat_param and whose fused-plan
         gradients are the matching views of flat_grad (contiguous unless shape / strides are given: a fused plan keeps
-        narrow towers inside zero-padded slabs).  Their m/v become the same views of one flat m/v (existing state is kept).
-        grad_views=True: `zero_grad()` zeroes flat_grad and hands its views out as `.grad` (generic autograd path)."""
-        m = torch.zeros_like(flat_param)
-        v = torch.zeros_like(flat_param)
+        narrow towers inside zero-padded slabs).  Their slots become the same views of one flat buffer per slot (existing
+        state is kept).  grad_views=True: `zero_grad()` zeroes flat_grad and hands its views out as `.grad` (generic
+        autograd path)."""
+        slots = [torch.full_like(flat_param, self.slot_init) for _ in self.slot_names]
 
         def view_of(flat, p, off, cnt, layout):
             if layout is None:
@@ -307,12 +314,13 @@ class KerasAdam:
         members = [(mb[0], mb[1], mb[2], mb[3] if len(mb) > 3 else None) for mb in members]
         for p, off, cnt, layout in members:
             old = self.state.get(id(p))
-            mv, vv = view_of(m, p, off, cnt, layout), view_of(v, p, off, cnt, layout)
+            new = {k: view_of(flat, p, off, cnt, layout) for k, flat in zip(self.slot_names, slots)}
             if old is not None:
-                mv.copy_(old['m'].reshape(p.shape))
-                vv.copy_(old['v'].reshape(p.shape))
-            self.state[id(p)] = {'m': mv, 'v': vv}
-        self._flat = (flat_param, flat_grad, m, v, int(n), {id(p): off for p, off, _, _ in members})
+                for k, view in new.items():
+                    view.copy_(old[k].reshape(p.shape))
+            self.state[id(p)] = new
+        self._flat = (flat_param, flat_grad, slots[0], slots[1] if len(slots) > 1 else None, int(n),
+                      {id(p): off for p, off, _, _ in members})
         self._flat_views = [(p, view_of(flat_grad, p, off, cnt, layout)) for p, off, cnt, layout in members] \
             if grad_views else None
         for p, off, cnt, layout in members:
@@ -321,49 +329,15 @@ class KerasAdam:
             for p, view in self._flat_views:
                 p._dt_grad_view = view
 
-    def _flat_member_views(self):
-        """{id(param): the parameter's view of the flat GRADIENT buffer} (same offset / shape / strides as its data)"""
+    def _flat_grad_view(self, p):
+        """flat-group member p's view of the flat GRADIENT buffer (same offset / shape / strides as its data)"""
         fp, fg = self._flat[0], self._flat[1]
-        out = {}
-        for p in self.params:
-            if id(p) in self._flat[5]:
-                off = (p.data.data_ptr() - fp.data_ptr()) // 4
-                out[id(p)] = torch.as_strided(fg, tuple(p.data.shape), tuple(p.data.stride()), off)
-        return out
-
-    def _dense_launch(self, dense, sp, st, advance):
-        """All dense tensors of the step in one launch (dt_adam_multi_step; chunks of 32 tensors)."""
-        if not dense:
-            return
-        if len(dense) == 1:
-            pp, gg, mm, vv, n = dense[0]
-            check(lib().dt_adam_dense_step(ptr(pp), ptr(gg), ptr(mm), ptr(vv), n, 0.0, self.b1, self.b2, self.eps,
-                                           sp, 1 if advance else 0, self.lr, st), 'dt_adam_dense_step')
-            return
-        import ctypes
-        T = len(dense)
-        arr = ctypes.c_void_p * T
-        ps, gs, ms, vs = (arr(*[t[k].data_ptr() for t in dense]) for k in range(4))
-        ns = (ctypes.c_int64 * T)(*[int(t[4]) for t in dense])
-        check(lib().dt_adam_multi_step(T, ctypes.cast(ps, ctypes.c_void_p), ctypes.cast(gs, ctypes.c_void_p),
-                                       ctypes.cast(ms, ctypes.c_void_p), ctypes.cast(vs, ctypes.c_void_p),
-                                       ctypes.cast(ns, ctypes.c_void_p), 0.0, self.b1, self.b2, self.eps, sp,
-                                       1 if advance else 0, self.lr, st), 'dt_adam_multi_step')
+        return torch.as_strided(fg, tuple(p.data.shape), tuple(p.data.stride()), (p.data.data_ptr() - fp.data_ptr()) // 4)
 
     def zero_grad(self, flat=True):
         """flat=True: members of the registered flat group get their (zeroed) views of the flat gradient buffer as
         `.grad` — backward kernels and autograd accumulate straight into it; flat=False: the caller (a fused step)
         fills the flat buffer itself."""
-        # _forward_backward(apply_rows=True) is a promise that step() follows at once: the rows looked up once were already
-        # updated inside the step.  A gradient of that kind still pending here means the promise was broken (the segments and
-        # the dense parameters never got their half of the update): fail loudly instead of training on half-applied steps
-        if not self._applied_in_step:
-            for layer in self.embedding_layers:
-                for grads in layer.sparse_grads.values():
-                    if any(getattr(g, 'fields', None) == -2 for g in grads):
-                        raise RuntimeError('_forward_backward(apply_rows=True) was not followed by optimizer.step(): the '
-                                           'table rows looked up once are updated, the segments and dense parameters are not')
-        self._applied_in_step = False
         for p in self.params:
             p.grad = None
         if flat and self._flat is not None and self._flat_views is not None:
@@ -373,69 +347,73 @@ class KerasAdam:
         for layer in self.embedding_layers:
             layer.sparse_grads.clear()
 
-    def applied_in_step(self):
-        """A fused train step (fused.FusedDeepFM with dt_deepfm_train_step_adam) has applied THIS step's whole update —
-        table rows, segments, every dense element — and advanced the device step state inside its own launches: the
-        `step()` call that follows only drops the gradients."""
-        self._applied_in_step = True
+    # -- the three launches, by optimizer.  ss: one entry per slot; tail: a dense item, (None, None, (None, ..), 0) for none --
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        raise NotImplementedError
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        raise NotImplementedError
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
+        raise NotImplementedError
+
+    def _dense_launch(self, dense, sp, st, advance):
+        """All dense tensors of the step in one launch (the library takes them in chunks of 32 tensors)."""
+        if not dense:
+            return
+        if len(dense) == 1:
+            pp, gg, ss, n = dense[0]
+            self._dense_call(pp, gg, ss, n, sp, 1 if advance else 0, st)
+            return
+        T = len(dense)
+        arr = ctypes.c_void_p * T
+        cols = [[d[0] for d in dense], [d[1] for d in dense]] + [[d[2][k] for d in dense] for k in range(len(self.slot_names))]
+        ps, gs, *ss = (ctypes.cast(arr(*[t.data_ptr() for t in col]), ctypes.c_void_p) for col in cols)
+        ns = ctypes.cast((ctypes.c_int64 * T)(*[int(d[3]) for d in dense]), ctypes.c_void_p)
+        self._multi_call(T, ps, gs, ss, ns, sp, 1 if advance else 0, st)
 
     def step(self):
         if not self.params:
             return
-        if self._applied_in_step:
-            self._applied_in_step = False
-            for layer in self.embedding_layers:
-                layer.sparse_grads.clear()
-            return
-        dev_state = self._state_tensor(self.params[0].device)
+        sp = ptr(self._state_tensor(self.params[0].device))
         st = stream_ptr()
-        sp = ptr(dev_state)
-        # every launch of the step reads lr_t from the device state; the LAST one advances it (no extra launch)
-        dense = []                                        # (param, grad, m, v, n)
+        # every launch of the step reads the device state; the LAST one advances it (no extra launch)
+        dense = []                                        # (param, grad, (slot, ..), n)
         flat_done = set()
         if self._flat is not None:
-            fp, fg, fm, fv, n, members = self._flat
-            base = fg.data_ptr()
-            in_flat = [p for p in self.params if id(p) in members and p.grad is not None and
-                       p.grad.data_ptr() == base + 4 * members[id(p)]]
-            if len(in_flat) == len(members):       # every member's gradient is its flat view: one launch
-                dense.append((fp, fg, fm, fv, n))
-                flat_done = set(members)
-            else:
-                # gradients that are NOT the flat views (the layer-by-layer path after a fused plan re-homed the
-                # parameters: a weighted step, DT_AMD_FUSED toggled, ...).  Members of a plan with a narrow tower are
-                # STRIDED views of zero-padded slabs (fused._mirror_in_flat), so the per-tensor kernels — which take
-                # (pointer, numel) — must not see them: scatter every member's gradient into its place of the flat
-                # gradient buffer and update the whole group with the one flat launch.  Pads have zero gradient and
-                # zero moments: they stay exactly zero.
-                with_grad = [p for p in self.params if id(p) in members and p.grad is not None]
-                if len(with_grad) == len(members):
-                    views = self._flat_member_views()
+            fp, fg, fs0, fs1, n, members = self._flat
+            with_grad = [p for p in self.params if id(p) in members and p.grad is not None]
+            if len(with_grad) == len(members):
+                # gradients that are NOT the members' views of the flat gradient buffer (the layer-by-layer path after a
+                # fused plan re-homed the parameters: a weighted step, DT_AMD_FUSED toggled, ...) are scattered into it:
+                # members of a plan with a narrow tower are STRIDED views of zero-padded slabs (fused._mirror_in_flat),
+                # which the per-tensor kernels — they take (pointer, numel) — must not see one by one.  Pads have a zero
+                # gradient (and zero moments): they stay exactly as they are.
+                in_flat = {id(p) for p in with_grad if p.grad.data_ptr() == fg.data_ptr() + 4 * members[id(p)]}
+                if len(in_flat) != len(members):
                     if not in_flat:
                         fg.zero_()
-                    flat_ids = {id(p) for p in in_flat}
                     for p in with_grad:
-                        if id(p) not in flat_ids:
-                            views[id(p)].copy_(p.grad.reshape(views[id(p)].shape))
-                    dense.append((fp, fg, fm, fv, n))
-                    flat_done = set(members)
+                        if id(p) not in in_flat:
+                            view = self._flat_grad_view(p)
+                            view.copy_(p.grad.reshape(view.shape))
+                dense.append((fp, fg, (fs0,) if fs1 is None else (fs0, fs1), n))       # one launch
+                flat_done = set(members)
         deferred = []                                     # (param, slots, contiguous copies) of strided tensors
         for p in self.params:
             if p.grad is None or id(p) in flat_done:
                 continue
             s = self._st(p)
-            if p.data.is_contiguous() and s['m'].is_contiguous() and s['v'].is_contiguous():
-                dense.append((p.data, p.grad.contiguous(), s['m'], s['v'], p.numel()))
+            ss = tuple(s[k] for k in self.slot_names)
+            if p.data.is_contiguous() and all(x.is_contiguous() for x in ss):
+                dense.append((p.data, p.grad.contiguous(), ss, p.numel()))
             else:
                 # a strided parameter / slot on its own (only some members of a flat group carry a gradient): update
                 # contiguous copies and write them back after the launches below
-                pc, mc, vc = p.data.contiguous(), s['m'].contiguous(), s['v'].contiguous()
-                dense.append((pc, p.grad.contiguous(), mc, vc, p.numel()))
-                deferred.append((p, s, pc, mc, vc))
-        sparse = []
-        for layer in self.embedding_layers:
-            for key, grads in layer.sparse_grads.items():
-                sparse.append((layer, key, grads))
+                pc, sc = p.data.contiguous(), tuple(x.contiguous() for x in ss)
+                dense.append((pc, p.grad.contiguous(), sc, p.numel()))
+                deferred.append((p, ss, pc, sc))
+        sparse = [(layer, key, grads) for layer in self.embedding_layers for key, grads in layer.sparse_grads.items()]
         # launch order: dense updates that cannot ride along, then the table updates; the last table update carries
         # one dense update (normally the model's flat buffer) in its trailing blocks and advances the state
         hook, self.pre_dense_hook = self.pre_dense_hook, None
@@ -446,11 +424,15 @@ class KerasAdam:
         if not dense_after:
             self._dense_launch(dense, sp, st, advance=not sparse)
         if not sparse and not dense:
-            check(lib().dt_adam_advance(sp, self.lr, self.b1, self.b2, st), 'dt_adam_advance')
+            check(lib().dt_adam_advance(sp, self.lr, *self._betas(), st), 'dt_adam_advance')
         for i, (layer, key, grads) in enumerate(sparse):
             table = layer.tables[key]
             s = self._st(table, rows=True)
             D = table.shape[1]
+            segmented = any(getattr(g, 'segments', None) is not None for g in grads)
+            in_step = any(getattr(g, 'fields', None) == -2 for g in grads)
+            if (segmented and not self.supports_row_segments) or (in_step and not self.supports_rows_in_step):
+                raise ValueError(f'{self._name}: a sparse gradient with segments or rows applied inside the step')
             if len(grads) == 1:
                 rows, values = grads[0].rows, grads[0].values
             else:
@@ -478,26 +460,98 @@ class KerasAdam:
                     s['n_slots'] = n_slots
                 slots, mark, n_slots = s['slots'], s['mark'], s['n_slots']
             is_last = i == len(sparse) - 1 and not (dense_after and dense)
-            tl = tail if (is_last and tail is not None) else (None, None, None, None, 0)
-            seg = grads[0].segments if (len(grads) == 1 and getattr(grads[0], 'segments', None) is not None) else None
-            if seg is None and any(getattr(g, 'segments', None) is not None for g in grads):
+            tl = tail if (is_last and tail is not None) else (None, None, (None,) * len(self.slot_names), 0)
+            seg = grads[0].segments if (segmented and len(grads) == 1) else None
+            if segmented and seg is None:
                 raise ValueError('a segmented sparse gradient cannot be concatenated with other pieces')
-            sg = [ptr(t) for t in seg[:5]] + [int(seg[5]), int(seg[6])] if seg is not None else [None] * 5 + [0, 0]
-            check(lib().dt_adam_rows_step_seg(ptr(table.data), ptr(s['m']), ptr(s['v']), ptr(rows), ptr(values), n,
-                                              D, fields, ptr(slots), n_slots, ptr(mark), 0.0,
-                                              self.b1, self.b2, self.eps, sp, ptr(tl[0]), ptr(tl[1]), ptr(tl[2]),
-                                              ptr(tl[3]), tl[4], 1 if is_last else 0, self.lr, *sg,
-                                              int(s['m'].stride(0)), st),
-                  'dt_adam_rows_step_seg')
+            self._rows_call(table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tl, 1 if is_last else 0, seg, st)
         if dense_after:
             hook()
             self._dense_launch(dense, sp, st, advance=True)
-        for p, s, pc, mc, vc in deferred:
+        for p, ss, pc, sc in deferred:
             p.data.copy_(pc)
-            s['m'].copy_(mc)
-            s['v'].copy_(vc)
+            for x, xc in zip(ss, sc):
+                x.copy_(xc)
         for layer in self.embedding_layers:
             layer.sparse_grads.clear()
+
+
+class KerasAdam(_DeviceOptimizer):
+    """keras.optimizers.Adam(learning_rate=1e-3, beta_1=.9, beta_2=.999, epsilon=1e-7):
+        lr_t = lr*sqrt(1-b2^t)/(1-b1^t);  p -= lr_t*m/(sqrt(v)+eps).
+    Dense parameters: one fused HIP launch for all of them — or for a whole registered flat group.
+    Packed embedding tables with a sparse gradient: duplicate lookups merged through a per-step hash of the row ids, then
+    a row-sparse ("lazy") update of only the rows touched this step — a documented deviation from Keras' dense
+    semantics for tables too large to sweep every step."""
+
+    supports_row_segments = True      # dt_adam_rows_step_seg
+    supports_rows_in_step = True
+    slot_names = ('m', 'v')
+    _name = 'Adam'
+
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+        super().__init__(params, embedding_layers)
+        self.lr, self.b1, self.b2, self.eps = learning_rate, beta_1, beta_2, epsilon
+        self._applied_in_step = False  # a fused step ran this step's whole update itself (applied_in_step)
+
+    def _betas(self):
+        return self.b1, self.b2
+
+    def _new_slot(self, p, rows):
+        """rows (the row-sparse table update): m and v of a row side by side in ONE [V, 2, D] array (a 128-byte line at
+        D = 16), so the update touches two random locations per row instead of three; `m` / `v` are its strided views."""
+        if not rows:
+            return super()._new_slot(p, rows)
+        mv = torch.zeros((p.shape[0], 2, p.shape[1]), dtype=p.dtype, device=p.device)
+        return {'m': mv[:, 0, :], 'v': mv[:, 1, :], 'mv': mv}
+
+    def _st(self, p, rows=False):
+        s = self.state.get(id(p))
+        if s is not None and not rows and 'mv' in s:          # the dense update needs contiguous slots: convert back
+            self.state[id(p)] = {'m': s['m'].contiguous(), 'v': s['v'].contiguous()}
+        return super()._st(p, rows)
+
+    def zero_grad(self, flat=True):
+        # _forward_backward(apply_rows=True) is a promise that step() follows at once: the rows looked up once were already
+        # updated inside the step.  A gradient of that kind still pending here means the promise was broken (the segments and
+        # the dense parameters never got their half of the update): fail loudly instead of training on half-applied steps
+        if not self._applied_in_step:
+            for layer in self.embedding_layers:
+                for grads in layer.sparse_grads.values():
+                    if any(getattr(g, 'fields', None) == -2 for g in grads):
+                        raise RuntimeError('_forward_backward(apply_rows=True) was not followed by optimizer.step(): the '
+                                           'table rows looked up once are updated, the segments and dense parameters are not')
+        self._applied_in_step = False
+        super().zero_grad(flat)
+
+    def applied_in_step(self):
+        """A fused train step (fused.FusedDeepFM with dt_deepfm_train_step_adam) has applied THIS step's whole update —
+        table rows, segments, every dense element — and advanced the device step state inside its own launches: the
+        `step()` call that follows only drops the gradients."""
+        self._applied_in_step = True
+
+    def step(self):
+        if self.params and self._applied_in_step:
+            self._applied_in_step = False
+            for layer in self.embedding_layers:
+                layer.sparse_grads.clear()
+            return
+        super().step()
+
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_adam_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, 0.0, self.b1, self.b2, self.eps, sp, advance,
+                                       self.lr, st), 'dt_adam_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_adam_multi_step(T, ps, gs, ss[0], ss[1], ns, 0.0, self.b1, self.b2, self.eps, sp, advance, self.lr, st),
+              'dt_adam_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
+        sg = [ptr(t) for t in seg[:5]] + [int(seg[5]), int(seg[6])] if seg is not None else [None] * 5 + [0, 0]
+        check(lib().dt_adam_rows_step_seg(ptr(table.data), ptr(s['m']), ptr(s['v']), ptr(rows), ptr(values), n, D, fields,
+                                          ptr(slots), n_slots, ptr(mark), 0.0, self.b1, self.b2, self.eps, sp, ptr(tail[0]),
+                                          ptr(tail[1]), ptr(tail[2][0]), ptr(tail[2][1]), tail[3], advance, self.lr, *sg,
+                                          int(s['m'].stride(0)), st), 'dt_adam_rows_step_seg')
 
 
 class SGD:
@@ -530,54 +584,16 @@ class SGD:
             layer.sparse_grads.clear()
 
 
-class _SlotOptimizer:
-    """What keras.optimizers.Adagrad and RMSprop (momentum 0) share: ONE slot per element and no bias correction.  The
-    protocol is KerasAdam's — `zero_grad(flat=...)`, `step()`, `register_flat_group`, `pre_dense_hook`, `state`, `t` — and so
-    is the launch order of a step: the dense tensors in one multi-tensor launch, then one row launch per packed table with a
-    sparse gradient, the last of which carries one dense update and advances the device-resident step counter.
-    Unlike Adam's, the row-sparse update IS Keras' result (a row that was not looked up has a zero gradient and does not
-    move).  The fused DeepFM / DCN plans run forward + backward and leave the whole update to `step()`, as they do for SGD."""
-
-    supports_row_segments = False     # the row entry points take no segments: the fused plans hand over plain (rows, values)
-    supports_rows_in_step = False
-    slot_names = ()                   # (the slot's name,): its key in `state[id(p)]` and in a checkpoint
-    slot_init = 0.0
+class _SlotOptimizer(_DeviceOptimizer):
+    """What keras.optimizers.Adagrad and RMSprop (momentum 0) share beyond the step driver: ONE slot per element, no bias
+    correction, and hyperparameters that travel with a checkpoint.  Unlike Adam's, their row-sparse update IS Keras' result
+    (a row that was not looked up has a zero gradient and does not move).  The row entry points take no segments: the fused
+    DeepFM / DCN plans run forward + backward, hand over plain (rows, values) and leave the whole update to `step()`, as
+    they do for SGD."""
 
     def __init__(self, params, embedding_layers, learning_rate, epsilon):
+        super().__init__(params, embedding_layers)
         self.lr, self.eps = float(learning_rate), float(epsilon)
-        self.params = [p for p in params if p.requires_grad]
-        self.state = {}
-        self.embedding_layers = list(embedding_layers)
-        self._dev_state = None        # device-resident step state (DT_ADAM_STATE_BYTES; t and the arrival counters)
-        self.pre_dense_hook = None    # as KerasAdam's: run right before the dense updates of a step
-        self._flat = None             # (flat_param, flat_grad, flat slot, None, n, {id(param): offset})
-        self._flat_views = None
-
-    def _state_tensor(self, device):
-        if self._dev_state is None:
-            self._dev_state = torch.zeros(68, dtype=torch.int32, device=device)     # DT_ADAM_STATE_BYTES / 4
-            check(lib().dt_adam_state_init(ptr(self._dev_state), self.lr, 0.0, 0.0, 0, stream_ptr()), 'dt_adam_state_init')
-        return self._dev_state
-
-    @property
-    def t(self):
-        """number of completed steps (keras `optimizer.iterations`)"""
-        return 0 if self._dev_state is None else int(self._dev_state[0].item()) - 1
-
-    @t.setter
-    def t(self, value):
-        if not self.params:
-            return
-        self.materialize()                 # pending decay belongs to the old step count
-        check(lib().dt_adam_state_init(ptr(self._state_tensor(self.params[0].device)), self.lr, 0.0, 0.0, int(value),
-                                       stream_ptr()), 'dt_adam_state_init')
-        self._restamp()
-
-    def materialize(self):
-        """make every slot Keras' slot (RMSprop applies the decay pending on the rows of its row-sparse tables)"""
-
-    def _restamp(self):
-        pass
 
     def slot(self, p):
         """the slot of parameter p as Keras holds it (shape of p), or None before p's first update"""
@@ -590,169 +606,6 @@ class _SlotOptimizer:
 
     def set_hyperparameters(self, hp):
         self.lr, self.eps = float(hp.get('learning_rate', self.lr)), float(hp.get('epsilon', self.eps))
-
-    def _new_slot(self, p, rows):
-        return {self.slot_names[0]: torch.full_like(p, self.slot_init)}
-
-    def _st(self, p, rows=False):
-        """slot of parameter p.  rows=True: the layout of the row-sparse table update (Adagrad: the same [V, D] array)"""
-        s = self.state.get(id(p))
-        if s is None:
-            s = self._new_slot(p, rows and p.dim() == 2)
-            self.state[id(p)] = s
-        return s
-
-    def register_flat_group(self, flat_param, flat_grad, members, n, grad_views=False):
-        """KerasAdam.register_flat_group with one slot: the members' slots become views of one flat slot buffer"""
-        key = self.slot_names[0]
-        flat_slot = torch.full_like(flat_param, self.slot_init)
-
-        def view_of(flat, p, off, cnt, layout):
-            if layout is None:
-                return flat[off:off + cnt].view(p.shape)
-            return torch.as_strided(flat, layout[0], layout[1], off)
-        members = [(mb[0], mb[1], mb[2], mb[3] if len(mb) > 3 else None) for mb in members]
-        for p, off, cnt, layout in members:
-            old = self.state.get(id(p))
-            sv = view_of(flat_slot, p, off, cnt, layout)
-            if old is not None:
-                sv.copy_(old[key].reshape(p.shape))
-            self.state[id(p)] = {key: sv}
-        self._flat = (flat_param, flat_grad, flat_slot, None, int(n), {id(p): off for p, off, _, _ in members})
-        self._flat_views = [(p, view_of(flat_grad, p, off, cnt, layout)) for p, off, cnt, layout in members] \
-            if grad_views else None
-        for p, off, cnt, layout in members:
-            p._dt_grad_view = None
-        if grad_views:
-            for p, view in self._flat_views:
-                p._dt_grad_view = view
-
-    def zero_grad(self, flat=True):
-        for p in self.params:
-            p.grad = None
-        if flat and self._flat is not None and self._flat_views is not None:
-            self._flat[1].zero_()
-            for p, view in self._flat_views:
-                p.grad = view
-        for layer in self.embedding_layers:
-            layer.sparse_grads.clear()
-
-    # the three launches, by optimizer
-    def _dense_call(self, p, g, s, n, sp, advance, st):
-        raise NotImplementedError
-
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        raise NotImplementedError
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
-        raise NotImplementedError
-
-    def _dense_launch(self, dense, sp, st, advance):
-        """All dense tensors of the step in one launch (chunks of 32 tensors)."""
-        if not dense:
-            return
-        if len(dense) == 1:
-            pp, gg, ss, n = dense[0]
-            self._dense_call(pp, gg, ss, n, sp, 1 if advance else 0, st)
-            return
-        import ctypes
-        T = len(dense)
-        arr = ctypes.c_void_p * T
-        ps, gs, ss = (ctypes.cast(arr(*[t[k].data_ptr() for t in dense]), ctypes.c_void_p) for k in range(3))
-        ns = ctypes.cast((ctypes.c_int64 * T)(*[int(t[3]) for t in dense]), ctypes.c_void_p)
-        self._multi_call(T, ps, gs, ss, ns, sp, 1 if advance else 0, st)
-
-    def step(self):
-        if not self.params:
-            return
-        key = self.slot_names[0]
-        sp = ptr(self._state_tensor(self.params[0].device))
-        st = stream_ptr()
-        dense = []                                        # (param, grad, slot, n)
-        flat_done = set()
-        if self._flat is not None:
-            fp, fg, fs, _, n, members = self._flat
-            with_grad = [p for p in self.params if id(p) in members and p.grad is not None]
-            if len(with_grad) == len(members):
-                # gradients that are not the members' views of the flat gradient buffer (the layer-by-layer path after a
-                # fused plan re-homed the parameters) are scattered into it: members of a plan with a narrow tower are
-                # strided views of zero-padded slabs, which the (pointer, numel) kernels must not see one by one.  Pads
-                # have a zero gradient: they stay exactly zero.
-                in_flat = {id(p) for p in with_grad if p.grad.data_ptr() == fg.data_ptr() + 4 * members[id(p)]}
-                if len(in_flat) != len(members):
-                    if not in_flat:
-                        fg.zero_()
-                    for p in with_grad:
-                        if id(p) not in in_flat:
-                            view = torch.as_strided(fg, tuple(p.data.shape), tuple(p.data.stride()),
-                                                    (p.data.data_ptr() - fp.data_ptr()) // 4)
-                            view.copy_(p.grad.reshape(view.shape))
-                dense.append((fp, fg, fs, n))
-                flat_done = set(members)
-        deferred = []                                     # (param, slot, contiguous copies) of strided tensors
-        for p in self.params:
-            if p.grad is None or id(p) in flat_done:
-                continue
-            s = self._st(p)[key]
-            if p.data.is_contiguous() and s.is_contiguous():
-                dense.append((p.data, p.grad.contiguous(), s, p.numel()))
-            else:
-                pc, sc = p.data.contiguous(), s.contiguous()
-                dense.append((pc, p.grad.contiguous(), sc, p.numel()))
-                deferred.append((p, s, pc, sc))
-        sparse = [(layer, k, grads) for layer in self.embedding_layers for k, grads in layer.sparse_grads.items()]
-        # launch order (KerasAdam.step): dense updates that cannot ride along, then the table updates; the last table
-        # update carries one dense update in its trailing blocks and advances the step counter
-        hook, self.pre_dense_hook = self.pre_dense_hook, None
-        dense_after = hook is not None and bool(sparse)     # table updates first, overlapping the pending reduce
-        tail = dense.pop(0) if (sparse and dense and not dense_after) else None
-        if hook is not None and not dense_after:
-            hook()
-        if not dense_after:
-            self._dense_launch(dense, sp, st, advance=not sparse)
-        if not sparse and not dense:
-            check(lib().dt_adam_advance(sp, self.lr, 0.0, 0.0, st), 'dt_adam_advance')
-        for i, (layer, k, grads) in enumerate(sparse):
-            table = layer.tables[k]
-            s = self._st(table, rows=True)
-            D = table.shape[1]
-            if any(getattr(g, 'segments', None) is not None or getattr(g, 'fields', None) == -2 for g in grads):
-                raise ValueError(f'{self._name}: a sparse gradient with segments or rows applied inside the step')
-            if len(grads) == 1:
-                rows, values = grads[0].rows, grads[0].values
-            else:
-                rows = torch.cat([g.rows.reshape(-1) for g in grads])
-                values = torch.cat([g.values.reshape(-1, D) for g in grads])
-            n = rows.numel()
-            fields = len(dict(layer.groups)[D]) if hasattr(layer, 'groups') else 0
-            hints = {getattr(g, 'fields', None) for g in grads}
-            if hints != {None}:                           # an explicit layout promise overrides the layer default
-                fields = hints.pop() if len(hints) == 1 else 0
-                fields = 0 if fields is None else int(fields)
-            if fields == -1 and len(grads) != 1:
-                fields = 0                                # distinct within each piece only
-            values = values if values.is_contiguous() else values.contiguous()
-            if fields == -1:
-                slots = mark = None
-                n_slots = 0
-            else:
-                n_slots = lib().dt_adam_rows_slots(n)
-                if s.get('n_slots', 0) < n_slots or s['mark'].numel() < n:
-                    s['slots'] = torch.zeros(n_slots, dtype=torch.int64, device=table.device)
-                    s['mark'] = torch.empty(n, dtype=torch.int32, device=table.device)
-                    s['n_slots'] = n_slots
-                slots, mark, n_slots = s['slots'], s['mark'], s['n_slots']
-            is_last = i == len(sparse) - 1 and not (dense_after and dense)
-            tl = tail if (is_last and tail is not None) else (None, None, None, 0)
-            self._rows_call(table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tl, 1 if is_last else 0, st)
-        if dense_after:
-            hook()
-            self._dense_launch(dense, sp, st, advance=True)
-        for p, s, pc, sc in deferred:
-            p.data.copy_(pc)
-            s.copy_(sc)
-        for layer in self.embedding_layers:
-            layer.sparse_grads.clear()
 
 
 class Adagrad(_SlotOptimizer):
@@ -773,17 +626,17 @@ class Adagrad(_SlotOptimizer):
     def hyperparameters(self):
         return dict(super().hyperparameters(), initial_accumulator_value=self.initial_accumulator_value)
 
-    def _dense_call(self, p, g, s, n, sp, advance, st):
-        check(lib().dt_adagrad_dense_step(ptr(p), ptr(g), ptr(s), n, self.lr, self.eps, sp, advance, st),
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_adagrad_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, self.lr, self.eps, sp, advance, st),
               'dt_adagrad_dense_step')
 
     def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_adagrad_multi_step(T, ps, gs, ss, ns, self.lr, self.eps, sp, advance, st), 'dt_adagrad_multi_step')
+        check(lib().dt_adagrad_multi_step(T, ps, gs, ss[0], ns, self.lr, self.eps, sp, advance, st), 'dt_adagrad_multi_step')
 
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
         acc = s['acc']
         check(lib().dt_adagrad_rows_step(ptr(table.data), ptr(acc), ptr(rows), ptr(values), n, D, fields, ptr(slots), n_slots,
-                                         ptr(mark), self.lr, self.eps, sp, ptr(tail[0]), ptr(tail[1]), ptr(tail[2]), tail[3],
+                                         ptr(mark), self.lr, self.eps, sp, ptr(tail[0]), ptr(tail[1]), ptr(tail[2][0]), tail[3],
                                          advance, int(acc.stride(0)), st), 'dt_adagrad_rows_step')
 
 
@@ -818,7 +671,7 @@ class RMSprop(_SlotOptimizer):
 
     def _new_slot(self, p, rows):
         if not rows:
-            return {'rms': torch.zeros_like(p)}
+            return super()._new_slot(p, rows)
         V, D = p.shape
         if self.stamp_in_record:
             rec = torch.zeros((V, D + 4), dtype=p.dtype, device=p.device)
@@ -858,19 +711,19 @@ class RMSprop(_SlotOptimizer):
             if s is not None and 'stamp' in s:
                 s['stamp'].copy_((self._dev_state[:1] - 1).expand(p.shape[0]))
 
-    def _dense_call(self, p, g, s, n, sp, advance, st):
-        check(lib().dt_rmsprop_dense_step(ptr(p), ptr(g), ptr(s), n, self.lr, self.rho, self.eps, sp, advance, st),
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_rmsprop_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, self.lr, self.rho, self.eps, sp, advance, st),
               'dt_rmsprop_dense_step')
 
     def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_rmsprop_multi_step(T, ps, gs, ss, ns, self.lr, self.rho, self.eps, sp, advance, st),
+        check(lib().dt_rmsprop_multi_step(T, ps, gs, ss[0], ns, self.lr, self.rho, self.eps, sp, advance, st),
               'dt_rmsprop_multi_step')
 
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, st):
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
         rms, stamp = s['rms'], s['stamp']
         check(lib().dt_rmsprop_rows_step(ptr(table.data), ptr(rms), ptr(stamp), ptr(rows), ptr(values), n, D, fields,
                                          ptr(slots), n_slots, ptr(mark), self.lr, self.rho, self.eps, sp, ptr(tail[0]),
-                                         ptr(tail[1]), ptr(tail[2]), tail[3], advance, int(rms.stride(0)),
+                                         ptr(tail[1]), ptr(tail[2][0]), tail[3], advance, int(rms.stride(0)),
                                          int(stamp.stride(0)), st), 'dt_rmsprop_rows_step')
 
 

@@ -545,3 +545,65 @@ def test_flat_dense_parameters_train_like_separate_tensors(dev, monkeypatch, opt
         models.append(dm)
     for (n0, p0), (_, p1) in zip(models[0].model.named_parameters(), models[1].model.named_parameters()):
         assert (p0 - p1).abs().max().item() <= W_BAR, n0
+
+
+@pytest.mark.parametrize('kind', ['adam', 'adagrad', 'rmsprop'])
+def test_flat_group_paths_equal_independent_tensors(dev, kind):
+    """A flat group of three members — [4, 6] (24 elements), [5, 8] (40) as a strided view inside a zero-padded [5, 16] slab,
+    [7] — registered once with grad_views=True, against the same parameters held as independent tensors under the same
+    optimizer, fed the same gradients.  Two steps each of: the gradients ARE the flat views (one flat launch); the
+    gradients are separate tensors (scattered into the flat gradient buffer, one flat launch); only the strided member has
+    a gradient (contiguous copies updated on their own and written back).  The update is element-wise, so after every step
+    parameters and slots are equal bit for bit (as test_multi_tensor_launch_equals_single_launches holds the multi launch
+    to the single ones), and what lies between the members — parameter and slots — keeps exactly its initial value."""
+    from deeptables_amd import training as T
+    g = torch.Generator().manual_seed(11)
+    keys = {'adam': ('m', 'v'), 'adagrad': ('acc',), 'rmsprop': ('rms',)}[kind]
+    make = (lambda ps: T.KerasAdam(ps)) if kind == 'adam' else (lambda ps: _make(kind, ps))
+    layout = ((5, 8), (16, 1))
+    specs = [((4, 6), 0, 24, None), ((5, 8), 64, 40, layout), ((7,), 144, 7, None)]
+    n_flat = 192
+    flat_p = torch.zeros(n_flat, device=dev)
+    flat_g = torch.zeros(n_flat, device=dev)
+    between = torch.ones(n_flat, dtype=torch.bool, device=dev)
+    members, twins = [], []
+    for shape, off, cnt, lay in specs:
+        w0 = torch.randn(shape, generator=g)
+        view = torch.as_strided(flat_p, lay[0], lay[1], off) if lay else flat_p[off:off + cnt].view(shape)
+        view.copy_(w0)
+        (torch.as_strided(between, lay[0], lay[1], off) if lay else between[off:off + cnt]).fill_(False)
+        p = torch.nn.Parameter(torch.empty(0, device=dev))
+        p.data = view
+        members.append((p, off, cnt, lay) if lay else (p, off, cnt))
+        twins.append(torch.nn.Parameter(w0.clone().to(dev)))
+    params = [mb[0] for mb in members]
+    assert not params[1].data.is_contiguous() and int(between.sum()) == n_flat - 71
+    opt, ref = make(params), make(twins)
+    opt.register_flat_group(flat_p, flat_g, members, n_flat, grad_views=True)
+    slot_init = [s.clone() for s in opt._flat[2:4] if s is not None]
+    for step, how in enumerate(('views', 'views', 'scatter', 'scatter', 'strided only', 'strided only')):
+        grads = [torch.randn(p.shape, generator=g).to(dev) * (3.0 if step % 2 else 0.1) for p in params]
+        before = [q.detach().clone() for q in twins]
+        opt.zero_grad(flat=how == 'views')
+        ref.zero_grad()
+        for i, (p, q, gr) in enumerate(zip(params, twins, grads)):
+            if how == 'strided only' and i != 1:
+                continue
+            if how == 'views':
+                assert p.grad is p._dt_grad_view
+                p.grad.copy_(gr)
+            else:
+                p.grad = gr.clone()
+            q.grad = gr.clone()
+        opt.step()
+        ref.step()
+        assert opt.t == ref.t == step + 1
+        for i, (p, q) in enumerate(zip(params, twins)):
+            assert torch.equal(p.detach(), q.detach()), (how, step, i)
+            for k in keys:
+                assert torch.equal(opt.state[id(p)][k], ref.state[id(q)][k]), (how, step, i, k)
+        assert float(flat_p[between].abs().max()) == 0.0, (how, step)
+        for s, s0 in zip([s for s in opt._flat[2:4] if s is not None], slot_init):
+            assert torch.equal(s[between], s0[between]), (how, step)
+        moved = [not torch.equal(q.detach(), q0) for q, q0 in zip(twins, before)]
+        assert moved == ([False, True, False] if how == 'strided only' else [True] * 3), (how, step)
