@@ -119,6 +119,23 @@ SIGNATURES = {
     'dt_rmsprop_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32,
                                       _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr]),
     'dt_rmsprop_rows_materialize': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_f32, _ptr, _ptr]),
+    # momentum SGD / Adamax / Ftrl (csrc/optim2.hip): dt_adagrad_*'s arguments, the second slot behind the first, the
+    # hyperparameters in place of (lr, eps): (lr, momentum, nesterov) / (lr, beta1, beta2, eps) / (lr, lr_power, l1, l2, l2_shrinkage)
+    'dt_sgdm_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_int, _ptr, _c_int, _ptr]),
+    'dt_sgdm_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _c_int, _ptr, _c_int, _ptr]),
+    'dt_sgdm_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32, _c_f32, _c_int,
+                                   _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr]),
+    'dt_adamax_dense_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
+    'dt_adamax_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _ptr, _c_int,
+                                      _ptr]),
+    'dt_adamax_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32, _c_f32,
+                                     _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr]),
+    'dt_ftrl_dense_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr, _c_int,
+                                    _ptr]),
+    'dt_ftrl_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _c_f32, _c_f32, _c_f32, _ptr, _c_int,
+                                    _ptr]),
+    'dt_ftrl_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32, _c_f32,
+                                   _c_f32, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr]),
     'dt_dense_supported': (_c_int, [_c_int] * 3),
     'dt_dense_workspace_bytes': (_c_i64, [_c_int] * 3),
     'dt_dense_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

@@ -2,8 +2,9 @@
 """Checkpoint format: one safetensors file holding every weight of the model under its
 KERAS name — `<layer name>/<weight name>` exactly as `keras.Model.save_weights` of the reference graph would
 name them (deepmodel.py:205-221 saves an .h5 of that model; deeptable.py:773-804 wraps it) — plus, optionally,
-the optimizer's slots (`optimizer/<weight>/<slot>`: m and v for Adam, acc for Adagrad, rms for RMSprop; the optimizer's
-name, step count and hyperparameters in the metadata).
+the optimizer's slots (`optimizer/<weight>/<slot>`: m and v for Adam, acc for Adagrad, rms for RMSprop, accumulator and
+linear for Ftrl, m and u for Adamax, momentum for SGD with momentum; the optimizer's name, step count and hyperparameters
+in the metadata).  The slots of a row-sparse table that live in one [V, 2, D] record are stored as two [V, D] tensors.
 
 The packed embedding table of `MultiColumnEmbedding` is stored as the reference's per-column variables
 `embeddings_{i}` (layers.py:863-877); Cross / CIN / BilinearInteraction parameter lists get the reference's
@@ -85,7 +86,8 @@ def _slot_names(optimizer):
 
 
 def save_model(model, path, optimizer=None, metadata=None):
-    """Write `path` (safetensors).  optimizer: a KerasAdam / Adagrad / RMSprop whose slots are stored next to the weights
+    """Write `path` (safetensors).  optimizer: a KerasAdam / Adagrad / RMSprop / Ftrl / Adamax / MomentumSGD whose slots are
+    stored next to the weights
     (an RMSprop first applies the decay pending on its row-sparse tables: the file holds Keras' slots)."""
     from safetensors.torch import save_file
     tensors = OrderedDict()
@@ -157,9 +159,12 @@ def load_model(model, path, optimizer=None, strict=True):
             if optimizer is not None and meta.get('optimizer') and hasattr(optimizer, 'state'):
                 name_here = getattr(optimizer, '_name', optimizer.__class__.__name__)
                 if meta['optimizer'] != name_here:
-                    raise ValueError(f'{path}: holds the slots of optimizer {meta["optimizer"]!r}, the model was compiled '
-                                     f'with {name_here!r}; load it without the optimizer or compile the model with '
-                                     f'optimizer={meta["optimizer"].lower()!r}')
+                    # (a file named 'SGD' holds momentum slots: plain 'sgd' has none to load them into)
+                    how = "{'class_name': 'SGD', 'config': {'momentum': ...}}" if meta['optimizer'] == 'SGD' \
+                        else repr(meta['optimizer'].lower())
+                    raise ValueError(f'{path}: holds the slots of optimizer {meta["optimizer"]!r} (one of Adam, Adagrad, '
+                                     f'RMSprop, Ftrl, Adamax, SGD with momentum), the model was compiled with {name_here!r}; '
+                                     f'load it without the optimizer or compile the model with optimizer={how}')
                 slots = _slot_names(optimizer)
                 if 'optimizer_hyperparameters' in meta and hasattr(optimizer, 'set_hyperparameters'):
                     optimizer.set_hyperparameters(json.loads(meta['optimizer_hyperparameters']))

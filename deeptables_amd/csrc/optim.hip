@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "adam_dev.h"
+#include "optim_dev.h"
 
 namespace dt {
 
@@ -48,9 +49,8 @@ __global__ __launch_bounds__(256) void k_adam_dense(float* __restrict__ p, const
 
 // Several parameter tensors in ONE launch (the layer-by-layer path has one small tensor per Dense / BN / Cross
 // variable: ~4.5 us of launch each).  The tensor descriptors travel as kernel arguments (no device-side table to keep
-// in sync, replayable from a hipGraph); a block finds its tensor by scanning the block offsets.
-constexpr int kMultiMax = 32;
-constexpr int kMultiPerBlock = 1024;          // elements per block (256 threads x 4)
+// in sync, replayable from a hipGraph); a block finds its tensor by scanning the block offsets (kMultiMax tensors,
+// kMultiPerBlock elements per block: optim_dev.h).
 struct AdamMulti {
     float* p[kMultiMax];
     const float* g[kMultiMax];
@@ -553,32 +553,7 @@ __device__ __forceinline__ void slot_update(float& p, float& s, float g, float l
     p -= lr * g / (sqrtf(s) + eps);
 }
 
-// t of the update this launch belongs to (1-based), read once per block; the step's last launch takes the arrival tickets
-// (adam_finish's scheme) and its last block advances t
-__device__ __forceinline__ int step_read_t(AdamState* st, int advance, unsigned& ticket) {
-    __shared__ int s_t;
-    ticket = kNoTicket;
-    if (!st) return 0;
-    if (threadIdx.x == 0) {
-        s_t = st->t;
-        if (advance) ticket = 0u;
-    }
-    __syncthreads();
-    return s_t;
-}
-__device__ __forceinline__ void step_finish(AdamState* st, unsigned ticket) {
-    if (ticket == kNoTicket) return;
-    const unsigned k = blockIdx.x % kAdamSub;
-    const unsigned expect = (gridDim.x + kAdamSub - 1 - k) / kAdamSub;
-    if (atomicAdd(&st->sub[k], 1u) == expect - 1) {
-        st->sub[k] = 0u;
-        const unsigned groups = gridDim.x < (unsigned)kAdamSub ? gridDim.x : (unsigned)kAdamSub;
-        if (atomicAdd(&st->done, 1u) == groups - 1) {
-            st->done = 0u;
-            st->t = st->t + 1;
-        }
-    }
-}
+// (step_read_t / step_finish — t of the update a launch belongs to, and the arrival tickets that advance it: optim_dev.h)
 
 // RMSprop's lazy decay: s *= rho^idle for a row that sat out `idle` steps.  Short gaps repeat the multiplication the dense
 // decay makes every step (the same bits); longer ones take one powf.
@@ -910,9 +885,10 @@ extern "C" int64_t dt_adam_rows_slots(int64_t n_rows) {
 
 // Pass 1 of every row step: merges the duplicate lookups of a row into its first occurrence (field-local LDS hashes or the
 // global hash).  -> *gslots: the global hash the owners must clear (NULL: not used), *mk: the owner marks (NULL: fields = -1,
-// the rows are already distinct and nothing is launched).  `who` names the entry point in the error text.
-static int rows_merge(const char* who, const int64_t* rows, float* values, int64_t n_rows, int D, int fields, void* slots,
-                      int64_t n_slots, int* mark, hipStream_t st, unsigned long long** gslots, int** mk) {
+// the rows are already distinct and nothing is launched).  `who` names the entry point in the error text.  (Declared in
+// optim_dev.h: optim2.hip's row steps start with the same pass.)
+int dt::rows_merge(const char* who, const int64_t* rows, float* values, int64_t n_rows, int D, int fields, void* slots,
+                   int64_t n_slots, int* mark, hipStream_t st, unsigned long long** gslots, int** mk) {
     *gslots = nullptr;
     *mk = mark;
     if (fields == -1) {
@@ -1021,8 +997,6 @@ extern "C" int dt_adam_rows_step(float* table, float* m, float* v, const int64_t
 }
 
 // ---- Adagrad / RMSprop entry points ------------------------------------------------------------------------------------------
-static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // the float4 body needs 16-byte aligned arrays; arrays that are only float aligned take the scalar loop
 static SlotTail slot_tail(float* p, const float* g, float* s, int64_t n) {
     return SlotTail{p, g, s, n, (aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(s, 16)) ? 1 : 0};

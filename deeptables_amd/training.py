@@ -229,7 +229,7 @@ DT_ADAM_STATE_WORDS = 272 // 4        # DT_ADAM_STATE_BYTES (include/dt_hip.h) i
 
 
 class _DeviceOptimizer:
-    """The step driver KerasAdam, Adagrad and RMSprop share.  One protocol — `zero_grad(flat=...)`, `step()`,
+    """The step driver KerasAdam, Adagrad, RMSprop, Ftrl, Adamax and MomentumSGD share.  One protocol — `zero_grad(flat=...)`, `step()`,
     `register_flat_group`, `pre_dense_hook`, `state`, `t` — and one launch order: the dense tensors in one multi-tensor
     launch (a registered flat group is ONE tensor: the fused train-step plans keep parameters and gradients of all dense
     layers in two contiguous buffers), then one row launch per packed table with a sparse gradient
@@ -242,7 +242,7 @@ class _DeviceOptimizer:
     supports_row_segments = False     # takes SparseRowGrad.segments
     supports_rows_in_step = False     # a fused step may apply the update of the rows looked up once itself (fields = -2)
     slot_names = ()                   # the slots' names: their keys in `state[id(p)]` and in a checkpoint
-    slot_init = 0.0
+    slot_init = 0.0                   # the slots' initial value: one number, or one per slot (a tuple matching slot_names)
 
     def __init__(self, params, embedding_layers):
         self.params = [p for p in params if p.requires_grad]
@@ -288,8 +288,12 @@ class _DeviceOptimizer:
         pass
 
     # -- slots --------------------------------------------------------------------------------------------
+    def _slot_inits(self):
+        v = self.slot_init
+        return tuple(v) if isinstance(v, (tuple, list)) else (v,) * len(self.slot_names)
+
     def _new_slot(self, p, rows):
-        return {k: torch.full_like(p, self.slot_init) for k in self.slot_names}
+        return {k: torch.full_like(p, v) for k, v in zip(self.slot_names, self._slot_inits())}
 
     def _st(self, p, rows=False):
         """slots of parameter p.  rows=True: in the layout of the row-sparse table update"""
@@ -305,7 +309,7 @@ class _DeviceOptimizer:
         narrow towers inside zero-padded slabs).  Their slots become the same views of one flat buffer per slot (existing
         state is kept).  grad_views=True: `zero_grad()` zeroes flat_grad and hands its views out as `.grad` (generic
         autograd path)."""
-        slots = [torch.full_like(flat_param, self.slot_init) for _ in self.slot_names]
+        slots = [torch.full_like(flat_param, v) for v in self._slot_inits()]
 
         def view_of(flat, p, off, cnt, layout):
             if layout is None:
@@ -555,12 +559,26 @@ class KerasAdam(_DeviceOptimizer):
 
 
 class SGD:
+    """keras.optimizers.SGD(learning_rate=0.01, momentum=0.0, nesterov=False).  momentum == 0: p -= lr*g, one launch per
+    tensor and per sparse-gradient piece, no state.  momentum != 0: `SGD(...)` returns a `MomentumSGD`, which runs on the
+    step driver (one slot `momentum`); both answer to the name 'SGD'."""
+
     _name = 'SGD'
 
-    def __init__(self, params, embedding_layers=(), learning_rate=0.01):
+    def __new__(cls, params=(), embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False):
+        if not 0 <= momentum <= 1:
+            raise ValueError(f'`momentum` must be in the range [0, 1], got {momentum!r}')
+        if cls is SGD and momentum != 0:
+            return MomentumSGD(params, embedding_layers, learning_rate, momentum, nesterov)
+        return super().__new__(cls)
+
+    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False):
         self.lr = learning_rate
         self.params = [p for p in params if p.requires_grad]
         self.embedding_layers = list(embedding_layers)
+
+    def hyperparameters(self):
+        return {'learning_rate': self.lr, 'momentum': 0.0, 'nesterov': False}
 
     def zero_grad(self):
         for p in self.params:
@@ -727,18 +745,227 @@ class RMSprop(_SlotOptimizer):
                                          int(stamp.stride(0)), st), 'dt_rmsprop_rows_step')
 
 
-OPTIMIZERS = {'adam': KerasAdam, 'sgd': SGD, 'adagrad': Adagrad, 'rmsprop': RMSprop}
+class _RowSparseOptimizer(_DeviceOptimizer):
+    """What momentum SGD, Adamax and Ftrl (csrc/optim2.hip) share beyond the step driver: one or two slots per element, each
+    with its own initial value, and hyperparameters that travel with a checkpoint.
+
+    Their row-sparse update is NOT Keras' dense result — a deviation of the kind of Adam's "lazy" rows (`KerasAdam`), and
+    unlike Adagrad's.  Only the looked-up rows are updated, duplicates summed first; every other row keeps its weights and
+    its slots bit for bit: its momentum does not coast, Adamax's `u` does not decay, and Ftrl neither shrinks it nor
+    recomputes it from (`linear`, `accumulator`).  That is TensorFlow's sparse apply, and what a table too large to sweep
+    every step needs; it takes no stamps and no `materialize()`.  A table with a DENSE gradient follows the formulas
+    literally, on every row.
+
+    The two slots of a row-sparse table live in ONE [V, 2, D] record (as `KerasAdam._new_slot`): a row update touches two
+    random locations, not three; the named slots are its strided views.  The row entry points take no segments: the fused
+    DeepFM / DCN plans run forward + backward and hand plain (rows, values) to `step()`."""
+
+    _hp = ()                          # constructor arguments beyond (params, embedding_layers), in order
+
+    def _new_slot(self, p, rows):
+        if not rows or len(self.slot_names) != 2:
+            return super()._new_slot(p, rows)
+        rec = torch.empty((p.shape[0], 2, p.shape[1]), dtype=p.dtype, device=p.device)
+        for k, v in enumerate(self._slot_inits()):
+            rec[:, k, :].fill_(v)
+        return {self.slot_names[0]: rec[:, 0, :], self.slot_names[1]: rec[:, 1, :], 'rec': rec}
+
+    def _st(self, p, rows=False):
+        s = self.state.get(id(p))
+        if s is not None and not rows and 'rec' in s:         # the dense update needs contiguous slots: convert back
+            self.state[id(p)] = {k: s[k].contiguous() for k in self.slot_names}
+        elif s is not None and rows and p.dim() == 2 and len(self.slot_names) == 2 and 'rec' not in s:
+            old, s = s, self._new_slot(p, True)
+            for k in self.slot_names:
+                s[k].copy_(old[k].reshape(p.shape))
+            self.state[id(p)] = s
+        return super()._st(p, rows)
+
+    def slot(self, p, name=None):
+        """the slot `name` (default: the first) of parameter p in the shape of p, or None before p's first update"""
+        s = self.state.get(id(p))
+        return None if s is None else s[name or self.slot_names[0]]
+
+    def hyperparameters(self):
+        return {k: getattr(self, k) for k in self._hp}
+
+    def set_hyperparameters(self, hp):
+        unknown = sorted(set(hp) - set(self._hp))
+        if unknown:
+            raise ValueError(f'{self._name}: unknown hyperparameters {unknown} (accepted: {list(self._hp)})')
+        self._check(**dict(self.hyperparameters(), **hp))
+        for k, v in hp.items():
+            setattr(self, k, type(getattr(self, k))(v))
+
+    @staticmethod
+    def _check(**hp):
+        pass
+
+    @property
+    def lr(self):
+        return self.learning_rate
+
+    def _tail_slots(self, tail):
+        return [ptr(x) for x in tail[2]]
+
+
+class MomentumSGD(_RowSparseOptimizer):
+    """keras.optimizers.SGD(learning_rate=0.01, momentum, nesterov=False) with momentum != 0 (what `SGD(...)` returns then):
+        m = momentum*m - lr*g;  p += m          (nesterov: p += momentum*m - lr*g),  m starts at 0.
+    Row-sparse tables: see `_RowSparseOptimizer` — rows that were not looked up do not coast on their momentum."""
+
+    _name = 'SGD'
+    slot_names = ('momentum',)
+    _hp = ('learning_rate', 'momentum', 'nesterov')
+
+    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.9, nesterov=False):
+        self._check(momentum=momentum)
+        super().__init__(params, embedding_layers)
+        self.learning_rate, self.momentum, self.nesterov = float(learning_rate), float(momentum), bool(nesterov)
+
+    @staticmethod
+    def _check(momentum=0.9, **_):
+        if not 0 < momentum <= 1:
+            raise ValueError(f'`momentum` must be in the range (0, 1] on the momentum path ([0, 1] for SGD), got {momentum!r}')
+
+    def _hpargs(self):
+        return self.learning_rate, self.momentum, int(self.nesterov)
+
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_sgdm_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, *self._hpargs(), sp, advance, st), 'dt_sgdm_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_sgdm_multi_step(T, ps, gs, ss[0], ns, *self._hpargs(), sp, advance, st), 'dt_sgdm_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
+        m = s['momentum']
+        check(lib().dt_sgdm_rows_step(ptr(table.data), ptr(m), ptr(rows), ptr(values), n, D, fields, ptr(slots), n_slots,
+                                      ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]), *self._tail_slots(tail), tail[3],
+                                      advance, int(m.stride(0)), st), 'dt_sgdm_rows_step')
+
+
+class Adamax(_RowSparseOptimizer):
+    """keras.optimizers.Adamax(learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+        m += (g - m)*(1 - beta_1);  u = max(beta_2*u, |g|);  p -= lr*m / ((1 - beta_1^t)*(u + eps)),  m and u start at 0.
+    beta_1^t is computed on the device from the device-resident step count, so a captured graph replays with the right power.
+    Row-sparse tables: see `_RowSparseOptimizer` — m and u of rows that were not looked up do not decay."""
+
+    _name = 'Adamax'
+    slot_names = ('m', 'u')
+    _hp = ('learning_rate', 'beta_1', 'beta_2', 'epsilon')
+
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
+        super().__init__(params, embedding_layers)
+        self.learning_rate, self.beta_1, self.beta_2, self.epsilon = float(learning_rate), float(beta_1), float(beta_2), \
+            float(epsilon)
+
+    def _hpargs(self):
+        return self.learning_rate, self.beta_1, self.beta_2, self.epsilon
+
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_adamax_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, *self._hpargs(), sp, advance, st),
+              'dt_adamax_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_adamax_multi_step(T, ps, gs, ss[0], ss[1], ns, *self._hpargs(), sp, advance, st), 'dt_adamax_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
+        m, u = s['m'], s['u']
+        check(lib().dt_adamax_rows_step(ptr(table.data), ptr(m), ptr(u), ptr(rows), ptr(values), n, D, fields, ptr(slots),
+                                        n_slots, ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]),
+                                        *self._tail_slots(tail), tail[3], advance, int(m.stride(0)), st), 'dt_adamax_rows_step')
+
+
+class Ftrl(_RowSparseOptimizer):
+    """keras.optimizers.Ftrl(learning_rate=1e-3, learning_rate_power=-0.5, initial_accumulator_value=0.1,
+    l1_regularization_strength=0, l2_regularization_strength=0, l2_shrinkage_regularization_strength=0, beta=0); slots
+    `accumulator` (n, starts at initial_accumulator_value) and `linear` (starts at 0); with l2' = l2 + beta/(2 lr):
+        g' = g + 2*l2_shrinkage*p;  n' = n + g^2;  linear += g' - (n'^(-lr_power) - n^(-lr_power))/lr * p
+        q = n'^(-lr_power)/lr + 2*l2';  p = (clip(linear, -l1, l1) - linear)/q;  n = n'
+    Three things to know:
+      * With g == 0 the formula does not leave p alone: the weight is a function of (linear, n), and a never-trained weight
+        with a zero gradient becomes exactly 0.  The dense path follows the formula literally.  The row-sparse path updates
+        the looked-up rows only (`_RowSparseOptimizer`): a deviation from Keras' dense semantics, as Adam's lazy rows are.
+      * q == 0 (n' == 0: initial_accumulator_value = 0, g = 0, l2 = beta = 0 — the zero pads of a fused plan's flat
+        group) writes p = 0 where Keras writes NaN.
+      * learning_rate_power == -0.5, the default, takes sqrtf; any other power <= 0 powf."""
+
+    _name = 'Ftrl'
+    slot_names = ('accumulator', 'linear')
+    _hp = ('learning_rate', 'learning_rate_power', 'initial_accumulator_value', 'l1_regularization_strength',
+           'l2_regularization_strength', 'l2_shrinkage_regularization_strength', 'beta')
+
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, learning_rate_power=-0.5,
+                 initial_accumulator_value=0.1, l1_regularization_strength=0.0, l2_regularization_strength=0.0,
+                 l2_shrinkage_regularization_strength=0.0, beta=0.0):
+        hp = dict(zip(self._hp, (learning_rate, learning_rate_power, initial_accumulator_value, l1_regularization_strength,
+                                 l2_regularization_strength, l2_shrinkage_regularization_strength, beta)))
+        self._check(**hp)
+        super().__init__(params, embedding_layers)
+        for k, v in hp.items():
+            setattr(self, k, float(v))
+
+    @staticmethod
+    def _check(**hp):
+        if hp['initial_accumulator_value'] < 0:
+            raise ValueError(f"`initial_accumulator_value` needs to be positive or zero, got {hp['initial_accumulator_value']!r}")
+        if hp['learning_rate_power'] > 0:
+            raise ValueError(f"`learning_rate_power` needs to be negative or zero, got {hp['learning_rate_power']!r}")
+        for k in ('l1_regularization_strength', 'l2_regularization_strength', 'l2_shrinkage_regularization_strength', 'beta'):
+            if hp[k] < 0:
+                raise ValueError(f'`{k}` needs to be positive or zero, got {hp[k]!r}')
+
+    @property
+    def slot_init(self):
+        return self.initial_accumulator_value, 0.0
+
+    def _hpargs(self):
+        l2 = self.l2_regularization_strength + self.beta / (2.0 * self.learning_rate)
+        return (self.learning_rate, self.learning_rate_power, self.l1_regularization_strength, l2,
+                self.l2_shrinkage_regularization_strength)
+
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        check(lib().dt_ftrl_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, *self._hpargs(), sp, advance, st),
+              'dt_ftrl_dense_step')
+
+    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
+        check(lib().dt_ftrl_multi_step(T, ps, gs, ss[0], ss[1], ns, *self._hpargs(), sp, advance, st), 'dt_ftrl_multi_step')
+
+    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
+        acc, lin = s['accumulator'], s['linear']
+        check(lib().dt_ftrl_rows_step(ptr(table.data), ptr(acc), ptr(lin), ptr(rows), ptr(values), n, D, fields, ptr(slots),
+                                      n_slots, ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]),
+                                      *self._tail_slots(tail), tail[3], advance, int(acc.stride(0)), st), 'dt_ftrl_rows_step')
+
+
+OPTIMIZERS = {'adam': KerasAdam, 'sgd': SGD, 'adagrad': Adagrad, 'rmsprop': RMSprop, 'ftrl': Ftrl, 'adamax': Adamax}
+
+
+def _config_keys(cls):
+    """the hyperparameters `cls` takes by name: its constructor's arguments behind (params, embedding_layers)"""
+    import inspect
+    return [k for k in inspect.signature(cls.__init__).parameters if k not in ('self', 'params', 'embedding_layers')]
 
 
 def make_optimizer(spec, params, embedding_layers):
+    """spec: 'auto' / None (Adam), a name of OPTIMIZERS in any letter case (Keras' defaults), Keras' serialised form
+    {'class_name': 'Ftrl', 'config': {'l1_regularization_strength': 1e-4}} for any of them (an unknown key of `config`
+    raises), or a callable (params, embedding_layers) -> optimizer."""
     if spec == 'auto' or spec is None:
         return KerasAdam(params, embedding_layers)
     if isinstance(spec, str) and spec.lower() in OPTIMIZERS:
         return OPTIMIZERS[spec.lower()](params, embedding_layers)
+    if isinstance(spec, dict) and isinstance(spec.get('class_name'), str) and spec['class_name'].lower() in OPTIMIZERS:
+        cls, config = OPTIMIZERS[spec['class_name'].lower()], dict(spec.get('config') or {})
+        unknown = sorted(set(config) - set(_config_keys(cls)))
+        if unknown:
+            raise ValueError(f"optimizer {spec['class_name']!r}: unknown config keys {unknown} (accepted: {_config_keys(cls)})")
+        return cls(params, embedding_layers, **config)
     if callable(spec):
         return spec(params, embedding_layers)
-    raise ValueError(f"Unsupported optimizer: {spec!r} (accepted: 'auto', {', '.join(repr(k) for k in OPTIMIZERS)}, or a "
-                     f'callable (params, embedding_layers) -> optimizer)')
+    raise ValueError(f"Unsupported optimizer: {spec!r} (accepted: 'auto', {', '.join(repr(k) for k in OPTIMIZERS)}, "
+                     f"{{'class_name': <one of these names>, 'config': {{...}}}}, or a callable (params, embedding_layers) "
+                     f'-> optimizer)')
 
 
 def flatten_dense_parameters(model, optimizer, exclude=()):

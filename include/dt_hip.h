@@ -344,6 +344,53 @@ int dt_rmsprop_rows_step(float* table, float* rms, int* stamp, const int64_t* ro
 int dt_rmsprop_rows_materialize(float* rms, int* stamp, int64_t V, int D, int slot_stride, int stamp_stride, float rho,
                                 const void* state, void* stream);
 
+/* keras.optimizers.SGD with momentum != 0, keras.optimizers.Adamax and keras.optimizers.Ftrl (Keras 3's formulas), selectable
+ * through ModelConfig.optimizer (csrc/optim2.hip).  Arguments as in their dt_adagrad_* counterparts — the same `state`
+ * (dt_adam_state_init with beta1 = beta2 = 0; the last launch of a step has advance != 0), the same float4 body / scalar loop
+ * for dense arrays, the same chunks of 32 tensors, the same rows / values / fields / slots / n_slots / mark and dense tail —
+ * with the second slot behind the first wherever a slot is passed and the hyperparameters in place of (lr, eps).
+ *     SGD:    m = momentum*m - lr*g ; p += m                           (nesterov != 0: p += momentum*m - lr*g); m starts at 0
+ *     Adamax: m += (g - m)*(1 - beta1) ; u = max(beta2*u, |g|) ; p -= lr*m / ((1 - beta1^t)*(u + eps));        m, u start at 0
+ *             t (1-based) is read from `state` on the device (required wherever an element is updated): a captured graph
+ *             replays the launch with the right power.
+ *     Ftrl:   g' = g + 2*l2_shrinkage*p ; n' = accum + g*g ; linear += g' - (n'^a - accum^a)/lr * p,   a = -lr_power
+ *             q = n'^a/lr + 2*l2 ; p = (clip(linear, -l1, l1) - linear)/q ; accum = n'
+ *             `l2` is l2_regularization_strength + beta/(2 lr), folded by the caller; the caller fills accum with
+ *             initial_accumulator_value, linear with 0.  q == 0 (n' == 0 and l2 == 0) writes p = 0 where Keras writes NaN.
+ *             lr_power == -0.5 takes sqrtf, any other lr_power <= 0 powf.  lr <= 0, lr_power > 0 or a negative l1 / l2 /
+ *             l2_shrinkage is refused.  With g == 0 the formula does NOT leave p alone (p is a function of linear and accum).
+ * Rows: the two slots of table row r are slot0 + r * slot_stride and slot1 + r * slot_stride (slot_stride >= D floats), so
+ * they may be two [V, D] arrays (slot_stride D) or ONE [V, 2, D] record (slot1 = slot0 + D, slot_stride 2 D: two random
+ * locations per row).  Only the looked-up rows are updated (duplicates summed first); every other row keeps p and its slots
+ * bit for bit — momentum does not coast, u does not decay, Ftrl's shrinkage is not applied: TensorFlow's sparse apply, a
+ * deviation from the dense formulas of the kind of Adam's lazy rows.                                                         */
+int dt_sgdm_dense_step(float* p, const float* g, float* mom, int64_t n, float lr, float momentum, int nesterov, void* state,
+                       int advance, void* stream);
+int dt_sgdm_multi_step(int count, float* const* p, const float* const* g, float* const* mom, const int64_t* n, float lr,
+                       float momentum, int nesterov, void* state, int advance, void* stream);
+int dt_sgdm_rows_step(float* table, float* mom, const int64_t* rows, float* values, int64_t n_rows, int D, int fields,
+                      void* slots, int64_t n_slots, int* mark, float lr, float momentum, int nesterov, void* state,
+                      float* dense_p, const float* dense_g, float* dense_mom, int64_t dense_n, int advance, int slot_stride,
+                      void* stream);
+int dt_adamax_dense_step(float* p, const float* g, float* m, float* u, int64_t n, float lr, float beta1, float beta2,
+                         float eps, void* state, int advance, void* stream);
+int dt_adamax_multi_step(int count, float* const* p, const float* const* g, float* const* m, float* const* u,
+                         const int64_t* n, float lr, float beta1, float beta2, float eps, void* state, int advance,
+                         void* stream);
+int dt_adamax_rows_step(float* table, float* m, float* u, const int64_t* rows, float* values, int64_t n_rows, int D,
+                        int fields, void* slots, int64_t n_slots, int* mark, float lr, float beta1, float beta2, float eps,
+                        void* state, float* dense_p, const float* dense_g, float* dense_m, float* dense_u, int64_t dense_n,
+                        int advance, int slot_stride, void* stream);
+int dt_ftrl_dense_step(float* p, const float* g, float* accum, float* linear, int64_t n, float lr, float lr_power, float l1,
+                       float l2, float l2_shrinkage, void* state, int advance, void* stream);
+int dt_ftrl_multi_step(int count, float* const* p, const float* const* g, float* const* accum, float* const* linear,
+                       const int64_t* n, float lr, float lr_power, float l1, float l2, float l2_shrinkage, void* state,
+                       int advance, void* stream);
+int dt_ftrl_rows_step(float* table, float* accum, float* linear, const int64_t* rows, float* values, int64_t n_rows, int D,
+                      int fields, void* slots, int64_t n_slots, int* mark, float lr, float lr_power, float l1, float l2,
+                      float l2_shrinkage, void* state, float* dense_p, const float* dense_g, float* dense_accum,
+                      float* dense_linear, int64_t dense_n, int advance, int slot_stride, void* stream);
+
 /* ---- Keras Dense (deepnets.dnn deepnets.py:401-427; Dense(1) logits / task_output deepmodel.py:291-292,455;
  *      Q/K/V/residual projections layers.py:104-108) --------------------------------------------------- *
  *   y [N,M] = act(x [N,K] . W [K,M] + bias [M]|NULL),  act in {DT_ACT_LINEAR, DT_ACT_RELU}.
