@@ -74,11 +74,13 @@ SIGNATURES = {
     'dt_cin_layer_bwd_bf16x3': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int,
                                          _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'dt_mha_core_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_f32, ctypes.c_uint32, _ptr,
-                                 _ptr, _ptr]),
-    'dt_mha_core_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
-                                 _c_f32, ctypes.c_uint32, _ptr, _ptr, _ptr, _ptr]),
+                                 _ptr, _ptr, _ptr]),
+    'dt_mha_core_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                 _c_f32, ctypes.c_uint32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     'dt_autoint_supported': (_c_int, [_c_int, _c_int, _c_int]),
+    'dt_mha_core_supported': (_c_int, [_c_int, _c_int, _c_int, _c_int]),
     'dt_autoint_dropout_hash': (ctypes.c_uint32, [ctypes.c_uint32] * 5),
+    'dt_autoint_dropout_threshold': (ctypes.c_uint32, [_c_f32]),
     'dt_autoint_fwd': (_c_int, [_ptr] * 9 + [_c_i64, _c_int, _c_int, _c_int, _c_f32, ctypes.c_uint32] + [_ptr] * 6 + [_c_int, _ptr]),
     'dt_autoint_bwd': (_c_int, [_ptr] * 11 + [_c_i64, _c_int, _c_int, _c_int, _c_f32, ctypes.c_uint32] + [_ptr] * 14 + [_c_int, _ptr]),
     'dt_autoint_fwd_bn': (_c_int, [_ptr] * 9 + [_c_i64, _c_int, _c_int, _c_int, _c_f32, ctypes.c_uint32, _ptr, _ptr, _c_f32, _c_f32]

@@ -1574,16 +1574,9 @@ extern "C" unsigned dt_autoint_dropout_hash(unsigned seed, unsigned b, unsigned 
         else DT_AI_LAUNCH(KERNEL, 16, 16, WAVES, __VA_ARGS__);                                                     \
     } while (0)
 
-static bool ai_drop(float rate, unsigned* thr, float* inv_keep) {
-    *thr = 0; *inv_keep = 1.f;
-    if (rate <= 0.f) return true;
-    if (rate >= 1.f) return false;
-    double t = (double)rate * 4294967296.0;
-    *thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
-    if (*thr == 0) *thr = 1;
-    *inv_keep = 1.0f / (1.0f - rate);
-    return true;
-}
+static bool ai_drop(float rate, unsigned* thr, float* inv_keep) { return autoint_drop(rate, thr, inv_keep); }
+
+extern "C" unsigned dt_autoint_dropout_threshold(float rate) { return autoint_drop_threshold(rate); }
 
 static bool ai_weights(const float* const* W, const float* const* b, int NP, AiW* w) {
     for (int i = 0; i < 4; ++i) {

@@ -47,6 +47,26 @@ inline int launch_status(const char* what) {
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// attention-weight dropout of autoint.hip and mha.hip: weight (b, h, i, j) is kept iff its hash >= the threshold.  The rate
+// arrives as a float, so the threshold is float32(rate) * 2^32 (exact in double), saturated, and never 0 for a rate > 0
+// (0 means "no dropout" to the kernels).  dt_autoint_dropout_threshold exports it.
+inline unsigned autoint_drop_threshold(float rate) {
+    if (!(rate > 0.f)) return 0u;
+    const double t = (double)rate * 4294967296.0;
+    const unsigned thr = t >= 4294967295.0 ? 4294967295u : (unsigned)t;
+    return thr ? thr : 1u;
+}
+
+// threshold and keep scale 1 / (1 - rate) in float32; false: the rate is outside [0, 1)
+inline bool autoint_drop(float rate, unsigned* thr, float* inv_keep) {
+    *thr = 0; *inv_keep = 1.f;
+    if (rate == 0.f) return true;
+    if (!(rate > 0.f && rate < 1.f)) return false;      // (a NaN too)
+    *thr = autoint_drop_threshold(rate);
+    *inv_keep = 1.0f / (1.0f - rate);
+    return true;
+}
+
 // ---- wave-level reductions (64 lanes) without LDS -------------------------------------------
 // __shfl_xor lowers to ds_bpermute_b32 (an LDS-crossbar round trip per step; six dependent ones per wave_sum).  DPP
 // moves cover the steps inside a 16-lane row, v_permlane16_swap / v_permlane32_swap (gfx950) the two across rows.

@@ -113,11 +113,27 @@ class MultiheadAttention(Layer):
         else:
             parts = [p(x) for p in projs]
         q, k, v = parts[0], parts[1], parts[2]
-        outputs = ops.mha_core(q, k, v, self.num_heads, grad_cols=len(parts), dropout_rate=rate, seed=seed)
+        if ops.mha_supported(x.shape[1], self.num_units, self.num_heads, rate):
+            outputs = ops.mha_core(q, k, v, self.num_heads, grad_cols=len(parts), dropout_rate=rate, seed=seed)
+        else:
+            # outside the attention kernels' domain (head width > 32, or attention dropout with more than 64 fields): the
+            # reference's op chain (layers.py:129-145), so the layer trains at any head width and field count as it does there
+            outputs = self._core_by_ops(q, k, v, rate)
         if self.use_residual:
             outputs = outputs + parts[3]
         outputs = torch.relu(outputs)
         return self.batch_normalize(outputs)
+
+    def _core_by_ops(self, q, k, v, rate):
+        """layers.py:129-145 with torch ops: heads split on the last axis, softmax(Q K^T / sqrt(d_h)), dropout on the
+        weights, . V, heads merged"""
+        B, F, D = q.shape
+        H = self.num_heads
+        heads = lambda t: t.reshape(B, F, H, D // H).permute(0, 2, 1, 3)
+        w = torch.softmax(torch.matmul(heads(q), heads(k).transpose(-1, -2)) / (D // H) ** 0.5, dim=-1)
+        if rate > 0:
+            w = torch.nn.functional.dropout(w, p=rate, training=True)
+        return torch.matmul(w, heads(v)).permute(0, 2, 1, 3).reshape(B, F, D)
 
     def get_config(self):
         c = super().get_config()

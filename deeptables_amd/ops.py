@@ -556,32 +556,47 @@ class _MhaCore(torch.autograd.Function):
         else:
             ld = lds.pop()
         out = torch.empty((B, F, D), dtype=torch.float32, device=q.device)
-        lse = torch.empty((B, H, F), dtype=torch.float32, device=q.device)
+        # (row maximum, 1 / normaliser) of every score row: what the backward rebuilds the probabilities from
+        stats = torch.empty((B, H, F, 2), dtype=torch.float32, device=q.device)
         check(lib().dt_mha_core_fwd(ptr(q), ptr(k), ptr(v), B, F, D, H, ld, float(rate), int(seed) & 0xFFFFFFFF,
-                                    ptr(out), ptr(lse), stream_ptr()), 'dt_mha_core_fwd')
-        ctx.save_for_backward(q, k, v, out, lse)
+                                    ptr(out), None, ptr(stats), stream_ptr()), 'dt_mha_core_fwd')
+        ctx.save_for_backward(q, k, v, stats)
         ctx.H, ctx.ld, ctx.drop = H, ld, (float(rate), int(seed) & 0xFFFFFFFF)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        q, k, v, out, lse = ctx.saved_tensors
-        B, F, D = out.shape
+        q, k, v, stats = ctx.saved_tensors
+        B, F, D = q.shape
         g = _f32c(g)
         # gq | gk | gv side by side in a buffer `grad_cols` blocks wide: when q/k/v are column blocks of a fused
         # projection output, split_cols' backward completes this buffer in place instead of concatenating
         W = ctx.grad_cols * D
-        G = torch.empty((B, F, W), dtype=torch.float32, device=out.device)
+        G = torch.empty((B, F, W), dtype=torch.float32, device=q.device)
         gq, gk, gv = G[..., :D], G[..., D:2 * D], G[..., 2 * D:3 * D]
-        check(lib().dt_mha_core_bwd(ptr(q), ptr(k), ptr(v), ptr(out), ptr(lse), ptr(g), B, F, D, ctx.H, ctx.ld,
-                                    W, ctx.drop[0], ctx.drop[1], ptr(gq), ptr(gk), ptr(gv), stream_ptr()),
+        ws = torch.empty((B, ctx.H, F), dtype=torch.float32, device=q.device)     # delta of every row, between the two launches
+        check(lib().dt_mha_core_bwd(ptr(q), ptr(k), ptr(v), ptr(stats), ptr(g), B, F, D, ctx.H, ctx.ld,
+                                    W, ctx.drop[0], ctx.drop[1], ptr(gq), ptr(gk), ptr(gv), ptr(ws), stream_ptr()),
               'dt_mha_core_bwd')
         return gq, gk, gv, None, None, None, None
 
 
+def mha_supported(F, D, num_heads, dropout_rate=0.0):
+    """dt_mha_core_supported: True when the forward AND the backward kernel take the shape (head width D / H <= 32, F <= 64
+    with attention dropout).  mha_core raises DtHipError on any other shape; MultiheadAttention.call asks first."""
+    return bool(lib().dt_mha_core_supported(int(F), int(D), int(num_heads), 1 if float(dropout_rate) > 0 else 0))
+
+
 def mha_core(q, k, v, num_heads, grad_cols=3, dropout_rate=0.0, seed=0):
     """grad_cols: width (in blocks of D) of the buffer the q/k/v gradients are laid out in (see split_cols).
-    dropout_rate / seed: Dropout on the attention weights (layers.py:141), mask = autoint_dropout_keep(seed, ...)."""
+    dropout_rate / seed: Dropout on the attention weights (layers.py:141), mask = autoint_dropout_keep(seed, ...).
+    Shapes outside mha_supported raise DtHipError here, in the forward: a tensor that needs a gradient is never handed
+    to a forward whose backward would refuse it."""
+    B, F, D = q.shape
+    if any(t.requires_grad for t in (q, k, v)) and torch.is_grad_enabled() and \
+            not mha_supported(F, D, num_heads, dropout_rate):
+        raise _lib.DtHipError(f'mha_core: F={F} D={D} H={num_heads} dropout={dropout_rate} is outside the kernels\' domain '
+                              f'(head width <= 32, F <= 64 with dropout): see mha_supported')
     return _MhaCore.apply(q, k, v, int(num_heads), int(grad_cols), float(dropout_rate), int(seed))
 
 
@@ -599,8 +614,18 @@ def autoint_dropout_keep(seed, B, H, F, rate, device='cpu'):
     j = torch.arange(F, dtype=torch.int64, device=device).view(1, 1, 1, F)
     x = (int(seed) & M32) ^ ((b * 0x9E3779B1) & M32) ^ (((h * 4096 + i * 64 + j) * 0x85EBCA77) & M32)
     x = x ^ (x >> 16); x = (x * 0x7FEB352D) & M32; x = x ^ (x >> 15); x = (x * 0x846CA68B) & M32; x = x ^ (x >> 16)
-    thr = min(max(int(float(rate) * 4294967296.0), 1), 4294967295)
-    return (x >= thr).to(torch.float32) / (1.0 - float(rate))
+    one, r32 = torch.tensor(1.0, dtype=torch.float32, device=device), torch.tensor(float(rate), dtype=torch.float32, device=device)
+    return (x >= autoint_dropout_threshold(rate)).to(torch.float32) * (one / (one - r32))
+
+
+def autoint_dropout_threshold(rate):
+    """dt_autoint_dropout_threshold: keep iff hash >= thr.  The kernels take the rate as a C float, so thr = float32(rate) *
+    2^32 (not the Python double's: 1288490240 and not 1288490188 at 0.3), saturated to 2^32 - 1, at least 1 for a rate > 0;
+    0 (no dropout) for rate <= 0"""
+    r = float(torch.tensor(float(rate), dtype=torch.float32))
+    if not r > 0.0:
+        return 0
+    return min(max(int(r * 4294967296.0), 1), 4294967295)
 
 
 _AUTOINT_WS = {}

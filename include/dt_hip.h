@@ -216,17 +216,25 @@ int dt_cin_pool_bwd(const float* g_hidden, const float* g_pooled, int64_t B, int
  * q,k,v [B,F,D] (already relu(Dense(x)), layers.py:123-125); H heads split on the last axis
  * (d_h = D/H); out[b,:,h] = softmax(q_h k_h^T / sqrt(d_h)) v_h, heads merged back on the last
  * axis -> out [B,F,D].  Nothing of size [B,H,F,F] is written: the forward saves only
- * lse [B,H,F] (log-sum-exp of each scaled score row) and the backward recomputes the
- * probabilities from q,k,lse and uses `out` for delta = rowsum(dO * O).
+ * stats [B,H,F,2] = (m, 1 / l) of each scaled score row (its maximum and the inverse of sum_j exp(s_j - m)) and the backward
+ * recomputes the probabilities as exp(s - m) * (1 / l), bit for bit the forward's weights.  lse [B,H,F] = m + log l is an output for
+ * callers that want it; the backward does not take it (one float cannot hold m + log l to better than 2^-24 |m|, and that
+ * much error in every probability is 1 % once the scores reach 1e5).  Either of lse and stats may be NULL (inference).
+ * The backward is two launches: ws [B,H,F] floats receives delta_i = sum_j p_ij keep_ij (dO_i . v_j) from the first.
  * ld: distance in floats between consecutive field rows of q/k/v (D when contiguous; 4D when they are column
  * blocks of one fused [B,F,4D] projection output); ldg: the same for grad_q/grad_k/grad_v.
  * dropout_rate / seed: Dropout on the attention weights (layers.py:141) with the keep-mask of dt_autoint_dropout_hash
- * (F <= 64 then); 0 at inference.                                                                   */
+ * (F <= 64 then) >= dt_autoint_dropout_threshold(dropout_rate); 0 at inference.
+ * Shape domain: head width D/H <= 64 in the forward and <= 32 in the backward, F <= 64 with dropout; outside it both
+ * return DT_ERR_UNSUPPORTED before any launch.  dt_mha_core_supported(F, D, H, dropout != 0) = 1 iff BOTH directions
+ * take the shape (what a layer that trains needs).  Rows are moved as float4 when d_h, D, ld (and ldg) are multiples of 4
+ * and every row pointer is 16-byte aligned, one float at a time otherwise: both give the same bits.     */
+int dt_mha_core_supported(int F, int D, int H, int dropout);
 int dt_mha_core_fwd(const float* q, const float* k, const float* v, int B, int F, int D, int H, int ld,
-                    float dropout_rate, unsigned seed, float* out, float* lse, void* stream);
-int dt_mha_core_bwd(const float* q, const float* k, const float* v, const float* out,
-                    const float* lse, const float* grad_out, int B, int F, int D, int H, int ld, int ldg,
-                    float dropout_rate, unsigned seed, float* grad_q, float* grad_k, float* grad_v, void* stream);
+                    float dropout_rate, unsigned seed, float* out, float* lse, float* stats, void* stream);
+int dt_mha_core_bwd(const float* q, const float* k, const float* v, const float* stats, const float* grad_out,
+                    int B, int F, int D, int H, int ld, int ldg, float dropout_rate, unsigned seed,
+                    float* grad_q, float* grad_k, float* grad_v, float* ws, void* stream);
 
 /* ---- a13 optimizer step (Keras Adam, models/deepmodel.py:321-322) ------------------------- *
  * Keras semantics: lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; p -= lr_t*m/(sqrt(v)+eps).
@@ -541,6 +549,9 @@ int dt_cin_layer_bwd_bf16x3(const float* x0, const float* xk, const float* W, co
 #define DT_AI_BF16X2 2
 int dt_autoint_supported(int F, int D, int H);
 unsigned dt_autoint_dropout_hash(unsigned seed, unsigned b, unsigned h, unsigned i, unsigned j);
+/* the keep threshold of the layer's and of dt_mha_core's attention dropout: float32(rate) * 2^32 saturated to 2^32 - 1, at
+ * least 1 for a rate > 0; 0 for rate <= 0 (no dropout) */
+unsigned dt_autoint_dropout_threshold(float rate);
 int dt_autoint_fwd(const float* x, const float* Wq, const float* Wk, const float* Wv, const float* Wr, const float* bq,
                    const float* bk, const float* bv, const float* br, int64_t B, int F, int D, int H,
                    float dropout_rate, unsigned seed, float* out_a, float* lse, const float* xn_mean, const float* xn_rstd,

@@ -46,6 +46,7 @@ CLAIMS = {
     ('autoint', 'float32'): ('fp32', 'fp32'),   # csrc/autoint.hip, fp32 MFMA
     ('autoint', 'bf16x2'): ('fp32', 'b17'),     # DT_AI_BF16X2: six products forward, three backward
     ('autoint', 'bf16'): ('b17', 'bf16'),       # DT_AI_BF16: two-part forward projection, plain bf16 backward (autoint.hip:138-144)
+    ('mha', 'float32'): ('fp32', 'fp32'),       # csrc/mha.hip: the attention core of every shape the fused layer does not take
     ('dense', 'float32'): ('fp32', 'fp32'),     # csrc/dense.hip
     ('cross', 'float32'): ('fp32', 'fp32'),     # csrc/cross.hip
     ('fm', 'float32'): ('fp32', 'fp32'),        # csrc/embedding.hip
@@ -73,7 +74,9 @@ COND_BAR = {'fp32': 2.0 * U, 'b17': 128 * U, 'bf16': 65536 * U}
 
 # Yardstick B: factor over the float32 CPU oracle's own error, per class, and the floor of that error.
 #   fp32: GPU worst 5.1x (SENET mean pooling, D = 33 summed in order), 4.2x (BN moving mean, mean 0 / std 1 at N = 16385), 3.7x (BN gamma
-#         through the timed step's m, exact tower), 2.5x (bilinear dx, outer product dW);   a two-part (16-bit) tower forward: logits
+#         through the timed step's m, exact tower), 2.5x (bilinear dx, outer product dW);   the attention core (csrc/mha.hip,
+#         tests/test_mha_kernels_gpu.py, max_rel and row_rel over 80 runs): grad_q 3.6x, out 2.1x, lse 2.1x, grad_v 2.1x, grad_k 1.5x,
+#         through ops.dense + split_cols + mha_core: grad_x 1.2x, grad_b 0.9x, grad_W 0.7x;   a two-part (16-bit) tower forward: logits
 #         ~40x (2e-5 against 5.3e-7)
 #   b17:  GPU worst 59x (autoint bf16x2 dx), 52x (timed step BN gamma, wgrad_heavy_bf16);   an 8-bit backward: >= 2e3x
 #   bf16: GPU worst 2.3e4x (autoint bf16 dx), 1.3e4x (plain-bf16 tower logits)
