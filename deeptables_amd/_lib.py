@@ -315,6 +315,19 @@ SIGNATURES = {
     'dt_cell_saves_input': (_c_int, [_c_int]),
     'dt_cell_fwd': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32, _ptr, _ptr]),
     'dt_cell_bwd': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32, _ptr, _ptr]),
+    # gradient clipping (csrc/gradclip.hip): rows, values, n, D, V, out_rows, out_vals, count, ws, stream / count, g[], n[], sums,
+    # ws, stream / out_rows, out_vals, n, D, count, row_offset, F, V, sums, ws, stream / mode (DT_CLIP_*), c, count, g[], n[],
+    # sum_index[], sums, n_sums, norm_out, stream / mode, c, out_rows, out_vals, n, D, count, row_offset, F, V, sums, sum_base,
+    # n_sums, norm_out, stream.  g / n / sum_index: HOST arrays
+    'dt_rows_coalesce_chunk': (_c_int, []),
+    'dt_rows_coalesce_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
+    'dt_rows_coalesce': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_grad_sumsq_workspace_bytes': (_c_i64, [_c_int, _ptr]),
+    'dt_grad_sumsq': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_rows_field_sumsq': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _c_i64, _ptr, _ptr, _ptr]),
+    'dt_grad_clip': (_c_int, [_c_int, _c_f32, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr]),
+    'dt_rows_clip': (_c_int, [_c_int, _c_f32, _ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _c_i64, _ptr, _c_int, _c_int,
+                              _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -346,6 +359,8 @@ DT_METRIC_Y_LABELS, DT_METRIC_Y_ONEHOT = 0, 1
 DT_METRIC_SUMS_BLOCKS, DT_METRIC_SUMS_WORDS = 256, 771      # dt_metric_sums' out: 3 result words + 3 per block
 DT_LOSS_BCE, DT_LOSS_CCE, DT_LOSS_MSE, DT_LOSS_MAE, DT_LOSS_BINARY_FOCAL, DT_LOSS_CATEGORICAL_FOCAL = 0, 1, 2, 3, 4, 5
 DT_LOSS_MAX_CLASSES = 4096
+DT_CLIP_VALUE, DT_CLIP_NORM, DT_CLIP_GLOBAL_NORM = 0, 1, 2
+DT_FIELD_SUMSQ_PARTS = 32
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

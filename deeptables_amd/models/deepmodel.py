@@ -278,6 +278,10 @@ class DeepModel:
 
     def fused_plan(self):
         """Whole-step kernel plan for this graph, if the library has one (deeptables_amd/fused.py)."""
+        if getattr(getattr(self, 'optimizer', None), 'clip', None) is not None:
+            # gradient clipping sits between the gradients and their update: no fused step may apply an update, and no plan is
+            # built (none re-homes a parameter); training runs layer by layer.  Inference plans are unaffected.
+            return None
         if not hasattr(self, '_fused_plan'):
             from ..fused import make_fused_plan
             self._fused_plan = make_fused_plan(self)
@@ -338,9 +342,16 @@ class DeepModel:
             loss.backward()
         return loss.detach(), logit.detach()
 
+    def _refuse_clipping_under(self, strategy):
+        clip = getattr(getattr(self, 'optimizer', None), 'clip', None)
+        if strategy is not None and clip is not None:
+            raise ValueError(f'`{clip[0]}` with a distribute_strategy: a norm over row-owned tables and exchanged gradients '
+                             f'needs an exchange of its own, which is not there; train on one device or without clipping')
+
     def train_step(self, inputs, y, sample_weight=None):
         """forward -> loss -> backward -> (data-parallel gradient exchange) -> optimizer step."""
         strategy = self.config.distribute_strategy
+        self._refuse_clipping_under(strategy)
         loss, logit = self._forward_backward(inputs, y, sample_weight, apply_rows=strategy is None)
         if strategy is not None:
             strategy.exchange_gradients(self.model, self.optimizer)
@@ -410,6 +421,7 @@ class DeepModel:
                              'DataParallelStrategy (RCCL) instance')
         if self.model is None:
             self.build(strategy.device if strategy is not None else None)
+        self._refuse_clipping_under(strategy)
         if strategy is not None:
             strategy.broadcast_parameters(self.model)
             if feed is not None:

@@ -227,8 +227,209 @@ def focal_from_logits(kind, loss_obj, logit, y, w, activate):
 # ---------------------------------------------------------------------------------------------
 DT_ADAM_STATE_WORDS = 272 // 4        # DT_ADAM_STATE_BYTES (include/dt_hip.h) in int32 words
 
+CLIP_KEYS = ('clipnorm', 'clipvalue', 'global_clipnorm')
+_CLIP_MODES = {'clipvalue': _lib.DT_CLIP_VALUE, 'clipnorm': _lib.DT_CLIP_NORM, 'global_clipnorm': _lib.DT_CLIP_GLOBAL_NORM}
 
-class _DeviceOptimizer:
+
+def check_clip(clipnorm=None, clipvalue=None, global_clipnorm=None):
+    """Keras' three clip arguments -> (key, c) or None: at most one may be set, and it must be a finite number > 0"""
+    given = [(k, v) for k, v in zip(CLIP_KEYS, (clipnorm, clipvalue, global_clipnorm)) if v is not None]
+    if len(given) > 1:
+        raise ValueError(f'Only one of `clipnorm`, `clipvalue` and `global_clipnorm` can be set, got {dict(given)}')
+    for k, v in given:
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or not v > 0:
+            raise ValueError(f'`{k}` must be a finite number greater than 0 (or None: off), got {v!r}')
+    return (given[0][0], float(given[0][1])) if given else None
+
+
+class _GradClip:
+    """keras.optimizers' `clipnorm` / `clipvalue` / `global_clipnorm` (BaseOptimizer._clip_gradients) for every optimizer here:
+    ONE stage at the head of `step()` (csrc/gradclip.hip), ahead of an update that is the unclipped optimizer's, bit for bit.
+    A variable is a Keras variable: a dense parameter, one column's `embeddings_i` (one field's row range of a packed
+    table), a VarLenColumnEmbedding table.  A table's gradient is its dense gradient: duplicate lookups are summed first
+    (dt_rows_coalesce), rows not looked up have gradient 0 and every formula maps 0 to 0, so they are never touched.
+    With a clip set no fused step may apply an update (`supports_row_segments` / `supports_rows_in_step` are False and
+    DeepModel.fused_plan() is None): training runs layer by layer."""
+
+    _clip = None                      # (key, c)
+    last_global_norm = None           # 0-dim float64 device tensor: sqrt(sum over the variables of sum g^2) of the last step
+    _row_segments = False
+    _rows_in_step = False
+
+    @property
+    def supports_row_segments(self):
+        """takes SparseRowGrad.segments"""
+        return self._row_segments and self._clip is None
+
+    @property
+    def supports_rows_in_step(self):
+        """a fused step may apply the update of the rows looked up once itself (fields = -2)"""
+        return self._rows_in_step and self._clip is None
+
+    clip = property(lambda self: self._clip, doc='(key, c) of the clip that is set, or None')
+    clipnorm = property(lambda self: self._clip_value('clipnorm'))
+    clipvalue = property(lambda self: self._clip_value('clipvalue'))
+    global_clipnorm = property(lambda self: self._clip_value('global_clipnorm'))
+
+    def _clip_value(self, key):
+        return self._clip[1] if self._clip is not None and self._clip[0] == key else None
+
+    def _set_clip(self, clipnorm=None, clipvalue=None, global_clipnorm=None):
+        self._clip = check_clip(clipnorm, clipvalue, global_clipnorm)
+
+    def _clip_hp(self):
+        """the part of `hyperparameters()` that says how gradients are clipped: empty when they are not"""
+        return {} if self._clip is None else {self._clip[0]: self._clip[1]}
+
+    def _load_clip_hp(self, hp):
+        """`set_hyperparameters`: clip keys in `hp` replace the setting as a whole -> hp without them"""
+        if any(k in hp for k in CLIP_KEYS):
+            self._set_clip(**{k: hp.get(k) for k in CLIP_KEYS})
+        return {k: v for k, v in hp.items() if k not in CLIP_KEYS}
+
+    # -- the stage ------------------------------------------------------------------------------------------
+    def _clip_buffer(self, name, numel, dtype, device):
+        """persistent scratch of the stage (a captured graph holds its address): grown, never shrunk"""
+        bufs = self.__dict__.setdefault('_clip_bufs', {})
+        t = bufs.get(name)
+        if t is None or t.numel() < numel or t.device != device:
+            t = torch.empty(max(int(numel), 1), dtype=dtype, device=device)
+            bufs[name] = t
+        return t
+
+    def _field_rows(self, layer, key, table):
+        """(host list [row_offset_0, .., V], device int64 [F]) of a packed table: where each column's variable starts"""
+        cache = self.__dict__.setdefault('_clip_fields', {})
+        hit = cache.get((id(layer), key))
+        if hit is None or hit[1].device != table.device:
+            dev_offs = getattr(layer, f'row_offset_{key}', None)
+            if hasattr(layer, 'input_dims') and hasattr(layer, 'groups'):
+                offs, o = [], 0
+                for i in dict(layer.groups)[table.shape[1]]:
+                    offs.append(o)
+                    o += int(layer.input_dims[i])
+            elif dev_offs is not None:
+                offs = [int(v) for v in dev_offs.tolist()]          # (once per table, at the first clipped step)
+            else:
+                offs = [0]
+            if dev_offs is None or dev_offs.device != table.device or dev_offs.dtype != torch.int64:
+                dev_offs = torch.tensor(offs, dtype=torch.int64, device=table.device)
+            hit = (offs + [int(table.shape[0])], dev_offs.contiguous())
+            cache[(id(layer), key)] = hit
+        return hit
+
+    def _flat_regions(self):
+        """[(element offset, span)] of a registered flat group's members inside the flat gradient.  A strided member (a
+        narrow tower inside a zero-padded slab) counts with the pads it encloses: their gradient is 0."""
+        regions = []
+        for off, cnt, layout in self._flat_members:
+            span = cnt if layout is None else 1 + sum((s - 1) * st for s, st in zip(*layout))
+            regions.append((int(off), int(span)))
+        end = 0
+        for off, span in sorted(regions):
+            if off < end or off + span > self._flat[4]:
+                raise ValueError('gradient clipping: two members of the flat group interleave, so a member is no region of it')
+            end = off + span
+        return regions
+
+    def clip_gradients(self):
+        """The clip stage of `step()`: afterwards every `.grad` (contiguous, clipped in place) and every table's
+        `sparse_grads` entry (ONE piece: the distinct rows ascending, then -1, with their summed and clipped gradients,
+        fields = -1) are what the unclipped optimizer is given.  No host synchronisation; replays in a captured graph."""
+        if self._clip is None:
+            return
+        key, c = self._clip
+        mode = _CLIP_MODES[key]
+        h, st = lib(), stream_ptr()
+        regions = []                                       # (address, elements) of the dense variables
+        flat_ids = ()
+        flat = getattr(self, '_flat', None)
+        if flat is not None:
+            fg, members = flat[1], flat[5]
+            with_grad = [p for p in self.params if id(p) in members and p.grad is not None]
+            if len(with_grad) == len(members):
+                outside = [p for p in with_grad if p.grad.data_ptr() != fg.data_ptr() + 4 * members[id(p)]]
+                if len(outside) == len(members):
+                    fg.zero_()
+                for p in outside:                          # (what step() would do: the stage needs it done first)
+                    view = self._flat_grad_view(p)
+                    view.copy_(p.grad.reshape(view.shape))
+                    p.grad = view
+                regions += [(fg.data_ptr() + 4 * off, span) for off, span in self._flat_regions()]
+                flat_ids = members
+        tables = {id(layer.tables[k]): (layer, k) for layer in self.embedding_layers for k in getattr(layer, 'tables', {})}
+        device = None
+        for p in self.params:
+            if p.grad is None:
+                continue
+            device = p.device
+            if id(p) in flat_ids:
+                continue
+            if not p.grad.is_contiguous():
+                p.grad = p.grad.contiguous()
+            g = p.grad
+            if id(p) in tables and p.dim() == 2:           # a packed table with a dense gradient: one variable per column
+                offs, D = self._field_rows(*tables[id(p)], p)[0], p.shape[1]
+                regions += [(g.data_ptr() + 4 * lo * D, (hi - lo) * D) for lo, hi in zip(offs[:-1], offs[1:])]
+            else:
+                regions.append((g.data_ptr(), g.numel()))
+        from .ops import SparseRowGrad
+        sparse, n_sums = [], len(regions)
+        for layer in self.embedding_layers:
+            for k, grads in list(layer.sparse_grads.items()):
+                if not grads:
+                    continue
+                if any(getattr(g, 'segments', None) is not None or getattr(g, 'fields', None) == -2 for g in grads):
+                    raise ValueError(f'{self._name}: gradient clipping takes plain (rows, values) sparse gradients: no segments, no '
+                                     f'rows applied inside a fused step')
+                table = layer.tables[k]
+                V, D = table.shape
+                device = table.device
+                rows = torch.cat([g.rows.reshape(-1) for g in grads]) if len(grads) > 1 else grads[0].rows.reshape(-1)
+                vals = torch.cat([g.values.reshape(-1, D) for g in grads]) if len(grads) > 1 else grads[0].values.reshape(-1, D)
+                rows, vals = rows.contiguous(), vals.contiguous()
+                n = rows.numel()
+                tag = f'{id(table)}'
+                out_rows = self._clip_buffer(tag + '/rows', n, torch.int64, device)[:n]
+                out_vals = self._clip_buffer(tag + '/vals', n * D, torch.float32, device)[:n * D].view(n, D)
+                count = self._clip_buffer(tag + '/count', 1, torch.int64, device)
+                need = int(h.dt_rows_coalesce_workspace_bytes(n, D))
+                if need < 0:
+                    check(need, 'dt_rows_coalesce_workspace_bytes')
+                ws = self._clip_buffer(tag + '/ws', need, torch.uint8, device)
+                check(h.dt_rows_coalesce(ptr(rows), ptr(vals), n, D, V, ptr(out_rows), ptr(out_vals), ptr(count), ptr(ws), st),
+                      'dt_rows_coalesce')
+                offs_dev = self._field_rows(layer, k, table)[1]
+                sparse.append((layer, k, out_rows, out_vals, count, n, D, V, offs_dev, n_sums))
+                n_sums += offs_dev.numel()
+        if device is None:
+            return
+        R = len(regions)
+        gs = ctypes.cast((ctypes.c_void_p * max(R, 1))(*[a for a, _ in regions]), ctypes.c_void_p)
+        ns = ctypes.cast((ctypes.c_int64 * max(R, 1))(*[int(m) for _, m in regions]), ctypes.c_void_p)
+        idx = ctypes.cast((ctypes.c_int * max(R, 1))(*range(R)), ctypes.c_void_p)
+        sums = self._clip_buffer('sums', n_sums, torch.float64, device)
+        if self.last_global_norm is None or self.last_global_norm.device != device:
+            self.last_global_norm = torch.zeros((), dtype=torch.float64, device=device)
+        if mode != _lib.DT_CLIP_VALUE:
+            need = int(h.dt_grad_sumsq_workspace_bytes(R, ns))
+            if need < 0:
+                check(need, 'dt_grad_sumsq_workspace_bytes')
+            ws = self._clip_buffer('sumsq_ws', (need + 7) // 8, torch.float64, device)
+            check(h.dt_grad_sumsq(R, gs, ns, ptr(sums), ptr(ws), st), 'dt_grad_sumsq')
+            for layer, k, out_rows, out_vals, count, n, D, V, offs_dev, base in sparse:
+                parts = self._clip_buffer(f'{id(layer.tables[k])}/parts', offs_dev.numel() * _lib.DT_FIELD_SUMSQ_PARTS,
+                                          torch.float64, device)
+                check(h.dt_rows_field_sumsq(ptr(out_rows), ptr(out_vals), n, D, ptr(count), ptr(offs_dev), offs_dev.numel(), V,
+                                            ctypes.c_void_p(sums.data_ptr() + 8 * base), ptr(parts), st), 'dt_rows_field_sumsq')
+        check(h.dt_grad_clip(mode, c, R, gs, ns, idx, ptr(sums), n_sums, ptr(self.last_global_norm), st), 'dt_grad_clip')
+        for layer, k, out_rows, out_vals, count, n, D, V, offs_dev, base in sparse:
+            check(h.dt_rows_clip(mode, c, ptr(out_rows), ptr(out_vals), n, D, ptr(count), ptr(offs_dev), offs_dev.numel(), V,
+                                 ptr(sums), base, n_sums, None, st), 'dt_rows_clip')
+            layer.sparse_grads[k] = [SparseRowGrad(out_rows, out_vals, fields=-1)]
+
+
+class _DeviceOptimizer(_GradClip):
     """The step driver KerasAdam, Adagrad, RMSprop, Ftrl, Adamax and MomentumSGD share.  One protocol — `zero_grad(flat=...)`, `step()`,
     `register_flat_group`, `pre_dense_hook`, `state`, `t` — and one launch order: the dense tensors in one multi-tensor
     launch (a registered flat group is ONE tensor: the fused train-step plans keep parameters and gradients of all dense
@@ -239,12 +440,13 @@ class _DeviceOptimizer:
     A subclass names its slots (`slot_names`, `slot_init`), spells out its three library calls (`_dense_call`, `_multi_call`,
     `_rows_call`) and, where a table's slots have a layout of their own, `_new_slot` / `_st`, `materialize` / `_restamp`."""
 
-    supports_row_segments = False     # takes SparseRowGrad.segments
-    supports_rows_in_step = False     # a fused step may apply the update of the rows looked up once itself (fields = -2)
+    _row_segments = False             # `supports_row_segments` while no clip is set: takes SparseRowGrad.segments
+    _rows_in_step = False             # `supports_rows_in_step` ...: a fused step may apply the update of the rows looked up once
     slot_names = ()                   # the slots' names: their keys in `state[id(p)]` and in a checkpoint
     slot_init = 0.0                   # the slots' initial value: one number, or one per slot (a tuple matching slot_names)
 
-    def __init__(self, params, embedding_layers):
+    def __init__(self, params, embedding_layers, clipnorm=None, clipvalue=None, global_clipnorm=None):
+        self._set_clip(clipnorm, clipvalue, global_clipnorm)
         self.params = [p for p in params if p.requires_grad]
         self.state = {}
         self.embedding_layers = list(embedding_layers)
@@ -325,6 +527,7 @@ class _DeviceOptimizer:
             self.state[id(p)] = new
         self._flat = (flat_param, flat_grad, slots[0], slots[1] if len(slots) > 1 else None, int(n),
                       {id(p): off for p, off, _, _ in members})
+        self._flat_members = [(off, cnt, layout) for _, off, cnt, layout in members]       # (clip_gradients: the variables)
         self._flat_views = [(p, view_of(flat_grad, p, off, cnt, layout)) for p, off, cnt, layout in members] \
             if grad_views else None
         for p, off, cnt, layout in members:
@@ -381,6 +584,12 @@ class _DeviceOptimizer:
             return
         sp = ptr(self._state_tensor(self.params[0].device))
         st = stream_ptr()
+        if self._clip is not None:
+            # the clip stage sees the gradients the update is given: after a pending exchange has landed
+            hook, self.pre_dense_hook = self.pre_dense_hook, None
+            if hook is not None:
+                hook()
+            self.clip_gradients()
         # every launch of the step reads the device state; the LAST one advances it (no extra launch)
         dense = []                                        # (param, grad, (slot, ..), n)
         flat_done = set()
@@ -488,18 +697,26 @@ class KerasAdam(_DeviceOptimizer):
     a row-sparse ("lazy") update of only the rows touched this step — a documented deviation from Keras' dense
     semantics for tables too large to sweep every step."""
 
-    supports_row_segments = True      # dt_adam_rows_step_seg
-    supports_rows_in_step = True
+    _row_segments = True              # dt_adam_rows_step_seg
+    _rows_in_step = True
     slot_names = ('m', 'v')
     _name = 'Adam'
 
-    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        super().__init__(params, embedding_layers)
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta_1, beta_2, epsilon
         self._applied_in_step = False  # a fused step ran this step's whole update itself (applied_in_step)
 
     def _betas(self):
         return self.b1, self.b2
+
+    def hyperparameters(self):
+        """what travels with a checkpoint: the clip setting alone (Adam's own arguments are the constructor's, as they were)"""
+        return self._clip_hp()
+
+    def set_hyperparameters(self, hp):
+        self._load_clip_hp(hp)
 
     def _new_slot(self, p, rows):
         """rows (the row-sparse table update): m and v of a row side by side in ONE [V, 2, D] array (a 128-byte line at
@@ -558,27 +775,33 @@ class KerasAdam(_DeviceOptimizer):
                                           int(s['m'].stride(0)), st), 'dt_adam_rows_step_seg')
 
 
-class SGD:
+class SGD(_GradClip):
     """keras.optimizers.SGD(learning_rate=0.01, momentum=0.0, nesterov=False).  momentum == 0: p -= lr*g, one launch per
     tensor and per sparse-gradient piece, no state.  momentum != 0: `SGD(...)` returns a `MomentumSGD`, which runs on the
     step driver (one slot `momentum`); both answer to the name 'SGD'."""
 
     _name = 'SGD'
 
-    def __new__(cls, params=(), embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False):
+    def __new__(cls, params=(), embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None,
+                clipvalue=None, global_clipnorm=None):
         if not 0 <= momentum <= 1:
             raise ValueError(f'`momentum` must be in the range [0, 1], got {momentum!r}')
         if cls is SGD and momentum != 0:
-            return MomentumSGD(params, embedding_layers, learning_rate, momentum, nesterov)
+            return MomentumSGD(params, embedding_layers, learning_rate, momentum, nesterov, clipnorm, clipvalue, global_clipnorm)
         return super().__new__(cls)
 
-    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False):
+    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None,
+                 clipvalue=None, global_clipnorm=None):
+        self._set_clip(clipnorm, clipvalue, global_clipnorm)
         self.lr = learning_rate
         self.params = [p for p in params if p.requires_grad]
         self.embedding_layers = list(embedding_layers)
 
     def hyperparameters(self):
-        return {'learning_rate': self.lr, 'momentum': 0.0, 'nesterov': False}
+        return dict({'learning_rate': self.lr, 'momentum': 0.0, 'nesterov': False}, **self._clip_hp())
+
+    def set_hyperparameters(self, hp):
+        self.lr = float(self._load_clip_hp(hp).get('learning_rate', self.lr))
 
     def zero_grad(self):
         for p in self.params:
@@ -588,6 +811,7 @@ class SGD:
 
     def step(self):
         st = stream_ptr()
+        self.clip_gradients()
         for p in self.params:
             if p.grad is not None:
                 g = p.grad.contiguous()
@@ -609,8 +833,8 @@ class _SlotOptimizer(_DeviceOptimizer):
     DeepFM / DCN plans run forward + backward, hand over plain (rows, values) and leave the whole update to `step()`, as
     they do for SGD."""
 
-    def __init__(self, params, embedding_layers, learning_rate, epsilon):
-        super().__init__(params, embedding_layers)
+    def __init__(self, params, embedding_layers, learning_rate, epsilon, clipnorm=None, clipvalue=None, global_clipnorm=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
         self.lr, self.eps = float(learning_rate), float(epsilon)
 
     def slot(self, p):
@@ -620,9 +844,10 @@ class _SlotOptimizer(_DeviceOptimizer):
         return None if s is None else s[self.slot_names[0]]
 
     def hyperparameters(self):
-        return {'learning_rate': self.lr, 'epsilon': self.eps}
+        return dict({'learning_rate': self.lr, 'epsilon': self.eps}, **self._clip_hp())
 
     def set_hyperparameters(self, hp):
+        hp = self._load_clip_hp(hp)
         self.lr, self.eps = float(hp.get('learning_rate', self.lr)), float(hp.get('epsilon', self.eps))
 
 
@@ -635,10 +860,11 @@ class Adagrad(_SlotOptimizer):
     _name = 'Adagrad'
     slot_names = ('acc',)
 
-    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7):
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None):
         if initial_accumulator_value < 0:
             raise ValueError(f'initial_accumulator_value must be non-negative, got {initial_accumulator_value}')
-        super().__init__(params, embedding_layers, learning_rate, epsilon)
+        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm)
         self.initial_accumulator_value = self.slot_init = float(initial_accumulator_value)
 
     def hyperparameters(self):
@@ -673,11 +899,12 @@ class RMSprop(_SlotOptimizer):
     # one 128-byte line at D = 32); True: the last 16 bytes of a [V, D + 4] slot record.  DESIGN.md §3.6 has the measurement.
     stamp_in_record = False
 
-    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False):
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None):
         if momentum != 0 or centered:
             raise ValueError('RMSprop: momentum != 0 and centered=True are not supported (Keras switches to another '
                              f'update formula for them); got momentum={momentum!r}, centered={centered!r}')
-        super().__init__(params, embedding_layers, learning_rate, epsilon)
+        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm)
         self.rho, self.momentum, self.centered = float(rho), 0.0, False
 
     def hyperparameters(self):
@@ -787,13 +1014,15 @@ class _RowSparseOptimizer(_DeviceOptimizer):
         return None if s is None else s[name or self.slot_names[0]]
 
     def hyperparameters(self):
-        return {k: getattr(self, k) for k in self._hp}
+        return dict({k: getattr(self, k) for k in self._hp}, **self._clip_hp())
 
     def set_hyperparameters(self, hp):
-        unknown = sorted(set(hp) - set(self._hp))
+        unknown = sorted(set(hp) - set(self._hp) - set(CLIP_KEYS))
         if unknown:
-            raise ValueError(f'{self._name}: unknown hyperparameters {unknown} (accepted: {list(self._hp)})')
-        self._check(**dict(self.hyperparameters(), **hp))
+            raise ValueError(f'{self._name}: unknown hyperparameters {unknown} (accepted: {list(self._hp + CLIP_KEYS)})')
+        check_clip(**{k: hp.get(k) for k in CLIP_KEYS})                   # a refused update changes nothing
+        self._check(**dict({k: getattr(self, k) for k in self._hp}, **{k: v for k, v in hp.items() if k not in CLIP_KEYS}))
+        hp = self._load_clip_hp(hp)
         for k, v in hp.items():
             setattr(self, k, type(getattr(self, k))(v))
 
@@ -818,9 +1047,10 @@ class MomentumSGD(_RowSparseOptimizer):
     slot_names = ('momentum',)
     _hp = ('learning_rate', 'momentum', 'nesterov')
 
-    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.9, nesterov=False):
+    def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.9, nesterov=False, clipnorm=None,
+                 clipvalue=None, global_clipnorm=None):
         self._check(momentum=momentum)
-        super().__init__(params, embedding_layers)
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
         self.learning_rate, self.momentum, self.nesterov = float(learning_rate), float(momentum), bool(nesterov)
 
     @staticmethod
@@ -854,8 +1084,9 @@ class Adamax(_RowSparseOptimizer):
     slot_names = ('m', 'u')
     _hp = ('learning_rate', 'beta_1', 'beta_2', 'epsilon')
 
-    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
-        super().__init__(params, embedding_layers)
+    def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
+                 clipnorm=None, clipvalue=None, global_clipnorm=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = float(learning_rate), float(beta_1), float(beta_2), \
             float(epsilon)
 
@@ -897,11 +1128,11 @@ class Ftrl(_RowSparseOptimizer):
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, learning_rate_power=-0.5,
                  initial_accumulator_value=0.1, l1_regularization_strength=0.0, l2_regularization_strength=0.0,
-                 l2_shrinkage_regularization_strength=0.0, beta=0.0):
+                 l2_shrinkage_regularization_strength=0.0, beta=0.0, clipnorm=None, clipvalue=None, global_clipnorm=None):
         hp = dict(zip(self._hp, (learning_rate, learning_rate_power, initial_accumulator_value, l1_regularization_strength,
                                  l2_regularization_strength, l2_shrinkage_regularization_strength, beta)))
         self._check(**hp)
-        super().__init__(params, embedding_layers)
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
         for k, v in hp.items():
             setattr(self, k, float(v))
 

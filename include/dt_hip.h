@@ -1357,6 +1357,64 @@ int dt_cell_fwd(const float* x, int64_t N, int C, int act, float rate, const uns
 int dt_cell_bwd(const float* g, const float* saved, int saved_is_input, int64_t N, int C, int act, float rate,
                 const unsigned* seed, unsigned salt, float* dx, void* stream);
 
+/* Gradient clipping on the device (csrc/gradclip.hip): keras.optimizers' clipvalue / clipnorm / global_clipnorm
+ * (BaseOptimizer._clip_gradients) ahead of any optimizer step, and the row-sparse table gradient with its duplicate lookups
+ * summed, which a norm or an element clamp of the TRUE per-row gradient needs.  Common rules: no float atomics, no block
+ * waits for another, every sum runs in an order fixed by the sizes and the id pattern alone (the same input gives the same
+ * bits), nothing is allocated, there is no host synchronisation, and every scalar a later kernel needs (sums, counts) is read
+ * from DEVICE memory, so a captured graph replays correctly.  Every argument is checked before the first launch: a negative
+ * size, a null pointer with something to do, a float / int64 / double array that is not aligned to its element, a null
+ * workspace or one that is not 16-byte aligned, an unknown mode and a c that is not a finite number > 0 are
+ * DT_ERR_INVALID_ARG.  A "variable" is one Keras variable: a dense tensor, or one field's row range of a packed table.
+ *
+ * dt_rows_coalesce: (rows int64 [n], values [n, D]) -> out_rows [n]: the distinct row ids ascending, then -1; out_vals [n, D]:
+ *   each distinct row's summed gradient, the tail exactly 0 (a sum of squares over all n D floats is the table's);
+ *   count[0] (int64, device) = distinct rows.  A row id outside [0, V) is a skipped lookup (-1 is the usual spelling).
+ *   V, the table's row count, must be in [1, 2^32 - 1]: ids are sort keys of 32 bits, 2^32 - 1 marks a skipped lookup.
+ *   n in [0, 2^31); n == 0 writes count[0] = 0 and looks at nothing else; any D >= 1 (16-byte pieces where D % 4 == 0 and
+ *   values / out_vals are 16-byte aligned; every route gives the same bits).  Built on dt_metric_sort_pairs keyed on the row
+ *   id with the lookup position as the value (stable: a row's lookups keep their order), then a scan of the segment heads
+ *   and a sum through that inverted index: the sorted positions are cut into chunks of dt_rows_coalesce_chunk() = 512; inside
+ *   a chunk every row's lookups are added in order; a row that spans chunks gets one partial per chunk and the partials are
+ *   added in chunk order — a hot row with thousands of lookups is never one thread's walk.  rows / values are not written
+ *   and must not overlap the outputs.  ws: dt_rows_coalesce_workspace_bytes(n, D) bytes.  19 launches.
+ * dt_grad_sumsq: sums[t] (double, device, [count]) = sum of g[t][i]^2 over n[t] elements, squares and sums in float64 (the
+ *   multi-tensor form of dt_reg_penalty: g / n are HOST arrays, 32 tensors per launch pair; a block sums one chunk of
+ *   dt_reg_chunk() elements in a fixed order, one block per tensor adds its partials in index order).  An empty tensor
+ *   gives 0.  ws: dt_grad_sumsq_workspace_bytes(count, n) bytes, 8-byte aligned.
+ * dt_rows_field_sumsq: for a coalesced table (out_rows ascending then -1, count[0] distinct rows): sums[f] (double, device,
+ *   [F]) = sum of squares of the rows in [row_offset[f], row_offset[f + 1]) (the last field ends at V); row_offset: DEVICE
+ *   int64 [F], ascending from 0.  A field is one contiguous range of the sorted rows, found by binary search on the
+ *   device; DT_FIELD_SUMSQ_PARTS blocks per field sum one slice each, one thread per field adds the slices in index order
+ *   (2 launches).  A field with no lookup gives 0.  ws: F * DT_FIELD_SUMSQ_PARTS doubles, 8-byte aligned.
+ * dt_grad_clip / dt_rows_clip: in place, mode DT_CLIP_*; c: the host constant; sums: the DEVICE array of n_sums doubles the
+ *   calls above filled, one per variable (not read by DT_CLIP_VALUE, may be NULL there):
+ *     DT_CLIP_VALUE        g = g < -c ? -c : (g > c ? c : g)                           (NaN stays NaN)
+ *     DT_CLIP_NORM         n_v = (float)sqrt(sums[v]);  g = fl(fl(g c) / max(n_v, c))
+ *     DT_CLIP_GLOBAL_NORM  N = (float)sqrt(sums[0] + sums[1] + ... in index order);  s = fl(c min(fl(1 / N), fl(1 / c))) +
+ *                          (N - N);  g = fl(g s): a non-finite N makes every gradient NaN, as Keras does
+ *   dt_grad_clip: tensor t is variable sum_index[t] (HOST int array; unused for the other modes, may be NULL there); 32
+ *   tensors per launch.  dt_rows_clip: row out_rows[j], j < count[0], belongs to the field f with row_offset[f] <= row <
+ *   row_offset[f + 1], which is variable sum_base + f.  norm_out (device double, or NULL): receives sqrt of the sum of all
+ *   n_sums entries (0 for DT_CLIP_VALUE).                                                                                  */
+#define DT_CLIP_VALUE 0
+#define DT_CLIP_NORM 1
+#define DT_CLIP_GLOBAL_NORM 2
+#define DT_FIELD_SUMSQ_PARTS 32
+int dt_rows_coalesce_chunk(void);
+int64_t dt_rows_coalesce_workspace_bytes(int64_t n, int D);
+int dt_rows_coalesce(const int64_t* rows, const float* values, int64_t n, int D, int64_t V, int64_t* out_rows, float* out_vals,
+                     int64_t* count, void* ws, void* stream);
+int64_t dt_grad_sumsq_workspace_bytes(int count, const int64_t* n);
+int dt_grad_sumsq(int count, const float* const* g, const int64_t* n, double* sums, void* ws, void* stream);
+int dt_rows_field_sumsq(const int64_t* out_rows, const float* out_vals, int64_t n, int D, const int64_t* count,
+                        const int64_t* row_offset, int F, int64_t V, double* sums, void* ws, void* stream);
+int dt_grad_clip(int mode, float c, int count, float* const* g, const int64_t* n, const int* sum_index, const double* sums,
+                 int n_sums, double* norm_out, void* stream);
+int dt_rows_clip(int mode, float c, const int64_t* out_rows, float* out_vals, int64_t n, int D, const int64_t* count,
+                 const int64_t* row_offset, int F, int64_t V, const double* sums, int sum_base, int n_sums, double* norm_out,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
