@@ -2203,7 +2203,6 @@ struct RowsAdam {
     int sstride;                 // floats between the slot records of consecutive rows (D: separate m / v arrays; 2 D: [V,2,D])
     const float* lr_t_dev;       // device-resident bias-corrected rate (AdamState), or NULL -> lr_t_host
     float lr_t_host, b1, b2, eps;
-    int wt;                      // write-through stores (st4_wt)
 };
 struct RowsEpi {
     const float *dXn, *X, *dz, *S, *wlin, *sc, *mean, *rstd;
@@ -2215,13 +2214,35 @@ struct RowsEpi {
     int field_major;
 };
 constexpr int kRowsUB = 4;
+constexpr int kRowsStage = 2;        // passes per pipeline stage of the fast body (two stages in flight = kRowsUB passes)
+
+// one stage of the fast body: a chunk of kRowsStage passes with every load of it issued
+struct RowsStage {
+    int64_t row[kRowsStage];
+    floatx4 gx[kRowsStage], xr[kRowsStage], sv[kRowsStage], mv[kRowsStage], vv[kRowsStage];
+    float dzv[kRowsStage];
+    int bb[kRowsStage];
+    bool ok[kRowsStage];
+    bool live;                       // the stage's work ticket lies inside the block's share (wave-uniform)
+};
 
 // One WAVE's share of the epilogue.  A wave covers the 16-byte pieces of one batch row (F D/4 <= 64: several rows per pass)
 // or one half of them (F D/4 in (64, 128]: `parts` = 2, wave w takes half w % 2), so its per-column constants are
 // loaded once; work = chunks of kRowsUB passes pulled from an LDS counter per part (`work`), shared by every wave of the
 // block that runs this function — the block's memory waves from the start, its matrix waves once their GEMM is stored
 // (k_wgrad_rows): with B = 8192 the matrix waves are done after ~28 K of the memory waves' ~69 K cycles.
-template <bool DCN>
+// FAST: the combination DeepModel.fit runs, fixed at compile time by the launch site — the in-step Adam (ad.table), no
+// embedding dropout (drop.thr == 0), row-major gradient rows.  Its loads are unconditional and sit in one basic block per
+// stage, and it runs as a two-stage software pipeline over chunks of kRowsStage passes: while a wave does the arithmetic and
+// the stores of chunk i, every load of chunk i + 1 (ticket -> ids -> streaming operands -> m, v) is already in flight, and
+// each wait for one of them counts only operations issued before the stores of chunk i.  (What is left per stage: the wait
+// for the ids of chunk i + 1 also covers the stores of chunk i - 1, issued just before them.  Measured at B = 8192, uniform
+// ids: 2 passes per stage 91.4 us per step, 3: 91.7, 4: 92.0; the specialised body without the pipeline 94.4, before 94.7.)
+// No read-after-write hazard
+// between chunks: a row with rows_out >= 0 occurs once in the batch (the election), segment members only store their own
+// gradient row.  (The one exception, an election overflow at B > 8192, is invalid already and flagged by check_dedupe.)
+// Every other combination takes the generic body.
+template <bool DCN, bool FAST>
 __device__ __forceinline__ void rows_epilogue_wave(unsigned* work, int first_tile, int tile_stride, const DeepFmDims& dm,
                                                    const RowsEpi& a, const RowsAdam& ad, const EmbDrop& drop) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2236,7 +2257,7 @@ __device__ __forceinline__ void rows_epilogue_wave(unsigned* work, int first_til
     const int f = piece / LPR, c = piece - f * LPR;
     const int col = 4 * piece;                             // = f * D + 4 c
     const int tiles = (dm.B + kTM - 1) / kTM;
-    const int chunk_rows = rpw * kRowsUB, chunks = (kTM + chunk_rows - 1) / chunk_rows;
+    const int chunk_rows = rpw * (FAST ? kRowsStage : kRowsUB), chunks = (kTM + chunk_rows - 1) / chunk_rows;
     int dshift = 0;
     while ((1 << dshift) < dm.D) ++dshift;
     const floatx4 ca = ld4(a.sc + col), cmu = ld4(a.mean + col);
@@ -2261,6 +2282,77 @@ __device__ __forceinline__ void rows_epilogue_wave(unsigned* work, int first_til
     }
     const float wl = DCN ? 0.f : a.wlin[f];
     const float lr_t = ad.lr_t_dev ? *ad.lr_t_dev : ad.lr_t_host;
+    if constexpr (FAST) {
+        // pulls the next work ticket and issues every load of its chunk, all from clamped (valid) addresses — also for a
+        // ticket past the end (live = false), whose results the wave discards before it leaves
+        auto fetch = [&](RowsStage& s) {
+            unsigned it = 0;
+            if (lane == 0) it = atomicAdd(&work[part], 1u);
+            it = __builtin_amdgcn_readfirstlane(it);
+            const int ti = (int)(it / (unsigned)chunks), ch = (int)(it - (unsigned)ti * (unsigned)chunks);
+            const int tile = first_tile + ti * tile_stride;
+            s.live = tile < tiles;
+            const int b0 = min(tile, tiles) * kTM;
+#pragma unroll
+            for (int k = 0; k < kRowsStage; ++k) {
+                const int r = ch * chunk_rows + k * rpw + rsub;
+                s.ok[k] = s.live && active && r < kTM && b0 + r < dm.B;
+                s.bb[k] = min(b0 + min(r, kTM - 1), dm.B - 1);
+                s.row[k] = a.rows_out[(int64_t)s.bb[k] * dm.F + f];
+            }
+#pragma unroll
+            for (int k = 0; k < kRowsStage; ++k) {
+                s.gx[k] = ld4(a.dXn + (int64_t)s.bb[k] * dm.CP + col);
+                s.xr[k] = ld4(a.X + (int64_t)s.bb[k] * dm.CP + col);
+                if (!DCN) {
+                    s.sv[k] = ld4(a.S + ((int64_t)s.bb[k] << dshift) + 4 * c);
+                    s.dzv[k] = a.dz[s.bb[k]];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kRowsStage; ++k) {
+                const int64_t rr = (s.ok[k] && s.row[k] >= 0) ? s.row[k] : 0;
+                s.mv[k] = ld4(ad.m + rr * ad.sstride + 4 * c);
+                s.vv[k] = ld4(ad.v + rr * ad.sstride + 4 * c);
+            }
+        };
+        // the arithmetic and the stores of a fetched chunk; p is the X tile's copy of the table row (see the generic body).
+        // Only the stores are divergent.
+        auto finish = [&](const RowsStage& s) {
+#pragma unroll
+            for (int k = 0; k < kRowsStage; ++k) {
+                floatx4 g = ca * (s.gx[k] - c1 - (s.xr[k] - cmu) * c2);
+                if (!DCN) g = g + s.dzv[k] * wl + s.dzv[k] * (s.sv[k] - s.xr[k]);
+                // Keras Adam (optim.hip): m, v, p of this 16-byte piece of the row
+                floatx4 mi = s.mv[k], vi = s.vv[k], pi = s.xr[k];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    mi[e] = ad.b1 * mi[e] + (1.f - ad.b1) * g[e];
+                    vi[e] = ad.b2 * vi[e] + (1.f - ad.b2) * g[e] * g[e];
+                    pi[e] -= lr_t * mi[e] / (sqrtf(vi[e]) + ad.eps);
+                }
+                if (s.ok[k] && s.row[k] >= 0) {
+                    st4(ad.m + s.row[k] * ad.sstride + 4 * c, mi);
+                    st4(ad.v + s.row[k] * ad.sstride + 4 * c, vi);
+                    st4(ad.table + (s.row[k] << dshift) + 4 * c, pi);
+                } else if (s.ok[k]) {                      // segment members: the lookup's own gradient row
+                    st4(a.grad_rows + (((int64_t)s.bb[k] * dm.F + f) << dshift) + 4 * c, g);
+                }
+            }
+        };
+        // two stages, unrolled by hand so that no stage's registers are copied (a copy would wait for the loads it moves)
+        RowsStage s0, s1;
+        fetch(s0);
+        for (;;) {
+            if (!s0.live) break;
+            fetch(s1);
+            finish(s0);
+            if (!s1.live) break;
+            fetch(s0);
+            finish(s1);
+        }
+        return;
+    }
     const unsigned dseed = drop.thr ? *drop.seed : 0u;
     for (;;) {
         unsigned it = 0;
@@ -2324,9 +2416,9 @@ __device__ __forceinline__ void rows_epilogue_wave(unsigned* work, int first_til
                         vi[e] = ad.b2 * vi[e] + (1.f - ad.b2) * g[e] * g[e];
                         pi[e] -= lr_t * mi[e] / (sqrtf(vi[e]) + ad.eps);
                     }
-                    st4_sel(ad.m + row[k] * ad.sstride + 4 * c, mi, ad.wt);
-                    st4_sel(ad.v + row[k] * ad.sstride + 4 * c, vi, ad.wt);
-                    st4_sel(ad.table + (row[k] << dshift) + 4 * c, pi, ad.wt);
+                    st4(ad.m + row[k] * ad.sstride + 4 * c, mi);
+                    st4(ad.v + row[k] * ad.sstride + 4 * c, vi);
+                    st4(ad.table + (row[k] << dshift) + 4 * c, pi);
                 } else if (ok[k]) {
                     if (a.field_major)   // model-parallel tables: [F,B,D], already divided by the world size
                         st4(a.grad_rows + (((int64_t)f * dm.B + bb[k]) << dshift) + 4 * c, g * a.grad_scale);
@@ -2338,7 +2430,9 @@ __device__ __forceinline__ void rows_epilogue_wave(unsigned* work, int first_til
     }
 }
 
-template <bool DCN, int WM = 0>      // WM: the weight-gradient GEMMs on fp32 MFMA (0), plain bf16 (1) or split-bf16 (2: wgrad_heavy_bf16)
+// WM: the weight-gradient GEMMs on fp32 MFMA (0), plain bf16 (1) or split-bf16 (2: wgrad_heavy_bf16); FAST: the row epilogue's
+// specialised body (rows_epilogue_wave)
+template <bool DCN, int WM = 0, bool FAST = false>
 __global__ __launch_bounds__(512) void k_wgrad_rows(const float* __restrict__ X, MlpParams p, DeepFmDims dm,
                                                     const float* __restrict__ H1, const float* __restrict__ dH1,
                                                     const float* __restrict__ dH2, int row_blocks, int rows_per_block,
@@ -2369,7 +2463,7 @@ __global__ __launch_bounds__(512) void k_wgrad_rows(const float* __restrict__ X,
             }
         }
         // the GEMM's partial tile is stored: the matrix waves take their share of what is left of the epilogue
-        if (matrix_waves_join) rows_epilogue_wave<DCN>(work, (int)blockIdx.x, (int)gridDim.x, dm, ep, ad, drop);
+        if (matrix_waves_join) rows_epilogue_wave<DCN, FAST>(work, (int)blockIdx.x, (int)gridDim.x, dm, ep, ad, drop);
         if (stamps_all && threadIdx.x == 0) stamps_all[(int64_t)blockIdx.x * 16 + 6] = __builtin_amdgcn_s_memtime();
     } else {
         if (stamps_rows && threadIdx.x == 256) stamps_rows[(int64_t)blockIdx.x * 16] = __builtin_amdgcn_s_memtime();
@@ -2378,7 +2472,7 @@ __global__ __launch_bounds__(512) void k_wgrad_rows(const float* __restrict__ X,
         // the finishing launch reads the step's rate from this copy, so that ONE of its threads may advance the device state
         // at any time (see k_finish_step: no arrival tickets)
         if (lr_snap && blockIdx.x == 0 && threadIdx.x == 256) *lr_snap = ad.lr_t_dev ? *ad.lr_t_dev : ad.lr_t_host;
-        rows_epilogue_wave<DCN>(work, (int)blockIdx.x, (int)gridDim.x, dm, ep, ad, drop);
+        rows_epilogue_wave<DCN, FAST>(work, (int)blockIdx.x, (int)gridDim.x, dm, ep, ad, drop);
         if (stamps_rows && threadIdx.x == 256) stamps_rows[(int64_t)blockIdx.x * 16 + 3] = __builtin_amdgcn_s_memtime();
     }
 }
@@ -2891,23 +2985,29 @@ static int tower_train_step(
         const RowsEpi ep{ws + wl.dXn, ws + wl.X, ws + wl.dz, ws + wl.S, w_lin, ws + wl.sc, ws + wl.mean, ws + wl.rstd,
                          rsrc, pl3.sdx, pl3.sdxx, rows_out, grad_rows, grad_rows_scale, grad_rows_field_major};
         // (measured in round 3: write-through row-update stores 118.1 vs 114.5 us per step, write-through tile outputs no
-        // change — the kernel boundaries do not wait for this data: plain stores)
-        RowsAdam ad = adam ? *adam : RowsAdam{nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, 0.f, 0.f, 0};
+        // change — the kernel boundaries do not wait for this data: plain stores; the row epilogue has no write-through arm)
+        RowsAdam ad = adam ? *adam : RowsAdam{nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0.f, 0.f, 0.f};
         const int join_env = 1;            // the matrix waves join the row epilogue once their tile is stored
         // the weight-gradient GEMMs follow the tower's mode: exact fp32 MFMA with the exact tower, split-bf16 (two parts, like
         // the tile kernel's backward products) with the split tower, plain bf16 in the 1e-2 mode; stamped diagnostics keep fp32
         const int wm = (!x3 || stamps) ? 0 : bf16_flag ? 1 : 2;
-#define DT_ED(DCNV, WMV)                                                                                                  \
+        // the row epilogue's specialised body (rows_epilogue_wave<.., FAST>): what DeepModel.fit runs — the in-step Adam, no
+        // embedding dropout, row-major gradient rows; everything else takes the generic body
+        const bool fast_rows = ad.table && !drop.thr && !grad_rows_field_major;
+#define DT_ED(DCNV, WMV, FASTV)                                                                                           \
     do {                                                                                                                  \
-        hipFuncSetAttribute((const void*)k_wgrad_rows<DCNV, WMV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsE);   \
-        hipLaunchKernelGGL((k_wgrad_rows<DCNV, WMV>), dim3(nmac * row_blocks), dim3(512), ldsE, st, ws + wl.X, mp, dm,       \
+        hipFuncSetAttribute((const void*)k_wgrad_rows<DCNV, WMV, FASTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsE); \
+        hipLaunchKernelGGL((k_wgrad_rows<DCNV, WMV, FASTV>), dim3(nmac * row_blocks), dim3(512), ldsE, st, ws + wl.X, mp, dm, \
                            ws + wl.H1, ws + wl.dH1, ws + wl.dH2, row_blocks, rows_per_block, ws + wl.wpart,                \
                            stamps ? stamps + (int64_t)tiles * 32 : nullptr, ep, ad, drop,                                 \
                            stamps ? stamps + (int64_t)tiles * 16 : nullptr, join_env, bnacc, (int)wl.bnacc_n, nx, gpt,    \
                            (adam && sdense) ? ws + wl.lrsnap : nullptr);                                               \
     } while (0)
-        if (dcn) { if (wm == 0) DT_ED(true, 0); else if (wm == 1) DT_ED(true, 1); else DT_ED(true, 2); }
-        else { if (wm == 0) DT_ED(false, 0); else if (wm == 1) DT_ED(false, 1); else DT_ED(false, 2); }
+#define DT_ED_W(DCNV, FASTV)                                                                                              \
+    do { if (wm == 0) DT_ED(DCNV, 0, FASTV); else if (wm == 1) DT_ED(DCNV, 1, FASTV); else DT_ED(DCNV, 2, FASTV); } while (0)
+        if (dcn) { if (fast_rows) DT_ED_W(true, true); else DT_ED_W(true, false); }
+        else { if (fast_rows) DT_ED_W(false, true); else DT_ED_W(false, false); }
+#undef DT_ED_W
 #undef DT_ED
         trace_mark(3, st);
         if (adam && sdense) {
@@ -2978,7 +3078,7 @@ static int step_adam_args(const char* what, float* table, int D, void* dedupe_ws
     DT_REQUIRE(((uintptr_t)table | (uintptr_t)adam_m | (uintptr_t)adam_v) % 16 == 0,
                "%s: table / slots must be 16-byte aligned", what);
     out->ad = RowsAdam{table, adam_m, adam_v, slot_stride, adam_state ? adam_state_lr_t(adam_state) : nullptr, lr_t, beta1,
-                       beta2, eps, 0};
+                       beta2, eps};
     out->sd = StepDense{dense_p, dense_m, dense_v, dense_n, adam_state, lr};
     out->ch = StepChain{next_idx, next_rows_out, next_dedupe_ws};
     return DT_OK;
