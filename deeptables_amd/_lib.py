@@ -33,6 +33,11 @@ SIGNATURES = {
     'dt_embedding_fwd': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr,
                                   _ptr, _ptr]),
     'dt_embedding_bwd_dense': (_c_int, [_ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
+    'dt_embedding_drop_pass_units': (_c_i64, []),
+    'dt_embedding_drop_fwd': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32,
+                                       _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_embedding_drop_bwd': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_f32, _ptr, ctypes.c_uint32, _ptr, _ptr, _ptr,
+                                       _ptr]),
     'dt_fm_fwd': (_c_int, [_ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_fm_bwd': (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_embed_fm_linear_fwd': (_c_int, [_ptr, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int,

@@ -27,6 +27,7 @@
 // one torch's CPU autograd takes for the definition deeptables_amd.functional.get_activation registers.
 #include <math.h>
 
+#include "cell_hash.h"
 #include "common.h"
 
 namespace dt {
@@ -38,23 +39,7 @@ constexpr int64_t kMaxElems = (int64_t)1 << 40;
 
 typedef float cell_f4 __attribute__((ext_vector_type(4)));
 
-// ---- the dropout hash --------------------------------------------------------------------------------------------------
-__host__ __device__ inline unsigned cell_mix(unsigned x) {           // the finalizer of ai_hash (csrc/autoint.hip)
-    x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-    return x;
-}
-// the part that is the same for every element of a launch
-__host__ __device__ inline unsigned cell_hash_head(unsigned seed, unsigned salt) { return cell_mix(seed ^ (salt * 0x9E3779B1u)); }
-// row, then column, each through a bijection of the running word: two elements of one launch collide only by chance
-__host__ __device__ inline unsigned cell_hash_tail(unsigned head, unsigned row, unsigned col) {
-    const unsigned r = cell_mix(head ^ (row * 0x85EBCA77u));
-    return cell_mix(r ^ (col * 0xC2B2AE3Du));
-}
-// keep iff hash >= thr, thr = rate * 2^32 saturated
-inline unsigned cell_threshold(float rate) {
-    const double t = (double)rate * 4294967296.0;
-    return t >= 4294967295.0 ? 4294967295u : (t <= 0.0 ? 0u : (unsigned)t);
-}
+// (the dropout hash: cell_hash.h, shared with csrc/emb_dropout.hip)
 
 // ---- activations -------------------------------------------------------------------------------------------------------
 constexpr float kLeakySlope = 0.2f;                    // [ext] keras.activations.leaky_relu's default negative_slope

@@ -191,6 +191,7 @@ def shape_of(x):
 class Layer(nn.Module):
     activity_regularizer = None     # a regularizers.Regularizer on the layer's outputs (Keras' Layer argument)
     records_own_activity = False    # the layer's `call` hands the penalised tensors to the sink itself (the embeddings)
+    takes_cell_seed = False         # the executing Model hands `call` its forward's CellSeed (the embedding layers' dropout)
     _activity_sink = None           # list the executing Model collects (tensor, (l1, l2)) in during ITS forward, else None
 
     def __init__(self, name=None, trainable=True, dtype=None, **kwargs):
@@ -744,7 +745,7 @@ class Model(nn.Module):
                 out = fetch(node.inputs)                      # its mask already ran inside the producing activation launch
             elif id(node) in self._cell_fused:
                 out = node.layer(fetch(node.inputs), cell_dropout=self._cell_fused[id(node)].cell_args(seeds))
-            elif type(node.layer) is Dropout:
+            elif type(node.layer) is Dropout or getattr(node.layer, 'takes_cell_seed', False):
                 out = node.layer(fetch(node.inputs), cell_seed=seeds)
             elif id(node) in self._fused_relu:
                 out = node.layer(fetch(node.inputs), fused_activation='relu')

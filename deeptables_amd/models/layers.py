@@ -14,7 +14,7 @@ from torch import nn
 
 from .. import ops, regularizers
 from ..functional import (Layer, Dense, Dropout, BatchNormalization, Activation, Concatenate, Flatten,  # noqa: F401
-                          Input, Lambda, Add, SpatialDropout1D, ReduceSum, initialize, get_activation)
+                          Input, Lambda, Add, SpatialDropout1D, ReduceSum, CellSeed, initialize, get_activation)
 from ..utils import consts  # noqa: F401
 
 
@@ -359,6 +359,13 @@ class CIN(Layer):
 DENSE_GRAD_MAX_ELEMS = 1 << 22
 
 
+def _fused_emb_dropout(layer, inputs):
+    """True when an embedding layer's dropout runs inside its gather launch (csrc/emb_dropout.hip): training, a rate that
+    needs a mask, ids on the GPU, and DT_AMD_EMB_DROPOUT not '0' (read at every call).  Everything else — evaluation, rate 0,
+    CPU tensors, the switch — keeps the layer's SpatialDropout1D modules."""
+    return layer.training and 0.0 < float(layer.dropout_rate) < 1.0 and inputs.is_cuda and ops.emb_dropout_enabled()
+
+
 class MultiColumnEmbedding(Layer):
     """One embedding table per categorical column, all looked up from one [B,F] input.
 
@@ -368,6 +375,7 @@ class MultiColumnEmbedding(Layer):
     views of one [B,F,D] block so the graph's three Concatenate layers over them cost nothing."""
 
     records_own_activity = True         # `call` records the packed block (or the dropped-out outputs), not F views
+    takes_cell_seed = True              # functional.Model hands `call` the forward's CellSeed
 
     def __init__(self, input_dims, output_dims, dropout_rate=0., embeddings_initializer='uniform',
                  embeddings_regularizer=None, activity_regularizer=None, embeddings_constraint=None,
@@ -423,6 +431,7 @@ class MultiColumnEmbedding(Layer):
             self.register_buffer(f'row_offset_d{D}', torch.from_numpy(offs), persistent=False)
             self.register_buffer(f'vocab_d{D}', torch.tensor(vocabs, dtype=torch.int32), persistent=False)
             self.register_buffer(f'cols_d{D}', torch.tensor(cols, dtype=torch.int64), persistent=False)
+            self.register_buffer(f'col_base_d{D}', torch.tensor(self.column_bases()[cols], dtype=torch.int32), persistent=False)
         self.register_buffer('oob_count', torch.zeros(1, dtype=torch.int32), persistent=False)
         self.dropouts = nn.ModuleList(
             [SpatialDropout1D(self.dropout_rate) for _ in self.input_dims]) if self.dropout_rate > 0 else []
@@ -471,30 +480,45 @@ class MultiColumnEmbedding(Layer):
             return None
         return inputs != 0
 
-    def lookup_group(self, inputs, D, cols):
+    def column_bases(self):
+        """col_base[i] = sum(output_dims[:i]): where column i starts in the concatenation of all of the layer's outputs — the
+        column coordinate of its dropout mask (csrc/emb_dropout.hip)"""
+        return np.concatenate([[0], np.cumsum(self.output_dims)[:-1]]).astype(np.int64)
+
+    def lookup_group(self, inputs, D, cols, drop_seed=None):
+        """drop_seed: the forward's seed word when the layer's dropout runs inside the gather launch, else None"""
         key = f'd{D}'
         table = self.tables[key]
         idx = inputs
         if len(self.groups) > 1 or len(cols) != inputs.shape[1]:
             idx = inputs.index_select(1, getattr(self, f'cols_{key}'))
         holder = _GroupHolder(self, key)
+        dropout = None if drop_seed is None else \
+            (self.dropout_rate, drop_seed, ops.cell_salt(self.name), getattr(self, f'col_base_{key}'))
         return ops.embedding_lookup(idx, table, getattr(self, f'row_offset_{key}'), getattr(self, f'vocab_{key}'),
                                     holder=holder, dense_grad=self.uses_dense_grad(D),
-                                    oob=self.oob_count if self.check_oob else None)
+                                    oob=self.oob_count if self.check_oob else None, dropout=dropout)
 
-    def call(self, inputs, **kwargs):
+    def call(self, inputs, cell_seed=None, **kwargs):
+        """cell_seed: the executing model's CellSeed (one draw per forward); a layer called on its own draws its own"""
         if inputs.shape[1] == 0:
             return []
         if inputs.dtype not in (torch.float32, torch.int32):
             inputs = inputs.to(torch.int32)
         out = [None] * len(self.input_dims)
+        # training with a mask on the GPU: the dropout runs inside each group's gather launch and its backward, the outputs
+        # are views of the dropped block (DT_AMD_EMB_DROPOUT=0: the per-column torch chain below)
+        drop_seed = None
+        if _fused_emb_dropout(self, inputs):
+            drop_seed = (cell_seed if cell_seed is not None else CellSeed())(inputs.device)
+        in_launch = drop_seed is not None or not self.dropout_rate > 0       # else: one SpatialDropout1D per column below
         for D, cols in self.groups:
-            emb, _rows = self.lookup_group(inputs, D, cols)       # [B, len(cols), D]
-            if not self.dropout_rate > 0:
+            emb, _rows = self.lookup_group(inputs, D, cols, drop_seed)       # [B, len(cols), D]
+            if in_launch:
                 self.record_activity([emb])        # the group's outputs in one piece: the same sum as its columns' views
             for k, i in enumerate(cols):
                 v = emb[:, k:k + 1, :]
-                if self.dropout_rate > 0:
+                if not in_launch:
                     v = self.dropouts[i](v)
                     self.record_activity([v])      # Keras penalises the layer's outputs: after their SpatialDropout1D
                 elif len(self.groups) == 1:
@@ -738,6 +762,7 @@ class VarLenColumnEmbedding(Layer):
     """One table shared by the L positions of a multi-valued column: [B,L] ids -> [B,1,L*D].
     The gather is the same HIP kernel as MultiColumnEmbedding with every 'field' pointing at one table."""
     records_own_activity = True         # `call` records the inner lookup, not the reshaped output
+    takes_cell_seed = True              # functional.Model hands `call` the forward's CellSeed
 
     def __init__(self, emb_vocab_size, emb_output_dim, embeddings_initializer='uniform',
                  embeddings_regularizer=None, activity_regularizer=None, dropout_rate=0., **kwargs):
@@ -761,11 +786,21 @@ class VarLenColumnEmbedding(Layer):
             self._weight_regularizers.append((self.embeddings, self.embeddings_regularizer))
         self.register_buffer('row_offset', torch.zeros(L, dtype=torch.int64))
         self.register_buffer('vocab', torch.full((L,), self.emb_vocab_size, dtype=torch.int32))
+        # position l starts at l * D of the [B, 1, L * D] output: the column coordinate of its dropout mask
+        self.register_buffer('col_base', torch.arange(L, dtype=torch.int32) * self.emb_output_dim, persistent=False)
         self.dropout = SpatialDropout1D(self.dropout_rate, name='var_len_emb_dropout') \
             if self.dropout_rate > 0 else None
         self.built = True
 
-    def call(self, inputs, **kwargs):
+    def call(self, inputs, cell_seed=None, **kwargs):
+        """cell_seed: the executing model's CellSeed (one draw per forward); a layer called on its own draws its own"""
+        # the dropout inside the gather launch, unless an activity penalty wants the inner Embedding's output BEFORE it
+        if _fused_emb_dropout(self, inputs) and \
+                (self._activity_sink is None or regularizers.active(self.activity_regularizer) is None):
+            seed = (cell_seed if cell_seed is not None else CellSeed())(inputs.device)
+            out, _rows = ops.embedding_lookup(inputs, self.embeddings, self.row_offset, self.vocab, dense_grad=True,
+                                              dropout=(self.dropout_rate, seed, ops.cell_salt(self.name), self.col_base))
+            return out.reshape(out.shape[0], 1, -1)
         out, _rows = ops.embedding_lookup(inputs, self.embeddings, self.row_offset, self.vocab, dense_grad=True)
         self.record_activity([out])        # the inner Embedding's [B, L, D] output, before the reshape and the dropout
         out = out.reshape(out.shape[0], 1, -1)

@@ -149,10 +149,89 @@ class _EmbeddingLookup(torch.autograd.Function):
         return None, g_table, None, None, None, None, None
 
 
-def embedding_lookup(idx, table, row_offset, vocab, holder=None, dense_grad=False, oob=None):
+def emb_dropout_enabled():
+    """DT_AMD_EMB_DROPOUT=0 (read at every call) restores the embedding layers' per-column torch SpatialDropout1D chain"""
+    return os.environ.get('DT_AMD_EMB_DROPOUT', '1') != '0'
+
+
+def _drop_args(rate, seed, col_base, F):
+    rate = float(rate)
+    if not 0.0 < rate < 1.0:
+        raise ValueError(f'embedding dropout rate {rate} outside (0, 1): without a mask, pass dropout=None')
+    if seed is None or not seed.is_cuda or seed.dtype != torch.int32 or seed.numel() != 1:
+        raise ValueError('embedding dropout needs the seed word, a one-element int32 tensor on the GPU (ops.draw_cell_seed)')
+    if not col_base.is_cuda or col_base.dtype != torch.int32 or col_base.numel() != F or not col_base.is_contiguous():
+        raise ValueError(f'embedding dropout: col_base must be a contiguous int32 GPU tensor of {F} elements')
+    return rate
+
+
+def embedding_drop_fwd_launch(idx, table, row_offset, vocab, rate, seed, salt, col_base, out, rows, oob):
+    """THE call of dt_embedding_drop_fwd (tests count the launches here)"""
+    B, F = idx.shape
+    check(lib().dt_embedding_drop_fwd(ptr(idx), _idx_kind(idx), ptr(table), ptr(row_offset), ptr(vocab), B, F, table.shape[1],
+                                      rate, ptr(seed), salt, ptr(col_base), ptr(out), ptr(rows), ptr(oob), stream_ptr()),
+          'dt_embedding_drop_fwd')
+
+
+def embedding_drop_bwd_launch(rows, g_out, rate, seed, salt, col_base, values=None, grad_table=None):
+    """THE call of dt_embedding_drop_bwd: sparse mode writes `values`, dense mode adds into `grad_table`"""
+    B, F = rows.shape
+    check(lib().dt_embedding_drop_bwd(ptr(rows), ptr(g_out), B, F, g_out.shape[-1], rate, ptr(seed), salt, ptr(col_base),
+                                      ptr(values), ptr(grad_table), stream_ptr()), 'dt_embedding_drop_bwd')
+
+
+class _EmbeddingDropLookup(torch.autograd.Function):
+    """_EmbeddingLookup with the layer's dropout inside both launches; rows and the seed word are all the backward keeps"""
+
+    @staticmethod
+    def forward(ctx, idx, table, row_offset, vocab, holder, dense_grad, oob, rate, seed, salt, col_base):
+        require_cuda(idx, table)
+        idx = idx.contiguous()
+        B, F = idx.shape
+        D = table.shape[1]
+        rate = _drop_args(rate, seed, col_base, F)
+        out = torch.empty((B, F, D), dtype=torch.float32, device=table.device)
+        rows = torch.empty((B, F), dtype=torch.int64, device=table.device)
+        embedding_drop_fwd_launch(idx, table, row_offset, vocab, rate, seed, salt, col_base, out, rows, oob)
+        ctx.holder = holder
+        ctx.dense_grad = dense_grad
+        ctx.table_shape = table.shape
+        ctx.drop = (rate, salt, col_base)           # col_base: a constant buffer of the layer, not an activation
+        ctx.save_for_backward(rows, seed)
+        ctx.mark_non_differentiable(rows)
+        return out, rows
+
+    @staticmethod
+    def backward(ctx, g_out, _g_rows):
+        rows, seed = ctx.saved_tensors
+        rate, salt, col_base = ctx.drop
+        g_out = _f32c(g_out)
+        D = ctx.table_shape[1]
+        g_table = None
+        if ctx.dense_grad:
+            g_table = torch.zeros(ctx.table_shape, dtype=torch.float32, device=g_out.device)
+            if rows.numel():
+                embedding_drop_bwd_launch(rows, g_out, rate, seed, salt, col_base, grad_table=g_table)
+        elif ctx.holder is not None:
+            values = torch.empty_like(g_out)
+            if rows.numel():
+                embedding_drop_bwd_launch(rows, g_out, rate, seed, salt, col_base, values=values)
+            ctx.holder.add_sparse_grad(SparseRowGrad(rows.reshape(-1), values.reshape(-1, D)))
+        return (None, g_table) + (None,) * 9
+
+
+def embedding_lookup(idx, table, row_offset, vocab, holder=None, dense_grad=False, oob=None, dropout=None):
     """-> (emb [B,F,D], rows [B,F] int64).  With dense_grad=False the table gradient is handed to
-    `holder.add_sparse_grad(SparseRowGrad)` instead of being densified."""
+    `holder.add_sparse_grad(SparseRowGrad)` instead of being densified.
+    dropout = (rate, seed, salt, col_base): the layer's embedding dropout inside the gather launch and its backward
+    (csrc/emb_dropout.hip) — 0 < rate < 1, seed the forward's word (draw_cell_seed), salt the layer's (cell_salt), col_base an
+    int32 [F] GPU tensor, each column's first position in the concatenation of all of the layer's outputs; emb is
+    table[rows] * cell_dropout_keep(seed, salt, B, sum of the layer's widths, rate)[:, col_base[f] + d]."""
     # a dummy requires-grad path is needed so backward runs even though `table.grad` stays None
+    if dropout is not None:
+        rate, seed, salt, col_base = dropout
+        return _EmbeddingDropLookup.apply(idx, table, row_offset, vocab, holder, dense_grad, oob, rate, seed,
+                                          int(salt) & 0xFFFFFFFF, col_base)
     return _EmbeddingLookup.apply(idx, table, row_offset, vocab, holder, dense_grad, oob)
 
 

@@ -96,6 +96,32 @@ int dt_embedding_fwd(const void* idx, int idx_kind, const float* table,
 int dt_embedding_bwd_dense(const int64_t* rows, const float* grad_out, int n_lookups, int D,
                            float* grad_table, void* stream);
 
+/* The gather with the layer's embedding dropout inside the launch (csrc/emb_dropout.hip): MultiColumnEmbedding's one
+ * SpatialDropout1D per column on its [B,1,D] output (models/layers.py:878-880, :900-902; VarLenColumnEmbedding's on the
+ * [B,1,L*D] output, :953-954, :962-963), i.e. element dropout with 1 / (1 - rate) scaling, forward and backward.
+ *   out[b,f,d] = table[row,d] * keep(b, col_base[f] + d),  keep = fl(1 / (1 - fl(rate))) where
+ *   dt_cell_dropout_hash(seed[0], salt, b, col_base[f] + d) >= dt_cell_dropout_threshold(rate), else 0
+ * — the cell hash (dt_cell_fwd), no third hash family and no mask tensor.  col_base: DEVICE int [F], the position of column
+ * f's first element in the concatenation of ALL of the layer's outputs in column order, so the packed tables of one layer
+ * (one call per D-group) use the slices of ONE [B, sum D] mask.  seed: DEVICE, one word, read by the kernel (a captured graph
+ * sees a fresh word at every replay); the backward recomputes keep from the same word and salt.
+ * dt_embedding_drop_fwd: every other argument, rows_out, oob_count and the zero row / row -1 of an out-of-range id as
+ *   dt_embedding_fwd; the kept values are the table's bits times the scale.
+ * dt_embedding_drop_bwd: ONE launch, exactly one of the two outputs non-NULL:
+ *   values     [B*F, D]  sparse mode: values[r,:] = grad_out[r,:] * keep — with rows the (indices, values) gradient pair
+ *   grad_table           dense mode:  grad_table[rows[r],:] += grad_out[r,:] * keep by float atomicAdd, rows < 0 skipped;
+ *                        zeroed by the caller; no masked intermediate exists.  rows may be NULL in sparse mode.
+ * 16-byte lanes for every D % 4 == 0 with 16-byte aligned table / out (grad_out / values), a power of two or not; floats for
+ * any other D and for the dense mode (consecutive lanes add to consecutive dwords).  A grid-stride loop over at most
+ * dt_embedding_drop_pass_units() units (16-byte lanes or floats) per pass.  Domain: 0 < rate < 1 (rate 0 is dt_embedding_fwd),
+ * B F D < 2^31 (32-bit index arithmetic); outside it, a null or misaligned pointer: DT_ERR_INVALID_ARG before any launch.   */
+int64_t dt_embedding_drop_pass_units(void);
+int dt_embedding_drop_fwd(const void* idx, int idx_kind, const float* table, const int64_t* row_offset,
+                          const int32_t* vocab, int B, int F, int D, float rate, const int* seed, unsigned salt,
+                          const int* col_base, float* out, int64_t* rows_out, int* oob_count, void* stream);
+int dt_embedding_drop_bwd(const int64_t* rows, const float* grad_out, int B, int F, int D, float rate, const int* seed,
+                          unsigned salt, const int* col_base, float* values, float* grad_table, void* stream);
+
 /* ---- a4  FM.call  (models/layers.py:53-62) ----------------------------------------------- *
  *   x [B,F,D] -> out [B]  = 0.5 * sum_d[(sum_f x)^2 - sum_f x^2]
  *   backward: grad_x[b,f,d] = grad_out[b] * (S[b,d] - x[b,f,d]),  S = sum_f x               */
