@@ -116,7 +116,7 @@ SIGNATURES = {
     'dt_bce_logits': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
     'dt_sgd_dense_step': (_c_int, [_ptr, _ptr, _c_i64, _c_f32, _ptr]),
     'dt_sgd_rows_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr]),
-    # Adagrad / RMSprop: one slot per element; the rows forms take dt_adam_rows_step's merge arguments (csrc/optim.hip)
+    # Adagrad / RMSprop: one slot per element; the rows forms take dt_adam_rows_step's merge arguments (csrc/optim_slots.hip)
     'dt_adagrad_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
     'dt_rmsprop_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
     'dt_adagrad_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _ptr, _c_int, _ptr]),
@@ -126,7 +126,7 @@ SIGNATURES = {
     'dt_rmsprop_rows_step': (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _c_i64, _ptr, _c_f32,
                                       _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _ptr]),
     'dt_rmsprop_rows_materialize': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _c_int, _c_int, _c_f32, _ptr, _ptr]),
-    # momentum SGD / Adamax / Ftrl (csrc/optim2.hip): dt_adagrad_*'s arguments, the second slot behind the first, the
+    # momentum SGD / Adamax / Ftrl (csrc/optim_slots.hip): dt_adagrad_*'s arguments, the second slot behind the first, the
     # hyperparameters in place of (lr, eps): (lr, momentum, nesterov) / (lr, beta1, beta2, eps) / (lr, lr_power, l1, l2, l2_shrinkage)
     'dt_sgdm_dense_step': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_f32, _c_f32, _c_int, _ptr, _c_int, _ptr]),
     'dt_sgdm_multi_step': (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_f32, _c_f32, _c_int, _ptr, _c_int, _ptr]),

@@ -12,6 +12,10 @@
 //    this step are touched (m/v of other rows do not decay — a documented deviation from
 //    Keras' dense semantics).  Duplicate lookups of a row are merged through a small
 //    hash of the step's row ids (see below); each distinct row is updated exactly once.
+//
+// Also here: that merge (rows_merge, the first pass of every optimizer's row step: optim_dev.h), plain SGD and the BCE loss.
+// Adagrad, RMSprop, momentum SGD, Adamax and Ftrl are optim_slots.hip; the step counter they share with Adam (step_read_t /
+// step_finish) is optim_dev.h.
 #include <stdlib.h>
 #include "common.h"
 #include "adam_dev.h"
@@ -540,202 +544,6 @@ __global__ __launch_bounds__(256) void k_rows_merge_segments(int64_t* __restrict
     }
 }
 
-// ---- Adagrad / RMSprop (keras.optimizers.Adagrad, keras.optimizers.RMSprop with momentum 0, not centered) -------------
-//     Adagrad: acc += g*g                   ; p -= lr * g / (sqrt(acc) + eps)        (acc starts at initial_accumulator_value)
-//     RMSprop: rms = rho*rms + (1-rho)*g*g  ; p -= lr * g / (sqrt(rms) + eps)        (rms starts at 0)
-// One slot per element instead of Adam's two, no bias correction: the learning rate is a plain kernel argument.  The step
-// state is Adam's (AdamState): only t and the arrival counters are used.  Every form of the update (dense, multi-tensor,
-// rows, dense tail) goes through slot_update, compiled without contraction, so that they agree bit for bit.
-template <bool RMS>
-__device__ __forceinline__ void slot_update(float& p, float& s, float g, float lr, float rho, float eps) {
-#pragma clang fp contract(off)
-    s = RMS ? rho * s + (1.f - rho) * (g * g) : s + g * g;
-    p -= lr * g / (sqrtf(s) + eps);
-}
-
-// (step_read_t / step_finish — t of the update a launch belongs to, and the arrival tickets that advance it: optim_dev.h)
-
-// RMSprop's lazy decay: s *= rho^idle for a row that sat out `idle` steps.  Short gaps repeat the multiplication the dense
-// decay makes every step (the same bits); longer ones take one powf.
-constexpr int kExactDecay = 8;
-__device__ __forceinline__ float decay_factor(float rho, int idle) {
-    return idle > kExactDecay ? powf(rho, (float)idle) : 1.f;
-}
-__device__ __forceinline__ float decayed(float s, float rho, int idle, float factor) {
-    if (idle > kExactDecay) return s * factor;
-    for (int k = 0; k < idle; ++k) s *= rho;
-    return s;
-}
-
-struct SlotTail {               // a dense update: n elements of p / g / slot; vec: all three 16-byte aligned
-    float* p;
-    const float* g;
-    float* s;
-    int64_t n;
-    int vec;
-};
-
-// float4 body, scalar tail
-template <bool RMS>
-__device__ __forceinline__ void slot_dense_range(const SlotTail& d, int64_t first, int64_t stride, float lr, float rho,
-                                                 float eps) {
-    const int64_t n4 = d.vec ? d.n >> 2 : 0;
-    for (int64_t i = first; i < n4; i += stride) {
-        const float4 g4 = reinterpret_cast<const float4*>(d.g)[i];
-        float4 s4 = reinterpret_cast<float4*>(d.s)[i], p4 = reinterpret_cast<float4*>(d.p)[i];
-        slot_update<RMS>(p4.x, s4.x, g4.x, lr, rho, eps);
-        slot_update<RMS>(p4.y, s4.y, g4.y, lr, rho, eps);
-        slot_update<RMS>(p4.z, s4.z, g4.z, lr, rho, eps);
-        slot_update<RMS>(p4.w, s4.w, g4.w, lr, rho, eps);
-        reinterpret_cast<float4*>(d.s)[i] = s4;
-        reinterpret_cast<float4*>(d.p)[i] = p4;
-    }
-    for (int64_t i = 4 * n4 + first; i < d.n; i += stride) {
-        float si = d.s[i], pi = d.p[i];
-        slot_update<RMS>(pi, si, d.g[i], lr, rho, eps);
-        d.s[i] = si;
-        d.p[i] = pi;
-    }
-}
-
-template <bool RMS>
-__global__ __launch_bounds__(256) void k_slot_dense(SlotTail d, float lr, float rho, float eps, AdamState* __restrict__ st,
-                                                    int advance) {
-    unsigned ticket;
-    step_read_t(st, advance, ticket);
-    slot_dense_range<RMS>(d, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x, lr, rho, eps);
-    step_finish(st, ticket);
-}
-
-struct SlotMulti {              // k_adam_multi's descriptor with one slot
-    float* p[kMultiMax];
-    const float* g[kMultiMax];
-    float* s[kMultiMax];
-    int n[kMultiMax];
-    int block_start[kMultiMax + 1];
-    int count;
-};
-
-template <bool RMS>
-__global__ __launch_bounds__(256) void k_slot_multi(SlotMulti d, float lr, float rho, float eps, AdamState* __restrict__ st,
-                                                    int advance) {
-    unsigned ticket;
-    step_read_t(st, advance, ticket);
-    int t = 0;
-    while (t + 1 < d.count && (int)blockIdx.x >= d.block_start[t + 1]) ++t;
-    const int first = (int)(blockIdx.x - d.block_start[t]) * kMultiPerBlock + (int)threadIdx.x;
-    const int end = min(d.n[t], (int)(blockIdx.x - d.block_start[t] + 1) * kMultiPerBlock);
-    for (int i = first; i < end; i += 256) {
-        float si = d.s[t][i], pi = d.p[t][i];
-        slot_update<RMS>(pi, si, d.g[t][i], lr, rho, eps);
-        d.s[t][i] = si;
-        d.p[t][i] = pi;
-    }
-    step_finish(st, ticket);
-}
-
-// Row update after the merge (k_rows_dedupe / k_rows_dedupe_fields, unchanged): the owner occurrence of every distinct row
-// updates that table row and its slot record — two random locations per row.  T = min(D / VW, 256) threads per row and
-// 256 / T whole rows per block: a row never straddles two blocks.  RMSprop needs that: `stamp` holds the step at which a
-// row's rms was last written; every thread of the row reads it, rms first takes the decay of the steps the row sat out,
-// rho^(t - stamp - 1) (decayed), and the row's first thread writes the new stamp only behind the block's barrier.
-template <bool RMS, int VW>
-__global__ __launch_bounds__(256) void k_slot_rows_owner(float* __restrict__ table, float* __restrict__ slot,
-                                                         int* __restrict__ stamp, const int64_t* __restrict__ rows,
-                                                         const float* __restrict__ values, int64_t n, int D,
-                                                         unsigned long long* __restrict__ hslots,
-                                                         const int* __restrict__ mark, float lr, float rho, float eps,
-                                                         AdamState* __restrict__ st, int row_blocks, SlotTail tail,
-                                                         int advance, int sstride, int tstride) {
-    unsigned ticket;
-    const int t = step_read_t(st, advance, ticket);
-    if ((int)blockIdx.x >= row_blocks) {      // trailing blocks: one dense update (the model's flat buffer)
-        slot_dense_range<RMS>(tail, (int64_t)(blockIdx.x - row_blocks) * blockDim.x + threadIdx.x,
-                              (int64_t)(gridDim.x - row_blocks) * blockDim.x, lr, rho, eps);
-        step_finish(st, ticket);
-        return;
-    }
-    const int lpr = D / VW;                                   // pieces (VW floats) per row
-    const int T = lpr < 256 ? lpr : 256, rpb = 256 / T;
-    const int r = (int)threadIdx.x / T, q0 = (int)threadIdx.x - r * T;
-    const int64_t occ = (int64_t)blockIdx.x * rpb + r;
-    int hs = -1;
-    int64_t row = 0;
-    if (r < rpb && occ < n) {
-        row = rows[occ];
-        hs = mark ? mark[occ] : (row >= 0 ? 0 : -1);          // no mark: rows are already distinct
-    }
-    const bool live = hs >= 0;
-    int idle = 0;
-    float decay = 1.f;
-    float gi[VW], si[VW], pi[VW];
-    // the first piece's loads are in flight together with the stamp's
-    if (live) {
-        const float* gsrc = values + occ * D + q0 * VW;
-        if (VW == 4) {
-            *reinterpret_cast<float4*>(gi) = *reinterpret_cast<const float4*>(gsrc);
-            *reinterpret_cast<float4*>(si) = *reinterpret_cast<const float4*>(slot + row * sstride + q0 * VW);
-            *reinterpret_cast<float4*>(pi) = *reinterpret_cast<const float4*>(table + row * D + q0 * VW);
-        } else {
-            gi[0] = gsrc[0]; si[0] = slot[row * sstride + q0]; pi[0] = table[row * D + q0];
-        }
-        if (RMS) {
-            idle = t - 1 - stamp[row * tstride];
-            decay = decay_factor(rho, idle);
-        }
-    }
-    if (RMS) __syncthreads();     // every thread of the block has its row's stamp before any of them is rewritten
-    if (live) {
-        for (int q = q0;;) {
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                if (RMS) si[k] = decayed(si[k], rho, idle, decay);
-                slot_update<RMS>(pi[k], si[k], gi[k], lr, rho, eps);
-            }
-            if (VW == 4) {
-                *reinterpret_cast<float4*>(slot + row * sstride + q * VW) = *reinterpret_cast<float4*>(si);
-                *reinterpret_cast<float4*>(table + row * D + q * VW) = *reinterpret_cast<float4*>(pi);
-            } else {
-                slot[row * sstride + q] = si[0]; table[row * D + q] = pi[0];
-            }
-            q += T;
-            if (q >= lpr) break;  // (more than 256 pieces per row: the thread walks the rest)
-#pragma unroll
-            for (int k = 0; k < VW; ++k) {
-                gi[k] = values[occ * D + q * VW + k]; si[k] = slot[row * sstride + q * VW + k];
-                pi[k] = table[row * D + q * VW + k];
-            }
-        }
-        if (q0 == 0) {
-            if (RMS) stamp[row * tstride] = t;
-            if (hslots) hslots[hs] = 0ULL;                    // global-hash merge: leave the hash empty for the next step
-        }
-    }
-    step_finish(st, ticket);
-}
-
-// RMSprop: the decay pending on every row (rho^(steps done - stamp)) applied to rms, then every stamp = steps done.  Two
-// launches, so that no thread reads a stamp another has rewritten.
-__global__ __launch_bounds__(256) void k_rms_materialize(float* __restrict__ rms, const int* __restrict__ stamp, int64_t V,
-                                                         int D, int sstride, int tstride, float rho,
-                                                         const AdamState* __restrict__ st) {
-    const int done = st->t - 1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V * D; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = i / D;
-        const int idle = done - stamp[row * tstride];
-        if (idle > 0) {
-            float* s = rms + row * sstride + (i - row * D);
-            *s = decayed(*s, rho, idle, decay_factor(rho, idle));
-        }
-    }
-}
-__global__ __launch_bounds__(256) void k_rms_restamp(int* __restrict__ stamp, int64_t V, int tstride,
-                                                     const AdamState* __restrict__ st) {
-    const int done = st->t - 1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += (int64_t)gridDim.x * blockDim.x)
-        stamp[i * tstride] = done;
-}
-
 }  // namespace dt
 
 using namespace dt;
@@ -886,7 +694,7 @@ extern "C" int64_t dt_adam_rows_slots(int64_t n_rows) {
 // Pass 1 of every row step: merges the duplicate lookups of a row into its first occurrence (field-local LDS hashes or the
 // global hash).  -> *gslots: the global hash the owners must clear (NULL: not used), *mk: the owner marks (NULL: fields = -1,
 // the rows are already distinct and nothing is launched).  `who` names the entry point in the error text.  (Declared in
-// optim_dev.h: optim2.hip's row steps start with the same pass.)
+// optim_dev.h: optim_slots.hip's row steps start with the same pass.)
 int dt::rows_merge(const char* who, const int64_t* rows, float* values, int64_t n_rows, int D, int fields, void* slots,
                    int64_t n_slots, int* mark, hipStream_t st, unsigned long long** gslots, int** mk) {
     *gslots = nullptr;
@@ -994,154 +802,4 @@ extern "C" int dt_adam_rows_step(float* table, float* m, float* v, const int64_t
                                  (m && v == m + D) ? 2 * D : D /* this older entry point has no stride argument: v = m + D means
                                                                   interleaved [V, 2, D] slots */,
                                  stream);
-}
-
-// ---- Adagrad / RMSprop entry points ------------------------------------------------------------------------------------------
-// the float4 body needs 16-byte aligned arrays; arrays that are only float aligned take the scalar loop
-static SlotTail slot_tail(float* p, const float* g, float* s, int64_t n) {
-    return SlotTail{p, g, s, n, (aligned_to(p, 16) && aligned_to(g, 16) && aligned_to(s, 16)) ? 1 : 0};
-}
-
-template <bool RMS>
-static int slot_dense_step(const char* who, float* p, const float* g, float* s, int64_t n, float lr, float rho, float eps,
-                           void* state, int advance, void* stream) {
-    DT_REQUIRE(n >= 0, "%s: n < 0", who);
-    DT_REQUIRE(!advance || state, "%s: advance needs the device state", who);
-    if (n == 0) return advance ? dt_adam_advance(state, 0.f, 0.f, 0.f, stream) : DT_OK;
-    DT_REQUIRE(p && g && s, "%s: null pointer", who);
-    DT_REQUIRE(aligned_to(p, 4) && aligned_to(g, 4) && aligned_to(s, 4), "%s: pointers must be float aligned", who);
-    int64_t blocks = (n / 4 + 255) / 256 + 1;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(k_slot_dense<RMS>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), slot_tail(p, g, s, n), lr,
-                       rho, eps, (AdamState*)state, advance);
-    return launch_status(who);
-}
-
-template <bool RMS>
-static int slot_multi_step(const char* who, int count, float* const* p, const float* const* g, float* const* s,
-                           const int64_t* n, float lr, float rho, float eps, void* state, int advance, void* stream) {
-    DT_REQUIRE(count >= 0 && (count == 0 || (p && g && s && n)), "%s: bad arguments", who);
-    DT_REQUIRE(!advance || state, "%s: advance needs the device state", who);
-    for (int t = 0; t < count; ++t)         // every tensor is checked before the first chunk is launched
-        DT_REQUIRE(n[t] >= 0 && n[t] < (1LL << 31) && (n[t] == 0 || (p[t] && g[t] && s[t])) && aligned_to(p[t], 4) &&
-                       aligned_to(g[t], 4) && aligned_to(s[t], 4),
-                   "%s: tensor %d: bad size, null or misaligned pointer", who, t);
-    bool launched = false, advanced = false;
-    for (int c0 = 0; c0 < count; c0 += kMultiMax) {
-        SlotMulti d;
-        d.count = count - c0 < kMultiMax ? count - c0 : kMultiMax;
-        int blocks = 0;
-        for (int t = 0; t < d.count; ++t) {
-            d.p[t] = p[c0 + t]; d.g[t] = g[c0 + t]; d.s[t] = s[c0 + t];
-            d.n[t] = (int)n[c0 + t];
-            d.block_start[t] = blocks;
-            blocks += (int)((n[c0 + t] + kMultiPerBlock - 1) / kMultiPerBlock);
-        }
-        d.block_start[d.count] = blocks;
-        if (blocks == 0) continue;
-        const bool last_chunk = c0 + kMultiMax >= count;
-        hipLaunchKernelGGL(k_slot_multi<RMS>, dim3(blocks), dim3(256), 0, as_stream(stream), d, lr, rho, eps, (AdamState*)state,
-                           (advance && last_chunk) ? 1 : 0);
-        launched = true;
-        advanced = advance && last_chunk;
-    }
-    if (advance && !advanced) return dt_adam_advance(state, 0.f, 0.f, 0.f, stream);
-    return launched ? launch_status(who) : DT_OK;
-}
-
-template <bool RMS>
-static int slot_rows_step(const char* who, float* table, float* slot, int* stamp, const int64_t* rows, float* values,
-                          int64_t n_rows, int D, int fields, void* slots, int64_t n_slots, int* mark, float lr, float rho,
-                          float eps, void* state, float* dense_p, const float* dense_g, float* dense_s, int64_t dense_n,
-                          int advance, int slot_stride, int stamp_stride, void* stream) {
-    DT_REQUIRE(n_rows >= 0 && D > 0 && fields >= -1 && dense_n >= 0, "%s: bad sizes", who);
-    DT_REQUIRE(slot_stride >= D, "%s: slot_stride %d < D = %d", who, slot_stride, D);
-    DT_REQUIRE(RMS ? state != nullptr : (!advance || state != nullptr),
-               RMS ? "%s: the step number is read from the device state" : "%s: advance needs the device state", who);
-    DT_REQUIRE(dense_n == 0 || (dense_p && dense_g && dense_s), "%s: null dense tail", who);
-    DT_REQUIRE(aligned_to(dense_p, 4) && aligned_to(dense_g, 4) && aligned_to(dense_s, 4),
-               "%s: dense tail pointers must be float aligned", who);
-    if (n_rows == 0)      // nothing sparse this step: the tail (and the advance) run as a plain dense step
-        return slot_dense_step<RMS>(who, dense_p, dense_g, dense_s, dense_n, lr, rho, eps, state, advance, stream);
-    DT_REQUIRE(table && slot && rows && values && (!RMS || stamp), "%s: null pointer", who);
-    DT_REQUIRE(n_rows < (1LL << 31), "%s: %lld occurrences do not fit the 32-bit slot field", who, (long long)n_rows);
-    const bool vec = D % 4 == 0;
-    const size_t al = vec ? 16 : 4;
-    DT_REQUIRE(aligned_to(table, al) && aligned_to(slot, al) && aligned_to(values, al) && (!vec || slot_stride % 4 == 0),
-               "%s: table, slot and values must be %d-byte aligned (D = %d, slot_stride = %d)", who, (int)al, D, slot_stride);
-    DT_REQUIRE(aligned_to(rows, 8) && aligned_to(slots, 8) && aligned_to(mark, 4), "%s: misaligned rows / slots / mark", who);
-    DT_REQUIRE(!RMS || (aligned_to(stamp, 4) && stamp_stride >= 1), "%s: misaligned stamp or stamp_stride < 1", who);
-    hipStream_t st = as_stream(stream);
-    unsigned long long* gslots = nullptr;
-    int* mk = mark;
-    if (const int rc = rows_merge(who, rows, values, n_rows, D, fields, slots, n_slots, mark, st, &gslots, &mk)) return rc;
-    const SlotTail tail = slot_tail(dense_p, dense_g, dense_s, dense_n);
-    int tail_blocks = (int)((dense_n / 4 + 255) / 256) + (dense_n ? 1 : 0);
-    if (tail_blocks > 1024) tail_blocks = 1024;
-    const int lpr = vec ? D / 4 : D;
-    const int rpb = 256 / (lpr < 256 ? lpr : 256);
-    const int row_blocks = (int)((n_rows + rpb - 1) / rpb);
-    const dim3 grid((unsigned)(row_blocks + tail_blocks));
-    if (vec)
-        hipLaunchKernelGGL((k_slot_rows_owner<RMS, 4>), grid, dim3(256), 0, st, table, slot, stamp, rows, values, n_rows, D,
-                           gslots, mk, lr, rho, eps, (AdamState*)state, row_blocks, tail, advance, slot_stride, stamp_stride);
-    else
-        hipLaunchKernelGGL((k_slot_rows_owner<RMS, 1>), grid, dim3(256), 0, st, table, slot, stamp, rows, values, n_rows, D,
-                           gslots, mk, lr, rho, eps, (AdamState*)state, row_blocks, tail, advance, slot_stride, stamp_stride);
-    return launch_status(who);
-}
-
-extern "C" int dt_adagrad_dense_step(float* p, const float* g, float* acc, int64_t n, float lr, float eps, void* state,
-                                     int advance, void* stream) {
-    return slot_dense_step<false>("dt_adagrad_dense_step", p, g, acc, n, lr, 0.f, eps, state, advance, stream);
-}
-
-extern "C" int dt_rmsprop_dense_step(float* p, const float* g, float* rms, int64_t n, float lr, float rho, float eps,
-                                     void* state, int advance, void* stream) {
-    return slot_dense_step<true>("dt_rmsprop_dense_step", p, g, rms, n, lr, rho, eps, state, advance, stream);
-}
-
-extern "C" int dt_adagrad_multi_step(int count, float* const* p, const float* const* g, float* const* acc, const int64_t* n,
-                                     float lr, float eps, void* state, int advance, void* stream) {
-    return slot_multi_step<false>("dt_adagrad_multi_step", count, p, g, acc, n, lr, 0.f, eps, state, advance, stream);
-}
-
-extern "C" int dt_rmsprop_multi_step(int count, float* const* p, const float* const* g, float* const* rms, const int64_t* n,
-                                     float lr, float rho, float eps, void* state, int advance, void* stream) {
-    return slot_multi_step<true>("dt_rmsprop_multi_step", count, p, g, rms, n, lr, rho, eps, state, advance, stream);
-}
-
-extern "C" int dt_adagrad_rows_step(float* table, float* acc, const int64_t* rows, float* values, int64_t n_rows, int D,
-                                    int fields, void* slots, int64_t n_slots, int* mark, float lr, float eps, void* state,
-                                    float* dense_p, const float* dense_g, float* dense_acc, int64_t dense_n, int advance,
-                                    int slot_stride, void* stream) {
-    return slot_rows_step<false>("dt_adagrad_rows_step", table, acc, nullptr, rows, values, n_rows, D, fields, slots, n_slots,
-                                 mark, lr, 0.f, eps, state, dense_p, dense_g, dense_acc, dense_n, advance, slot_stride, 1,
-                                 stream);
-}
-
-extern "C" int dt_rmsprop_rows_step(float* table, float* rms, int* stamp, const int64_t* rows, float* values, int64_t n_rows,
-                                    int D, int fields, void* slots, int64_t n_slots, int* mark, float lr, float rho, float eps,
-                                    void* state, float* dense_p, const float* dense_g, float* dense_rms, int64_t dense_n,
-                                    int advance, int slot_stride, int stamp_stride, void* stream) {
-    return slot_rows_step<true>("dt_rmsprop_rows_step", table, rms, stamp, rows, values, n_rows, D, fields, slots, n_slots, mark,
-                                lr, rho, eps, state, dense_p, dense_g, dense_rms, dense_n, advance, slot_stride, stamp_stride,
-                                stream);
-}
-
-extern "C" int dt_rmsprop_rows_materialize(float* rms, int* stamp, int64_t V, int D, int slot_stride, int stamp_stride,
-                                           float rho, const void* state, void* stream) {
-    DT_REQUIRE(V >= 0 && D > 0 && slot_stride >= D && stamp_stride >= 1, "dt_rmsprop_rows_materialize: bad sizes");
-    if (V == 0) return DT_OK;
-    DT_REQUIRE(rms && stamp && state, "dt_rmsprop_rows_materialize: null pointer");
-    DT_REQUIRE(aligned_to(rms, 4) && aligned_to(stamp, 4), "dt_rmsprop_rows_materialize: misaligned pointer");
-    hipStream_t st = as_stream(stream);
-    int64_t blocks = (V * D + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_rms_materialize, dim3((unsigned)blocks), dim3(256), 0, st, rms, stamp, V, D, slot_stride, stamp_stride,
-                       rho, (const AdamState*)state);
-    blocks = (V + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(k_rms_restamp, dim3((unsigned)blocks), dim3(256), 0, st, stamp, V, stamp_stride, (const AdamState*)state);
-    return launch_status("dt_rmsprop_rows_materialize");
 }

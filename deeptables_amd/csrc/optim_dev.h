@@ -1,4 +1,4 @@
-// optim_dev.h — what the optimizer translation units (optim.hip, optim2.hip) share beyond adam_dev.h: the step counter's
+// optim_dev.h — what the optimizer translation units (optim.hip, optim_slots.hip) share beyond adam_dev.h: the step counter's
 // read / advance for optimizers without a device-side rate, the multi-tensor launch geometry and pass 1 of every row step.
 #pragma once
 #include "common.h"
@@ -7,7 +7,7 @@
 namespace dt {
 
 // Several parameter tensors in ONE launch: the tensor descriptors travel as kernel arguments, a block finds its tensor by
-// scanning the block offsets (k_adam_multi, k_slot_multi, k_slot2_multi)
+// scanning the block offsets (k_adam_multi of optim.hip, k_slot_multi of optim_slots.hip)
 constexpr int kMultiMax = 32;
 constexpr int kMultiPerBlock = 1024;          // elements per block (256 threads x 4)
 

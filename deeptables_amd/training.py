@@ -437,10 +437,13 @@ class _DeviceOptimizer(_GradClip):
     (MultiColumnEmbedding.sparse_grads), the last of which carries one dense update in its trailing blocks and advances the
     step state.  The step counter (and Adam's lr_t) live on the device (dt_adam_state_init / dt_adam_advance), so a
     captured hipGraph of the step replays with the right step.
-    A subclass names its slots (`slot_names`, `slot_init`), spells out its three library calls (`_dense_call`, `_multi_call`,
-    `_rows_call`) and, where a table's slots have a layout of their own, `_new_slot` / `_st`, `materialize` / `_restamp`."""
+    A subclass names its slots (`slot_names`, `slot_init`) and its entry points (`_entry`, `_hpargs()`; RMSprop's stamps go
+    through `_rows_extra`), from which `_dense_call`, `_multi_call` and `_rows_call` are built — KerasAdam, whose entry points
+    take other arguments, spells the three out — and, where a table's slots have a layout of their own, `_new_slot` / `_st`,
+    `materialize` / `_restamp`."""
 
-    _row_segments = False             # `supports_row_segments` while no clip is set: takes SparseRowGrad.segments
+    _entry = None                     # stem of the library's entry points: dt_<_entry>_{dense,multi,rows}_step
+    _row_segments = False            # `supports_row_segments` while no clip is set: takes SparseRowGrad.segments
     _rows_in_step = False             # `supports_rows_in_step` ...: a fused step may apply the update of the rows looked up once
     slot_names = ()                   # the slots' names: their keys in `state[id(p)]` and in a checkpoint
     slot_init = 0.0                   # the slots' initial value: one number, or one per slot (a tuple matching slot_names)
@@ -554,15 +557,33 @@ class _DeviceOptimizer(_GradClip):
         for layer in self.embedding_layers:
             layer.sparse_grads.clear()
 
-    # -- the three launches, by optimizer.  ss: one entry per slot; tail: a dense item, (None, None, (None, ..), 0) for none --
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
+    # -- the three launches.  ss: one entry per slot; tail: a dense item, (None, None, (None, ..), 0) for none.  The slot
+    # optimizers' entry points (csrc/optim_slots.hip) share one argument order: the slots behind the parameter, the
+    # hyperparameters in the middle --
+    def _hpargs(self):
+        """the hyperparameters, in the order dt_<_entry>_*_step take them"""
         raise NotImplementedError
+
+    def _rows_extra(self, s):
+        """what dt_<_entry>_rows_step takes beyond the shared arguments: (pointers behind the slots, ints behind slot_stride)"""
+        return (), ()
+
+    def _call(self, form, *args):
+        name = f'dt_{self._entry}_{form}_step'
+        check(getattr(lib(), name)(*args), name)
+
+    def _dense_call(self, p, g, ss, n, sp, advance, st):
+        self._call('dense', ptr(p), ptr(g), *map(ptr, ss), n, *self._hpargs(), sp, advance, st)
 
     def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        raise NotImplementedError
+        self._call('multi', T, ps, gs, *ss, ns, *self._hpargs(), sp, advance, st)
 
     def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        raise NotImplementedError
+        ss = [s[k] for k in self.slot_names]
+        behind_slots, behind_stride = self._rows_extra(s)
+        self._call('rows', ptr(table.data), *map(ptr, ss), *behind_slots, ptr(rows), ptr(values), n, D, fields, ptr(slots),
+                   n_slots, ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]), *map(ptr, tail[2]), tail[3], advance,
+                   int(ss[0].stride(0)), *behind_stride, st)
 
     def _dense_launch(self, dense, sp, st, advance):
         """All dense tensors of the step in one launch (the library takes them in chunks of 32 tensors)."""
@@ -858,6 +879,7 @@ class Adagrad(_SlotOptimizer):
     the other rows keep p and acc bit for bit."""
 
     _name = 'Adagrad'
+    _entry = 'adagrad'
     slot_names = ('acc',)
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7,
@@ -870,18 +892,8 @@ class Adagrad(_SlotOptimizer):
     def hyperparameters(self):
         return dict(super().hyperparameters(), initial_accumulator_value=self.initial_accumulator_value)
 
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
-        check(lib().dt_adagrad_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, self.lr, self.eps, sp, advance, st),
-              'dt_adagrad_dense_step')
-
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_adagrad_multi_step(T, ps, gs, ss[0], ns, self.lr, self.eps, sp, advance, st), 'dt_adagrad_multi_step')
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        acc = s['acc']
-        check(lib().dt_adagrad_rows_step(ptr(table.data), ptr(acc), ptr(rows), ptr(values), n, D, fields, ptr(slots), n_slots,
-                                         ptr(mark), self.lr, self.eps, sp, ptr(tail[0]), ptr(tail[1]), ptr(tail[2][0]), tail[3],
-                                         advance, int(acc.stride(0)), st), 'dt_adagrad_rows_step')
+    def _hpargs(self):
+        return self.lr, self.eps
 
 
 class RMSprop(_SlotOptimizer):
@@ -894,6 +906,7 @@ class RMSprop(_SlotOptimizer):
     is pending on all rows, after which `rms` is Keras' slot (`slot(p)` and checkpoint.save_model call it)."""
 
     _name = 'RMSprop'
+    _entry = 'rmsprop'
     slot_names = ('rms',)
     # where a row-sparse table's stamps live: False: an int32 [V] array of their own (rms rows stay 16 D bytes apart:
     # one 128-byte line at D = 32); True: the last 16 bytes of a [V, D + 4] slot record.  DESIGN.md §3.6 has the measurement.
@@ -956,25 +969,16 @@ class RMSprop(_SlotOptimizer):
             if s is not None and 'stamp' in s:
                 s['stamp'].copy_((self._dev_state[:1] - 1).expand(p.shape[0]))
 
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
-        check(lib().dt_rmsprop_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, self.lr, self.rho, self.eps, sp, advance, st),
-              'dt_rmsprop_dense_step')
+    def _hpargs(self):
+        return self.lr, self.rho, self.eps
 
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_rmsprop_multi_step(T, ps, gs, ss[0], ns, self.lr, self.rho, self.eps, sp, advance, st),
-              'dt_rmsprop_multi_step')
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        rms, stamp = s['rms'], s['stamp']
-        check(lib().dt_rmsprop_rows_step(ptr(table.data), ptr(rms), ptr(stamp), ptr(rows), ptr(values), n, D, fields,
-                                         ptr(slots), n_slots, ptr(mark), self.lr, self.rho, self.eps, sp, ptr(tail[0]),
-                                         ptr(tail[1]), ptr(tail[2][0]), tail[3], advance, int(rms.stride(0)),
-                                         int(stamp.stride(0)), st), 'dt_rmsprop_rows_step')
+    def _rows_extra(self, s):
+        return (ptr(s['stamp']),), (int(s['stamp'].stride(0)),)
 
 
 class _RowSparseOptimizer(_DeviceOptimizer):
-    """What momentum SGD, Adamax and Ftrl (csrc/optim2.hip) share beyond the step driver: one or two slots per element, each
-    with its own initial value, and hyperparameters that travel with a checkpoint.
+    """What momentum SGD, Adamax and Ftrl (csrc/optim_slots.hip) share beyond the step driver: one or two slots per element,
+    each with its own initial value, and hyperparameters that travel with a checkpoint.
 
     Their row-sparse update is NOT Keras' dense result — a deviation of the kind of Adam's "lazy" rows (`KerasAdam`), and
     unlike Adagrad's.  Only the looked-up rows are updated, duplicates summed first; every other row keeps its weights and
@@ -1034,9 +1038,6 @@ class _RowSparseOptimizer(_DeviceOptimizer):
     def lr(self):
         return self.learning_rate
 
-    def _tail_slots(self, tail):
-        return [ptr(x) for x in tail[2]]
-
 
 class MomentumSGD(_RowSparseOptimizer):
     """keras.optimizers.SGD(learning_rate=0.01, momentum, nesterov=False) with momentum != 0 (what `SGD(...)` returns then):
@@ -1044,6 +1045,7 @@ class MomentumSGD(_RowSparseOptimizer):
     Row-sparse tables: see `_RowSparseOptimizer` — rows that were not looked up do not coast on their momentum."""
 
     _name = 'SGD'
+    _entry = 'sgdm'
     slot_names = ('momentum',)
     _hp = ('learning_rate', 'momentum', 'nesterov')
 
@@ -1061,18 +1063,6 @@ class MomentumSGD(_RowSparseOptimizer):
     def _hpargs(self):
         return self.learning_rate, self.momentum, int(self.nesterov)
 
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
-        check(lib().dt_sgdm_dense_step(ptr(p), ptr(g), ptr(ss[0]), n, *self._hpargs(), sp, advance, st), 'dt_sgdm_dense_step')
-
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_sgdm_multi_step(T, ps, gs, ss[0], ns, *self._hpargs(), sp, advance, st), 'dt_sgdm_multi_step')
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        m = s['momentum']
-        check(lib().dt_sgdm_rows_step(ptr(table.data), ptr(m), ptr(rows), ptr(values), n, D, fields, ptr(slots), n_slots,
-                                      ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]), *self._tail_slots(tail), tail[3],
-                                      advance, int(m.stride(0)), st), 'dt_sgdm_rows_step')
-
 
 class Adamax(_RowSparseOptimizer):
     """keras.optimizers.Adamax(learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7):
@@ -1081,6 +1071,7 @@ class Adamax(_RowSparseOptimizer):
     Row-sparse tables: see `_RowSparseOptimizer` — m and u of rows that were not looked up do not decay."""
 
     _name = 'Adamax'
+    _entry = 'adamax'
     slot_names = ('m', 'u')
     _hp = ('learning_rate', 'beta_1', 'beta_2', 'epsilon')
 
@@ -1092,19 +1083,6 @@ class Adamax(_RowSparseOptimizer):
 
     def _hpargs(self):
         return self.learning_rate, self.beta_1, self.beta_2, self.epsilon
-
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
-        check(lib().dt_adamax_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, *self._hpargs(), sp, advance, st),
-              'dt_adamax_dense_step')
-
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_adamax_multi_step(T, ps, gs, ss[0], ss[1], ns, *self._hpargs(), sp, advance, st), 'dt_adamax_multi_step')
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        m, u = s['m'], s['u']
-        check(lib().dt_adamax_rows_step(ptr(table.data), ptr(m), ptr(u), ptr(rows), ptr(values), n, D, fields, ptr(slots),
-                                        n_slots, ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]),
-                                        *self._tail_slots(tail), tail[3], advance, int(m.stride(0)), st), 'dt_adamax_rows_step')
 
 
 class Ftrl(_RowSparseOptimizer):
@@ -1122,6 +1100,7 @@ class Ftrl(_RowSparseOptimizer):
       * learning_rate_power == -0.5, the default, takes sqrtf; any other power <= 0 powf."""
 
     _name = 'Ftrl'
+    _entry = 'ftrl'
     slot_names = ('accumulator', 'linear')
     _hp = ('learning_rate', 'learning_rate_power', 'initial_accumulator_value', 'l1_regularization_strength',
            'l2_regularization_strength', 'l2_shrinkage_regularization_strength', 'beta')
@@ -1154,19 +1133,6 @@ class Ftrl(_RowSparseOptimizer):
         l2 = self.l2_regularization_strength + self.beta / (2.0 * self.learning_rate)
         return (self.learning_rate, self.learning_rate_power, self.l1_regularization_strength, l2,
                 self.l2_shrinkage_regularization_strength)
-
-    def _dense_call(self, p, g, ss, n, sp, advance, st):
-        check(lib().dt_ftrl_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, *self._hpargs(), sp, advance, st),
-              'dt_ftrl_dense_step')
-
-    def _multi_call(self, T, ps, gs, ss, ns, sp, advance, st):
-        check(lib().dt_ftrl_multi_step(T, ps, gs, ss[0], ss[1], ns, *self._hpargs(), sp, advance, st), 'dt_ftrl_multi_step')
-
-    def _rows_call(self, table, s, rows, values, n, D, fields, slots, n_slots, mark, sp, tail, advance, seg, st):
-        acc, lin = s['accumulator'], s['linear']
-        check(lib().dt_ftrl_rows_step(ptr(table.data), ptr(acc), ptr(lin), ptr(rows), ptr(values), n, D, fields, ptr(slots),
-                                      n_slots, ptr(mark), *self._hpargs(), sp, ptr(tail[0]), ptr(tail[1]),
-                                      *self._tail_slots(tail), tail[3], advance, int(acc.stride(0)), st), 'dt_ftrl_rows_step')
 
 
 OPTIMIZERS = {'adam': KerasAdam, 'sgd': SGD, 'adagrad': Adagrad, 'rmsprop': RMSprop, 'ftrl': Ftrl, 'adamax': Adamax}

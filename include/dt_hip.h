@@ -379,7 +379,7 @@ int dt_rmsprop_rows_materialize(float* rms, int* stamp, int64_t V, int D, int sl
                                 const void* state, void* stream);
 
 /* keras.optimizers.SGD with momentum != 0, keras.optimizers.Adamax and keras.optimizers.Ftrl (Keras 3's formulas), selectable
- * through ModelConfig.optimizer (csrc/optim2.hip).  Arguments as in their dt_adagrad_* counterparts — the same `state`
+ * through ModelConfig.optimizer (csrc/optim_slots.hip).  Arguments as in their dt_adagrad_* counterparts — the same `state`
  * (dt_adam_state_init with beta1 = beta2 = 0; the last launch of a step has advance != 0), the same float4 body / scalar loop
  * for dense arrays, the same chunks of 32 tensors, the same rows / values / fields / slots / n_slots / mark and dense tail —
  * with the second slot behind the first wherever a slot is passed and the hyperparameters in place of (lr, eps).

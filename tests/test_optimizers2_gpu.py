@@ -1,5 +1,5 @@
 # -*- coding:utf-8 -*-
-"""GPU: the momentum SGD, Adamax and Ftrl kernels (csrc/optim2.hip dt_sgdm_* / dt_adamax_* / dt_ftrl_*) and
+"""GPU: the momentum SGD, Adamax and Ftrl kernels (csrc/optim_slots.hip dt_sgdm_* / dt_adamax_* / dt_ftrl_*) and
 `training.SGD(momentum != 0)` / `training.Adamax` / `training.Ftrl` against the float64 restatement of Keras 3's formulas in
 tests/optimizers2_reference.py.
 

@@ -2,7 +2,7 @@
 """Momentum SGD, Adamax and Ftrl without a GPU: what `make_optimizer` accepts (names and Keras' serialised dict), the refused
 hyperparameters, `SGD(momentum=0)` as the class and code path it was, the float64 restatements the GPU tests compare against
 (tests/optimizers2_reference.py) pinned on hand-computed cases, and the argument checks of the nine entry points
-(csrc/optim2.hip)."""
+(csrc/optim_slots.hip)."""
 import ctypes
 import functools
 import math

@@ -1,5 +1,5 @@
 # -*- coding:utf-8 -*-
-"""GPU: the Adagrad and RMSprop kernels (csrc/optim.hip dt_adagrad_* / dt_rmsprop_*) and `training.Adagrad` /
+"""GPU: the Adagrad and RMSprop kernels (csrc/optim_slots.hip dt_adagrad_* / dt_rmsprop_*) and `training.Adagrad` /
 `training.RMSprop` against the float64 restatement of Keras' formulas in tests/optim_reference.py.
 
 Bars.  The update is fp32 element-wise arithmetic, the class of Adam's, and is held to the bars tests/test_optim_gpu.py

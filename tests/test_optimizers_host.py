@@ -1,5 +1,5 @@
 # -*- coding:utf-8 -*-
-"""Adagrad and RMSprop without a GPU: what `make_optimizer` accepts, the C-ABI of the new entry points (csrc/optim.hip)
+"""Adagrad and RMSprop without a GPU: what `make_optimizer` accepts, the C-ABI of the entry points (csrc/optim_slots.hip)
 and their argument checks, the float64 restatements the GPU tests compare against (tests/optim_reference.py), and a
 DeepModel compiled with one of them."""
 import ctypes
