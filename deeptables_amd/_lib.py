@@ -303,6 +303,12 @@ SIGNATURES = {
     'dt_metric_auc': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
     'dt_metric_sums': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr]),
     'dt_metric_argmax_hits': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
+    # ... log loss + precision / recall counts, MSLE / MAPE sums, top-k hits + categorical cross-entropy, AUC + average precision
+    'dt_score_binary': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
+    'dt_score_regression': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr]),
+    'dt_score_categorical': (_c_int, [_ptr, _ptr, _c_int, _c_i64, _c_int, _c_int, _ptr, _ptr]),
+    'dt_score_ranking_workspace_bytes': (_c_i64, [_c_i64]),
+    'dt_score_ranking': (_c_int, [_ptr, _ptr, _c_i64, _ptr, _ptr, _ptr]),
     # keras.regularizers.L1L2 (csrc/regularizer.hip): HOST arrays of device pointers / sizes / coefficients, one per tensor
     'dt_reg_chunk': (_c_int, []),
     'dt_reg_penalty_workspace_bytes': (_c_i64, [_c_int, _ptr]),
@@ -362,6 +368,9 @@ DT_ACT_LINEAR, DT_ACT_RELU = 0, 1
 DT_DENSE_X3, DT_DENSE_BF16 = 1, 2      # dt_dense_x3_*: split-bf16 (fp32 bars forward) / plain bf16
 DT_METRIC_Y_LABELS, DT_METRIC_Y_ONEHOT = 0, 1
 DT_METRIC_SUMS_BLOCKS, DT_METRIC_SUMS_WORDS = 256, 771      # dt_metric_sums' out: 3 result words + 3 per block
+# dt_score_*' out: result words + that many per block; a thread per row up to DT_SCORE_THREAD_ROW_MAX_C classes
+DT_SCORE_BLOCKS, DT_SCORE_THREAD_ROW_MAX_C = 256, 32
+DT_SCORE_BINARY_WORDS, DT_SCORE_REGRESSION_WORDS, DT_SCORE_CATEGORICAL_WORDS, DT_SCORE_RANKING_WORDS = 1285, 514, 514, 262
 DT_LOSS_BCE, DT_LOSS_CCE, DT_LOSS_MSE, DT_LOSS_MAE, DT_LOSS_BINARY_FOCAL, DT_LOSS_CATEGORICAL_FOCAL = 0, 1, 2, 3, 4, 5
 DT_LOSS_MAX_CLASSES = 4096
 DT_CLIP_VALUE, DT_CLIP_NORM, DT_CLIP_GLOBAL_NORM = 0, 1, 2

@@ -18,6 +18,9 @@
 // AUC (k_auc_*): keys = order-preserving uint32 of the score (-0.0 -> +0.0 first), values = 1 for label 1, else 0; after the
 //   sort a reduce-then-scan over tiles (three launches) gives, for every group of equal keys, where it starts and how many
 //   negatives precede it; one thread per group then adds pos_g * (2 * negs_before_g + neg_g) into U2 (64-bit integers).
+// Scores (k_score_*, k_ap_*; dt_score_*): log loss with the precision / recall counts, MSLE / MAPE, top-k hits with the
+//   categorical cross-entropy, and average precision from the AUC's group arrays — float64 from the float32 inputs, every sum
+//   a per-block partial added by one block in a fixed order.
 #include "common.h"
 
 namespace dt {
@@ -412,6 +415,311 @@ inline unsigned stride_blocks(int64_t n) {
     return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
 }
 
+// ---- scores: log loss, precision / recall counts, top-k hits, MSLE / MAPE, average precision -------------------------------
+// Every pass below is k_sums_partial's scheme: a block adds what it saw in a fixed order and writes its partial words behind
+// the result words of `out` (W result words, then W words per block); k_score_final, one block, adds the partials in block
+// order.  The block count is a function of the shape alone, so the same input gives the same bits.
+constexpr int kScoreBlocks = DT_SCORE_BLOCKS;
+static_assert(kScoreBlocks <= kThreads, "k_score_final: one thread per partial");
+static_assert(DT_SCORE_BINARY_WORDS == 5 + 5 * kScoreBlocks && DT_SCORE_REGRESSION_WORDS == 2 + 2 * kScoreBlocks &&
+              DT_SCORE_CATEGORICAL_WORDS == 2 + 2 * kScoreBlocks && DT_SCORE_RANKING_WORDS == 6 + kScoreBlocks, "out layouts");
+constexpr int kThreadRowMaxC = DT_SCORE_THREAD_ROW_MAX_C;     // a thread per row up to here, a wave per row beyond
+constexpr double kClipLo = (double)1e-7f;                     // Keras' epsilon as float32 ...
+constexpr double kClipHi = (double)(1.0f - 1e-7f);            // ... and 1 - epsilon, subtracted in float32 (0.99999988...)
+
+// numpy.clip(p, lo, hi): a NaN fails both comparisons and comes out as it went in (fmin / fmax would drop it)
+__device__ __forceinline__ double clip_prob(double p) { return p < kClipLo ? kClipLo : (p > kClipHi ? kClipHi : p); }
+// numpy.maximum(x, lo), NaN kept
+__device__ __forceinline__ double at_least_lo(double x) { return x < kClipLo ? kClipLo : x; }
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+// the class a float label names, -1 when it names none of [0, C) (a NaN too)
+__device__ __forceinline__ int label_class(float y, int C) { return (y >= 0.0f && (double)y < (double)C) ? (int)y : -1; }
+
+__device__ __forceinline__ void score_partial(u64* __restrict__ out, int W, int k, u64 v) { out[W + W * blockIdx.x + k] = v; }
+__device__ __forceinline__ void score_partial(u64* __restrict__ out, int W, int k, double v) {
+    out[W + W * blockIdx.x + k] = (u64)__double_as_longlong(v);
+}
+
+// NI integer words, then ND float64 words
+template <int NI, int ND>
+__global__ __launch_bounds__(kThreads) void k_score_final(u64* __restrict__ out, int blocks) {
+    [[maybe_unused]] __shared__ u64 shi[kWaves];
+    __shared__ double shd[kWaves];
+    constexpr int W = NI + ND;
+    const bool live = (int)threadIdx.x < blocks;          // blocks <= kScoreBlocks <= kThreads
+    const u64* part = out + W + W * threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < NI; ++k) {
+        const u64 s = block_sum<u64>(live ? part[k] : 0, shi);
+        if (threadIdx.x == 0) out[k] = s;
+    }
+#pragma unroll
+    for (int k = NI; k < W; ++k) {
+        const double s = block_sum<double>(live ? __longlong_as_double((long long)part[k]) : 0.0, shd);
+        if (threadIdx.x == 0) out[k] = (u64)__double_as_longlong(s);
+    }
+}
+
+// out: TP, FP, FN, TN (int64), sum of -(y log q + (1 - y) log(1 - q)) (double); LABELS: y = (class of the row == column)
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_score_binary(const float* __restrict__ y_true, const float* __restrict__ y_prob,
+                                                           int64_t total, int C, u64* __restrict__ out) {
+    __shared__ uint32_t shc[kWaves];
+    __shared__ double shd[kWaves];
+    uint32_t tp = 0, fp = 0, fn = 0, tn = 0;
+    double ce = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < total; i += (int64_t)gridDim.x * kThreads) {
+        const float pf = y_prob[i];
+        double y;
+        if (KIND == DT_METRIC_Y_LABELS) {
+            const int64_t r = i / C;
+            y = label_class(y_true[r], C) == (int)(i - r * C) ? 1.0 : 0.0;
+        } else {
+            y = (double)y_true[i];
+        }
+        const uint32_t pp = pf > 0.5f, yp = y != 0.0;
+        tp += pp & yp;
+        fp += pp & (yp ^ 1u);
+        fn += (pp ^ 1u) & yp;
+        tn += (pp ^ 1u) & (yp ^ 1u);
+        const double q = clip_prob((double)pf);
+        // a hard label makes one of the two products an exact zero (q is finite inside [lo, hi]): that logarithm is skipped
+        const bool sane = q == q;
+        const double a = (sane && y == 0.0) ? 0.0 : y * log(q);
+        const double b = (sane && y == 1.0) ? 0.0 : (1.0 - y) * log(1.0 - q);
+        ce += -(a + b);
+    }
+    // a thread sees at most total / kThreads + 1 elements: 32 bits hold the block's counts
+    tp = block_sum<uint32_t>(tp, shc);
+    fp = block_sum<uint32_t>(fp, shc);
+    fn = block_sum<uint32_t>(fn, shc);
+    tn = block_sum<uint32_t>(tn, shc);
+    ce = block_sum<double>(ce, shd);
+    if (threadIdx.x == 0) {
+        score_partial(out, 5, 0, (u64)tp);
+        score_partial(out, 5, 1, (u64)fp);
+        score_partial(out, 5, 2, (u64)fn);
+        score_partial(out, 5, 3, (u64)tn);
+        score_partial(out, 5, 4, ce);
+    }
+}
+
+// out: sum (log(max(p, lo) + 1) - log(max(y, lo) + 1))^2, sum |y - p| / max(|y|, lo)
+__global__ __launch_bounds__(kThreads) void k_score_regression(const float* __restrict__ y_true, const float* __restrict__ y_pred,
+                                                               int64_t n, u64* __restrict__ out) {
+    __shared__ double shd[kWaves];
+    double sl = 0.0, pe = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const double p = (double)y_pred[i], y = (double)y_true[i];
+        const double d = log(at_least_lo(p) + 1.0) - log(at_least_lo(y) + 1.0);
+        sl += d * d;
+        pe += fabs(y - p) / at_least_lo(fabs(y));
+    }
+    sl = block_sum<double>(sl, shd);
+    pe = block_sum<double>(pe, shd);
+    if (threadIdx.x == 0) {
+        score_partial(out, 2, 0, sl);
+        score_partial(out, 2, 1, pe);
+    }
+}
+
+// the row pass: out = rows whose target class is among the k best (int64), sum of the rows' categorical cross-entropy.
+// target: the label, or the first maximum of the one-hot row found by `v > best` from class 0 on (k_argmax_hits' scan).
+// A thread per row: every sum over the classes runs in class order.
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_score_rows_thread(const float* __restrict__ y_prob, const float* __restrict__ y_true,
+                                                                int64_t n, int C, int k, u64* __restrict__ out) {
+    __shared__ uint32_t shc[kWaves];
+    __shared__ double shd[kWaves];
+    uint32_t hits = 0;
+    double ce = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < n; r += (int64_t)gridDim.x * kThreads) {
+        const float* p = y_prob + r * C;
+        const float* t = y_true + r * C;                 // (ONEHOT only)
+        double s = 0.0;
+        for (int c = 0; c < C; ++c) s += (double)p[c];
+        int target;
+        if (KIND == DT_METRIC_Y_ONEHOT) {
+            target = 0;
+            float tv = t[0];
+            for (int c = 1; c < C; ++c) {
+                const float v = t[c];
+                if (v > tv) { tv = v; target = c; }
+            }
+        } else {
+            target = label_class(y_true[r], C);
+        }
+        if (target >= 0) {
+            const float pt = p[target];
+            int above = 0;
+            for (int c = 0; c < C; ++c) above += p[c] > pt;
+            hits += (pt == pt) && above < k;
+        }
+        if (KIND == DT_METRIC_Y_ONEHOT) {
+            double acc = 0.0;
+            for (int c = 0; c < C; ++c) {
+                const double y = (double)t[c], q = clip_prob((double)p[c] / s);
+                if (!(y == 0.0 && q == q)) acc += y * log(q);         // (0 * a finite logarithm: skipped)
+            }
+            ce += -acc;
+        } else {
+            ce += target >= 0 ? -log(clip_prob((double)p[target] / s)) : quiet_nan();
+        }
+    }
+    hits = block_sum<uint32_t>(hits, shc);
+    ce = block_sum<double>(ce, shd);
+    if (threadIdx.x == 0) {
+        score_partial(out, 2, 0, (u64)hits);
+        score_partial(out, 2, 1, ce);
+    }
+}
+
+// lane 0 gets partial[0] of: for o = 32, 16, ... 1: partial[l] += partial[l + o] for l < o
+__device__ __forceinline__ double wave_tree_sum(double v) {
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
+    return v;
+}
+
+// A wave per row, for wide rows: lane l takes classes l, l + 64, ... in that order, and the lanes' partial sums are added by
+// wave_tree_sum.  Counts and the target class do not depend on the order.
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_score_rows_wave(const float* __restrict__ y_prob, const float* __restrict__ y_true,
+                                                              int64_t n, int C, int k, u64* __restrict__ out) {
+    __shared__ uint32_t shc[kWaves];
+    __shared__ double shd[kWaves];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    constexpr int kNone = 0x7fffffff;
+    uint32_t hits = 0;          // lane 0 of every wave counts for its rows
+    double ce = 0.0;
+    for (int64_t r = (int64_t)blockIdx.x * kWaves + wave; r < n; r += (int64_t)gridDim.x * kWaves) {
+        const float* p = y_prob + r * C;
+        const float* t = y_true + r * C;                 // (ONEHOT only)
+        double s = 0.0;
+        for (int c = lane; c < C; c += kWave) s += (double)p[c];
+        s = __shfl(wave_tree_sum(s), 0, kWave);
+        int target;
+        if (KIND == DT_METRIC_Y_ONEHOT) {
+            // the scan's answer without the scan: class 0 if t[0] is a NaN, else the lowest class holding the largest non-NaN value
+            int bi = kNone;
+            float bv = 0.f;
+            for (int c = lane; c < C; c += kWave) {
+                const float v = t[c];
+                if (v == v && (bi == kNone || v > bv)) { bv = v; bi = c; }
+            }
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) {
+                const float ov = __shfl_down(bv, o, kWave);
+                const int oi = __shfl_down(bi, o, kWave);
+                if (oi != kNone && (bi == kNone || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+            }
+            target = __shfl(bi, 0, kWave);
+            const float t0 = t[0];
+            if (target == kNone || t0 != t0) target = 0;
+        } else {
+            target = label_class(y_true[r], C);
+        }
+        bool hit = false;
+        if (target >= 0) {
+            const float pt = p[target];
+            int above = 0;
+            for (int c = lane; c < C; c += kWave) above += p[c] > pt;
+#pragma unroll
+            for (int o = kWave / 2; o > 0; o >>= 1) above += __shfl_down(above, o, kWave);
+            hit = (pt == pt) && above < k;      // (lane 0's `above` is the row's)
+        }
+        double loss;
+        if (KIND == DT_METRIC_Y_ONEHOT) {
+            double acc = 0.0;
+            for (int c = lane; c < C; c += kWave) {
+                const double y = (double)t[c], q = clip_prob((double)p[c] / s);
+                if (!(y == 0.0 && q == q)) acc += y * log(q);
+            }
+            loss = -wave_tree_sum(acc);
+        } else {
+            loss = target >= 0 ? -log(clip_prob((double)p[target] / s)) : quiet_nan();
+        }
+        if (lane == 0) {
+            hits += hit;
+            ce += loss;
+        }
+    }
+    if (lane != 0) ce = 0.0;
+    hits = block_sum<uint32_t>(hits, shc);
+    ce = block_sum<double>(ce, shd);
+    if (threadIdx.x == 0) {
+        score_partial(out, 2, 0, (u64)hits);
+        score_partial(out, 2, 1, ce);
+    }
+}
+
+// average precision over the groups k_auc_groups compacted (ascending score): group g holds pos_g positives, TPcum = the
+// positives at or above it, n - start = everything at or above it.  out6: dt_metric_auc's five words (P is complete: an
+// earlier launch counted it), then the sum of pos_g * TPcum / (n - start); partials behind.
+__global__ __launch_bounds__(kThreads) void k_ap_partial(const uint32_t* __restrict__ group_start, const uint32_t* __restrict__ group_negs_before,
+                                                         const uint32_t* __restrict__ meta, int64_t n, u64* __restrict__ out6) {
+    __shared__ double shd[kWaves];
+    int64_t groups = meta[0];
+    if (groups > n) groups = n;
+    const uint32_t all_negs = meta[1];
+    const u64 P = out6[1];
+    double acc = 0.0;
+    for (int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x; g < groups; g += (int64_t)gridDim.x * kThreads) {
+        const uint32_t s = group_start[g], nb = group_negs_before[g];
+        const uint32_t e = g + 1 < groups ? group_start[g + 1] : (uint32_t)n;
+        const uint32_t nb1 = g + 1 < groups ? group_negs_before[g + 1] : all_negs;
+        const u64 pos = (u64)(e - s) - (nb1 - nb);
+        if (pos) acc += (double)pos * (double)(P - (s - nb)) / (double)(n - s);
+    }
+    acc = block_sum<double>(acc, shd);
+    if (threadIdx.x == 0) out6[6 + blockIdx.x] = (u64)__double_as_longlong(acc);
+}
+
+__global__ __launch_bounds__(kThreads) void k_ap_final(u64* __restrict__ out6, int blocks) {
+    __shared__ double shd[kWaves];
+    const double v = (int)threadIdx.x < blocks ? __longlong_as_double((long long)out6[6 + threadIdx.x]) : 0.0;
+    const double s = block_sum<double>(v, shd);
+    if (threadIdx.x == 0) out6[5] = (u64)__double_as_longlong(s);
+}
+
+// ceil(work / per_block) blocks, at most kScoreBlocks
+inline int score_blocks(int64_t work, int64_t per_block) {
+    const int64_t b = (work + per_block - 1) / per_block;
+    return (int)(b < kScoreBlocks ? b : kScoreBlocks);
+}
+
+struct AucArrays {
+    uint32_t *group_start, *group_negs, *meta;
+};
+
+// dt_metric_auc's launches; the compacted group arrays stay in the workspace
+int auc_launches(const float* score, const float* label, int64_t n, void* ws, u64* out, hipStream_t st, const char* what,
+                 AucArrays* arrays) {
+    const int64_t tiles = tiles_of(n);
+    char* w = reinterpret_cast<char*>(ws);
+    uint32_t* keys = reinterpret_cast<uint32_t*>(w);
+    uint32_t* vals = reinterpret_cast<uint32_t*>(w + a256(4 * n));
+    char* sort_ws = w + 2 * a256(4 * n);
+    u64* tile_sums = reinterpret_cast<u64*>(sort_ws + sort_ws_bytes(n));
+    uint32_t* meta = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(tile_sums) + a256(8 * tiles));
+    // the sort's two scratch arrays are free once it has finished: the groups' starts and negatives-before live there
+    uint32_t* group_start = reinterpret_cast<uint32_t*>(sort_ws);
+    uint32_t* group_negs = reinterpret_cast<uint32_t*>(sort_ws + a256(4 * n));
+    if (hipMemsetAsync(out, 0, 5 * sizeof(u64), st) != hipSuccess) return launch_status(what);
+    hipLaunchKernelGGL(k_auc_keys, dim3(stride_blocks(n)), dim3(kThreads), 0, st, score, label, n, keys, vals, out);
+    int rc = sort_pairs(keys, vals, n, keys, vals, sort_ws, st, what);       // in place: pass 0 reads, pass 1 writes
+    if (rc != DT_OK) return rc;
+    hipLaunchKernelGGL(k_auc_tile_sums, dim3((unsigned)tiles), dim3(kThreads), 0, st, keys, vals, n, tile_sums);
+    hipLaunchKernelGGL(k_auc_tile_scan, dim3(1), dim3(kThreads), 0, st, tile_sums, tiles, meta);
+    hipLaunchKernelGGL(k_auc_groups, dim3((unsigned)tiles), dim3(kThreads), 0, st, keys, vals, n, tile_sums, group_start,
+                       group_negs);
+    hipLaunchKernelGGL(k_auc_u2, dim3(stride_blocks(n)), dim3(kThreads), 0, st, group_start, group_negs, meta, n, out);
+    arrays->group_start = group_start;
+    arrays->group_negs = group_negs;
+    arrays->meta = meta;
+    return launch_status(what);
+}
+
 }  // namespace
 }  // namespace dt
 
@@ -449,28 +757,98 @@ extern "C" int dt_metric_auc(const float* score, const float* label, int64_t n, 
     DT_REQUIRE(aligned(score, 4) && aligned(label, 4), "dt_metric_auc: score / label are not 4-byte aligned");
     DT_REQUIRE(aligned(out5, 8), "dt_metric_auc: out5 is not 8-byte aligned");
     DT_REQUIRE(aligned(ws, 16), "dt_metric_auc: the workspace is not 16-byte aligned");
+    AucArrays arrays;
+    return auc_launches(score, label, n, ws, reinterpret_cast<u64*>(out5), as_stream(stream), "dt_metric_auc", &arrays);
+}
+
+extern "C" int64_t dt_score_ranking_workspace_bytes(int64_t n) {
+    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_score_ranking_workspace_bytes: n = %lld outside [0, 2^31)", (long long)n);
+    return auc_ws_bytes(n);
+}
+
+extern "C" int dt_score_ranking(const float* score, const float* label, int64_t n, void* ws, void* out, void* stream) {
+    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_score_ranking: n = %lld outside [0, 2^31)", (long long)n);
+    if (n == 0) return DT_OK;
+    DT_REQUIRE(score && label && out, "dt_score_ranking: null pointer");
+    DT_REQUIRE(ws, "dt_score_ranking: null workspace (dt_score_ranking_workspace_bytes)");
+    DT_REQUIRE(aligned(score, 4) && aligned(label, 4), "dt_score_ranking: score / label are not 4-byte aligned");
+    DT_REQUIRE(aligned(out, 8), "dt_score_ranking: out is not 8-byte aligned");
+    DT_REQUIRE(aligned(ws, 16), "dt_score_ranking: the workspace is not 16-byte aligned");
     hipStream_t st = as_stream(stream);
-    const int64_t tiles = tiles_of(n);
-    char* w = reinterpret_cast<char*>(ws);
-    uint32_t* keys = reinterpret_cast<uint32_t*>(w);
-    uint32_t* vals = reinterpret_cast<uint32_t*>(w + a256(4 * n));
-    char* sort_ws = w + 2 * a256(4 * n);
-    u64* tile_sums = reinterpret_cast<u64*>(sort_ws + sort_ws_bytes(n));
-    uint32_t* meta = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(tile_sums) + a256(8 * tiles));
-    // the sort's two scratch arrays are free once it has finished: the groups' starts and negatives-before live there
-    uint32_t* group_start = reinterpret_cast<uint32_t*>(sort_ws);
-    uint32_t* group_negs = reinterpret_cast<uint32_t*>(sort_ws + a256(4 * n));
-    u64* out = reinterpret_cast<u64*>(out5);
-    if (hipMemsetAsync(out, 0, 5 * sizeof(u64), st) != hipSuccess) return launch_status("dt_metric_auc");
-    hipLaunchKernelGGL(k_auc_keys, dim3(stride_blocks(n)), dim3(kThreads), 0, st, score, label, n, keys, vals, out);
-    int rc = sort_pairs(keys, vals, n, keys, vals, sort_ws, st, "dt_metric_auc");       // in place: pass 0 reads, pass 1 writes
+    u64* o = reinterpret_cast<u64*>(out);
+    AucArrays a;
+    int rc = auc_launches(score, label, n, ws, o, st, "dt_score_ranking", &a);
     if (rc != DT_OK) return rc;
-    hipLaunchKernelGGL(k_auc_tile_sums, dim3((unsigned)tiles), dim3(kThreads), 0, st, keys, vals, n, tile_sums);
-    hipLaunchKernelGGL(k_auc_tile_scan, dim3(1), dim3(kThreads), 0, st, tile_sums, tiles, meta);
-    hipLaunchKernelGGL(k_auc_groups, dim3((unsigned)tiles), dim3(kThreads), 0, st, keys, vals, n, tile_sums, group_start,
-                       group_negs);
-    hipLaunchKernelGGL(k_auc_u2, dim3(stride_blocks(n)), dim3(kThreads), 0, st, group_start, group_negs, meta, n, out);
-    return launch_status("dt_metric_auc");
+    const int blocks = score_blocks(n, 4 * kThreads);        // (the number of groups is the device's to know: at most n)
+    hipLaunchKernelGGL(k_ap_partial, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.group_start, a.group_negs, a.meta, n, o);
+    hipLaunchKernelGGL(k_ap_final, dim3(1), dim3(kThreads), 0, st, o, blocks);
+    return launch_status("dt_score_ranking");
+}
+
+// the checks the three passes share; on success *total = n * C
+static int score_args(const char* what, const void* y_true, const void* y_prob, int64_t n, int C, int min_C, const void* out,
+                      int64_t* total) {
+    DT_REQUIRE(n >= 0 && n < kMaxN, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
+    DT_REQUIRE(C >= min_C, "%s: C = %d, at least %d here", what, C, min_C);
+    DT_REQUIRE(n * (int64_t)C < kMaxN, "%s: n * C = %lld x %d overflows 2^31 elements", what, (long long)n, C);
+    *total = n * (int64_t)C;
+    if (n == 0) return DT_OK;
+    DT_REQUIRE(y_true && y_prob && out, "%s: null pointer", what);
+    DT_REQUIRE(aligned(y_true, 4) && aligned(y_prob, 4), "%s: y_true / y_prob are not 4-byte aligned", what);
+    DT_REQUIRE(aligned(out, 8), "%s: out is not 8-byte aligned", what);
+    return DT_OK;
+}
+
+extern "C" int dt_score_binary(const float* y_true, const float* y_prob, int y_kind, int64_t n, int C, void* out, void* stream) {
+    DT_REQUIRE(y_kind == DT_METRIC_Y_LABELS || y_kind == DT_METRIC_Y_ONEHOT, "dt_score_binary: unknown y_kind %d", y_kind);
+    int64_t total;
+    int rc = score_args("dt_score_binary", y_true, y_prob, n, C, y_kind == DT_METRIC_Y_LABELS ? 2 : 1, out, &total);
+    if (rc != DT_OK || n == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    u64* o = reinterpret_cast<u64*>(out);
+    const int blocks = score_blocks(total, 4 * kThreads);
+    if (y_kind == DT_METRIC_Y_LABELS)
+        hipLaunchKernelGGL(k_score_binary<DT_METRIC_Y_LABELS>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_true, y_prob, total, C, o);
+    else
+        hipLaunchKernelGGL(k_score_binary<DT_METRIC_Y_ONEHOT>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_true, y_prob, total, C, o);
+    hipLaunchKernelGGL((k_score_final<4, 1>), dim3(1), dim3(kThreads), 0, st, o, blocks);
+    return launch_status("dt_score_binary");
+}
+
+extern "C" int dt_score_regression(const float* y_true, const float* y_pred, int64_t n, void* out, void* stream) {
+    int64_t total;
+    int rc = score_args("dt_score_regression", y_true, y_pred, n, 1, 1, out, &total);
+    if (rc != DT_OK || n == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    u64* o = reinterpret_cast<u64*>(out);
+    const int blocks = score_blocks(n, 4 * kThreads);
+    hipLaunchKernelGGL(k_score_regression, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_true, y_pred, n, o);
+    hipLaunchKernelGGL((k_score_final<0, 2>), dim3(1), dim3(kThreads), 0, st, o, blocks);
+    return launch_status("dt_score_regression");
+}
+
+extern "C" int dt_score_categorical(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int k, void* out,
+                                    void* stream) {
+    DT_REQUIRE(y_kind == DT_METRIC_Y_LABELS || y_kind == DT_METRIC_Y_ONEHOT, "dt_score_categorical: unknown y_kind %d", y_kind);
+    DT_REQUIRE(k >= 1, "dt_score_categorical: k = %d, top-k needs k >= 1", k);
+    int64_t total;
+    int rc = score_args("dt_score_categorical", y_true, y_prob, n, C, 2, out, &total);
+    if (rc != DT_OK || n == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    u64* o = reinterpret_cast<u64*>(out);
+    const bool wide = C > kThreadRowMaxC;
+    const int blocks = score_blocks(n, wide ? kWaves : kThreads);
+    const bool onehot = y_kind == DT_METRIC_Y_ONEHOT;
+    if (wide && onehot)
+        hipLaunchKernelGGL(k_score_rows_wave<DT_METRIC_Y_ONEHOT>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_prob, y_true, n, C, k, o);
+    else if (wide)
+        hipLaunchKernelGGL(k_score_rows_wave<DT_METRIC_Y_LABELS>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_prob, y_true, n, C, k, o);
+    else if (onehot)
+        hipLaunchKernelGGL(k_score_rows_thread<DT_METRIC_Y_ONEHOT>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_prob, y_true, n, C, k, o);
+    else
+        hipLaunchKernelGGL(k_score_rows_thread<DT_METRIC_Y_LABELS>, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_prob, y_true, n, C, k, o);
+    hipLaunchKernelGGL((k_score_final<1, 1>), dim3(1), dim3(kThreads), 0, st, o, blocks);
+    return launch_status("dt_score_categorical");
 }
 
 extern "C" int dt_metric_sums(const float* y_true, const float* y_prob, int64_t n, void* out, void* stream) {

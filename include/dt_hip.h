@@ -1286,6 +1286,48 @@ int dt_metric_auc(const float* score, const float* label, int64_t n, void* ws, i
 int dt_metric_sums(const float* y_true, const float* y_prob, int64_t n, void* out, void* stream);
 int dt_metric_argmax_hits(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int64_t* out, void* stream);
 
+/* More epoch metrics on the device (csrc/metrics.hip): log loss, precision / recall, top-k accuracy, MSLE / MAPE and average
+ * precision, i.e. the rest of what the `metrics=[...]` of deepmodel.py's compile (:324-338) names and its fit / evaluate report
+ * (:471-475, :526-530; keras.metrics and sklearn on the host before).  The rules of the dt_metric_* block hold: no block
+ * waits for another, integer results are exact, float64 sums are per-block partials (at most DT_SCORE_BLOCKS, a function of
+ * the shape alone) added by one block in a fixed order, so the same input gives the same bits.  Every `out` is an array of
+ * 8-byte words: the result words first, the partials behind them (scratch).  Everything is computed in float64 from the
+ * float32 inputs; lo = (double)1e-7f, hi = (double)(1.0f - 1e-7f); clip(x) = numpy.clip(x, lo, hi) and max(x, lo) =
+ * numpy.maximum: a NaN stays a NaN.  Refused with DT_ERR_INVALID_ARG before any launch: n outside [0, 2^31), n * C of 2^31
+ * and more, C below 2 (below 1 for dt_score_binary's element-wise form), k < 1, an unknown y_kind, a null pointer or
+ * workspace, a float array off 4-byte alignment, an `out` off 8-byte alignment, a workspace off 16-byte alignment.  n == 0 is
+ * a no-op that looks at no pointer.  A float label names class (int)label when 0 <= label < C and no class otherwise.
+ *
+ * dt_score_binary: over the n * C elements of y_prob; y_kind DT_METRIC_Y_ONEHOT: y_true has n * C elements too (binary [n],
+ *   multilabel or one-hot [n, C]; soft labels allowed), DT_METRIC_Y_LABELS: y_true [n] labels, y = (label's class == column).
+ *   out (DT_SCORE_BINARY_WORDS): [0] TP [1] FP [2] FN [3] TN (int64; predicted positive: p > 0.5, label positive: y != 0)
+ *   [4] double sum of -(y log q + (1 - y) log(1 - q)), q = clip(p).  2 launches.
+ * dt_score_regression: out (DT_SCORE_REGRESSION_WORDS): [0] double sum (log(max(p, lo) + 1) - log(max(y, lo) + 1))^2
+ *   [1] double sum |y - p| / max(|y|, lo).  2 launches.
+ * dt_score_categorical: rows of y_prob [n, C] against y_true [n] (DT_METRIC_Y_LABELS) or [n, C] (DT_METRIC_Y_ONEHOT).  The
+ *   target class is the label's, or the first maximum of the y_true row (`v > best` from class 0 on).  out
+ *   (DT_SCORE_CATEGORICAL_WORDS): [0] int64 rows with fewer than k classes scoring above the target (in_top_k: ties across
+ *   the boundary are all in; a NaN target score, or a label naming no class, misses) [1] double sum over rows of
+ *   -sum_c y_c log(clip(p_c / s)), s = sum_c p_c (LABELS: -log(clip(p_label / s)), NaN for a label naming no class).
+ *   C <= DT_SCORE_THREAD_ROW_MAX_C: a thread per row, both sums in class order.  Wider: a wave per row, lane l adds classes
+ *   l, l + 64, ... in that order, then partial[l] += partial[l + o] for o = 32, 16, ... 1.  2 launches.
+ * dt_score_ranking: dt_metric_auc (same workspace layout, same kernels, same five words) plus average precision from the
+ *   compacted groups of equal score.  out (DT_SCORE_RANKING_WORDS): [0..4] dt_metric_auc's out5 [5] double sum over groups
+ *   of pos_g * TPcum_g / (n - start_g), TPcum_g = positives scoring at least the group's, n - start_g = rows scoring at least
+ *   it; AP = out[5] / P = sklearn.metrics.average_precision_score.  The caller returns nan and takes its host path where
+ *   it does for AUC.  21 launches: dt_metric_auc's 19, the groups' terms, their sum.                                     */
+#define DT_SCORE_BLOCKS 256
+#define DT_SCORE_BINARY_WORDS 1285
+#define DT_SCORE_REGRESSION_WORDS 514
+#define DT_SCORE_CATEGORICAL_WORDS 514
+#define DT_SCORE_RANKING_WORDS 262
+#define DT_SCORE_THREAD_ROW_MAX_C 32
+int dt_score_binary(const float* y_true, const float* y_prob, int y_kind, int64_t n, int C, void* out, void* stream);
+int dt_score_regression(const float* y_true, const float* y_pred, int64_t n, void* out, void* stream);
+int dt_score_categorical(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int k, void* out, void* stream);
+int64_t dt_score_ranking_workspace_bytes(int64_t n);
+int dt_score_ranking(const float* score, const float* label, int64_t n, void* ws, void* out, void* stream);
+
 /* keras.regularizers.L1L2 on the device (csrc/regularizer.hip): penalty and gradient of `count` float32 tensors per call, tensor
  * t being (x[t], n[t] elements, l1[t], l2[t]).  x / out / n / l1 / l2 are HOST arrays (of device pointers, sizes and
  * coefficients); the descriptors travel as kernel arguments, 32 tensors per launch.  Common rules: a member with n == 0
