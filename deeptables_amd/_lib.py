@@ -339,6 +339,18 @@ SIGNATURES = {
     'dt_grad_clip': (_c_int, [_c_int, _c_f32, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _ptr]),
     'dt_rows_clip': (_c_int, [_c_int, _c_f32, _ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _c_int, _c_i64, _ptr, _c_int, _c_int,
                               _ptr, _ptr]),
+    # weight decay and the weights' moving average around any optimizer step (csrc/optim_stages.hip): state, steps_done, stream /
+    # state, stream / count, p[], n[], weight_decay, lr, stream / count, p[], avg[], n[], momentum, state, stream (p / avg / n:
+    # HOST arrays) / table, avg, stamp, rows, n, D, V, row_offset, field_on, F, decay, weight_decay, lr, momentum, state, stream /
+    # table, avg, stamp, rows, n, D, V, momentum, state, stream / table, avg, stamp, V, D, momentum, state, stream
+    'dt_stage_state_init': (_c_int, [_ptr, _c_int, _ptr]),
+    'dt_stage_advance': (_c_int, [_ptr, _ptr]),
+    'dt_decay_multi': (_c_int, [_c_int, _ptr, _ptr, _c_f32, _c_f32, _ptr]),
+    'dt_ema_multi': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_f32, _ptr, _ptr]),
+    'dt_rows_stage_pre': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_i64, _ptr, _ptr, _c_int, _c_int, _c_f32, _c_f32,
+                                   _c_f32, _ptr, _ptr]),
+    'dt_rows_stage_post': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_i64, _c_f32, _ptr, _ptr]),
+    'dt_ema_rows_materialize': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

@@ -5,6 +5,9 @@ name them (deepmodel.py:205-221 saves an .h5 of that model; deeptable.py:773-804
 the optimizer's slots (`optimizer/<weight>/<slot>`: m and v for Adam, acc for Adagrad, rms for RMSprop, accumulator and
 linear for Ftrl, m and u for Adamax, momentum for SGD with momentum; the optimizer's name, step count and hyperparameters
 in the metadata).  The slots of a row-sparse table that live in one [V, 2, D] record are stored as two [V, D] tensors.
+With `weight_decay` / `use_ema` set (training._StepStages; plain SGD too) the file also holds the weights' moving averages
+(`optimizer/<weight>/average`, and `.../average_stamp` for a row-sparse table), and in the metadata the stage's step count
+and the decay exclusions as patterns over these names.
 
 The packed embedding table of `MultiColumnEmbedding` is stored as the reference's per-column variables
 `embeddings_{i}` (layers.py:863-877); Cross / CIN / BilinearInteraction parameter lists get the reference's
@@ -94,29 +97,39 @@ def save_model(model, path, optimizer=None, metadata=None):
     for name, t in named_weights(model).items():
         tensors[name] = t.detach().to('cpu').contiguous()
     meta = {'format': FORMAT}
-    if optimizer is not None and hasattr(optimizer, 'state'):
+    # the slots of an optimizer that has any, and what weight_decay / use_ema keep of one that runs those stages (plain SGD too)
+    has_slots, with_stages = hasattr(optimizer, 'state'), bool(getattr(optimizer, 'stages', False))
+    if optimizer is not None and (has_slots or with_stages):
         if hasattr(optimizer, 'materialize'):
             optimizer.materialize()
-        by_id = {id(t): name for name, t in named_weights(model).items()}
         by_ptr = {}
         for name, t in named_weights(model).items():
             by_ptr.setdefault(t.untyped_storage().data_ptr(), []).append((name, t))
+        averages, stamps = getattr(optimizer, '_averages', {}), getattr(optimizer, '_stamps', {})
         for p in list(getattr(optimizer, 'params', [])):
-            st = optimizer.state.get(id(p))
-            if st is None:
+            st = optimizer.state.get(id(p)) if has_slots else None
+            avg = averages.get(id(p)) if with_stages else None
+            if st is None and avg is None:
                 continue
             # a parameter may be stored as several Keras variables (packed table -> embeddings_i): slice the slots
             views = [(n, t) for n, t in by_ptr.get(p.untyped_storage().data_ptr(), [])
                      if _inside(t, p)]
             for name, t in views:
                 off = (t.data_ptr() - p.data_ptr()) // 4
-                for slot in _slot_names(optimizer):      # (a table's slots may be strided views of one slot record)
+                for slot in () if st is None else _slot_names(optimizer):      # (slots may be strided views of one slot record)
                     tensors[f'optimizer/{name}/{slot}'] = _slot_piece(st[slot], off, t).detach().to('cpu').contiguous()
+                if avg is not None:                      # the weights' moving average, kept like a slot
+                    tensors[f'optimizer/{name}/average'] = _slot_piece(avg, off, t).detach().to('cpu').contiguous()
+                    if id(p) in stamps:                  # ... of a row-sparse table: the step each row was last averaged at
+                        r0 = off // p.shape[1]
+                        tensors[f'optimizer/{name}/average_stamp'] = stamps[id(p)][r0:r0 + t.shape[0]].to('cpu').contiguous()
         meta['optimizer'] = getattr(optimizer, '_name', optimizer.__class__.__name__)
         meta['optimizer_iterations'] = str(int(getattr(optimizer, 't', 0)))
         if hasattr(optimizer, 'hyperparameters'):
             meta['optimizer_hyperparameters'] = json.dumps(optimizer.hyperparameters())
-        del by_id
+        if with_stages:
+            meta['optimizer_stage_iterations'] = str(int(optimizer.stage_t))
+            meta['optimizer_decay_exclusions'] = json.dumps(optimizer.decay_exclusions(named_weights(model)))
     if metadata:
         meta.update({k: v if isinstance(v, str) else json.dumps(v) for k, v in metadata.items()})
     save_file(tensors, path, metadata=meta)
@@ -156,7 +169,9 @@ def load_model(model, path, optimizer=None, strict=True):
                     raise ValueError(f'{name}: file has shape {tuple(src.shape)}, model {tuple(t.shape)}')
                 t.copy_(src.to(t.dtype))
                 seen.add(name)
-            if optimizer is not None and meta.get('optimizer') and hasattr(optimizer, 'state'):
+            has_slots = hasattr(optimizer, 'state')
+            staged = hasattr(optimizer, 'stage_t') and 'optimizer_stage_iterations' in meta
+            if optimizer is not None and meta.get('optimizer') and (has_slots or staged):
                 name_here = getattr(optimizer, '_name', optimizer.__class__.__name__)
                 if meta['optimizer'] != name_here:
                     # (a file named 'SGD' holds momentum slots: plain 'sgd' has none to load them into)
@@ -169,7 +184,13 @@ def load_model(model, path, optimizer=None, strict=True):
                 if 'optimizer_hyperparameters' in meta and hasattr(optimizer, 'set_hyperparameters'):
                     optimizer.set_hyperparameters(json.loads(meta['optimizer_hyperparameters']))
                 # the step count first: slots created below start with nothing pending at THAT count
-                optimizer.t = int(meta.get('optimizer_iterations', '0'))
+                if has_slots:
+                    optimizer.t = int(meta.get('optimizer_iterations', '0'))
+                if staged:
+                    if getattr(optimizer, '_var_names', None) is None:
+                        optimizer.set_variable_names(lambda: named_weights(model))
+                    optimizer._load_decay_exclusions(json.loads(meta.get('optimizer_decay_exclusions', '[]')))
+                    optimizer.stage_t = int(meta['optimizer_stage_iterations'])
                 by_ptr = {}
                 for name, t in targets.items():
                     by_ptr.setdefault(t.untyped_storage().data_ptr(), []).append((name, t))
@@ -179,13 +200,22 @@ def load_model(model, path, optimizer=None, strict=True):
                     # never convert a slot layout while loading: a table that already holds the interleaved [V,2,D] slot
                     # record keeps it (captured graphs hold its address; `_slot_piece` reads through row-strided views),
                     # and state created here for a packed 2-D table is created in the layout the row update uses
-                    st = optimizer.state.get(id(p))
-                    if st is None:
+                    st = optimizer.state.get(id(p)) if has_slots else None
+                    if st is None and has_slots:
                         st = optimizer._st(p, rows=id(p) in row_sparse)
                     for name, t in by_ptr.get(p.untyped_storage().data_ptr(), []):
-                        if not _inside(t, p) or f'optimizer/{name}/{slots[0]}' not in keys:
+                        if not _inside(t, p):
                             continue
                         off = (t.data_ptr() - p.data_ptr()) // 4
+                        if staged and f'optimizer/{name}/average' in keys:
+                            dst = _slot_piece(optimizer._average_of(p), off, t)
+                            dst.copy_(f.get_tensor(f'optimizer/{name}/average').reshape(dst.shape))
+                            if f'optimizer/{name}/average_stamp' in keys:
+                                r0 = off // p.shape[1]
+                                optimizer._row_stamps(p)[r0:r0 + t.shape[0]].copy_(
+                                    f.get_tensor(f'optimizer/{name}/average_stamp'))
+                        if st is None or f'optimizer/{name}/{slots[0]}' not in keys:
+                            continue
                         for slot in slots:
                             dst = _slot_piece(st[slot], off, t)
                             dst.copy_(f.get_tensor(f'optimizer/{name}/{slot}').reshape(dst.shape))

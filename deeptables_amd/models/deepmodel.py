@@ -145,6 +145,10 @@ class DeepModel:
         self.loss_name = loss_name
         emb_layers = [l for l in model.layers if isinstance(l, MultiColumnEmbedding)]
         self.optimizer = training.make_optimizer(optimizer, list(model.parameters()), emb_layers)
+        if hasattr(self.optimizer, 'set_variable_names'):
+            # what exclude_from_weight_decay(var_names=...) matches: the variables' checkpoint names, looked up when needed
+            from .. import checkpoint
+            self.optimizer.set_variable_names(lambda: checkpoint.named_weights(model))
         self.model_desc.optimizer = self.optimizer
         self.model_desc.loss = loss_name
 
@@ -282,6 +286,9 @@ class DeepModel:
             # gradient clipping sits between the gradients and their update: no fused step may apply an update, and no plan is
             # built (none re-homes a parameter); training runs layer by layer.  Inference plans are unaffected.
             return None
+        if getattr(getattr(self, 'optimizer', None), 'stages', False):
+            # weight_decay / use_ema sit around the update in the same way: no fused step may apply an un-decayed update
+            return None
         if not hasattr(self, '_fused_plan'):
             from ..fused import make_fused_plan
             self._fused_plan = make_fused_plan(self)
@@ -347,6 +354,11 @@ class DeepModel:
         if strategy is not None and clip is not None:
             raise ValueError(f'`{clip[0]}` with a distribute_strategy: a norm over row-owned tables and exchanged gradients '
                              f'needs an exchange of its own, which is not there; train on one device or without clipping')
+        opt = getattr(self, 'optimizer', None)
+        if strategy is not None and getattr(opt, 'stages', False):
+            which = '`weight_decay`' if opt.weight_decay is not None else '`use_ema`'
+            raise ValueError(f'{which} with a distribute_strategy: the decay and the moving average of row-owned tables and '
+                             f'exchanged gradients are not there; train on one device or without it')
 
     def train_step(self, inputs, y, sample_weight=None):
         """forward -> loss -> backward -> (data-parallel gradient exchange) -> optimizer step."""
@@ -524,6 +536,8 @@ class DeepModel:
                     stop = True
             if stop:
                 break
+        if getattr(self.optimizer, 'use_ema', False):
+            self.optimizer.finalize_variable_values()      # Keras' fit ends on the averaged weights
         self._sync_sharded_tables()
         for cb in callbacks or []:
             if hasattr(cb, 'on_train_end'):

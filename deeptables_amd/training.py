@@ -332,10 +332,33 @@ class _GradClip:
             end = off + span
         return regions
 
+    def _coalesce(self, table, grads):
+        """dt_rows_coalesce of a table's sparse gradient pieces into the stage's persistent buffers -> (out_rows [n]: the
+        distinct rows ascending, then -1; out_vals [n, D]: their summed gradients; count: device int64 [1]; n)"""
+        h = lib()
+        V, D = table.shape
+        device = table.device
+        rows = torch.cat([g.rows.reshape(-1) for g in grads]) if len(grads) > 1 else grads[0].rows.reshape(-1)
+        vals = torch.cat([g.values.reshape(-1, D) for g in grads]) if len(grads) > 1 else grads[0].values.reshape(-1, D)
+        rows, vals = rows.contiguous(), vals.contiguous()
+        n = rows.numel()
+        tag = f'{id(table)}'
+        out_rows = self._clip_buffer(tag + '/rows', n, torch.int64, device)[:n]
+        out_vals = self._clip_buffer(tag + '/vals', n * D, torch.float32, device)[:n * D].view(n, D)
+        count = self._clip_buffer(tag + '/count', 1, torch.int64, device)
+        need = int(h.dt_rows_coalesce_workspace_bytes(n, D))
+        if need < 0:
+            check(need, 'dt_rows_coalesce_workspace_bytes')
+        ws = self._clip_buffer(tag + '/ws', need, torch.uint8, device)
+        check(h.dt_rows_coalesce(ptr(rows), ptr(vals), n, D, V, ptr(out_rows), ptr(out_vals), ptr(count), ptr(ws), stream_ptr()),
+              'dt_rows_coalesce')
+        return out_rows, out_vals, count, n
+
     def clip_gradients(self):
         """The clip stage of `step()`: afterwards every `.grad` (contiguous, clipped in place) and every table's
         `sparse_grads` entry (ONE piece: the distinct rows ascending, then -1, with their summed and clipped gradients,
         fields = -1) are what the unclipped optimizer is given.  No host synchronisation; replays in a captured graph."""
+        self._step_coalesced = {}                          # id(table) -> (out_rows, n): the tables this step's clip coalesced
         if self._clip is None:
             return
         key, c = self._clip
@@ -385,20 +408,8 @@ class _GradClip:
                 table = layer.tables[k]
                 V, D = table.shape
                 device = table.device
-                rows = torch.cat([g.rows.reshape(-1) for g in grads]) if len(grads) > 1 else grads[0].rows.reshape(-1)
-                vals = torch.cat([g.values.reshape(-1, D) for g in grads]) if len(grads) > 1 else grads[0].values.reshape(-1, D)
-                rows, vals = rows.contiguous(), vals.contiguous()
-                n = rows.numel()
-                tag = f'{id(table)}'
-                out_rows = self._clip_buffer(tag + '/rows', n, torch.int64, device)[:n]
-                out_vals = self._clip_buffer(tag + '/vals', n * D, torch.float32, device)[:n * D].view(n, D)
-                count = self._clip_buffer(tag + '/count', 1, torch.int64, device)
-                need = int(h.dt_rows_coalesce_workspace_bytes(n, D))
-                if need < 0:
-                    check(need, 'dt_rows_coalesce_workspace_bytes')
-                ws = self._clip_buffer(tag + '/ws', need, torch.uint8, device)
-                check(h.dt_rows_coalesce(ptr(rows), ptr(vals), n, D, V, ptr(out_rows), ptr(out_vals), ptr(count), ptr(ws), st),
-                      'dt_rows_coalesce')
+                out_rows, out_vals, count, n = self._coalesce(table, grads)
+                self._step_coalesced[id(table)] = (out_rows, n)
                 offs_dev = self._field_rows(layer, k, table)[1]
                 sparse.append((layer, k, out_rows, out_vals, count, n, D, V, offs_dev, n_sums))
                 n_sums += offs_dev.numel()
@@ -429,7 +440,376 @@ class _GradClip:
             layer.sparse_grads[k] = [SparseRowGrad(out_rows, out_vals, fields=-1)]
 
 
-class _DeviceOptimizer(_GradClip):
+STAGE_KEYS = ('weight_decay', 'use_ema', 'ema_momentum')
+DT_STAGE_STATE_WORDS = 16 // 4        # DT_STAGE_STATE_BYTES (include/dt_hip.h) in int32 words
+
+
+def _is_number(v):
+    return isinstance(v, (int, float)) and not isinstance(v, bool)
+
+
+def check_stages(weight_decay=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None):
+    """Keras' base-optimizer arguments -> (weight_decay or None, use_ema, ema_momentum): the decay a finite number >= 0 (None:
+    off), the momentum in [0, 1]; `ema_overwrite_frequency` is not supported"""
+    if weight_decay is not None and not (_is_number(weight_decay) and math.isfinite(weight_decay) and weight_decay >= 0):
+        raise ValueError(f'`weight_decay` must be a finite number >= 0 (or None: off), got {weight_decay!r}')
+    if not isinstance(use_ema, (bool, np.bool_)):
+        raise ValueError(f'`use_ema` must be True or False, got {use_ema!r}')
+    if not (_is_number(ema_momentum) and 0 <= ema_momentum <= 1):
+        raise ValueError(f'`ema_momentum` must be in the range [0, 1], got {ema_momentum!r}')
+    if ema_overwrite_frequency is not None:
+        raise ValueError(f'`ema_overwrite_frequency` is not supported (got {ema_overwrite_frequency!r}): the weights are '
+                         f'overwritten with their average once, by `finalize_variable_values()` at the end of `fit`')
+    return (None if weight_decay is None else float(weight_decay)), bool(use_ema), float(ema_momentum)
+
+
+class _StepStages(_GradClip):
+    """keras.optimizers' `weight_decay` (BaseOptimizer._apply_weight_decay; `Adam(weight_decay=...)` is AdamW) and `use_ema` /
+    `ema_momentum` for every optimizer here, as stages around an update that is the plain optimizer's, bit for bit
+    (csrc/optim_stages.hip).  `step()` runs: the clip stage, the decay p = p - (p*wd)*lr of every variable that is not
+    excluded (the gradient was taken at the un-decayed p), the update, then a = m*a + (1 - m)*p with m = 0 at the stage's first
+    step, and the stage's own device-resident step count goes up by one.  A variable is a Keras variable, as in `_GradClip`.
+    Row-sparse tables (a sparse gradient: above DENSE_GRAD_MAX_ELEMS): duplicates are summed first (dt_rows_coalesce), and
+      * only the looked-up rows decay — a deviation of the `_RowSparseOptimizer` kind: a row that was not looked up keeps its
+        weight.  (Catching it up when it is looked up again would be wrong: that step's forward has read it already.)
+      * the average is exact with respect to the weights as they moved here: a row that is not looked up has a constant
+        weight w, so the k average steps it missed are a = w + m^k*(a - w), applied when the row is looked up next (an int32
+        stamp per row holds the step its average was last written at) or by `materialize()` for all rows at once.
+    With either argument set no fused step may apply an update (`supports_row_segments` / `supports_rows_in_step` are False and
+    DeepModel.fused_plan() is None).  Averages are kept like slots: a flat group's are views of one flat buffer, zero pads
+    stay zero, checkpoint.save_model stores them next to the slots."""
+
+    weight_decay = None
+    use_ema = False
+    ema_momentum = 0.99
+    _stage_dev = None                 # the stage's device-resident step count (DT_STAGE_STATE_BYTES)
+    _stage_started = False
+    _var_names = None                 # {checkpoint name: tensor}, or a callable that returns it
+
+    @property
+    def stages(self):
+        """either argument is set: `step()` runs more than the plain optimizer's launches"""
+        return self.weight_decay is not None or self.use_ema
+
+    @property
+    def supports_row_segments(self):
+        return _GradClip.supports_row_segments.fget(self) and not self.stages
+
+    @property
+    def supports_rows_in_step(self):
+        return _GradClip.supports_rows_in_step.fget(self) and not self.stages
+
+    def _set_stages(self, weight_decay=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None):
+        self.weight_decay, self.use_ema, self.ema_momentum = check_stages(weight_decay, use_ema, ema_momentum,
+                                                                          ema_overwrite_frequency)
+        self._averages = {}           # id(param) -> its average, in the shape of the parameter
+        self._stamps = {}             # id(table) -> int32 [V]: the step each row's average was last written at
+        self._wd_tensors = []         # exclude_from_weight_decay(var_list=...)
+        self._wd_patterns = []        # ... (var_names=...)
+        self._wd_resolved = None      # the tensors the patterns name, looked up at the first step
+
+    def _stage_hp(self):
+        """the part of `hyperparameters()` that belongs to the stages: only what is set"""
+        hp = {} if self.weight_decay is None else {'weight_decay': self.weight_decay}
+        if self.use_ema:
+            hp.update(use_ema=True, ema_momentum=self.ema_momentum)
+        return hp
+
+    def _base_hp(self):
+        return dict(self._clip_hp(), **self._stage_hp())
+
+    def _load_stage_hp(self, hp):
+        """`set_hyperparameters`: stage keys in `hp` update the setting -> hp without them"""
+        if any(k in hp for k in STAGE_KEYS):
+            self.weight_decay, self.use_ema, self.ema_momentum = check_stages(
+                hp.get('weight_decay', self.weight_decay), hp.get('use_ema', self.use_ema),
+                hp.get('ema_momentum', self.ema_momentum))
+        return {k: v for k, v in hp.items() if k not in STAGE_KEYS}
+
+    def _load_base_hp(self, hp):
+        return self._load_stage_hp(self._load_clip_hp(hp))
+
+    # -- which variables decay -------------------------------------------------------------------------------
+    def set_variable_names(self, names):
+        """{`layer/weight`: tensor} (checkpoint.named_weights), or a callable returning it: what `exclude_from_weight_decay(
+        var_names=...)` matches against.  DeepModel binds its model's names when it compiles the optimizer."""
+        self._var_names = names
+
+    def variable_names(self):
+        names = self._var_names
+        return dict(names() if callable(names) else names or {})
+
+    def exclude_from_weight_decay(self, var_list=None, var_names=None):
+        """Keras' BaseOptimizer.exclude_from_weight_decay: the parameters of `var_list` (a dense parameter, a packed table, one
+        column's `embeddings_i`) and every variable whose checkpoint name `layer/weight` matches (`re.search`) one of the patterns
+        `var_names` do not decay.  Only before the first `step()`."""
+        if self._stage_started:
+            raise ValueError('exclude_from_weight_decay() can only be called before the first step()')
+        import re
+        for pattern in var_names or []:
+            re.compile(pattern)
+        self._wd_tensors += [v.data if isinstance(v, torch.nn.Parameter) else v for v in (var_list or [])]
+        self._wd_patterns += list(var_names or [])
+        self._wd_resolved = None
+
+    def _excluded_tensors(self):
+        if self._wd_resolved is None:
+            import re
+            named = []
+            if self._wd_patterns:
+                names = self.variable_names()
+                if not names:
+                    raise ValueError('exclude_from_weight_decay(var_names=...) needs the variables\' names: compile the optimizer '
+                                     'through DeepModel or call set_variable_names({name: tensor})')
+                named = [t for name, t in names.items() if any(re.search(p, name) for p in self._wd_patterns)]
+            self._wd_resolved = named
+        return self._wd_tensors + self._wd_resolved
+
+    def decay_exclusions(self, names=None):
+        """the exclusions as patterns over checkpoint names (what a checkpoint stores): the patterns given, and `^name$` for
+        every named variable inside a tensor of `var_list`"""
+        import re
+        names = self.variable_names() if names is None else names
+        spans = [(t.data_ptr(), t.data_ptr() + 4 * self._span(t)) for t in self._wd_tensors]
+        inside = [name for name, t in names.items() if t.is_floating_point() and
+                  any(lo <= t.data_ptr() and t.data_ptr() + 4 * self._span(t) <= hi for lo, hi in spans)]
+        return list(self._wd_patterns) + ['^' + re.escape(name) + '$' for name in inside]
+
+    def _load_decay_exclusions(self, patterns):
+        self._wd_tensors, self._wd_patterns, self._wd_resolved = [], list(patterns), None
+
+    @staticmethod
+    def _span(t):
+        """elements between the first and the last element of t, both included (a strided block counts with what it encloses)"""
+        return 1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride())) if t.numel() else 0
+
+    def _decays(self, skip, address, elements):
+        return not any(lo <= address and address + 4 * elements <= hi for lo, hi in skip)
+
+    # -- the stage's step count ------------------------------------------------------------------------------
+    def _stage_state(self, device):
+        if self._stage_dev is None or self._stage_dev.device != device:
+            done = 0 if self._stage_dev is None else int(self._stage_dev[0].item())
+            self._stage_dev = torch.zeros(DT_STAGE_STATE_WORDS, dtype=torch.int32, device=device)
+            check(lib().dt_stage_state_init(ptr(self._stage_dev), done, stream_ptr()), 'dt_stage_state_init')
+        return self._stage_dev
+
+    @property
+    def stage_t(self):
+        """steps the stages have run (device resident; the moving average's t)"""
+        return 0 if self._stage_dev is None else int(self._stage_dev[0].item())
+
+    @stage_t.setter
+    def stage_t(self, value):
+        if not self.params:
+            return
+        self._materialize_averages()       # what is pending belongs to the old count
+        check(lib().dt_stage_state_init(ptr(self._stage_state(self.params[0].device)), int(value), stream_ptr()),
+              'dt_stage_state_init')
+        for stamp in self._stamps.values():
+            stamp.copy_(self._stage_dev[:1].expand(stamp.shape[0]))
+
+    # -- averages --------------------------------------------------------------------------------------------
+    def _flat_average(self):
+        fa = self._averages.get('flat')
+        if fa is None or fa.shape != self._flat[0].shape:
+            fa = self._averages['flat'] = self._flat[0].detach().clone()
+        return fa
+
+    def _average_of(self, p):
+        """the average of parameter p (created as a copy of p): a view of the flat average for a flat-group member"""
+        a = self._averages.get(id(p))
+        if a is None:
+            flat = getattr(self, '_flat', None)
+            if flat is not None and id(p) in flat[5]:
+                a = torch.as_strided(self._flat_average(), tuple(p.data.shape), tuple(p.data.stride()),
+                                     (p.data.data_ptr() - flat[0].data_ptr()) // 4)
+            else:
+                a = p.data.detach().clone(memory_format=torch.contiguous_format)
+            self._averages[id(p)] = a
+        return a
+
+    def _rehome_flat_averages(self):
+        """`register_flat_group`: the members' averages become views of one flat buffer (existing values are kept)"""
+        if not self._averages:
+            return
+        self._averages.pop('flat', None)
+        for p in self.params:
+            if id(p) in self._flat[5]:
+                old = self._averages.pop(id(p), None)
+                if old is not None:
+                    self._average_of(p).copy_(old.reshape(p.shape))
+
+    def _row_stamps(self, table):
+        """the stamps of a row-sparse table's average: a new array says that nothing is pending"""
+        stamp = self._stamps.get(id(table))
+        if stamp is None:
+            stamp = self._stage_state(table.device)[:1].expand(table.shape[0]).contiguous()
+            self._stamps[id(table)] = stamp
+        return stamp
+
+    def _materialize_averages(self):
+        for p in getattr(self, 'params', ()):
+            stamp, a = self._stamps.get(id(p)), self._averages.get(id(p))
+            if stamp is not None and a is not None:
+                check(lib().dt_ema_rows_materialize(ptr(p.data), ptr(a), ptr(stamp), p.shape[0], p.shape[1], self.ema_momentum,
+                                                    ptr(self._stage_state(p.device)), stream_ptr()), 'dt_ema_rows_materialize')
+
+    def materialize(self):
+        """bring every row-sparse table's average up to the steps done (a pending catch-up is applied, the rows restamped)"""
+        self._materialize_averages()
+
+    def average(self, p):
+        """the moving average of p — a parameter, or a view of one (a column's `embeddings_i`) — in its shape; None before its
+        first averaged step.  A row-sparse table's average is materialised first."""
+        self._materialize_averages()
+        a = self._averages.get(id(p))
+        if a is not None or not torch.is_tensor(p):
+            return a
+        from .checkpoint import _inside, _slot_piece
+        for q in self.params:
+            if id(q) in self._averages and _inside(p, q.data):
+                return _slot_piece(self._averages[id(q)], (p.data_ptr() - q.data_ptr()) // 4, p)
+        return None
+
+    def finalize_variable_values(self):
+        """Keras' BaseOptimizer.finalize_variable_values: with `use_ema`, every variable is overwritten with its average
+        (DeepModel.fit calls it once after the last epoch)"""
+        if not self.use_ema:
+            return
+        self._materialize_averages()
+        with torch.no_grad():
+            for p in self.params:
+                a = self._averages.get(id(p))
+                if a is not None:
+                    p.data.copy_(a)
+
+    # -- the stages --------------------------------------------------------------------------------------------
+    def _stage_buffer(self, name, build):
+        bufs = self.__dict__.setdefault('_stage_bufs', {})
+        if name not in bufs:
+            bufs[name] = build()
+        return bufs[name]
+
+    @staticmethod
+    def _host_arrays(regions):
+        """[(address, ..., elements)] -> one ctypes array of addresses per leading column and one of the sizes"""
+        R = len(regions)
+        cols = [ctypes.cast((ctypes.c_void_p * R)(*[r[c] for r in regions]), ctypes.c_void_p)
+                for c in range(len(regions[0]) - 1)]
+        return cols + [ctypes.cast((ctypes.c_int64 * R)(*[int(r[-1]) for r in regions]), ctypes.c_void_p)]
+
+    def _stage_tables(self):
+        return {id(layer.tables[k]): (layer, k) for layer in self.embedding_layers for k in getattr(layer, 'tables', {})}
+
+    def _stages_before(self):
+        """Behind the clip stage and ahead of the update: every table's sparse gradient becomes ONE coalesced piece (fields =
+        -1) unless the clip stage made it one, the looked-up rows' averages catch up and the rows decay, the dense variables
+        decay.  -> what `_stages_after` needs.  No host synchronisation; replays in a captured graph."""
+        from .ops import SparseRowGrad
+        h, st = lib(), stream_ptr()
+        self._stage_started = True
+        wd, lr = self.weight_decay, float(self.lr)
+        skip = [(t.data_ptr(), t.data_ptr() + 4 * self._span(t)) for t in self._excluded_tensors()] if wd is not None else []
+        tables = self._stage_tables()
+        flat = getattr(self, '_flat', None)
+        members = flat[5] if flat is not None else {}
+        if flat is not None and sum(1 for p in self.params if id(p) in members and p.grad is not None) != len(members):
+            flat, members = None, {}
+        singles = [p for p in self.params if p.grad is not None and id(p) not in members]
+        rows_ctx = []
+        for layer in self.embedding_layers:
+            for k, grads in list(layer.sparse_grads.items()):
+                if not grads:
+                    continue
+                table = layer.tables[k]
+                V, D = table.shape
+                done = getattr(self, '_step_coalesced', {}).get(id(table))
+                if done is None:
+                    if any(getattr(g, 'segments', None) is not None or getattr(g, 'fields', None) == -2 for g in grads):
+                        raise ValueError(f'{self._name}: weight_decay / use_ema take plain (rows, values) sparse gradients: no '
+                                         f'segments, no rows applied inside a fused step')
+                    out_rows, out_vals, count, n = self._coalesce(table, grads)
+                    layer.sparse_grads[k] = [SparseRowGrad(out_rows, out_vals, fields=-1)]
+                else:
+                    out_rows, n = done
+                offs, offs_dev = self._field_rows(layer, k, table)
+                on = [self._decays(skip, table.data_ptr() + 4 * lo * D, (hi - lo) * D) for lo, hi in zip(offs[:-1], offs[1:])]
+                decay = wd is not None and any(on)
+                field_on = None
+                if decay and not all(on):
+                    field_on = self._stage_buffer(f'{id(table)}/on/{on}', lambda: torch.tensor(on, dtype=torch.int32,
+                                                                                                 device=table.device))
+                avg = stamp = sp = None
+                if self.use_ema:
+                    sp = self._stage_state(table.device)
+                    avg, stamp = self._average_of(table), self._row_stamps(table)
+                check(h.dt_rows_stage_pre(ptr(table.data), ptr(avg), ptr(stamp), ptr(out_rows), n, D, V, ptr(offs_dev),
+                                          ptr(field_on), offs_dev.numel(), 1 if decay else 0, wd or 0.0, lr, self.ema_momentum,
+                                          ptr(sp), st), 'dt_rows_stage_pre')
+                rows_ctx.append((table, avg, stamp, out_rows, n, D, V))
+        if wd is not None:
+            regions, back = [], []
+            if flat is not None:
+                regions += [(flat[0].data_ptr() + 4 * off, span) for off, span in self._flat_regions()]
+            for p in singles:
+                if id(p) in tables and p.dim() == 2 and p.data.is_contiguous():     # a packed table with a dense gradient
+                    offs, D = self._field_rows(*tables[id(p)], p)[0], p.shape[1]
+                    regions += [(p.data_ptr() + 4 * lo * D, (hi - lo) * D) for lo, hi in zip(offs[:-1], offs[1:])]
+                elif p.data.is_contiguous():
+                    regions.append((p.data_ptr(), p.numel()))
+                elif self._decays(skip, p.data_ptr(), self._span(p.data)):
+                    # a strided parameter on its own (only some members of a flat group carry a gradient): through a copy
+                    pc = p.data.contiguous()
+                    back.append((p, pc))
+                    regions.append((pc.data_ptr(), pc.numel()))
+            regions = [r for r in regions if r[1] > 0 and self._decays(skip, *r)]
+            if regions:
+                check(h.dt_decay_multi(len(regions), *self._host_arrays(regions), wd, lr, st), 'dt_decay_multi')
+            for p, pc in back:
+                p.data.copy_(pc)
+        return flat, singles, rows_ctx
+
+    def _stages_after(self, ctx):
+        """Behind the update: the looked-up rows' and the dense variables' averages take this step, the stage's count goes up"""
+        if not self.use_ema:
+            return
+        h, st = lib(), stream_ptr()
+        flat, singles, rows_ctx = ctx
+        device = None
+        for table, avg, stamp, out_rows, n, D, V in rows_ctx:
+            device = table.device
+            check(h.dt_rows_stage_post(ptr(table.data), ptr(avg), ptr(stamp), ptr(out_rows), n, D, V, self.ema_momentum,
+                                       ptr(self._stage_state(device)), st), 'dt_rows_stage_post')
+        regions, back = [], []
+        if flat is not None:
+            regions.append((flat[0].data_ptr(), self._flat_average().data_ptr(), flat[4]))
+            for p in self.params:
+                if id(p) in flat[5]:
+                    self._average_of(p)
+        for p in singles:
+            a = self._average_of(p)
+            if id(p) in self._stamps:
+                raise ValueError(f'{self._name}: use_ema: a table whose average is kept row by row (it had sparse gradients) '
+                                 f'got a dense gradient')
+            pc = p.data if p.data.is_contiguous() else p.data.contiguous()
+            ac = a if a.is_contiguous() else a.contiguous()
+            if ac is not a:
+                back.append((a, ac))
+            regions.append((pc.data_ptr(), ac.data_ptr(), p.numel(), pc))
+        regions = [r for r in regions if r[2] > 0]
+        if regions:
+            device = flat[0].device if flat is not None else singles[0].device
+            check(h.dt_ema_multi(len(regions), *self._host_arrays([r[:3] for r in regions]), self.ema_momentum,
+                                 ptr(self._stage_state(device)), st), 'dt_ema_multi')
+        for a, ac in back:
+            a.copy_(ac)
+        if device is None:
+            return
+        check(h.dt_stage_advance(ptr(self._stage_state(device)), st), 'dt_stage_advance')
+
+
+class _DeviceOptimizer(_StepStages):
     """The step driver KerasAdam, Adagrad, RMSprop, Ftrl, Adamax and MomentumSGD share.  One protocol — `zero_grad(flat=...)`, `step()`,
     `register_flat_group`, `pre_dense_hook`, `state`, `t` — and one launch order: the dense tensors in one multi-tensor
     launch (a registered flat group is ONE tensor: the fused train-step plans keep parameters and gradients of all dense
@@ -448,8 +828,10 @@ class _DeviceOptimizer(_GradClip):
     slot_names = ()                   # the slots' names: their keys in `state[id(p)]` and in a checkpoint
     slot_init = 0.0                   # the slots' initial value: one number, or one per slot (a tuple matching slot_names)
 
-    def __init__(self, params, embedding_layers, clipnorm=None, clipvalue=None, global_clipnorm=None):
+    def __init__(self, params, embedding_layers, clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None,
+                 use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None):
         self._set_clip(clipnorm, clipvalue, global_clipnorm)
+        self._set_stages(weight_decay, use_ema, ema_momentum, ema_overwrite_frequency)
         self.params = [p for p in params if p.requires_grad]
         self.state = {}
         self.embedding_layers = list(embedding_layers)
@@ -487,7 +869,9 @@ class _DeviceOptimizer(_GradClip):
         self._restamp()
 
     def materialize(self):
-        """make every slot Keras' slot (RMSprop applies the decay pending on the rows of its row-sparse tables)"""
+        """make every slot Keras' slot (RMSprop applies the decay pending on the rows of its row-sparse tables) and every
+        average current (`_StepStages.materialize`)"""
+        self._materialize_averages()
 
     def _restamp(self):
         pass
@@ -535,6 +919,7 @@ class _DeviceOptimizer(_GradClip):
             if grad_views else None
         for p, off, cnt, layout in members:
             p._dt_grad_view = None
+        self._rehome_flat_averages()
         if grad_views:                       # same tensor objects in both places (`p.grad is p._dt_grad_view`)
             for p, view in self._flat_views:
                 p._dt_grad_view = view
@@ -605,12 +990,14 @@ class _DeviceOptimizer(_GradClip):
             return
         sp = ptr(self._state_tensor(self.params[0].device))
         st = stream_ptr()
-        if self._clip is not None:
+        if self._clip is not None or self.stages:
             # the clip stage sees the gradients the update is given: after a pending exchange has landed
             hook, self.pre_dense_hook = self.pre_dense_hook, None
             if hook is not None:
                 hook()
             self.clip_gradients()
+        # weight decay ahead of the update, the moving average behind it: the update between them is the plain optimizer's
+        stages = self._stages_before() if self.stages else None
         # every launch of the step reads the device state; the LAST one advances it (no extra launch)
         dense = []                                        # (param, grad, (slot, ..), n)
         flat_done = set()
@@ -706,6 +1093,8 @@ class _DeviceOptimizer(_GradClip):
             p.data.copy_(pc)
             for x, xc in zip(ss, sc):
                 x.copy_(xc)
+        if stages is not None:
+            self._stages_after(stages)
         for layer in self.embedding_layers:
             layer.sparse_grads.clear()
 
@@ -724,8 +1113,10 @@ class KerasAdam(_DeviceOptimizer):
     _name = 'Adam'
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None):
-        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
+                         ema_overwrite_frequency)
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta_1, beta_2, epsilon
         self._applied_in_step = False  # a fused step ran this step's whole update itself (applied_in_step)
 
@@ -733,11 +1124,12 @@ class KerasAdam(_DeviceOptimizer):
         return self.b1, self.b2
 
     def hyperparameters(self):
-        """what travels with a checkpoint: the clip setting alone (Adam's own arguments are the constructor's, as they were)"""
-        return self._clip_hp()
+        """what travels with a checkpoint: the clip, decay and average settings alone (Adam's own arguments are the
+        constructor's, as they were)"""
+        return self._base_hp()
 
     def set_hyperparameters(self, hp):
-        self._load_clip_hp(hp)
+        self._load_base_hp(hp)
 
     def _new_slot(self, p, rows):
         """rows (the row-sparse table update): m and v of a row side by side in ONE [V, 2, D] array (a 128-byte line at
@@ -796,7 +1188,7 @@ class KerasAdam(_DeviceOptimizer):
                                           int(s['m'].stride(0)), st), 'dt_adam_rows_step_seg')
 
 
-class SGD(_GradClip):
+class SGD(_StepStages):
     """keras.optimizers.SGD(learning_rate=0.01, momentum=0.0, nesterov=False).  momentum == 0: p -= lr*g, one launch per
     tensor and per sparse-gradient piece, no state.  momentum != 0: `SGD(...)` returns a `MomentumSGD`, which runs on the
     step driver (one slot `momentum`); both answer to the name 'SGD'."""
@@ -804,25 +1196,29 @@ class SGD(_GradClip):
     _name = 'SGD'
 
     def __new__(cls, params=(), embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None,
-                clipvalue=None, global_clipnorm=None):
+                clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                ema_overwrite_frequency=None):
         if not 0 <= momentum <= 1:
             raise ValueError(f'`momentum` must be in the range [0, 1], got {momentum!r}')
         if cls is SGD and momentum != 0:
-            return MomentumSGD(params, embedding_layers, learning_rate, momentum, nesterov, clipnorm, clipvalue, global_clipnorm)
+            return MomentumSGD(params, embedding_layers, learning_rate, momentum, nesterov, clipnorm, clipvalue, global_clipnorm,
+                               weight_decay, use_ema, ema_momentum, ema_overwrite_frequency)
         return super().__new__(cls)
 
     def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.0, nesterov=False, clipnorm=None,
-                 clipvalue=None, global_clipnorm=None):
+                 clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
         self._set_clip(clipnorm, clipvalue, global_clipnorm)
+        self._set_stages(weight_decay, use_ema, ema_momentum, ema_overwrite_frequency)
         self.lr = learning_rate
         self.params = [p for p in params if p.requires_grad]
         self.embedding_layers = list(embedding_layers)
 
     def hyperparameters(self):
-        return dict({'learning_rate': self.lr, 'momentum': 0.0, 'nesterov': False}, **self._clip_hp())
+        return dict({'learning_rate': self.lr, 'momentum': 0.0, 'nesterov': False}, **self._base_hp())
 
     def set_hyperparameters(self, hp):
-        self.lr = float(self._load_clip_hp(hp).get('learning_rate', self.lr))
+        self.lr = float(self._load_base_hp(hp).get('learning_rate', self.lr))
 
     def zero_grad(self):
         for p in self.params:
@@ -833,6 +1229,7 @@ class SGD(_GradClip):
     def step(self):
         st = stream_ptr()
         self.clip_gradients()
+        stages = self._stages_before() if self.stages else None
         for p in self.params:
             if p.grad is not None:
                 g = p.grad.contiguous()
@@ -844,6 +1241,9 @@ class SGD(_GradClip):
                     vals = gr.values if gr.values.is_contiguous() else gr.values.contiguous()
                     check(lib().dt_sgd_rows_step(ptr(table.data), ptr(gr.rows), ptr(vals), gr.rows.numel(),
                                                  table.shape[1], self.lr, st), 'dt_sgd_rows_step')
+        if stages is not None:
+            self._stages_after(stages)
+        for layer in self.embedding_layers:
             layer.sparse_grads.clear()
 
 
@@ -854,8 +1254,10 @@ class _SlotOptimizer(_DeviceOptimizer):
     DeepFM / DCN plans run forward + backward, hand over plain (rows, values) and leave the whole update to `step()`, as
     they do for SGD."""
 
-    def __init__(self, params, embedding_layers, learning_rate, epsilon, clipnorm=None, clipvalue=None, global_clipnorm=None):
-        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
+    def __init__(self, params, embedding_layers, learning_rate, epsilon, clipnorm=None, clipvalue=None, global_clipnorm=None,
+                 weight_decay=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
+                         ema_overwrite_frequency)
         self.lr, self.eps = float(learning_rate), float(epsilon)
 
     def slot(self, p):
@@ -865,10 +1267,10 @@ class _SlotOptimizer(_DeviceOptimizer):
         return None if s is None else s[self.slot_names[0]]
 
     def hyperparameters(self):
-        return dict({'learning_rate': self.lr, 'epsilon': self.eps}, **self._clip_hp())
+        return dict({'learning_rate': self.lr, 'epsilon': self.eps}, **self._base_hp())
 
     def set_hyperparameters(self, hp):
-        hp = self._load_clip_hp(hp)
+        hp = self._load_base_hp(hp)
         self.lr, self.eps = float(hp.get('learning_rate', self.lr)), float(hp.get('epsilon', self.eps))
 
 
@@ -883,10 +1285,12 @@ class Adagrad(_SlotOptimizer):
     slot_names = ('acc',)
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, initial_accumulator_value=0.1, epsilon=1e-7,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None):
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
         if initial_accumulator_value < 0:
             raise ValueError(f'initial_accumulator_value must be non-negative, got {initial_accumulator_value}')
-        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm)
+        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm, weight_decay,
+                         use_ema, ema_momentum, ema_overwrite_frequency)
         self.initial_accumulator_value = self.slot_init = float(initial_accumulator_value)
 
     def hyperparameters(self):
@@ -913,11 +1317,13 @@ class RMSprop(_SlotOptimizer):
     stamp_in_record = False
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, rho=0.9, momentum=0.0, epsilon=1e-7, centered=False,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None):
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
         if momentum != 0 or centered:
             raise ValueError('RMSprop: momentum != 0 and centered=True are not supported (Keras switches to another '
                              f'update formula for them); got momentum={momentum!r}, centered={centered!r}')
-        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm)
+        super().__init__(params, embedding_layers, learning_rate, epsilon, clipnorm, clipvalue, global_clipnorm, weight_decay,
+                         use_ema, ema_momentum, ema_overwrite_frequency)
         self.rho, self.momentum, self.centered = float(rho), 0.0, False
 
     def hyperparameters(self):
@@ -962,6 +1368,7 @@ class RMSprop(_SlotOptimizer):
             s = self.state.get(id(p))
             if s is not None and 'stamp' in s:
                 self._materialize_one(p, s)
+        self._materialize_averages()
 
     def _restamp(self):
         for p in self.params:
@@ -1018,15 +1425,18 @@ class _RowSparseOptimizer(_DeviceOptimizer):
         return None if s is None else s[name or self.slot_names[0]]
 
     def hyperparameters(self):
-        return dict({k: getattr(self, k) for k in self._hp}, **self._clip_hp())
+        return dict({k: getattr(self, k) for k in self._hp}, **self._base_hp())
 
     def set_hyperparameters(self, hp):
-        unknown = sorted(set(hp) - set(self._hp) - set(CLIP_KEYS))
+        unknown = sorted(set(hp) - set(self._hp) - set(CLIP_KEYS) - set(STAGE_KEYS))
         if unknown:
-            raise ValueError(f'{self._name}: unknown hyperparameters {unknown} (accepted: {list(self._hp + CLIP_KEYS)})')
+            raise ValueError(f'{self._name}: unknown hyperparameters {unknown} (accepted: '
+                             f'{list(self._hp + CLIP_KEYS + STAGE_KEYS)})')
         check_clip(**{k: hp.get(k) for k in CLIP_KEYS})                   # a refused update changes nothing
-        self._check(**dict({k: getattr(self, k) for k in self._hp}, **{k: v for k, v in hp.items() if k not in CLIP_KEYS}))
-        hp = self._load_clip_hp(hp)
+        check_stages(**{k: hp[k] for k in STAGE_KEYS if k in hp})
+        self._check(**dict({k: getattr(self, k) for k in self._hp},
+                           **{k: v for k, v in hp.items() if k not in CLIP_KEYS + STAGE_KEYS}))
+        hp = self._load_base_hp(hp)
         for k, v in hp.items():
             setattr(self, k, type(getattr(self, k))(v))
 
@@ -1050,9 +1460,11 @@ class MomentumSGD(_RowSparseOptimizer):
     _hp = ('learning_rate', 'momentum', 'nesterov')
 
     def __init__(self, params, embedding_layers=(), learning_rate=0.01, momentum=0.9, nesterov=False, clipnorm=None,
-                 clipvalue=None, global_clipnorm=None):
+                 clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
         self._check(momentum=momentum)
-        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
+                         ema_overwrite_frequency)
         self.learning_rate, self.momentum, self.nesterov = float(learning_rate), float(momentum), bool(nesterov)
 
     @staticmethod
@@ -1076,8 +1488,10 @@ class Adamax(_RowSparseOptimizer):
     _hp = ('learning_rate', 'beta_1', 'beta_2', 'epsilon')
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
-                 clipnorm=None, clipvalue=None, global_clipnorm=None):
-        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
+                 clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
+                 ema_overwrite_frequency=None):
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
+                         ema_overwrite_frequency)
         self.learning_rate, self.beta_1, self.beta_2, self.epsilon = float(learning_rate), float(beta_1), float(beta_2), \
             float(epsilon)
 
@@ -1107,11 +1521,13 @@ class Ftrl(_RowSparseOptimizer):
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, learning_rate_power=-0.5,
                  initial_accumulator_value=0.1, l1_regularization_strength=0.0, l2_regularization_strength=0.0,
-                 l2_shrinkage_regularization_strength=0.0, beta=0.0, clipnorm=None, clipvalue=None, global_clipnorm=None):
+                 l2_shrinkage_regularization_strength=0.0, beta=0.0, clipnorm=None, clipvalue=None, global_clipnorm=None,
+                 weight_decay=None, use_ema=False, ema_momentum=0.99, ema_overwrite_frequency=None):
         hp = dict(zip(self._hp, (learning_rate, learning_rate_power, initial_accumulator_value, l1_regularization_strength,
                                  l2_regularization_strength, l2_shrinkage_regularization_strength, beta)))
         self._check(**hp)
-        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm)
+        super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
+                         ema_overwrite_frequency)
         for k, v in hp.items():
             setattr(self, k, float(v))
 

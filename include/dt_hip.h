@@ -1483,6 +1483,44 @@ int dt_rows_clip(int mode, float c, const int64_t* out_rows, float* out_vals, in
                  const int64_t* row_offset, int F, int64_t V, const double* sums, int sum_base, int n_sums, double* norm_out,
                  void* stream);
 
+/* keras.optimizers' `weight_decay` and `use_ema` / `ema_momentum` (BaseOptimizer._apply_weight_decay ahead of every
+ * optimizer's update, the moving average of the weights behind it) as stages around any dt_*_step (csrc/optim_stages.hip).
+ * float32, each formula evaluated in this order without contraction:
+ *     decay                       p = p - (p * weight_decay) * lr                (lr: the optimizer's plain learning rate)
+ *     average, step t (1-based)   a = m * a + (1 - m) * p,  m = 0 at t == 1, momentum afterwards
+ *     a row idle for k steps      a = w + momentum^k * (a - w)     (k average steps on a constant weight w; k <= 8: the
+ *                                 multiplication repeated, beyond: powf; k == 0 leaves a as it is)
+ * `state` (DT_STAGE_STATE_BYTES device bytes): {int32 done = the steps the stage has completed}, written by
+ * dt_stage_state_init, read on the device by every launch that averages (a captured graph replays them) and advanced by
+ * dt_stage_advance, the LAST launch of a step.  Nothing here synchronises with the host or allocates.  Every argument is
+ * checked before the first launch: negative sizes, null pointers with something to do, misaligned arrays, a weight_decay
+ * that is not a finite number >= 0 and a momentum outside [0, 1] are DT_ERR_INVALID_ARG.
+ * dt_decay_multi / dt_ema_multi: `count` regions (p[t], n[t]) — p / avg / n are HOST arrays, 32 regions per launch, 1024
+ *   elements per block; a region whose pointers are 16-byte aligned takes 16-byte pieces and a scalar tail, any other the
+ *   scalar loop (the same bits).  An excluded variable is simply not in the list.
+ * dt_rows_stage_pre / dt_rows_stage_post: around the row update of a packed table [V, D], over rows [n]: the DISTINCT row
+ *   ids dt_rows_coalesce emits (ascending, then -1: skipped, as is any id outside [0, V)).  16-byte pieces where D % 4 == 0
+ *   (table and avg 16-byte aligned then), min(D / 4 or D, 256) threads per row, a row never straddles a block.
+ *   pre:  avg != NULL: the row's average first catches up with the k = done - stamp[row] steps it sat out; then, decay != 0:
+ *         the row decays — unless field_on (DEVICE int32 [F], NULL: all on) is 0 for the field f with row_offset[f] <= row <
+ *         row_offset[f + 1] (row_offset: DEVICE int64 [F] ascending from 0; one column's `embeddings_i`).
+ *   post: the step's average of the updated row, then stamp[row] = done + 1.
+ *   Rows that were not looked up keep weight, average and stamp bit for bit.
+ * dt_ema_rows_materialize: the catch-up for every row of the table, then every stamp = done (2 launches).                 */
+#define DT_STAGE_STATE_BYTES 16
+int dt_stage_state_init(void* state, int steps_done, void* stream);
+int dt_stage_advance(void* state, void* stream);
+int dt_decay_multi(int count, float* const* p, const int64_t* n, float weight_decay, float lr, void* stream);
+int dt_ema_multi(int count, const float* const* p, float* const* avg, const int64_t* n, float momentum, const void* state,
+                 void* stream);
+int dt_rows_stage_pre(float* table, float* avg, const int* stamp, const int64_t* rows, int64_t n, int D, int64_t V,
+                      const int64_t* row_offset, const int* field_on, int F, int decay, float weight_decay, float lr,
+                      float momentum, const void* state, void* stream);
+int dt_rows_stage_post(const float* table, float* avg, int* stamp, const int64_t* rows, int64_t n, int D, int64_t V,
+                       float momentum, const void* state, void* stream);
+int dt_ema_rows_materialize(const float* table, float* avg, int* stamp, int64_t V, int D, float momentum, const void* state,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
