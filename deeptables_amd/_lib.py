@@ -318,6 +318,14 @@ SIGNATURES = {
     # alpha, loss [1], dz (or NULL: value only), workspace, stream
     'dt_loss_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
     'dt_loss': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr]),
+    # Keras' regression losses from the model output (csrc/loss_reg.hip): kind = DT_LOSS_HUBER .. DT_LOSS_POISSON, p, t, w (or
+    # NULL), rows, classes, delta, loss [1], dz (or NULL), workspace, stream
+    'dt_loss_reg_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
+    'dt_loss_reg': (_c_int, [_c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr, _ptr, _ptr, _ptr]),
+    # GHMCLoss.calc (csrc/loss_reg.hip): z, t, mask (or NULL), n, bins, momentum, float32(1 - momentum), acc_sum [bins] (updated
+    # in place; NULL at momentum 0), loss [1], dz (or NULL), workspace, stream
+    'dt_ghmc_workspace_bytes': (_c_i64, [_c_i64, _c_int]),
+    'dt_ghmc': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # Activation -> (Dropout) of a tower cell in one launch each way (csrc/cell.hip): x, N, C, act (CELL_ACT_CODES), rate, the
     # DEVICE seed word, salt, out, stream / g, saved, saved_is_input, N, C, act, rate, seed, salt, dx, stream
     'dt_cell_dropout_hash': (ctypes.c_uint32, [ctypes.c_uint32] * 4),
@@ -384,7 +392,9 @@ DT_METRIC_SUMS_BLOCKS, DT_METRIC_SUMS_WORDS = 256, 771      # dt_metric_sums' ou
 DT_SCORE_BLOCKS, DT_SCORE_THREAD_ROW_MAX_C = 256, 32
 DT_SCORE_BINARY_WORDS, DT_SCORE_REGRESSION_WORDS, DT_SCORE_CATEGORICAL_WORDS, DT_SCORE_RANKING_WORDS = 1285, 514, 514, 262
 DT_LOSS_BCE, DT_LOSS_CCE, DT_LOSS_MSE, DT_LOSS_MAE, DT_LOSS_BINARY_FOCAL, DT_LOSS_CATEGORICAL_FOCAL = 0, 1, 2, 3, 4, 5
+DT_LOSS_HUBER, DT_LOSS_LOG_COSH, DT_LOSS_MSLE, DT_LOSS_MAPE, DT_LOSS_POISSON = 6, 7, 8, 9, 10     # dt_loss_reg's kinds
 DT_LOSS_MAX_CLASSES = 4096
+DT_GHMC_MAX_BINS = 256
 DT_CLIP_VALUE, DT_CLIP_NORM, DT_CLIP_GLOBAL_NORM = 0, 1, 2
 DT_FIELD_SUMSQ_PARTS = 32
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)

@@ -17,16 +17,11 @@
 //
 // Stable forms: BCE max(z,0) - z t + log1p(exp(-|z|)); softmax through the row maximum with log p = (z - m) - log sum exp(z - m)
 // (never log(softmax)); 1 - p of a softmax entry as -expm1(log p); 1 - sigmoid(z) as sigmoid(-z); log sigmoid(z) as -softplus(-z).
-#include <math.h>
-
-#include "common.h"
+#include "loss_sum.h"
 
 namespace dt {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / kWave;
-constexpr int kElemChunk = 2048;              // elements per block of the element-wise kinds
 constexpr int kRowsPerBlock = kWaves;         // rows per block of the categorical kinds
 constexpr int kOneRows = 64;                  // categorical kinds: one block takes the whole problem up to this many rows ...
 constexpr int kOneElems = 16384;              // ... and this many elements
@@ -58,23 +53,6 @@ struct LossArgs {
     double c1, c0;           // BINARY_FOCAL: the constant an element with t != 1 / t != 0 adds (sign of the loss included)
 };
 
-// lanes by halving; every lane returns lane 0's total
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_down(v, o, kWave);
-    return __shfl(v, 0, kWave);
-}
-
-// the waves' values in order; thread 0 holds the block's sum
-__device__ __forceinline__ double waves_in_order(double wave_value, double* sh) {
-    if ((threadIdx.x & (kWave - 1)) == 0) sh[threadIdx.x / kWave] = wave_value;
-    __syncthreads();
-    double all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) all += sh[w];
-    return all;
-}
-
 __device__ __forceinline__ void finish_block(const LossArgs& a, double block_sum) {
     if (threadIdx.x == 0) {
         if (a.final) a.loss[0] = (float)(block_sum * a.inv);
@@ -82,10 +60,6 @@ __device__ __forceinline__ void finish_block(const LossArgs& a, double block_sum
     }
 }
 
-__device__ __forceinline__ float sigmoid_f(float z) {
-    const float e = expf(-fabsf(z));
-    return z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-}
 __device__ __forceinline__ float softplus_f(float z) { return fmaxf(z, 0.f) + log1pf(expf(-fabsf(z))); }
 
 // one side of the binary focal loss for an element whose target selects it.  (p, q) = (sigmoid(z), sigmoid(-z)) for t == 1 and
@@ -251,16 +225,6 @@ __global__ __launch_bounds__(kThreads) void k_loss_rows(LossArgs a) {
         acc += (double)wb * cat_row<REG>(a, a.z + off, a.t + off, a.dz ? a.dz + off : nullptr, wb * a.scale, lane);
     }
     finish_block(a, waves_in_order(acc, sh));
-}
-
-__global__ __launch_bounds__(kThreads) void k_loss_total(const double* __restrict__ partial, int64_t count, double inv,
-                                                         float* __restrict__ loss) {
-    __shared__ double sh[kWaves];
-    double s = 0;
-    for (int64_t i = threadIdx.x; i < count; i += kThreads) s += partial[i];
-    s = wave_sum_f64(s);
-    const double all = waves_in_order(s, sh);
-    if (threadIdx.x == 0) loss[0] = (float)(all * inv);
 }
 
 inline bool is_categorical(int kind) { return kind == DT_LOSS_CCE || kind == DT_LOSS_CATEGORICAL_FOCAL; }

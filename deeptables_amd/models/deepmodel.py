@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import deepnets
-from .layers import BinaryFocalLoss, CategoricalFocalLoss, MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
+from .layers import BinaryFocalLoss, CategoricalFocalLoss, GHMCLoss, MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
 from .. import functional as F
 from .. import _lib, training
 from ..functional import Dense, Concatenate, Flatten, Input, Add, BatchNormalization, Dropout, Model
@@ -128,7 +128,8 @@ class DeepModel:
         return Model(inputs=all_inputs, outputs=output)
 
     def _compile_model(self, model, task, num_classes, optimizer, loss):
-        if loss == 'auto':
+        self.loss_delta = 1.0                # keras.losses.Huber's default; the dict form of the loss may carry another
+        if isinstance(loss, str) and loss == 'auto':
             if task in (consts.TASK_BINARY, consts.TASK_MULTILABEL):
                 loss_name = 'binary_crossentropy'
             elif task == consts.TASK_REGRESSION:
@@ -139,6 +140,15 @@ class DeepModel:
                 raise RuntimeError(f'unseen task "{task}"')
         elif isinstance(loss, str):
             loss_name = loss
+        elif isinstance(loss, dict):
+            # the serialised form, as `optimizer=` takes it: {'class_name': 'Huber', 'config': {'delta': 2.0}}
+            loss_name, params = training.resolve_loss(loss)
+            self.loss_delta = params.get('delta', 1.0)
+        elif isinstance(loss, GHMCLoss):
+            if task not in (consts.TASK_BINARY, consts.TASK_MULTILABEL):
+                raise ValueError(f'GHMCLoss weighs sigmoid outputs: it trains the binary and multilabel tasks, not {task!r}')
+            loss_name = 'GHMCLoss'
+            self._custom_loss = loss
         else:
             loss_name = getattr(loss, '__name__', 'custom')
             self._custom_loss = loss
@@ -246,12 +256,19 @@ class DeepModel:
     def _loss(self, logit, y, sample_weight=None):
         """The data loss of a batch from the LOGITS, with Keras' per-row weights (sample_weight x class_weight).  The named
         losses and the layers module's focal losses (reduction 'auto') run in csrc/loss.hip on the device (training.py);
-        any other callable, and a focal loss with another reduction, gets the activated probabilities."""
+        any other callable, and a focal loss with another reduction, gets the activated probabilities.
+        Keras' regression losses (huber, log_cosh, msle, mape, poisson) apply to the model's OUTPUT: for the regression task
+        that is the logit and csrc/loss_reg.hip serves it; for any other task they are evaluated in torch ops on
+        `_activate(logit)` and autograd carries the gradient through the activation.  A GHMCLoss gets `calc(logit, y)`."""
         name = self.loss_name
         custom = getattr(self, '_custom_loss', None)
         if custom is None:
             if name not in training.LOSS_NAMES:
                 raise ValueError(f'Unsupported loss: {name}')
+            if name in training.REG_LOSS_KINDS:
+                linear = getattr(self, 'output_activation', None) is None
+                return training.regression_loss(name, logit if linear else self._activate(logit), y, sample_weight,
+                                                getattr(self, 'loss_delta', 1.0), device=linear)
             if sample_weight is not None:
                 return training.weighted_loss(name, logit, y, sample_weight)
             if name == 'binary_crossentropy':
@@ -261,6 +278,11 @@ class DeepModel:
             if name in ('mse', 'mean_squared_error'):
                 return training.mse(logit, y)
             return training.mae(logit, y)
+        if isinstance(custom, GHMCLoss):
+            if sample_weight is not None:
+                raise ValueError('sample / class weights with loss GHMCLoss: it is one scalar over all elements, weighted by '
+                                 'its own histogram, so a per-row weight has no defined place in it')
+            return custom.calc(logit, y)
         if isinstance(custom, BinaryFocalLoss):
             if sample_weight is not None:
                 raise ValueError('sample / class weights with loss BinaryFocalLoss: its `call` returns one scalar already '

@@ -823,7 +823,8 @@ class VarLenColumnEmbedding(Layer):
 # PROBABILITIES, in torch ops.  A train / evaluate step does not go through `call`: DeepModel._loss hands a BinaryFocalLoss or
 # CategoricalFocalLoss (reduction 'auto') to csrc/loss.hip, which evaluates the same loss and its gradient from the logits in
 # at most two launches (dt_loss, DT_LOSS_BINARY_FOCAL / DT_LOSS_CATEGORICAL_FOCAL).  `call` serves CPU tensors, other
-# reductions, DT_AMD_DEVICE_LOSS=0 and direct use.  GHMCLoss is not a keras Loss and stays in torch ops.
+# reductions, DT_AMD_DEVICE_LOSS=0 and direct use.  GHMCLoss is not a keras Loss: its `calc(logits, targets)` runs in
+# csrc/loss_reg.hip (dt_ghmc) for float32 GPU tensors and in torch ops otherwise.
 # =============================================================================================
 K_EPSILON = 1e-7   # keras.backend.epsilon()
 
@@ -891,11 +892,15 @@ class CategoricalFocalLoss(_Loss):
 
 class GHMCLoss:
     """Gradient Harmonising Mechanism (classification) loss on logits with a momentum-smoothed histogram of
-    gradient lengths (layers.py:1084-1163)."""
+    gradient lengths (layers.py:1084-1163).  `calc` on float32 GPU tensors is one dt_ghmc call (csrc/loss_reg.hip, at most four
+    launches, capture safe); `acc_sum` is then one float32 device tensor, created at the first such call and updated in place.
+    CPU tensors, other dtypes and DT_AMD_DEVICE_LOSS=0 run the torch body below, which also leaves the gradient lengths in
+    `self.g` (the device call keeps none).  ModelConfig(loss=GHMCLoss(...)) trains the binary and multilabel tasks."""
 
     def __init__(self, bins=10, momentum=0.75):
         self.bins = bins
         self.momentum = momentum
+        self.__name__ = 'GHMCLoss'
         self.edges_left, self.edges_right = self.get_edges(self.bins)
         if momentum > 0:
             self.acc_sum = self.get_acc_sum(self.bins)
@@ -911,6 +916,10 @@ class GHMCLoss:
         return torch.zeros(bins, dtype=torch.float32)
 
     def calc(self, input, target, mask=None, is_mask=False):
+        from .. import training
+        loss = training.ghmc_from_logits(self, input, target, mask if is_mask else None)
+        if loss is not None:
+            return loss
         dev = input.device
         target = target.reshape(input.shape).to(input.dtype)
         edges_left, edges_right = self.edges_left.to(dev), self.edges_right.to(dev)

@@ -1391,6 +1391,50 @@ int64_t dt_loss_workspace_bytes(int64_t rows, int classes);
 int dt_loss(int kind, const float* z, const float* t, const float* w, int64_t rows, int classes, float gamma, float alpha,
             float* loss, float* dz, void* workspace, void* stream);
 
+/* The regression losses of Keras 3 on the device (csrc/loss_reg.hip): keras.losses.Huber / LogCosh /
+ * MeanSquaredLogarithmicError / MeanAbsolutePercentageError / Poisson on the model OUTPUT p [rows, classes] (the regression
+ * task's `task_output`, which has no activation), the target t [rows, classes] and the per-row weight w [rows] (NULL: 1), with
+ * reduction SUM_OVER_BATCH_SIZE: loss[0] = sum_b w_b mean_c f / rows, dz = w_b g / (rows classes) (dz NULL: the value only);
+ * e = p - t, eps = float32(1e-7):
+ *   DT_LOSS_HUBER     f = 0.5 e^2 where |e| <= delta, else delta |e| - 0.5 delta^2      g = e, else delta sign(e)
+ *   DT_LOSS_LOG_COSH  f = log cosh e, formed as log1p(2 sinh^2(e / 2)) below |e| = 10 and |e| - ln 2 above (Keras' e +
+ *                     softplus(-2e) - ln 2 cancels for small e)                          g = tanh e
+ *   DT_LOSS_MSLE      f = (a - b)^2, a = log1p(max(p, eps)), b = log1p(max(t, eps))      g = 2 (a - b) / (max(p, eps) + 1) where
+ *                     p >= eps, else 0
+ *   DT_LOSS_MAPE      f = 100 |e| / max(|t|, eps)                                        g = 100 sign(e) / max(|t|, eps), sign(0) = 0
+ *   DT_LOSS_POISSON   f = p - t log(p + eps)  (NaN for p + eps < 0, as in Keras)         g = 1 - t / (p + eps)
+ * Geometry, sums, determinism, workspace rules and domain are dt_loss' (at most two launches, one double per block of 2048
+ * elements in `workspace`, dt_loss_reg_workspace_bytes(rows, classes) bytes, 8-byte aligned).  delta is read by DT_LOSS_HUBER
+ * only and must be finite and > 0.  The kind codes continue dt_loss' so that a code names one loss; each entry point takes
+ * only its own.                                                                                                              */
+#define DT_LOSS_HUBER 6
+#define DT_LOSS_LOG_COSH 7
+#define DT_LOSS_MSLE 8
+#define DT_LOSS_MAPE 9
+#define DT_LOSS_POISSON 10
+int64_t dt_loss_reg_workspace_bytes(int64_t rows, int classes);
+int dt_loss_reg(int kind, const float* p, const float* t, const float* w, int64_t rows, int classes, float delta, float* loss,
+                float* dz, void* workspace, void* stream);
+
+/* GHMCLoss.calc (layers.py:1111-1163) on the device (csrc/loss_reg.hip), over the n elements of the logits z, the targets t and
+ * the optional mask (NULL: is_mask False; an element counts where mask > 0).  g = |sigmoid(z) - t| in float32 puts an element
+ * into bin b iff L_b <= g < R_b, L_b = float32(b / bins), R_b = float32((b + 1) / bins), R_{bins-1} = float32(1 + 1e-6); an
+ * element in no bin (a target of -1) or masked out has weight 0 and gradient 0.  The counts are exact integers (LDS integer
+ * atomics per block, added in block order); tot = max(n, 1) or max(#mask > 0, 1); nvalid = the number of non-empty bins; with
+ * momentum > 0 acc_sum [bins] is updated IN PLACE for the non-empty bins, acc_b = fl(fl(momentum acc_b) + fl(one_minus_momentum
+ * count_b)) (one_minus_momentum: float32(1 - momentum) as the caller rounds it), and the bin weight is w_b = fl(fl(tot /
+ * denom_b) / nvalid), denom_b = acc_b or count_b at momentum 0.
+ *   loss[0] = sum_e w_bin(e) (max(z,0) - z t + log1p(exp(-|z|))) / tot        (float64 sum in a fixed order)
+ *   dz[e]   = w_bin(e) (sigmoid(z) - t) / tot                                  (NULL: the value only; the weights carry no gradient)
+ * nvalid = 0 gives NaN, as the torch chain does.  At most four launches (counts, bins, elements, total), one when n <= 2048; the
+ * same bits on every run.  workspace: dt_ghmc_workspace_bytes(n, bins) bytes, 8-byte aligned, contents irrelevant before and
+ * after.  Domain: 1 <= n < 2^40, 1 <= bins <= DT_GHMC_MAX_BINS, 0 <= momentum < 1, acc_sum non-null when momentum > 0; anything
+ * else, a null z / t / loss / workspace or a misaligned pointer is DT_ERR_INVALID_ARG before the first launch.              */
+#define DT_GHMC_MAX_BINS 256
+int64_t dt_ghmc_workspace_bytes(int64_t n, int bins);
+int dt_ghmc(const float* z, const float* t, const float* mask, int64_t n, int bins, float momentum, float one_minus_momentum,
+            float* acc_sum, float* loss, float* dz, void* workspace, void* stream);
+
 /* ---- the tail of a DNN tower cell: Activation -> (Dropout) in one launch each way (csrc/cell.hip) ------------------------ *
  * Over x [N, C] fp32:  out = keep * act(x)  and  dx = g * keep * act'(.), keep = 0 or 1 / (1 - rate) by the counter hash
  * dt_cell_dropout_hash(seed[0], salt, row, col) >= dt_cell_dropout_threshold(rate) — recomputed by the backward from the same

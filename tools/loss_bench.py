@@ -3,9 +3,12 @@
 (training.device_loss: at most two launches, backward hands out the saved dz) and through the torch op chains that
 DT_AMD_DEVICE_LOSS=0 restores (the code of the commit before the kernels), at B = 8192 and C = 1, 10, 100 over the kinds that
 apply to each C, with and without per-row weights.  The unweighted binary cross-entropy is not a row: it keeps its own
-one-launch kernel (dt_bce_logits) on both legs.
+one-launch kernel (dt_bce_logits) on both legs.  `--set reg` times csrc/loss_reg.hip instead: Keras' regression losses
+(training.regression_loss -> dt_loss_reg) and GHMCLoss.calc (dt_ghmc) at [8192, 1] and [8192, 16], each against its torch
+chain under DT_AMD_DEVICE_LOSS=0 — for GHM-C that chain is the `calc` of the commit before the kernel.
 
     python tools/loss_bench.py --out profiles/losses.jsonl
+    python tools/loss_bench.py --set reg --out profiles/losses_reg.jsonl
     rocprofv3 --kernel-trace --output-format csv -d <dir> -o kernel -- python tools/loss_bench.py --count kernel
     rocprofv3 --kernel-trace --output-format csv -d <dir> -o torch  -- python tools/loss_bench.py --count torch
     python tools/loss_bench.py --trace kernel=<dir>/.../kernel_kernel_trace.csv --trace torch=<...> --out profiles/losses.jsonl
@@ -34,6 +37,8 @@ ROWS = [('bce', 1, True), ('mse', 1, False), ('mse', 1, True), ('mae', 1, False)
     [r for C in (10, 100) for r in (('bce', C, True), ('cce', C, False), ('cce', C, True), ('mse', C, False), ('mae', C, False),
                                     ('binary_focal', C, False), ('categorical_focal', C, False),
                                     ('categorical_focal', C, True))]
+REG_KINDS = ('huber', 'log_cosh', 'msle', 'mape', 'poisson')
+ROWS_REG = [(k, C, False) for C in (1, 16) for k in REG_KINDS + ('ghmc',)] + [('huber', 1, True), ('huber', 16, True)]
 NAMES = {'bce': 'binary_crossentropy', 'cce': 'categorical_crossentropy', 'mse': 'mse', 'mae': 'mae'}
 MARKER = 'k_sgd_dense'          # a kernel no loss path launches: dt_sgd_dense_step on a scratch tensor separates the rows
 
@@ -48,7 +53,19 @@ def make_case(kind, C, weighted, dev):
     from deeptables_amd import _lib, training
     from deeptables_amd.models.layers import BinaryFocalLoss, CategoricalFocalLoss
     g = torch.Generator().manual_seed(100 * C + len(kind))
+    if kind in REG_KINDS:
+        # predictions and targets in [0.05, 5]: inside the domain of every kind (MSLE, Poisson), off MAPE's |t| = 0
+        z = (torch.rand(BATCH, C, generator=g) * 4.95 + 0.05).to(dev).requires_grad_(True)
+        y = (torch.rand(BATCH, C, generator=g) * 4.95 + 0.05).to(dev)
+        w = (torch.rand(BATCH, generator=g) + 0.5).to(dev) if weighted else None
+        return z, lambda zz: training.regression_loss(kind, zz, y, w)
     z = torch.randn(BATCH, C, generator=g).to(dev).requires_grad_(True)
+    if kind == 'ghmc':
+        # one object per path, so that both see the same sequence of calls and carry the same acc_sum
+        from deeptables_amd.models.layers import GHMCLoss
+        y = (torch.rand(BATCH, C, generator=g) < 0.25).float().to(dev)
+        objs = {'1': GHMCLoss(bins=10, momentum=0.75), '0': GHMCLoss(bins=10, momentum=0.75)}
+        return z, lambda zz: objs[os.environ['DT_AMD_DEVICE_LOSS']].calc(zz, y)
     if kind in ('bce', 'binary_focal'):
         y = (torch.rand(BATCH, C, generator=g) < 0.25).float().to(dev)
     elif kind in ('mse', 'mae'):
@@ -80,7 +97,7 @@ def one_call(z, fn, unit):
     return loss
 
 
-def split_trace(path, calls):
+def split_trace(path, calls, rows=ROWS):
     """launches per call of every row from a --count run's kernel trace: dispatches in start order, split at the markers"""
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r['Start_Timestamp']))
     segments, names = [0], [{}]
@@ -92,10 +109,10 @@ def split_trace(path, calls):
             segments[-1] += 1
             short = r['Kernel_Name'].split('(')[0][-60:]
             names[-1][short] = names[-1].get(short, 0) + 1
-    body = segments[1:1 + len(ROWS)]             # segment 0: set-up and the warm pass
-    if len(body) != len(ROWS):
-        raise SystemExit(f'{path}: {len(segments)} segments for {len(ROWS)} rows')
-    return {row_id(*row): {'launches_per_call': n / calls, 'kernels': len(k)} for row, n, k in zip(ROWS, body, names[1:])}
+    body = segments[1:1 + len(rows)]             # segment 0: set-up and the warm pass
+    if len(body) != len(rows):
+        raise SystemExit(f'{path}: {len(segments)} segments for {len(rows)} rows')
+    return {row_id(*row): {'launches_per_call': n / calls, 'kernels': len(k)} for row, n, k in zip(rows, body, names[1:])}
 
 
 def main():
@@ -106,11 +123,13 @@ def main():
     ap.add_argument('--count', choices=['kernel', 'torch'], default=None)
     ap.add_argument('--trace', action='append', default=[], help='kernel=<kernel_trace.csv> / torch=<kernel_trace.csv>')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--set', choices=['train', 'reg'], default='train', help="reg: the rows of csrc/loss_reg.hip")
     a = ap.parse_args()
+    rows = ROWS_REG if a.set == 'reg' else ROWS
     traces = {}
     for spec in a.trace:
         path, _, file = spec.partition('=')
-        traces[path] = split_trace(file, a.calls)
+        traces[path] = split_trace(file, a.calls, rows)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit('loss_bench needs the GPU: nothing is measured without one')
@@ -119,7 +138,7 @@ def main():
     from deeptables_amd._lib import check, lib, ptr, stream_ptr
     dev = torch.device('cuda', 0)
     unit = training.unit_grad(dev)
-    cases = [(row, make_case(*row, dev)) for row in ROWS]
+    cases = [(row, make_case(*row, dev)) for row in rows]
     if a.count:
         scratch = torch.zeros(64, device=dev)
         set_path(a.count)
@@ -131,7 +150,7 @@ def main():
                 one_call(z, fn, unit)
         check(lib().dt_sgd_dense_step(ptr(scratch), ptr(scratch), 64, 0.0, stream_ptr()), 'marker')
         torch.cuda.synchronize()
-        print(json.dumps({'tool': 'loss_bench', 'count': a.count, 'rows': len(ROWS), 'calls': a.calls}))
+        print(json.dumps({'tool': 'loss_bench', 'count': a.count, 'rows': len(rows), 'calls': a.calls}))
         return
     if a.repeats * a.calls < 200:
         raise SystemExit('--repeats x --calls: at least 200 timed calls per path')
@@ -141,7 +160,8 @@ def main():
         res = {'tool': 'loss_bench', 'row': row_id(*row), 'kind': kind, 'batch': BATCH, 'classes': C, 'weighted': weighted,
                'source_hash': g.source_hash(), 'repeats': a.repeats, 'calls_per_window': a.calls, 'warmup': a.warmup,
                # the commit before the kernels has no torch path for these rows at all: they raised
-               'parent_runs_this_row': not (kind == 'mae' or (kind == 'categorical_focal' and weighted))}
+               'parent_runs_this_row': not (kind == 'mae' or (kind == 'categorical_focal' and weighted))
+               if a.set == 'train' else kind == 'ghmc'}
         value, us = {}, {'kernel': [], 'torch': []}
         for path in ('kernel', 'torch'):
             set_path(path)
