@@ -1,10 +1,10 @@
 // loss_reg.hip — the regression losses of Keras (Huber, log-cosh, MSLE, MAPE, Poisson) and the GHM-C loss of the layers
 // module on the device (gfx950, wave64): value and gradient in a few launches (include/dt_hip.h: dt_loss_reg, dt_ghmc).
 //
-// dt_loss_reg has dt_loss' element-wise geometry (loss_sum.h): a block of 256 threads takes 2048 consecutive elements of the
-// flat [rows * classes] array, thread t the elements t, t + 256, ... (coalesced); per-element math is float32, every sum is
-// float64 in a fixed order, one double per block goes into the workspace and k_loss_total adds them; one block that covers the
-// problem writes the loss itself.  No float atomics, nothing zeroed beforehand, the same bits with and without dz.
+// dt_loss_reg is k_loss_elem of loss_sum.h, dt_loss' element-wise kernel, over the five terms of this file: per-element math is
+// float32, every sum is float64 in a fixed order, one double per block goes into the workspace and k_loss_total adds them; one
+// block that covers the problem writes the loss itself.  No float atomics, nothing zeroed beforehand, the same bits with and
+// without dz.
 //
 // log-cosh: Keras writes e + softplus(-2e) - ln 2, which cancels for small e (the value is e^2 / 2, the float32 form carries
 // ~1e-7 absolute).  Here log cosh e = log1p(2 sinh^2(e / 2)) for |e| < 10 — no cancellation, relative accuracy of a few ulp at
@@ -16,7 +16,8 @@
 //                          also the count of mask > 0
 //   pass 2  k_ghmc_bins    one block: the counts added in index order (exact integers), nvalid, tot, the in-place momentum
 //                          update of acc_sum for the non-empty bins, the bin weights into the workspace
-//   pass 3  k_ghmc_elem    the bin again by the same instructions, f = BCE from the logit, the float64 partial of f w, dz
+//   pass 3  k_ghmc_elem    the bin again by the same instructions, f = BCE from the logit (BceTerm of loss_sum.h, as is
+//                          sigmoid(z) - t of both passes), the float64 partial of f w, dz
 //   pass 4  k_ghmc_total   the partials in order, divided by tot
 // and a problem that one block covers is one launch (k_ghmc_one: the same steps behind block barriers).  The only atomics are
 // integer LDS atomics, whose result does not depend on their order.
@@ -25,87 +26,41 @@
 namespace dt {
 namespace {
 
-constexpr int64_t kMaxRows = (int64_t)1 << 31;
-constexpr int64_t kMaxElems = (int64_t)1 << 40;   // rows * classes: the block count of a launch stays below 2^31
-constexpr float kEps = 1e-7f;                     // keras.backend.epsilon()
 constexpr float kLn2 = 0.6931471805599453f;
 constexpr float kLogCoshSwitch = 10.f;
 
-inline bool shape_ok(int64_t rows, int classes) {
-    return rows >= 1 && rows < kMaxRows && classes >= 1 && classes <= DT_LOSS_MAX_CLASSES && rows * classes < kMaxElems;
-}
-inline int64_t elem_blocks(int64_t n) { return (n + kElemChunk - 1) / kElemChunk; }
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// the five element-wise kinds
-// ---------------------------------------------------------------------------------------------------------------------------
-struct RegArgs {
-    const float* p;          // predictions [rows * classes]
-    const float* t;
-    const float* w;          // [rows] or null
-    float* dz;               // [rows * classes] or null
-    float* loss;             // [1]
-    double* partial;         // one double per block
-    int64_t n;
-    int classes;
-    int final;               // the launch has one block, which writes the loss itself
+// the five element-wise kinds: (f, g) of a prediction p and its target t
+template <int KIND>
+struct RegTerm : NoTail {
     float delta;             // Huber
-    float scale;             // fl(1 / (rows classes)): dz = w_b * scale * g
-    double inv;              // the same in double: loss = inv * sum
+    __device__ __forceinline__ void operator()(float p, float t, float* f, float* g) const {
+        if (KIND == DT_LOSS_HUBER) {
+            const float e = p - t, a = fabsf(e);
+            const bool quad = a <= delta;
+            *f = quad ? 0.5f * e * e : delta * a - 0.5f * delta * delta;
+            *g = quad ? e : (e > 0.f ? delta : -delta);
+        } else if (KIND == DT_LOSS_LOG_COSH) {
+            const float e = p - t, a = fabsf(e);
+            const float s = sinhf(0.5f * fminf(a, kLogCoshSwitch));
+            *f = a < kLogCoshSwitch ? log1pf(2.f * s * s) : a - kLn2;
+            *g = tanhf(e);
+        } else if (KIND == DT_LOSS_MSLE) {
+            const float pc = fmaxf(p, kEps), tc = fmaxf(t, kEps);
+            const float d = log1pf(pc) - log1pf(tc);
+            *f = d * d;
+            *g = p >= kEps ? 2.f * d / (pc + 1.f) : 0.f;
+        } else if (KIND == DT_LOSS_MAPE) {
+            const float e = p - t;
+            const float d = fmaxf(fabsf(t), kEps);
+            *f = 100.f * fabsf(e) / d;
+            *g = e > 0.f ? 100.f / d : (e < 0.f ? -100.f / d : 0.f);
+        } else {                                                           // DT_LOSS_POISSON
+            const float q = p + kEps;
+            *f = p - t * logf(q);                                          // q < 0: NaN, as in Keras
+            *g = 1.f - t / q;
+        }
+    }
 };
-
-template <int KIND>
-__device__ __forceinline__ void reg_elem(float p, float t, float delta, float* f, float* g) {
-    if (KIND == DT_LOSS_HUBER) {
-        const float e = p - t, a = fabsf(e);
-        const bool quad = a <= delta;
-        *f = quad ? 0.5f * e * e : delta * a - 0.5f * delta * delta;
-        *g = quad ? e : (e > 0.f ? delta : -delta);
-    } else if (KIND == DT_LOSS_LOG_COSH) {
-        const float e = p - t, a = fabsf(e);
-        const float s = sinhf(0.5f * fminf(a, kLogCoshSwitch));
-        *f = a < kLogCoshSwitch ? log1pf(2.f * s * s) : a - kLn2;
-        *g = tanhf(e);
-    } else if (KIND == DT_LOSS_MSLE) {
-        const float pc = fmaxf(p, kEps), tc = fmaxf(t, kEps);
-        const float d = log1pf(pc) - log1pf(tc);
-        *f = d * d;
-        *g = p >= kEps ? 2.f * d / (pc + 1.f) : 0.f;
-    } else if (KIND == DT_LOSS_MAPE) {
-        const float e = p - t;
-        const float d = fmaxf(fabsf(t), kEps);
-        *f = 100.f * fabsf(e) / d;
-        *g = e > 0.f ? 100.f / d : (e < 0.f ? -100.f / d : 0.f);
-    } else {                                                           // DT_LOSS_POISSON
-        const float q = p + kEps;
-        *f = p - t * logf(q);                                          // q < 0: NaN, as in Keras
-        *g = 1.f - t / q;
-    }
-}
-
-template <int KIND>
-__global__ __launch_bounds__(kThreads) void k_loss_reg(RegArgs a) {
-    __shared__ double sh[kWaves];
-    const int64_t lo = (int64_t)blockIdx.x * kElemChunk;
-    const int64_t rest = a.n - lo;
-    const int m = rest < kElemChunk ? (int)rest : kElemChunk;          // >= 1: the host counts ceil(n / kElemChunk) blocks
-    const int C = a.classes;
-    double s = 0;
-    for (int i = threadIdx.x; i < m; i += kThreads) {
-        const int64_t e = lo + i;                                       // < n
-        const float wb = a.w ? a.w[e / C] : 1.f;                        // e / C < rows
-        float f, g;
-        reg_elem<KIND>(a.p[e], a.t[e], a.delta, &f, &g);
-        s += (double)wb * (double)f;
-        if (a.dz) a.dz[e] = (wb * a.scale) * g;
-    }
-    s = wave_sum_f64(s);
-    const double all = waves_in_order(s, sh);
-    if (threadIdx.x == 0) {
-        if (a.final) a.loss[0] = (float)(all * a.inv);
-        else a.partial[blockIdx.x] = all;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // GHM-C
@@ -142,12 +97,13 @@ __device__ __forceinline__ void ghmc_edges(float* edge, int bins) {
         edge[b] = b < bins ? (float)((double)b / (double)bins) : (float)(1.0 + 1e-6);
 }
 
-// the bin of an element, or `bins` when it lies in none (g > 1 + 1e-6: an ignored target; a NaN) or is masked out
-__device__ __forceinline__ int ghmc_bin(float z, float t, const float* mask, int64_t e, const float* edge, int bins,
-                                        float* diff) {
-    const float d = sigmoid_f(z) - t;
-    *diff = d;
-    const float g = fabsf(d);
+// the bin of element e, or `bins` when it lies in none (g > 1 + 1e-6: an ignored target; a NaN) or is masked out; leaves the
+// element's BCE term in *f and sigmoid(z) - t in *diff
+__device__ __forceinline__ int ghmc_bin(const GhmcArgs& a, int64_t e, const float* edge, float* f, float* diff) {
+    BceTerm{}(a.z[e], a.t[e], f, diff);
+    const float* mask = a.mask;
+    const int bins = a.bins;
+    const float g = fabsf(*diff);
     if (mask && !(mask[e] > 0.f)) return bins;
     if (!(g < edge[bins])) return bins;
     int b = (int)(g * (float)bins);
@@ -160,8 +116,8 @@ __device__ __forceinline__ int ghmc_bin(float z, float t, const float* mask, int
 __device__ __forceinline__ void ghmc_count_block(const GhmcArgs& a, const float* edge, unsigned* hist, int64_t lo, int m) {
     for (int i = threadIdx.x; i < m; i += kThreads) {
         const int64_t e = lo + i;
-        float d;
-        const int b = ghmc_bin(a.z[e], a.t[e], a.mask, e, edge, a.bins, &d);
+        float f, d;
+        const int b = ghmc_bin(a, e, edge, &f, &d);
         if (b < a.bins) atomicAdd(&hist[b], 1u);
         if (a.mask && a.mask[e] > 0.f) atomicAdd(&hist[a.bins], 1u);
     }
@@ -207,10 +163,8 @@ __device__ __forceinline__ double ghmc_elem_block(const GhmcArgs& a, const float
     double s = 0;
     for (int i = threadIdx.x; i < m; i += kThreads) {
         const int64_t e = lo + i;
-        const float z = a.z[e], t = a.t[e];
-        float d;
-        const int b = ghmc_bin(z, t, a.mask, e, edge, a.bins, &d);
-        const float f = fmaxf(z, 0.f) - z * t + log1pf(expf(-fabsf(z)));
+        float f, d;
+        const int b = ghmc_bin(a, e, edge, &f, &d);
         s += (double)f * (double)w[b];
         if (a.dz) a.dz[e] = wdz[b] * d;
     }
@@ -322,32 +276,18 @@ extern "C" int dt_loss_reg(int kind, const float* p, const float* t, const float
     DT_REQUIRE(kind >= DT_LOSS_HUBER && kind <= DT_LOSS_POISSON, "dt_loss_reg: unknown kind %d", kind);
     DT_REQUIRE(shape_ok(rows, classes), "dt_loss_reg: rows %lld, classes %d outside 1 <= rows < 2^31, 1 <= classes <= %d",
                (long long)rows, classes, DT_LOSS_MAX_CLASSES);
-    DT_REQUIRE(p && t && loss, "dt_loss_reg: null predictions, targets or loss");
-    DT_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "dt_loss_reg: null or misaligned workspace");
-    DT_REQUIRE(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(w) |
-                 reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(dz)) & 3) == 0,
-               "dt_loss_reg: misaligned pointer");
+    if (int rc = check_buffers("dt_loss_reg", "predictions", p, t, loss, workspace, addr(w) | addr(dz))) return rc;
     DT_REQUIRE(kind != DT_LOSS_HUBER || (delta > 0.f && delta <= 3.0e38f), "dt_loss_reg: delta %g is not finite and > 0",
                (double)delta);
-    RegArgs a;
-    a.p = p; a.t = t; a.w = w; a.dz = dz; a.loss = loss;
-    a.partial = reinterpret_cast<double*>(workspace);
-    a.n = rows * classes; a.classes = classes; a.delta = delta;
-    a.inv = 1.0 / ((double)rows * (double)classes);
-    a.scale = (float)a.inv;
-    const int64_t blocks = elem_blocks(a.n);
-    a.final = blocks == 1;
+    const ElemArgs a = elem_args(p, t, w, rows, classes, loss, dz, workspace);
     hipStream_t st = as_stream(stream);
-    const dim3 grid((unsigned)blocks), block(kThreads);
     switch (kind) {
-        case DT_LOSS_HUBER: hipLaunchKernelGGL(k_loss_reg<DT_LOSS_HUBER>, grid, block, 0, st, a); break;
-        case DT_LOSS_LOG_COSH: hipLaunchKernelGGL(k_loss_reg<DT_LOSS_LOG_COSH>, grid, block, 0, st, a); break;
-        case DT_LOSS_MSLE: hipLaunchKernelGGL(k_loss_reg<DT_LOSS_MSLE>, grid, block, 0, st, a); break;
-        case DT_LOSS_MAPE: hipLaunchKernelGGL(k_loss_reg<DT_LOSS_MAPE>, grid, block, 0, st, a); break;
-        default: hipLaunchKernelGGL(k_loss_reg<DT_LOSS_POISSON>, grid, block, 0, st, a); break;
+        case DT_LOSS_HUBER: launch_elem(a, RegTerm<DT_LOSS_HUBER>{{}, delta}, st); break;
+        case DT_LOSS_LOG_COSH: launch_elem(a, RegTerm<DT_LOSS_LOG_COSH>{{}, delta}, st); break;
+        case DT_LOSS_MSLE: launch_elem(a, RegTerm<DT_LOSS_MSLE>{{}, delta}, st); break;
+        case DT_LOSS_MAPE: launch_elem(a, RegTerm<DT_LOSS_MAPE>{{}, delta}, st); break;
+        default: launch_elem(a, RegTerm<DT_LOSS_POISSON>{{}, delta}, st); break;
     }
-    if (blocks > 1)
-        hipLaunchKernelGGL(k_loss_total, dim3(1), dim3(kThreads), 0, st, (const double*)a.partial, blocks, a.inv, loss);
     return launch_status("dt_loss_reg");
 }
 
@@ -365,11 +305,7 @@ extern "C" int dt_ghmc(const float* z, const float* t, const float* mask, int64_
                        float one_minus_momentum, float* acc_sum, float* loss, float* dz, void* workspace, void* stream) {
     DT_REQUIRE(ghmc_shape_ok(n, bins), "dt_ghmc: n %lld, bins %d outside 1 <= n < 2^40, 1 <= bins <= %d", (long long)n, bins,
                kMaxBins);
-    DT_REQUIRE(z && t && loss, "dt_ghmc: null logits, targets or loss");
-    DT_REQUIRE(workspace && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "dt_ghmc: null or misaligned workspace");
-    DT_REQUIRE(((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(mask) |
-                 reinterpret_cast<uintptr_t>(acc_sum) | reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(dz)) &
-                3) == 0, "dt_ghmc: misaligned pointer");
+    if (int rc = check_buffers("dt_ghmc", "logits", z, t, loss, workspace, addr(mask) | addr(acc_sum) | addr(dz))) return rc;
     DT_REQUIRE(momentum >= 0.f && momentum < 1.f, "dt_ghmc: momentum %g outside [0, 1)", (double)momentum);
     DT_REQUIRE(momentum == 0.f || (one_minus_momentum > 0.f && one_minus_momentum <= 1.f),
                "dt_ghmc: 1 - momentum %g outside (0, 1]", (double)one_minus_momentum);

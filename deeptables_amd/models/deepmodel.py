@@ -15,7 +15,7 @@ import torch
 from . import deepnets
 from .layers import BinaryFocalLoss, CategoricalFocalLoss, GHMCLoss, MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
 from .. import functional as F
-from .. import _lib, training
+from .. import _lib, losses, training
 from ..functional import Dense, Concatenate, Flatten, Input, Add, BatchNormalization, Dropout, Model
 from ..utils import consts
 
@@ -142,7 +142,7 @@ class DeepModel:
             loss_name = loss
         elif isinstance(loss, dict):
             # the serialised form, as `optimizer=` takes it: {'class_name': 'Huber', 'config': {'delta': 2.0}}
-            loss_name, params = training.resolve_loss(loss)
+            loss_name, params = losses.resolve_loss(loss)
             self.loss_delta = params.get('delta', 1.0)
         elif isinstance(loss, GHMCLoss):
             if task not in (consts.TASK_BINARY, consts.TASK_MULTILABEL):
@@ -255,7 +255,7 @@ class DeepModel:
     # ------------------------------------------------------------------------------------------
     def _loss(self, logit, y, sample_weight=None):
         """The data loss of a batch from the LOGITS, with Keras' per-row weights (sample_weight x class_weight).  The named
-        losses and the layers module's focal losses (reduction 'auto') run in csrc/loss.hip on the device (training.py);
+        losses and the layers module's focal losses (reduction 'auto') run in csrc/loss.hip on the device (losses.py);
         any other callable, and a focal loss with another reduction, gets the activated probabilities.
         Keras' regression losses (huber, log_cosh, msle, mape, poisson) apply to the model's OUTPUT: for the regression task
         that is the logit and csrc/loss_reg.hip serves it; for any other task they are evaluated in torch ops on
@@ -263,21 +263,9 @@ class DeepModel:
         name = self.loss_name
         custom = getattr(self, '_custom_loss', None)
         if custom is None:
-            if name not in training.LOSS_NAMES:
-                raise ValueError(f'Unsupported loss: {name}')
-            if name in training.REG_LOSS_KINDS:
-                linear = getattr(self, 'output_activation', None) is None
-                return training.regression_loss(name, logit if linear else self._activate(logit), y, sample_weight,
-                                                getattr(self, 'loss_delta', 1.0), device=linear)
-            if sample_weight is not None:
-                return training.weighted_loss(name, logit, y, sample_weight)
-            if name == 'binary_crossentropy':
-                return training.bce_from_logits(logit, y)
-            if name == 'categorical_crossentropy':
-                return training.categorical_ce_from_logits(logit, y)
-            if name in ('mse', 'mean_squared_error'):
-                return training.mse(logit, y)
-            return training.mae(logit, y)
+            from_logit = getattr(self, 'output_activation', None) is None or name not in losses.REG_LOSS_KINDS
+            return losses.named_loss(name, logit if from_logit else self._activate(logit), y, sample_weight,
+                                     getattr(self, 'loss_delta', 1.0), device=from_logit)
         if isinstance(custom, GHMCLoss):
             if sample_weight is not None:
                 raise ValueError('sample / class weights with loss GHMCLoss: it is one scalar over all elements, weighted by '
@@ -288,9 +276,9 @@ class DeepModel:
                 raise ValueError('sample / class weights with loss BinaryFocalLoss: its `call` returns one scalar already '
                                  'averaged over the batch, so a per-row weight has no defined place in it')
             if custom.reduction == 'auto':
-                return training.focal_from_logits(_lib.DT_LOSS_BINARY_FOCAL, custom, logit, y, None, self._activate)
+                return losses.focal_from_logits(_lib.DT_LOSS_BINARY_FOCAL, custom, logit, y, None, self._activate)
         elif isinstance(custom, CategoricalFocalLoss) and custom.reduction == 'auto':
-            return training.focal_from_logits(_lib.DT_LOSS_CATEGORICAL_FOCAL, custom, logit, y, sample_weight, self._activate)
+            return losses.focal_from_logits(_lib.DT_LOSS_CATEGORICAL_FOCAL, custom, logit, y, sample_weight, self._activate)
         if sample_weight is not None:
             raise ValueError(f'sample / class weights with loss {name!r}')
         return custom(y, self._activate(logit))
@@ -366,7 +354,7 @@ class DeepModel:
         if penalty is not None:
             loss = loss + penalty
         if loss.dim() == 0 and loss.dtype == torch.float32:
-            loss.backward(training.unit_grad(loss.device))      # no ones-fill launch (and the BCE skips the multiply)
+            loss.backward(losses.unit_grad(loss.device))      # no ones-fill launch (and the BCE skips the multiply)
         else:
             loss.backward()
         return loss.detach(), logit.detach()

@@ -12,9 +12,10 @@ import os
 import torch
 from torch import nn
 
-from .. import ops, regularizers
+from .. import losses, ops, regularizers
 from ..functional import (Layer, Dense, Dropout, BatchNormalization, Activation, Concatenate, Flatten,  # noqa: F401
                           Input, Lambda, Add, SpatialDropout1D, ReduceSum, CellSeed, initialize, get_activation)
+from ..losses import K_EPSILON   # keras.backend.epsilon()
 from ..utils import consts  # noqa: F401
 
 
@@ -826,9 +827,6 @@ class VarLenColumnEmbedding(Layer):
 # reductions, DT_AMD_DEVICE_LOSS=0 and direct use.  GHMCLoss is not a keras Loss: its `calc(logits, targets)` runs in
 # csrc/loss_reg.hip (dt_ghmc) for float32 GPU tensors and in torch ops otherwise.
 # =============================================================================================
-K_EPSILON = 1e-7   # keras.backend.epsilon()
-
-
 class _Loss:
     """keras.losses.Loss protocol: __call__(y_true, y_pred) = reduction(call(...)); AUTO = mean over the batch."""
 
@@ -916,8 +914,7 @@ class GHMCLoss:
         return torch.zeros(bins, dtype=torch.float32)
 
     def calc(self, input, target, mask=None, is_mask=False):
-        from .. import training
-        loss = training.ghmc_from_logits(self, input, target, mask if is_mask else None)
+        loss = losses.ghmc_from_logits(self, input, target, mask if is_mask else None)
         if loss is not None:
             return loss
         dev = input.device

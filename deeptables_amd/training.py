@@ -24,369 +24,6 @@ if DEFAULT_STEPS_PER_EXECUTION != 'auto':
 
 
 # ---------------------------------------------------------------------------------------------
-# losses (keras.losses.* selected by DeepModel.__compile_model, deepmodel.py:324-338)
-# ---------------------------------------------------------------------------------------------
-_UNIT_GRAD = {}
-
-
-def unit_grad(device):
-    """the constant 1.0 `loss.backward()` would allocate and fill at every step: a cached 0-dim tensor per device.  A loss
-    function that sees it as its incoming gradient (same storage) skips the multiplication by it."""
-    key = str(device)
-    if key not in _UNIT_GRAD:
-        _UNIT_GRAD[key] = torch.ones((), dtype=torch.float32, device=device)
-    return _UNIT_GRAD[key]
-
-
-def _is_unit_grad(g):
-    u = _UNIT_GRAD.get(str(g.device))
-    return u is not None and g.dim() == 0 and g.data_ptr() == u.data_ptr()
-
-
-class _BceFromLogits(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, y):
-        z, y = z.contiguous(), y.contiguous()
-        loss = torch.empty(1, dtype=torch.float32, device=z.device)
-        dz = torch.empty_like(z)
-        check(lib().dt_bce_logits(ptr(z), ptr(y), z.numel(), ptr(loss), ptr(dz), stream_ptr()), 'dt_bce_logits')
-        ctx.save_for_backward(dz)
-        return loss[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return (dz if _is_unit_grad(g) else dz * g), None
-
-
-def bce_from_logits(logit, y):
-    """BinaryCrossentropy on a sigmoid output evaluated from the logits (stable form); one HIP launch for the
-    loss and its gradient on the GPU."""
-    z = logit.reshape(y.shape[0], -1)
-    y = y.reshape(z.shape).to(z.dtype)
-    if z.is_cuda and z.dtype == torch.float32:
-        return _BceFromLogits.apply(z, y)
-    return (torch.clamp(z, min=0) - z * y + torch.log1p(torch.exp(-z.abs()))).mean()
-
-
-# ---------------------------------------------------------------------------------------------
-# the losses on the device (csrc/loss.hip): value and gradient from the logits in at most two launches
-# ---------------------------------------------------------------------------------------------
-LOSS_KINDS = {'binary_crossentropy': _lib.DT_LOSS_BCE, 'categorical_crossentropy': _lib.DT_LOSS_CCE,
-              'mse': _lib.DT_LOSS_MSE, 'mean_squared_error': _lib.DT_LOSS_MSE,
-              'mae': _lib.DT_LOSS_MAE, 'mean_absolute_error': _lib.DT_LOSS_MAE}
-# Keras' regression losses (csrc/loss_reg.hip, dt_loss_reg): they see the model's OUTPUT, which is the logit for the regression
-# task only — any other task evaluates the torch restatement on the activated output
-REG_LOSS_KINDS = {'huber': _lib.DT_LOSS_HUBER, 'log_cosh': _lib.DT_LOSS_LOG_COSH, 'logcosh': _lib.DT_LOSS_LOG_COSH,
-                  'msle': _lib.DT_LOSS_MSLE, 'mean_squared_logarithmic_error': _lib.DT_LOSS_MSLE,
-                  'mape': _lib.DT_LOSS_MAPE, 'mean_absolute_percentage_error': _lib.DT_LOSS_MAPE,
-                  'poisson': _lib.DT_LOSS_POISSON}
-LOSS_KINDS.update(REG_LOSS_KINDS)
-LOSS_NAMES = tuple(LOSS_KINDS)            # the loss strings DeepModel compiles
-_CATEGORICAL_KINDS = (_lib.DT_LOSS_CCE, _lib.DT_LOSS_CATEGORICAL_FOCAL)
-
-
-def _on_device(t):
-    return torch.is_tensor(t) and t.is_cuda
-
-
-def device_loss_enabled():
-    """DT_AMD_DEVICE_LOSS=0 restores the torch op chains everywhere (the comparison leg of the tests and of
-    tools/loss_bench.py)"""
-    return os.environ.get('DT_AMD_DEVICE_LOSS', '1') != '0'
-
-
-class _DeviceLoss(torch.autograd.Function):
-    """dt_loss: loss and d loss / d logits together in the forward; dz is written only when the logits ask for a gradient
-    (evaluate runs under no_grad: value only).  backward hands out the saved dz itself when the incoming gradient is
-    `unit_grad`, else one multiply."""
-
-    @staticmethod
-    def forward(ctx, z, t, w, kind, gamma, alpha, want_dz):
-        z, t = z.contiguous(), t.contiguous()
-        w = None if w is None else w.contiguous()
-        rows, classes = z.shape
-        h = lib()
-        need = h.dt_loss_workspace_bytes(rows, classes)
-        if need < 0:
-            check(int(need), 'dt_loss_workspace_bytes')
-        # one allocation: the loss word (8 bytes, so that the partials behind it are 8-byte aligned), then the workspace
-        buf = torch.empty(2 + int(need) // 4, dtype=torch.float32, device=z.device)
-        dz = torch.empty_like(z) if want_dz else None
-        check(h.dt_loss(int(kind), ptr(z), ptr(t), ptr(w), rows, classes, float(gamma), float(alpha), ptr(buf), ptr(dz),
-                        ctypes.c_void_p(buf.data_ptr() + 8), stream_ptr()), 'dt_loss')
-        if dz is not None:
-            ctx.save_for_backward(dz)
-        return buf[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return (dz if _is_unit_grad(g) else dz * g), None, None, None, None, None, None
-
-
-def device_loss_supported(kind, z, t, w=None):
-    """True when `device_loss` serves this call: DT_AMD_DEVICE_LOSS not '0', float32 tensors on the GPU, logits [rows, classes]
-    inside dt_loss' domain with as many targets, one weight per row — and none for the binary focal loss"""
-    if not device_loss_enabled():
-        return False
-    if not (_on_device(z) and z.dtype == torch.float32 and z.dim() == 2 and _on_device(t) and t.dtype == torch.float32 and
-            t.shape == z.shape):
-        return False
-    rows, classes = z.shape
-    if not (1 <= rows < (1 << 31) and 1 <= classes <= _lib.DT_LOSS_MAX_CLASSES and rows * classes < (1 << 40)):
-        return False
-    if kind in _CATEGORICAL_KINDS and classes < 2:
-        return False
-    if w is not None:
-        if kind == _lib.DT_LOSS_BINARY_FOCAL:
-            return False
-        if not (_on_device(w) and w.dtype == torch.float32 and w.numel() == rows):
-            return False
-    return True
-
-
-def device_loss(kind, logit, y, w=None, gamma=0.0, alpha=0.0):
-    """The loss `kind` (DT_LOSS_*) of logits [B, ...] against targets y with per-row weights w [B] (None: 1) through
-    csrc/loss.hip, or None when the call is outside `device_loss_supported` — the caller then takes its torch path."""
-    B = logit.shape[0]
-    if B == 0 or y.numel() != logit.numel():
-        return None
-    z = logit.reshape(B, -1)
-    t = y.reshape(z.shape)
-    t = t if t.dtype == z.dtype else t.to(z.dtype)
-    w = None if w is None else w.reshape(-1)
-    if not device_loss_supported(kind, z, t, w):
-        return None
-    return _DeviceLoss.apply(z, t, w, kind, gamma, alpha, torch.is_grad_enabled() and z.requires_grad)
-
-
-K_EPSILON = 1e-7            # keras.backend.epsilon()
-
-
-def _per_row_loss(loss_name, z, t, delta=1.0):
-    """l_b [B] of a named loss in torch ops, in the dtype of z: the definition the kernels are held to (Keras 3's own forms)"""
-    kind = REG_LOSS_KINDS.get(loss_name)
-    if kind == _lib.DT_LOSS_HUBER:
-        e = z - t
-        a = e.abs()
-        return torch.where(a <= delta, 0.5 * e * e, delta * a - 0.5 * delta * delta).mean(-1)
-    if kind == _lib.DT_LOSS_LOG_COSH:
-        e = z - t
-        return (e + torch.nn.functional.softplus(-2.0 * e) - math.log(2.0)).mean(-1)
-    if kind == _lib.DT_LOSS_MSLE:
-        d = torch.log(torch.clamp(z, min=K_EPSILON) + 1.0) - torch.log(torch.clamp(t, min=K_EPSILON) + 1.0)
-        return (d * d).mean(-1)
-    if kind == _lib.DT_LOSS_MAPE:
-        return 100.0 * ((t - z) / torch.clamp(t.abs(), min=K_EPSILON)).abs().mean(-1)
-    if kind == _lib.DT_LOSS_POISSON:
-        return (z - t * torch.log(z + K_EPSILON)).mean(-1)
-    if loss_name == 'binary_crossentropy':
-        return (torch.clamp(z, min=0) - z * t + torch.log1p(torch.exp(-z.abs()))).mean(-1)
-    if loss_name == 'categorical_crossentropy':
-        return -(torch.log_softmax(z, dim=-1) * t).sum(-1)
-    if loss_name in ('mse', 'mean_squared_error'):
-        return ((z - t) ** 2).mean(-1)
-    if loss_name in ('mae', 'mean_absolute_error'):
-        return (z - t).abs().mean(-1)
-    raise ValueError(f'sample / class weights with loss {loss_name!r}')
-
-
-class _DeviceRegLoss(torch.autograd.Function):
-    """dt_loss_reg, in the manner of _DeviceLoss: loss and d loss / d output together in the forward, dz only when the output
-    asks for a gradient, the saved dz itself handed out for `unit_grad`."""
-
-    @staticmethod
-    def forward(ctx, p, t, w, kind, delta, want_dz):
-        p, t = p.contiguous(), t.contiguous()
-        w = None if w is None else w.contiguous()
-        rows, classes = p.shape
-        h = lib()
-        need = h.dt_loss_reg_workspace_bytes(rows, classes)
-        if need < 0:
-            check(int(need), 'dt_loss_reg_workspace_bytes')
-        buf = torch.empty(2 + int(need) // 4, dtype=torch.float32, device=p.device)     # the loss word, then the workspace
-        dz = torch.empty_like(p) if want_dz else None
-        check(h.dt_loss_reg(int(kind), ptr(p), ptr(t), ptr(w), rows, classes, float(delta), ptr(buf), ptr(dz),
-                            ctypes.c_void_p(buf.data_ptr() + 8), stream_ptr()), 'dt_loss_reg')
-        if dz is not None:
-            ctx.save_for_backward(dz)
-        return buf[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return (dz if _is_unit_grad(g) else dz * g), None, None, None, None, None
-
-
-def check_huber_delta(delta):
-    delta = float(delta)
-    if not (math.isfinite(delta) and delta > 0):
-        raise ValueError(f'Huber: delta must be finite and > 0, got {delta!r}')
-    return delta
-
-
-def regression_loss(loss_name, pred, y, w=None, delta=1.0, device=True):
-    """keras.losses.Huber / LogCosh / MeanSquaredLogarithmicError / MeanAbsolutePercentageError / Poisson of the model output
-    `pred` [B, ...] against y with per-row weights w [B] (None: 1), reduction SUM_OVER_BATCH_SIZE.  One dt_loss_reg call
-    (csrc/loss_reg.hip) for float32 GPU tensors; `_per_row_loss` in torch ops for CPU tensors, other dtypes, DT_AMD_DEVICE_LOSS=0
-    and device=False (an output that is an activation of the logits: autograd carries the gradient through it)."""
-    kind = REG_LOSS_KINDS[loss_name]
-    B = y.shape[0]
-    z = pred.reshape(B, -1)
-    if y.numel() != z.numel():
-        raise ValueError(f'loss {loss_name!r}: targets of shape {tuple(y.shape)} for an output of shape {tuple(pred.shape)}')
-    t = y.reshape(z.shape)
-    t = t if t.dtype == z.dtype else t.to(z.dtype)
-    wv = None if w is None else w.reshape(-1).to(z.dtype)
-    if kind == _lib.DT_LOSS_HUBER:
-        delta = check_huber_delta(delta)
-    if device and B > 0 and _on_device(z) and device_loss_supported(kind, z, t, wv):
-        return _DeviceRegLoss.apply(z, t, wv, kind, delta, torch.is_grad_enabled() and z.requires_grad)
-    per = _per_row_loss(loss_name, z, t, delta)
-    return (per if wv is None else per * wv).sum() / B
-
-
-# the serialised form of a loss, {'class_name': ..., 'config': {...}}, as `optimizer=` takes it: Keras class name -> loss string
-LOSS_CLASSES = {'BinaryCrossentropy': 'binary_crossentropy', 'CategoricalCrossentropy': 'categorical_crossentropy',
-                'MeanSquaredError': 'mean_squared_error', 'MeanAbsoluteError': 'mean_absolute_error',
-                'Huber': 'huber', 'LogCosh': 'log_cosh', 'MeanSquaredLogarithmicError': 'mean_squared_logarithmic_error',
-                'MeanAbsolutePercentageError': 'mean_absolute_percentage_error', 'Poisson': 'poisson'}
-_LOSS_REDUCTIONS = ('auto', 'sum_over_batch_size')
-
-
-def resolve_loss(spec):
-    """{'class_name': 'Huber', 'config': {'delta': 2.0}} -> ('huber', {'delta': 2.0}).  Accepted config keys: `delta` (Huber
-    only), `name`, `reduction` in ('auto', 'sum_over_batch_size'), and `from_logits` / `label_smoothing` at their defaults —
-    the steps evaluate one reduction and no smoothing, so anything else raises instead of being ignored."""
-    cls = spec.get('class_name')
-    if cls not in LOSS_CLASSES:
-        raise ValueError(f'Unsupported loss: {cls!r} (class names: {sorted(LOSS_CLASSES)})')
-    config = dict(spec.get('config') or {})
-    config.pop('name', None)
-    reduction = config.pop('reduction', 'auto')
-    if reduction not in _LOSS_REDUCTIONS:
-        raise ValueError(f'loss {cls!r}: reduction {reduction!r} is not supported (accepted: {_LOSS_REDUCTIONS})')
-    if config.pop('from_logits', False) not in (False, None):
-        raise ValueError(f'loss {cls!r}: from_logits=True is not supported (the model output carries the task activation)')
-    if config.pop('label_smoothing', 0.0) not in (0, 0.0, None):
-        raise ValueError(f'loss {cls!r}: label_smoothing is not supported')
-    params = {}
-    if cls == 'Huber' and 'delta' in config:
-        params['delta'] = check_huber_delta(config.pop('delta'))
-    if config:
-        raise ValueError(f'loss {cls!r}: unknown config keys {sorted(config)} (accepted: delta (Huber), name, reduction)')
-    return LOSS_CLASSES[cls], params
-
-
-def weighted_loss(loss_name, logit, y, w, delta=1.0):
-    """Keras `sample_weight` / `class_weight` semantics (keras Model.fit -> compile loss with reduction
-    SUM_OVER_BATCH_SIZE): per-sample loss times its weight, summed, divided by the batch size.  On the device one dt_loss
-    call (csrc/loss.hip) — dt_loss_reg for the regression losses; element-wise torch on [B, outputs] for CPU tensors and
-    with DT_AMD_DEVICE_LOSS=0."""
-    if loss_name not in LOSS_KINDS:
-        raise ValueError(f'sample / class weights with loss {loss_name!r}')
-    if loss_name in REG_LOSS_KINDS:
-        return regression_loss(loss_name, logit, y, w, delta)
-    B = y.shape[0]
-    if _on_device(logit):
-        loss = device_loss(LOSS_KINDS[loss_name], logit, y, w.to(logit.dtype))
-        if loss is not None:
-            return loss
-    z = logit.reshape(B, -1)
-    t = y.reshape(B, -1).to(z.dtype)
-    return (_per_row_loss(loss_name, z, t) * w.reshape(B).to(z.dtype)).sum() / B
-
-
-def categorical_ce_from_logits(logit, y_onehot):
-    if _on_device(logit):
-        loss = device_loss(_lib.DT_LOSS_CCE, logit, y_onehot)
-        if loss is not None:
-            return loss
-    return -(torch.log_softmax(logit, dim=-1) * y_onehot).sum(-1).mean()
-
-
-def mse(pred, y):
-    if _on_device(pred):
-        loss = device_loss(_lib.DT_LOSS_MSE, pred, y)
-        if loss is not None:
-            return loss
-    return ((pred.reshape(y.shape[0], -1) - y.reshape(y.shape[0], -1).to(pred.dtype)) ** 2).mean()
-
-
-def mae(pred, y):
-    """keras.losses.MeanAbsoluteError ('mae' / 'mean_absolute_error')"""
-    if _on_device(pred):
-        loss = device_loss(_lib.DT_LOSS_MAE, pred, y)
-        if loss is not None:
-            return loss
-    return (pred.reshape(y.shape[0], -1) - y.reshape(y.shape[0], -1).to(pred.dtype)).abs().mean()
-
-
-def focal_from_logits(kind, loss_obj, logit, y, w, activate):
-    """layers.BinaryFocalLoss / CategoricalFocalLoss (reduction 'auto') of a step: from the logits through dt_loss on the
-    device, carrying the object's gamma and alpha; otherwise the object's own `call` on `activate(logit)` — for the
-    categorical loss, whose `call` returns one value per row, with Keras' per-row weights."""
-    if _on_device(logit):
-        loss = device_loss(kind, logit, y, w, loss_obj.gamma, loss_obj.alpha)
-        if loss is not None:
-            return loss
-    if w is None:
-        return loss_obj(y, activate(logit))
-    B = y.shape[0]
-    prob = activate(logit)
-    return (loss_obj.call(y, prob).reshape(B) * w.reshape(B).to(prob.dtype)).sum() / B
-
-
-class _DeviceGhmc(torch.autograd.Function):
-    """dt_ghmc: GHMCLoss.calc's value, gradient and in-place `acc_sum` update in at most four launches (csrc/loss_reg.hip)"""
-
-    @staticmethod
-    def forward(ctx, z, t, mask, acc, bins, momentum, want_dz):
-        z, t = z.contiguous(), t.contiguous()
-        n = z.numel()
-        h = lib()
-        need = h.dt_ghmc_workspace_bytes(n, int(bins))
-        if need < 0:
-            check(int(need), 'dt_ghmc_workspace_bytes')
-        buf = torch.empty(2 + int(need) // 4, dtype=torch.float32, device=z.device)     # the loss word, then the workspace
-        dz = torch.empty_like(z) if want_dz else None
-        # float32(1 - momentum) rounded from the double, as torch rounds the scalar of `(1 - mmt) * num_in_bin`
-        check(h.dt_ghmc(ptr(z), ptr(t), ptr(mask), n, int(bins), float(momentum), 1.0 - float(momentum), ptr(acc), ptr(buf),
-                        ptr(dz), ctypes.c_void_p(buf.data_ptr() + 8), stream_ptr()), 'dt_ghmc')
-        if dz is not None:
-            ctx.save_for_backward(dz)
-        return buf[0]
-
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return (dz if _is_unit_grad(g) else dz * g), None, None, None, None, None, None
-
-
-def ghmc_from_logits(loss_obj, logit, target, mask=None):
-    """layers.GHMCLoss.calc on the device, or None when the call is outside dt_ghmc's domain (the caller then runs its torch
-    body): float32 GPU logits with as many targets (and mask entries), 1 <= bins <= DT_GHMC_MAX_BINS, 0 <= momentum < 1,
-    DT_AMD_DEVICE_LOSS not '0'.  `loss_obj.acc_sum` becomes ONE float32 tensor on the logits' device at the first call and is
-    updated in place from then on — by every replay of a captured graph too."""
-    if not (device_loss_enabled() and _on_device(logit) and logit.dtype == torch.float32 and torch.is_tensor(target)):
-        return None
-    n, bins, mmt = logit.numel(), int(loss_obj.bins), float(loss_obj.momentum)
-    if not (1 <= n < (1 << 40) and target.numel() == n and 1 <= bins <= _lib.DT_GHMC_MAX_BINS and 0 <= mmt < 1):
-        return None
-    if mask is not None and not (torch.is_tensor(mask) and mask.numel() == n):
-        return None
-    t = target.reshape(logit.shape).to(device=logit.device, dtype=torch.float32)
-    m = None if mask is None else mask.reshape(logit.shape).to(device=logit.device, dtype=torch.float32).contiguous()
-    acc = None
-    if mmt > 0:
-        acc = loss_obj.acc_sum
-        if not (acc.is_cuda and acc.device == logit.device and acc.dtype == torch.float32 and acc.is_contiguous()):
-            acc = loss_obj.acc_sum = acc.detach().to(device=logit.device, dtype=torch.float32).contiguous()
-    return _DeviceGhmc.apply(logit, t, m, acc, bins, mmt, torch.is_grad_enabled() and logit.requires_grad)
-
-
-# ---------------------------------------------------------------------------------------------
 # optimizers with slots and a device-resident step state: Adam, Adagrad, RMSprop
 # ---------------------------------------------------------------------------------------------
 DT_ADAM_STATE_WORDS = 272 // 4        # DT_ADAM_STATE_BYTES (include/dt_hip.h) in int32 words

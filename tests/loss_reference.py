@@ -1,7 +1,7 @@
 # -*- coding:utf-8 -*-
 """The losses of a train step restated from the LOGITS in torch, in whatever precision the inputs carry (float64: the
 reference; float32 on the CPU: the fp32 class of yardstick B) — the contract of csrc/loss.hip (dt_loss) and of
-training.device_loss.  Gradients come from autograd on these forms, never from a second derivation.
+losses.device_loss.  Gradients come from autograd on these forms, never from a second derivation.
 
     total = sum_b w_b l_b / B             (Keras SUM_OVER_BATCH_SIZE; w_b = sample_weight x class_weight, 1 without weights)
 

@@ -354,14 +354,14 @@ def test_row_weights_of_the_fused_steps_are_validated():
 
 
 def test_unit_gradient_is_recognised_by_storage_not_by_value():
-    """training.unit_grad: the cached 1.0 handed to loss.backward(); a loss function skips the multiplication only for THAT
+    """losses.unit_grad: the cached 1.0 handed to loss.backward(); a loss function skips the multiplication only for THAT
     tensor — another tensor holding 1.0 (or a scaled loss's gradient) is multiplied as usual"""
-    from deeptables_amd import training
-    u = training.unit_grad(torch.device('cpu'))
-    assert u.dim() == 0 and float(u) == 1.0 and training.unit_grad(torch.device('cpu')) is u
-    assert training._is_unit_grad(u)
-    assert not training._is_unit_grad(torch.ones(()))
-    assert not training._is_unit_grad(torch.ones(1))
+    from deeptables_amd import losses
+    u = losses.unit_grad(torch.device('cpu'))
+    assert u.dim() == 0 and float(u) == 1.0 and losses.unit_grad(torch.device('cpu')) is u
+    assert losses._is_unit_grad(u)
+    assert not losses._is_unit_grad(torch.ones(()))
+    assert not losses._is_unit_grad(torch.ones(1))
 
 
 def test_header_constants_equal_the_binding_s():

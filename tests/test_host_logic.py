@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """CPU: host-side logic added in round 2 that needs no kernel — the per-lookup view of a segmented sparse gradient
-(ops.SparseRowGrad.expanded), Keras' sample / class weighting of the loss (training.weighted_loss), the feed carrying
+(ops.SparseRowGrad.expanded), Keras' sample / class weighting of the loss (losses.named_loss), the feed carrying
 per-row weights through a shuffle (training.TableBatches), balanced class weights (DeepTable.get_class_weight)."""
 import os
 
@@ -32,24 +32,24 @@ def test_segmented_sparse_grad_expands_to_one_entry_per_lookup():
 
 
 def test_weighted_loss_follows_keras_sample_weight_semantics():
-    from deeptables_amd import training
+    from deeptables_amd import losses
     g = torch.Generator().manual_seed(0)
     z = torch.randn(17, 1, generator=g, dtype=torch.float64)
     y = (torch.rand(17, 1, generator=g) < 0.4).double()
     w = torch.rand(17, generator=g, dtype=torch.float64) * 3
     p = torch.sigmoid(z)
     per = -(y * torch.log(p) + (1 - y) * torch.log(1 - p)).reshape(-1)
-    assert abs(float(training.weighted_loss('binary_crossentropy', z, y, w)) - float((per * w).sum() / 17)) < 1e-12
+    assert abs(float(losses.named_loss('binary_crossentropy', z, y, w)) - float((per * w).sum() / 17)) < 1e-12
     # all-ones weights = the unweighted mean
-    assert abs(float(training.weighted_loss('binary_crossentropy', z, y, torch.ones(17, dtype=torch.float64))) -
-               float(training.bce_from_logits(z, y))) < 1e-12
+    assert abs(float(losses.named_loss('binary_crossentropy', z, y, torch.ones(17, dtype=torch.float64))) -
+               float(losses.named_loss('binary_crossentropy', z, y))) < 1e-12
     zc = torch.randn(9, 4, generator=g, dtype=torch.float64)
     yc = torch.eye(4, dtype=torch.float64)[torch.randint(0, 4, (9,), generator=g)]
     wc = torch.rand(9, generator=g, dtype=torch.float64)
     per_c = -(torch.log_softmax(zc, -1) * yc).sum(-1)
-    assert abs(float(training.weighted_loss('categorical_crossentropy', zc, yc, wc)) - float((per_c * wc).sum() / 9)) < 1e-12
+    assert abs(float(losses.named_loss('categorical_crossentropy', zc, yc, wc)) - float((per_c * wc).sum() / 9)) < 1e-12
     yr = torch.randn(17, 1, generator=g, dtype=torch.float64)
-    assert abs(float(training.weighted_loss('mse', z, yr, w)) - float((((z - yr) ** 2).reshape(-1) * w).sum() / 17)) < 1e-12
+    assert abs(float(losses.named_loss('mse', z, yr, w)) - float((((z - yr) ** 2).reshape(-1) * w).sum() / 17)) < 1e-12
 
 
 def test_feed_carries_row_weights_through_the_shuffle():

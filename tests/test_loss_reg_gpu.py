@@ -311,13 +311,13 @@ def _capture(dev, static_z, step):
 
 
 def test_huber_loss_and_backward_replay_from_a_captured_graph(dev):
-    from deeptables_amd import training
+    from deeptables_amd import losses
     za, t = _draw('huber', 2049, 1, 9)
     zb, _ = _draw('huber', 2049, 1, 10)
-    td, unit = t.to(dev), training.unit_grad(dev)
+    td, unit = t.to(dev), losses.unit_grad(dev)
 
     def step(zz):
-        loss = training.regression_loss('huber', zz, td, None, 0.5)
+        loss = losses.named_loss('huber', zz, td, None, 0.5)
         assert type(loss.grad_fn).__name__ == '_DeviceRegLossBackward'
         (g,) = torch.autograd.grad(loss, zz, unit)
         return loss, g
@@ -337,11 +337,11 @@ def test_huber_loss_and_backward_replay_from_a_captured_graph(dev):
 
 
 def test_ghmc_replays_update_acc_sum_like_eager_calls(dev):
-    from deeptables_amd import training
+    from deeptables_amd import losses
     from deeptables_amd.models.layers import GHMCLoss
     shape = (1000, 5)
     draws = [_ghmc_draw(shape, 10, 90 + i) for i in range(3)]
-    td, unit = draws[0][1].to(dev), training.unit_grad(dev)
+    td, unit = draws[0][1].to(dev), losses.unit_grad(dev)
     eager_ghm, ghm = GHMCLoss(10, 0.75), GHMCLoss(10, 0.75)
 
     def make(obj):

@@ -119,11 +119,11 @@ def _build(task, num_classes, loss):
 
 
 def test_names_resolve_and_cpu_model_loss_is_the_restatement():
-    from deeptables_amd import _lib, training
-    assert {n: training.LOSS_KINDS[n] for n in NAMES} == {n: LRR.kind_code(k) for n, k in NAMES.items()}
-    assert set(NAMES) <= set(training.LOSS_NAMES)
+    from deeptables_amd import _lib, losses
+    assert {n: losses.LOSS_KINDS[n] for n in NAMES} == {n: LRR.kind_code(k) for n, k in NAMES.items()}
+    assert set(NAMES) <= set(losses.LOSS_NAMES)
     for bad in ('hinge', 'MAE ', 'Huber', 'huber '):
-        assert bad not in training.LOSS_NAMES
+        assert bad not in losses.LOSS_NAMES
     g = torch.Generator().manual_seed(4)
     z = torch.rand(9, 1, generator=g) * 3 + 0.2
     y = torch.rand(9, 1, generator=g) * 3 + 0.2
@@ -144,8 +144,8 @@ def test_names_resolve_and_cpu_model_loss_is_the_restatement():
 
 
 def test_serialised_form():
-    from deeptables_amd import training
-    r = training.resolve_loss
+    from deeptables_amd import losses
+    r = losses.resolve_loss
     assert r({'class_name': 'Huber', 'config': {'delta': 2.0}}) == ('huber', {'delta': 2.0})
     assert r({'class_name': 'Huber'}) == ('huber', {})
     assert r({'class_name': 'LogCosh', 'config': {'name': 'lc', 'reduction': 'sum_over_batch_size'}}) == ('log_cosh', {})

@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """GPU: the loss kernels of csrc/loss.hip (dt_loss) against the float64 restatement of tests/loss_reference.py, the autograd
-function over them (training.device_loss), and the losses through DeepModel's train_step, fit and evaluate.
+function over them (losses.device_loss), and the losses through DeepModel's train_step, fit and evaluate.
 
 Bars, both from the project: yardstick B of tests/precision.py — the kernel's error is at most STEP_BAR['fp32'] x
 max(err_f32, FLOOR), err_f32 the error of the same restatement evaluated in float32 on the CPU; relative error for the
@@ -220,14 +220,14 @@ def test_same_bits_on_every_call_and_without_dz(dev, kind, shape):
 
 
 def test_autograd_unit_gradient_and_scaled_gradient(dev):
-    """backward returns the saved dz ITSELF for training.unit_grad (no launch) and dz * g for any other scalar"""
-    from deeptables_amd import _lib, training
+    """backward returns the saved dz ITSELF for losses.unit_grad (no launch) and dz * g for any other scalar"""
+    from deeptables_amd import _lib, losses
     z0, t = _draw('cce', 65, 3, 7)
     z = z0.to(dev).requires_grad_(True)
-    loss = training.device_loss(_lib.DT_LOSS_CCE, z, t.to(dev), _weights(65, 8).to(dev))
+    loss = losses.device_loss(_lib.DT_LOSS_CCE, z, t.to(dev), _weights(65, 8).to(dev))
     assert type(loss.grad_fn).__name__ == '_DeviceLossBackward' and loss.dim() == 0 and loss.dtype == torch.float32
     saved = loss.grad_fn.saved_tensors[0]
-    (g1,) = torch.autograd.grad(loss, z, training.unit_grad(dev), retain_graph=True)
+    (g1,) = torch.autograd.grad(loss, z, losses.unit_grad(dev), retain_graph=True)
     assert g1.data_ptr() == saved.data_ptr() and torch.equal(g1, saved)
     s = torch.tensor(0.375, device=dev)
     (g2,) = torch.autograd.grad(loss, z, s)
@@ -235,21 +235,21 @@ def test_autograd_unit_gradient_and_scaled_gradient(dev):
     kl, kd = _kernel(dev, 'cce', z0, t, _weights(65, 8))
     assert torch.equal(loss.detach().cpu().reshape(1), kl) and torch.equal(saved.cpu(), kd)
     with torch.no_grad():                                        # evaluate: the value only, the same bits
-        lv = training.device_loss(_lib.DT_LOSS_CCE, z, t.to(dev), _weights(65, 8).to(dev))
+        lv = losses.device_loss(_lib.DT_LOSS_CCE, z, t.to(dev), _weights(65, 8).to(dev))
     assert lv.grad_fn is None and torch.equal(lv.cpu().reshape(1), kl)
 
 
 def test_loss_and_backward_replay_from_a_captured_graph(dev):
     """CCE, B = 64, C = 3: one capture of loss + backward, replayed on new logits in the static buffers = the eager bits"""
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, losses
     za, t = _draw('cce', 64, 3, 9)
     zb, _ = _draw('cce', 64, 3, 10)
     td = t.to(dev)
-    unit = training.unit_grad(dev)
+    unit = losses.unit_grad(dev)
 
     def eager(zv):
         zz = zv.to(dev).requires_grad_(True)
-        loss = training.device_loss(_lib.DT_LOSS_CCE, zz, td)
+        loss = losses.device_loss(_lib.DT_LOSS_CCE, zz, td)
         (g,) = torch.autograd.grad(loss, zz, unit)
         return loss.detach().clone(), g.clone()
     want_a, want_b = eager(za), eager(zb)
@@ -258,12 +258,12 @@ def test_loss_and_backward_replay_from_a_captured_graph(dev):
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):                                # warm-up off the default stream, as torch asks
         for _ in range(2):
-            loss = training.device_loss(_lib.DT_LOSS_CCE, static_z, td)
+            loss = losses.device_loss(_lib.DT_LOSS_CCE, static_z, td)
             torch.autograd.grad(loss, static_z, unit)
     torch.cuda.current_stream().wait_stream(side)
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        loss = training.device_loss(_lib.DT_LOSS_CCE, static_z, td)
+        loss = losses.device_loss(_lib.DT_LOSS_CCE, static_z, td)
         (grad,) = torch.autograd.grad(loss, static_z, unit)
     for zv, want in ((zb, want_b), (za, want_a)):
         with torch.no_grad():
@@ -399,7 +399,7 @@ def _fit_first_loss(dm, df, labels, **kw):
 
 def test_fit_with_categorical_focal_loss_and_class_weight(dev):
     """fit(loss=CategoricalFocalLoss(), class_weight=...) — the imbalanced-data case — runs, on the kernel, and its first-step
-    loss is the restatement's.  Without the feature training.weighted_loss raises ValueError for this loss."""
+    loss is the restatement's.  Without the feature losses.named_loss raises ValueError for this loss."""
     from deeptables_amd.models.layers import CategoricalFocalLoss
     df, rng = _frame(B, 2)
     labels = rng.randint(0, 3, B)
@@ -446,7 +446,7 @@ def test_binary_focal_loss_with_sample_weight_raises(dev):
 def test_evaluate_loss_is_the_weighted_mean_of_the_batch_losses(dev):
     """evaluate on 40 rows in batches of 16, 16 and 8: its loss = sum_b n_b L_b / 40, L_b the kernel's value (dz = NULL) on
     batch b's logits"""
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, losses
     df, rng = _frame(40, 5)
     labels = rng.randint(0, 3, 40)
     dm = _model('multiclass', 3, 'auto')
@@ -456,7 +456,7 @@ def test_evaluate_loss_is_the_weighted_mean_of_the_batch_losses(dev):
     want, per = 0.0, []
     for s, n in ((0, 16), (16, 16), (32, 8)):
         with torch.no_grad():
-            lb = training.device_loss(_lib.DT_LOSS_CCE, logits[s:s + n], t[s:s + n])
+            lb = losses.device_loss(_lib.DT_LOSS_CCE, logits[s:s + n], t[s:s + n])
         assert lb is not None and lb.grad_fn is None
         per.append(float(lb))
         want += n * float(lb)

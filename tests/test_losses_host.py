@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """CPU: the float64 restatement of the losses (tests/loss_reference.py) against the recorded fixtures of the reference's own
-code, the host-side dispatch of training.device_loss / DeepModel._loss with a stubbed library call, the errors, dt_loss'
+code, the host-side dispatch of losses.device_loss / DeepModel._loss with a stubbed library call, the errors, dt_loss'
 argument validation (before any launch, so it runs without a GPU) and the ctypes signatures against the header."""
 import json
 import os
@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import loss_reference as LR
+from tests import loss_reg_reference as LRR
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -71,29 +72,38 @@ def test_restatement_closed_forms_and_gradients():
 
 
 def test_cpu_paths_keep_their_values():
-    """training.* on CPU tensors (and so with DT_AMD_DEVICE_LOSS=0): the restatement's values in float64"""
-    from deeptables_amd import training
+    """losses.* on CPU tensors (and so with DT_AMD_DEVICE_LOSS=0): the restatement's values in float64"""
+    from deeptables_amd import losses
     from deeptables_amd.models.layers import BinaryFocalLoss, CategoricalFocalLoss
     g = torch.Generator().manual_seed(3)
     z = torch.randn(11, 4, generator=g, dtype=torch.float64)
     y = torch.randn(11, 4, generator=g, dtype=torch.float64)
     t = torch.eye(4, dtype=torch.float64)[torch.randint(0, 4, (11,), generator=g)]
     w = torch.rand(11, generator=g, dtype=torch.float64)
-    assert abs(float(training.mae(z, y)) - float(LR.total('mae', z, y))) <= 1e-14
-    assert abs(float(training.mse(z, y)) - float(LR.total('mse', z, y))) <= 1e-14
-    assert abs(float(training.categorical_ce_from_logits(z, t)) - float(LR.total('cce', z, t))) <= 1e-14
-    for name, kind, tt in (('mae', 'mae', y), ('mean_absolute_error', 'mae', y), ('mean_squared_error', 'mse', y),
-                           ('categorical_crossentropy', 'cce', t), ('binary_crossentropy', 'bce', (y > 0).double())):
-        assert abs(float(training.weighted_loss(name, z, tt, w)) - float(LR.total(kind, z, tt, w))) <= 1e-12, name
+    # predictions and targets of the regression names in [1, 1.25]: inside the domain of MSLE and Poisson, and MAPE's value (a
+    # percentage) stays below 16, where the absolute bars below are still several float64 ulp
+    p, q = (torch.rand(11, 4, generator=g, dtype=torch.float64) * 0.25 + 1.0 for _ in range(2))
+    targets = {'bce': (y > 0).double(), 'cce': t, 'mse': y, 'mae': y}
+    for name, code in losses.LOSS_KINDS.items():
+        if name in losses.REG_LOSS_KINDS:
+            kind = next(k for k in LRR.KINDS if LRR.kind_code(k) == code)
+            ref, zz, tt = LRR.total, p, q
+        else:
+            kind = next(k for k in LR.KINDS if LR.kind_code(k) == code)
+            ref, zz, tt = LR.total, z, targets[kind]
+        for ww, bar in ((None, 1e-14), (w, 1e-12)):
+            got, want = float(losses.named_loss(name, zz, tt, ww)), float(ref(kind, zz, tt, ww))
+            print(name, 'weighted' if ww is not None else 'unweighted', got, want, abs(got - want))
+            assert abs(got - want) <= bar, name
     soft = lambda q: torch.softmax(q, dim=-1)
     cf = CategoricalFocalLoss(gamma=1.5, alpha=0.4)
-    assert abs(float(training.focal_from_logits(5, cf, z, t, w, soft)) - float(LR.total('categorical_focal', z, t, w, 1.5, 0.4))) <= 1e-14
-    assert abs(float(training.focal_from_logits(5, cf, z, t, None, soft)) - float(LR.total('categorical_focal', z, t, None, 1.5, 0.4))) <= 1e-14
+    assert abs(float(losses.focal_from_logits(5, cf, z, t, w, soft)) - float(LR.total('categorical_focal', z, t, w, 1.5, 0.4))) <= 1e-14
+    assert abs(float(losses.focal_from_logits(5, cf, z, t, None, soft)) - float(LR.total('categorical_focal', z, t, None, 1.5, 0.4))) <= 1e-14
     bf = BinaryFocalLoss(gamma=0.5, alpha=0.3)
     tb = (y > 0).double()
-    assert abs(float(training.focal_from_logits(4, bf, z, tb, None, torch.sigmoid)) - float(LR.total('binary_focal', z, tb, None, 0.5, 0.3))) <= 1e-14
+    assert abs(float(losses.focal_from_logits(4, bf, z, tb, None, torch.sigmoid)) - float(LR.total('binary_focal', z, tb, None, 0.5, 0.3))) <= 1e-14
     with pytest.raises(ValueError):
-        training.weighted_loss('hinge', z, y, w)
+        losses.named_loss('hinge', z, y, w)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -128,12 +138,12 @@ def _fake_model(loss_name, custom=None, activation='softmax'):
 def test_dispatch_table(monkeypatch):
     """which loss and weight combination goes to dt_loss, with which kind, and which keeps its torch path; tensors are made to
     look device resident and the library call is a recorder.  DT_AMD_DEVICE_LOSS=0: nothing reaches the library."""
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, losses
     from deeptables_amd.models.layers import BinaryFocalLoss, CategoricalFocalLoss
     rec = _Recorder()
-    monkeypatch.setattr(training, 'lib', lambda: rec)
-    monkeypatch.setattr(training, 'stream_ptr', lambda: None)
-    monkeypatch.setattr(training, '_on_device', lambda t: torch.is_tensor(t))
+    monkeypatch.setattr(losses, 'lib', lambda: rec)
+    monkeypatch.setattr(losses, 'stream_ptr', lambda: None)
+    monkeypatch.setattr(losses, '_on_device', lambda t: torch.is_tensor(t))
     g = torch.Generator().manual_seed(1)
     z = torch.randn(6, 3, generator=g).requires_grad_(True)
     z1 = torch.randn(6, 1, generator=g).requires_grad_(True)
@@ -186,15 +196,15 @@ def test_dispatch_table(monkeypatch):
     # outside the kernel's domain the host keeps its torch path: too many classes, float64 logits
     rec.calls.clear()
     wide = torch.randn(2, _lib.DT_LOSS_MAX_CLASSES + 1)
-    assert training.device_loss(_lib.DT_LOSS_MSE, wide, wide) is None
-    assert training.device_loss(_lib.DT_LOSS_MSE, z1.double(), y1.double()) is None
-    assert training.device_loss(_lib.DT_LOSS_BINARY_FOCAL, z1, y1, w) is None
+    assert losses.device_loss(_lib.DT_LOSS_MSE, wide, wide) is None
+    assert losses.device_loss(_lib.DT_LOSS_MSE, z1.double(), y1.double()) is None
+    assert losses.device_loss(_lib.DT_LOSS_BINARY_FOCAL, z1, y1, w) is None
     assert rec.calls == []
-    float(training.mse(wide, wide))
+    float(losses.named_loss('mse', wide, wide))
 
 
 def test_unit_gradient_is_handed_out_without_a_multiply(monkeypatch):
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, losses
     import ctypes
 
     class Filling(_Recorder):
@@ -203,14 +213,14 @@ def test_unit_gradient_is_handed_out_without_a_multiply(monkeypatch):
             out[:] = [float(i) for i in range(rows * classes)]
             return 0
     rec = Filling()
-    monkeypatch.setattr(training, 'lib', lambda: rec)
-    monkeypatch.setattr(training, 'stream_ptr', lambda: None)
-    monkeypatch.setattr(training, '_on_device', lambda t: torch.is_tensor(t))
+    monkeypatch.setattr(losses, 'lib', lambda: rec)
+    monkeypatch.setattr(losses, 'stream_ptr', lambda: None)
+    monkeypatch.setattr(losses, '_on_device', lambda t: torch.is_tensor(t))
     z = torch.randn(5, 3).requires_grad_(True)
-    loss = training.device_loss(_lib.DT_LOSS_CCE, z, torch.eye(3)[[0, 1, 2, 0, 1]])
+    loss = losses.device_loss(_lib.DT_LOSS_CCE, z, torch.eye(3)[[0, 1, 2, 0, 1]])
     saved = loss.grad_fn.saved_tensors[0]
     assert torch.equal(saved, torch.arange(15.0).reshape(5, 3))
-    (g1,) = torch.autograd.grad(loss, z, training.unit_grad('cpu'), retain_graph=True)
+    (g1,) = torch.autograd.grad(loss, z, losses.unit_grad('cpu'), retain_graph=True)
     assert g1.data_ptr() == saved.data_ptr()
     (g2,) = torch.autograd.grad(loss, z, torch.tensor(0.5))
     assert g2.data_ptr() != saved.data_ptr() and torch.equal(g2, saved * 0.5)

@@ -1,10 +1,10 @@
 # -*- coding:utf-8 -*-
 """Times loss + backward of a train step's loss on resident logits both ways (GPU, not a test): through csrc/loss.hip
-(training.device_loss: at most two launches, backward hands out the saved dz) and through the torch op chains that
+(losses.device_loss: at most two launches, backward hands out the saved dz) and through the torch op chains that
 DT_AMD_DEVICE_LOSS=0 restores (the code of the commit before the kernels), at B = 8192 and C = 1, 10, 100 over the kinds that
 apply to each C, with and without per-row weights.  The unweighted binary cross-entropy is not a row: it keeps its own
 one-launch kernel (dt_bce_logits) on both legs.  `--set reg` times csrc/loss_reg.hip instead: Keras' regression losses
-(training.regression_loss -> dt_loss_reg) and GHMCLoss.calc (dt_ghmc) at [8192, 1] and [8192, 16], each against its torch
+(losses.named_loss -> dt_loss_reg) and GHMCLoss.calc (dt_ghmc) at [8192, 1] and [8192, 16], each against its torch
 chain under DT_AMD_DEVICE_LOSS=0 — for GHM-C that chain is the `calc` of the commit before the kernel.
 
     python tools/loss_bench.py --out profiles/losses.jsonl
@@ -14,7 +14,7 @@ chain under DT_AMD_DEVICE_LOSS=0 — for GHM-C that chain is the `calc` of the c
     python tools/loss_bench.py --trace kernel=<dir>/.../kernel_kernel_trace.csv --trace torch=<...> --out profiles/losses.jsonl
 
 Method: one process; logits, targets and weights are device resident; the call is what DeepModel._forward_backward does
-with the logits — the loss function, then `loss.backward(training.unit_grad)` into a leaf whose .grad was dropped.  Both paths
+with the logits — the loss function, then `loss.backward(losses.unit_grad)` into a leaf whose .grad was dropped.  Both paths
 are warmed up, then alternated window by window: `--repeats` windows of `--calls` calls per path, each window between two
 device events (the second one synchronised); a window's time per call is its time / calls; the median of the windows is
 reported with min and max.  These are CALL times, host enqueue included — at these sizes the host is the slower side on
@@ -50,7 +50,7 @@ def row_id(kind, C, weighted):
 def make_case(kind, C, weighted, dev):
     """(leaf logits, fn(z) -> loss) on seeded data: one-hot targets for the categorical kinds, 0 / 1 for the binary ones"""
     import torch
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, losses
     from deeptables_amd.models.layers import BinaryFocalLoss, CategoricalFocalLoss
     g = torch.Generator().manual_seed(100 * C + len(kind))
     if kind in REG_KINDS:
@@ -58,7 +58,7 @@ def make_case(kind, C, weighted, dev):
         z = (torch.rand(BATCH, C, generator=g) * 4.95 + 0.05).to(dev).requires_grad_(True)
         y = (torch.rand(BATCH, C, generator=g) * 4.95 + 0.05).to(dev)
         w = (torch.rand(BATCH, generator=g) + 0.5).to(dev) if weighted else None
-        return z, lambda zz: training.regression_loss(kind, zz, y, w)
+        return z, lambda zz: losses.named_loss(kind, zz, y, w)
     z = torch.randn(BATCH, C, generator=g).to(dev).requires_grad_(True)
     if kind == 'ghmc':
         # one object per path, so that both see the same sequence of calls and carry the same acc_sum
@@ -75,15 +75,12 @@ def make_case(kind, C, weighted, dev):
     w = (torch.rand(BATCH, generator=g) + 0.5).to(dev) if weighted else None
     if kind == 'binary_focal':
         obj = BinaryFocalLoss()
-        return z, lambda zz: training.focal_from_logits(_lib.DT_LOSS_BINARY_FOCAL, obj, zz, y, None, torch.sigmoid)
+        return z, lambda zz: losses.focal_from_logits(_lib.DT_LOSS_BINARY_FOCAL, obj, zz, y, None, torch.sigmoid)
     if kind == 'categorical_focal':
         obj = CategoricalFocalLoss()
-        return z, lambda zz: training.focal_from_logits(_lib.DT_LOSS_CATEGORICAL_FOCAL, obj, zz, y, w,
-                                                        lambda t: torch.softmax(t, dim=-1))
-    if weighted:
-        return z, lambda zz: training.weighted_loss(NAMES[kind], zz, y, w)
-    fn = {'cce': training.categorical_ce_from_logits, 'mse': training.mse, 'mae': training.mae}[kind]
-    return z, lambda zz: fn(zz, y)
+        return z, lambda zz: losses.focal_from_logits(_lib.DT_LOSS_CATEGORICAL_FOCAL, obj, zz, y, w,
+                                                      lambda t: torch.softmax(t, dim=-1))
+    return z, lambda zz: losses.named_loss(NAMES[kind], zz, y, w)
 
 
 def set_path(path):
@@ -134,10 +131,10 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit('loss_bench needs the GPU: nothing is measured without one')
     import __graft_entry__ as g
-    from deeptables_amd import _lib, training
+    from deeptables_amd import losses
     from deeptables_amd._lib import check, lib, ptr, stream_ptr
     dev = torch.device('cuda', 0)
-    unit = training.unit_grad(dev)
+    unit = losses.unit_grad(dev)
     cases = [(row, make_case(*row, dev)) for row in rows]
     if a.count:
         scratch = torch.zeros(64, device=dev)
