@@ -359,6 +359,15 @@ SIGNATURES = {
                                    _c_f32, _ptr, _ptr]),
     'dt_rows_stage_post': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_i64, _c_f32, _ptr, _ptr]),
     'dt_ema_rows_materialize': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _c_f32, _ptr, _ptr]),
+    # Keras' dense Adam result on a row-sparse table through per-row stamps (csrc/adam_exact.hip): table, m, v, slot_stride,
+    # stamp, idx, idx_kind, row_offset, vocab, B, F, D, V, lr, beta1, beta2, eps, state, stream / table, m, v, slot_stride, stamp,
+    # V, D, lr, beta1, beta2, eps, state, stream / stamp, rows, n, V, state, stream
+    'dt_adam_exact_supported': (_c_int, [_c_int]),
+    'dt_adam_rows_catchup': (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _ptr, _ptr, _c_int, _c_int, _c_int, _c_i64,
+                                      _c_f32, _c_f32, _c_f32, _c_f32, _ptr, _ptr]),
+    'dt_adam_rows_materialize': (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _c_f32, _c_f32, _ptr,
+                                          _ptr]),
+    'dt_adam_rows_stamp': (_c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

@@ -153,6 +153,8 @@ def load_model(model, path, optimizer=None, strict=True):
     from safetensors import safe_open
     targets = named_weights(model)
     seen = set()
+    if getattr(optimizer, 'exact_rows', False):
+        optimizer.materialize()           # idle steps pending on the live tables belong to the weights that are replaced
     with safe_open(path, framework='pt', device='cpu') as f:
         meta = f.metadata() or {}
         if meta.get('format') != FORMAT:

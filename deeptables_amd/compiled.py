@@ -424,6 +424,8 @@ class CompiledTrainLoop:
             plan.sharded_post(self.B, self.strategy)
         elif g is not None:
             g.replay()
+            if self.with_optimizer and hasattr(self.dm.optimizer, 'steps_replayed'):
+                self.dm.optimizer.steps_replayed()      # (its step() ran inside the graph, not on the host)
             if self._graph_out_refs is not None:
                 self._out_refs = dict(self._graph_out_refs)     # (an eager remainder step may have replaced entry 0)
             if self.dp or not self.with_optimizer:

@@ -299,6 +299,9 @@ class DeepModel:
         if getattr(getattr(self, 'optimizer', None), 'stages', False):
             # weight_decay / use_ema sit around the update in the same way: no fused step may apply an un-decayed update
             return None
+        if getattr(getattr(self, 'optimizer', None), 'exact_rows', False):
+            # Adam's exact rows are brought up to date ahead of the layer's gather: a fused step has its own gather
+            return None
         if not hasattr(self, '_fused_plan'):
             from ..fused import make_fused_plan
             self._fused_plan = make_fused_plan(self)
@@ -369,6 +372,15 @@ class DeepModel:
             which = '`weight_decay`' if opt.weight_decay is not None else '`use_ema`'
             raise ValueError(f'{which} with a distribute_strategy: the decay and the moving average of row-owned tables and '
                              f'exchanged gradients are not there; train on one device or without it')
+        if strategy is not None and getattr(opt, 'exact_rows', False):
+            raise ValueError('`exact_rows` with a distribute_strategy: the stamps of row-owned tables and exchanged gradients '
+                             'are not there; train on one device or without it')
+
+    def _materialize_tables(self):
+        """Adam's `exact_rows`: every table row is brought up to the steps done before something reads the tables past the
+        layers' gather — an inference plan, a checkpoint.  Free while no step ran since the last time."""
+        if getattr(getattr(self, 'optimizer', None), 'exact_rows', False):
+            self.optimizer.materialize()
 
     def train_step(self, inputs, y, sample_weight=None):
         """forward -> loss -> backward -> (data-parallel gradient exchange) -> optimizer step."""
@@ -548,6 +560,7 @@ class DeepModel:
                 break
         if getattr(self.optimizer, 'use_ema', False):
             self.optimizer.finalize_variable_values()      # Keras' fit ends on the averaged weights
+        self._materialize_tables()                         # ... and on tables whose every row has taken every step
         self._sync_sharded_tables()
         for cb in callbacks or []:
             if hasattr(cb, 'on_train_end'):
@@ -574,6 +587,8 @@ class DeepModel:
         # activity penalties need the layers' outputs, so such a model evaluates on the layer path (predict keeps its plan)
         with_activity = bool(self.model.activity_layers())
         plan = None if with_activity else self.inference_plan()
+        if plan is not None:
+            self._materialize_tables()
         self.model.collect_eval_activity = with_activity
         try:
             with torch.no_grad():
@@ -611,6 +626,7 @@ class DeepModel:
         model.eval()
         plan = self.inference_plan() if model is self.model else None     # (apply()'s proxy models: the layer path)
         if plan is not None:
+            self._materialize_tables()
             with torch.no_grad():
                 logit, out = plan.run_batches(data, batch_size, activate=activate)
             return (out if activate else logit).cpu().numpy()
@@ -661,6 +677,7 @@ class DeepModel:
             raise ValueError('save(include_optimizer=True) under ShardedEmbeddingStrategy: every rank holds the Adam '
                              'moments of its own fields only; save without the optimizer, or train with replicated tables')
         os.makedirs(os.path.dirname(os.path.abspath(filepath)) or '.', exist_ok=True)
+        self._materialize_tables()          # (also without the optimizer: the weights themselves are what is pending)
         checkpoint.save_model(self.model, filepath, optimizer=self.optimizer if include_optimizer else None,
                               metadata={'task': str(self.task), 'nets': [str(n) for n in self.config.nets]})
 

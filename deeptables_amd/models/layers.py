@@ -399,6 +399,9 @@ class MultiColumnEmbedding(Layer):
         self.activity_regularizer = regularizers.get(activity_regularizer, 'embeddings_activity_regularizer')
         self.sparse_grads = {}      # group key -> list[SparseRowGrad] (filled by backward)
         self.check_oob = False
+        # callable (group key, the group's ids [B, F]) run ahead of the gather of a row-sparse table, in training and in
+        # evaluation alike: training.KerasAdam(exact_rows=True) brings the rows the batch looks up up to date there
+        self.pre_lookup = None
 
     def build(self, input_shape):
         if input_shape[1] == 0:
@@ -494,6 +497,8 @@ class MultiColumnEmbedding(Layer):
         if len(self.groups) > 1 or len(cols) != inputs.shape[1]:
             idx = inputs.index_select(1, getattr(self, f'cols_{key}'))
         holder = _GroupHolder(self, key)
+        if self.pre_lookup is not None and not self.uses_dense_grad(D):
+            self.pre_lookup(key, idx)
         dropout = None if drop_seed is None else \
             (self.dropout_rate, drop_seed, ops.cell_salt(self.name), getattr(self, f'col_base_{key}'))
         return ops.embedding_lookup(idx, table, getattr(self, f'row_offset_{key}'), getattr(self, f'vocab_{key}'),

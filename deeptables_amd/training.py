@@ -906,44 +906,168 @@ class KerasAdam(_DeviceOptimizer):
     Dense parameters: one fused HIP launch for all of them — or for a whole registered flat group.
     Packed embedding tables with a sparse gradient: duplicate lookups merged through a per-step hash of the row ids, then
     a row-sparse ("lazy") update of only the rows touched this step — a documented deviation from Keras' dense
-    semantics for tables too large to sweep every step."""
+    semantics for tables too large to sweep every step.
+
+    exact_rows=True closes that deviation (csrc/adam_exact.hip): Keras gives a row that was not looked up
+    gradient 0 and still moves it — m and v decay, the weight coasts on the decayed momentum.  Here such a row waits: an int32
+    stamp per row holds the number of steps its weight and slots are current through, and the k idle steps it owes are paid
+    before anything reads it — by a launch ahead of the gather for the rows a batch looks up (the embedding layers'
+    `pre_lookup` hook, in training and in evaluation alike), by `materialize()` for all rows at once (DeepModel calls it before
+    an inference plan reads the tables and before it saves).  The row update itself is the lazy path's: for a row that is
+    current it IS Keras' dense step.  Weights are Keras' after every step, m and v to rounding.  No fused step runs in this
+    mode (`supports_row_segments` / `supports_rows_in_step` are False, DeepModel.fused_plan() is None), and it is refused
+    together with `weight_decay`, `use_ema` or a distribute_strategy, whose lazy-row rules would need a joint definition."""
 
     _row_segments = True              # dt_adam_rows_step_seg
     _rows_in_step = True
     slot_names = ('m', 'v')
     _name = 'Adam'
+    exact_rows = False
+    _pending = False                  # exact_rows: a step ran since the last sweep (`materialize()` costs nothing otherwise)
 
     def __init__(self, params, embedding_layers=(), learning_rate=1e-3, beta_1=0.9, beta_2=0.999, epsilon=1e-7,
                  clipnorm=None, clipvalue=None, global_clipnorm=None, weight_decay=None, use_ema=False, ema_momentum=0.99,
-                 ema_overwrite_frequency=None):
+                 ema_overwrite_frequency=None, exact_rows=False):
         super().__init__(params, embedding_layers, clipnorm, clipvalue, global_clipnorm, weight_decay, use_ema, ema_momentum,
                          ema_overwrite_frequency)
         self.lr, self.b1, self.b2, self.eps = learning_rate, beta_1, beta_2, epsilon
         self._applied_in_step = False  # a fused step ran this step's whole update itself (applied_in_step)
+        self._set_exact_rows(exact_rows)
 
     def _betas(self):
         return self.b1, self.b2
 
+    # -- exact_rows ---------------------------------------------------------------------------------------
+    @staticmethod
+    def idle_term_ratio(beta_1, beta_2):
+        """rho = sup_t (lr_{t+1} / lr_t) * beta_1 / sqrt(beta_2): the most by which the term lr_t m / (sqrt(v) + eps) of an idle
+        row can grow from one step to the next (m shrinks by beta_1, sqrt(v) + eps by sqrt(beta_2) at the most).  rho < 1 is
+        what lets the catch-up loop stop early.  lr_t / lr = sqrt(1 - beta_2^t) / (1 - beta_1^t) tends to 1: the supremum is
+        taken over the steps until both powers are below 1e-18 (four million steps at the most), and 1 for all later ones."""
+        b1, b2 = float(beta_1), float(beta_2)
+        if not (0.0 <= b1 < 1.0 and 0.0 < b2 < 1.0):
+            return math.inf
+        if b1 == 0.0:
+            return 0.0
+        n = int(min(math.ceil(math.log(1e-18) / math.log(max(b1, b2))) + 2, 1 << 22))
+        t = np.arange(1, n + 1, dtype=np.float64)
+        lr_t = np.sqrt(-np.expm1(t * math.log(b2))) / -np.expm1(t * math.log(b1))
+        return float(max(1.0, (lr_t[1:] / lr_t[:-1]).max()) * b1 / math.sqrt(b2))
+
+    def _set_exact_rows(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise ValueError(f'`exact_rows` must be True or False, got {on!r}')
+        on = bool(on)
+        if on:
+            if self.stages:
+                which = '`weight_decay`' if self.weight_decay is not None else '`use_ema`'
+                raise ValueError(f'Adam: `exact_rows` with {which}: the decay and the moving average of a row that waits for its '
+                                 f'idle steps have no definition yet; use one or the other')
+            rho = self.idle_term_ratio(self.b1, self.b2)
+            if not rho < 1.0:
+                raise ValueError(f'Adam: `exact_rows` needs beta_1 < sqrt(beta_2) with room to spare: the idle steps of a row are '
+                                 f'summed until their terms stop moving the weight, and with beta_1={self.b1!r}, '
+                                 f'beta_2={self.b2!r} a term can be {rho:.4g} times the one before it (the bound must be < 1)')
+        if on != self.exact_rows:
+            import functools
+            if not on:
+                self.materialize()             # what is pending belongs to the mode that is being left
+                for s in self.state.values():
+                    s.pop('stamp', None)
+            for layer in self.embedding_layers:
+                layer.pre_lookup = functools.partial(self._pre_lookup, layer) if on else None
+        self.exact_rows = on
+
+    @property
+    def supports_row_segments(self):
+        return _StepStages.supports_row_segments.fget(self) and not self.exact_rows
+
+    @property
+    def supports_rows_in_step(self):
+        return _StepStages.supports_rows_in_step.fget(self) and not self.exact_rows
+
+    def _pre_lookup(self, layer, key, idx):
+        """the layers' hook, ahead of the gather of `idx` [B, F] from `layer.tables[key]`: the rows the batch looks up pay
+        the idle steps they owe (dt_adam_rows_catchup).  No host synchronisation; replays in a captured graph."""
+        table = layer.tables[key]
+        if not table.requires_grad or not table.is_cuda:
+            return
+        s = self._st(table, rows=True)
+        idx = idx.contiguous()
+        from .ops import _idx_kind
+        B, F = idx.shape
+        V, D = table.shape
+        check(lib().dt_adam_rows_catchup(ptr(table.data), ptr(s['m']), ptr(s['v']), int(s['m'].stride(0)), ptr(s['stamp']),
+                                         ptr(idx), _idx_kind(idx), ptr(getattr(layer, f'row_offset_{key}')),
+                                         ptr(getattr(layer, f'vocab_{key}')), B, F, D, V, self.lr, self.b1, self.b2, self.eps,
+                                         ptr(self._state_tensor(table.device)), stream_ptr()), 'dt_adam_rows_catchup')
+
+    def _materialize_one(self, p, s):
+        check(lib().dt_adam_rows_materialize(ptr(p.data), ptr(s['m']), ptr(s['v']), int(s['m'].stride(0)), ptr(s['stamp']),
+                                             p.shape[0], p.shape[1], self.lr, self.b1, self.b2, self.eps,
+                                             ptr(self._state_tensor(p.device)), stream_ptr()), 'dt_adam_rows_materialize')
+
+    def materialize(self):
+        """exact_rows: every row of every row-sparse table pays the idle steps it owes — weights, m and v are Keras' for the
+        steps done, every stamp is current.  Free while no step ran since the last sweep."""
+        if self._pending:
+            for p in self.params:
+                s = self.state.get(id(p))
+                if s is not None and 'stamp' in s:
+                    self._materialize_one(p, s)
+            self._pending = False
+        self._materialize_averages()
+
+    def steps_replayed(self):
+        """a captured graph that holds this optimizer's step was replayed (compiled.CompiledTrainLoop): `step()` did not run
+        on the host, yet rows are pending again"""
+        self._pending = self.exact_rows
+
+    def _restamp(self):
+        for p in self.params:
+            s = self.state.get(id(p))
+            if s is not None and 'stamp' in s:
+                s['stamp'].copy_((self._dev_state[:1] - 1).expand(p.shape[0]))
+
     def hyperparameters(self):
-        """what travels with a checkpoint: the clip, decay and average settings alone (Adam's own arguments are the
-        constructor's, as they were)"""
-        return self._base_hp()
+        """what travels with a checkpoint: the clip, decay and average settings and `exact_rows`, each only when set (Adam's
+        other arguments are the constructor's, as they were)"""
+        return dict(self._base_hp(), **({'exact_rows': True} if self.exact_rows else {}))
 
     def set_hyperparameters(self, hp):
-        self._load_base_hp(hp)
+        before = (self._clip, self.weight_decay, self.use_ema, self.ema_momentum)
+        rest = self._load_base_hp(hp)
+        try:
+            want = bool(rest.get('exact_rows', self.exact_rows))
+            if want != self.exact_rows or (want and self.stages):
+                self._set_exact_rows(want)      # (raises when the stages just loaded do not go with the mode)
+        except ValueError:
+            self._clip, self.weight_decay, self.use_ema, self.ema_momentum = before     # a refused update changes nothing
+            raise
 
     def _new_slot(self, p, rows):
         """rows (the row-sparse table update): m and v of a row side by side in ONE [V, 2, D] array (a 128-byte line at
-        D = 16), so the update touches two random locations per row instead of three; `m` / `v` are its strided views."""
+        D = 16), so the update touches two random locations per row instead of three; `m` / `v` are its strided views.
+        exact_rows: and `stamp`, int32 [V], created as the steps done: nothing is pending on a new slot."""
         if not rows:
             return super()._new_slot(p, rows)
         mv = torch.zeros((p.shape[0], 2, p.shape[1]), dtype=p.dtype, device=p.device)
-        return {'m': mv[:, 0, :], 'v': mv[:, 1, :], 'mv': mv}
+        s = {'m': mv[:, 0, :], 'v': mv[:, 1, :], 'mv': mv}
+        if self.exact_rows:
+            s['stamp'] = (self._state_tensor(p.device)[:1] - 1).expand(p.shape[0]).contiguous()
+        return s
 
     def _st(self, p, rows=False):
         s = self.state.get(id(p))
         if s is not None and not rows and 'mv' in s:          # the dense update needs contiguous slots: convert back
+            if 'stamp' in s:                                  # ... of a table that is current
+                self._materialize_one(p, s)
             self.state[id(p)] = {'m': s['m'].contiguous(), 'v': s['v'].contiguous()}
+        elif s is not None and rows and self.exact_rows and p.dim() == 2 and 'stamp' not in s:
+            old, s = s, self._new_slot(p, True)               # slots from before the mode (or a dense update): current
+            s['m'].copy_(old['m'].reshape(p.shape))
+            s['v'].copy_(old['v'].reshape(p.shape))
+            self.state[id(p)] = s
         return super()._st(p, rows)
 
     def zero_grad(self, flat=True):
@@ -971,7 +1095,24 @@ class KerasAdam(_DeviceOptimizer):
             for layer in self.embedding_layers:
                 layer.sparse_grads.clear()
             return
+        if not (self.exact_rows and self.params):
+            super().step()
+            return
+        # exact_rows: the rows this step updates are current through it once its last update has advanced the state — a launch
+        # of its own, so that a forward that no step follows leaves consistent stamps too
+        updated = [(layer.tables[key], [g.rows for g in grads]) for layer in self.embedding_layers
+                   for key, grads in layer.sparse_grads.items() if grads]
+        self._pending = True
         super().step()
+        for table, pieces in updated:
+            s = self.state.get(id(table))
+            if s is None or 'stamp' not in s:
+                continue
+            for rows in pieces:
+                rows = rows.reshape(-1)
+                rows = rows if rows.is_contiguous() else rows.contiguous()
+                check(lib().dt_adam_rows_stamp(ptr(s['stamp']), ptr(rows), rows.numel(), table.shape[0],
+                                               ptr(self._state_tensor(table.device)), stream_ptr()), 'dt_adam_rows_stamp')
 
     def _dense_call(self, p, g, ss, n, sp, advance, st):
         check(lib().dt_adam_dense_step(ptr(p), ptr(g), ptr(ss[0]), ptr(ss[1]), n, 0.0, self.b1, self.b2, self.eps, sp, advance,

@@ -1565,6 +1565,39 @@ int dt_rows_stage_post(const float* table, float* avg, int* stamp, const int64_t
 int dt_ema_rows_materialize(const float* table, float* avg, int* stamp, int64_t V, int D, float momentum, const void* state,
                             void* stream);
 
+/* Keras' DENSE Adam result on a row-sparse table (csrc/adam_exact.hip; training.KerasAdam(exact_rows=True)).  The reference's
+ * default optimizer, keras.optimizers.Adam(learning_rate=0.001) (deepmodel.py:319-322), is applied to the densified embedding
+ * gradient: a row that was not looked up has gradient 0 and still takes every step t (1-based),
+ *     m = beta1 m;  v = beta2 v;  p = p - lr_t m / (sqrt(v) + eps),   lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t).
+ * Here such a row waits: stamp (int32 [V]) holds the number of steps its p, m and v are current through, and a row that is
+ * needed while c = AdamState.t - 1 steps are complete (read from the DEVICE `state` of dt_adam_state_init, so a captured
+ * graph replays these launches) first pays the k = c - stamp[row] idle steps above.  float32, every formula in the order
+ * written without contraction; beta1^t and beta2^t are running products seeded by one powf each; an element leaves the loop
+ * at the first step whose term is 0, or leaves p unchanged and is below 2^-26 |p| (no later term can change p: they shrink by
+ * sup_t (lr_{t+1} / lr_t) beta1 / sqrt(beta2) < 1, which the caller has checked), and its m and v take the rest of their
+ * decay as one powf each.  m, v: the row's slots at m + row * slot_stride and v + row * slot_stride (one [V, 2, D] record:
+ * v = m + D, slot_stride = 2 D; two arrays: slot_stride = D).  16-byte pieces where D % 4 == 0, slot_stride % 4 == 0 and
+ * table, m and v are 16-byte aligned, floats otherwise; min(pieces, 256) threads per row, a row never straddles a block.
+ * Nothing synchronises with the host or allocates.  Negative sizes, null or misaligned pointers with something to do,
+ * overlapping slots, an unknown idx_kind and betas outside 0 <= beta1 < 1, 0 < beta2 < 1, beta1 < sqrt(beta2) are
+ * DT_ERR_INVALID_ARG before any launch.
+ * dt_adam_exact_supported(D): 1 for the D these entry points take (every D >= 1).
+ * dt_adam_rows_catchup: ahead of the gather of a batch, with the gather's own (idx, idx_kind, row_offset, vocab, B, F): one
+ *   thread group per lookup; an id outside [0, vocab[f]) or a row >= V touches nothing.  The group's first lane claims the
+ *   row by an integer atomicExch of stamp[row] to c; when the old value is c already (another lookup of the row in this
+ *   batch owns it, or nothing is pending) the group leaves, so duplicates need no merge: what reads the row is a later launch.
+ * dt_adam_rows_materialize: the same for every row of the table (every stamp = c afterwards); a row whose m and v are all
+ *   zero — never looked up — is restamped without its weights being written.
+ * dt_adam_rows_stamp: behind the step's last row update (dt_adam_rows_step_seg, which for a row that is current IS Keras'
+ *   dense step and has advanced the state): stamp[row] = AdamState.t - 1 for rows [n] (int64; -1 and ids >= V skipped).    */
+int dt_adam_exact_supported(int D);
+int dt_adam_rows_catchup(float* table, float* m, float* v, int slot_stride, int* stamp, const void* idx, int idx_kind,
+                         const int64_t* row_offset, const int32_t* vocab, int B, int F, int D, int64_t V, float lr,
+                         float beta1, float beta2, float eps, const void* state, void* stream);
+int dt_adam_rows_materialize(float* table, float* m, float* v, int slot_stride, int* stamp, int64_t V, int D, float lr,
+                             float beta1, float beta2, float eps, const void* state, void* stream);
+int dt_adam_rows_stamp(int* stamp, const int64_t* rows, int64_t n, int64_t V, const void* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
