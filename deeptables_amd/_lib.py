@@ -145,6 +145,7 @@ SIGNATURES = {
                                    _c_f32, _c_f32, _c_f32, _ptr, _ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr]),
     'dt_dense_supported': (_c_int, [_c_int] * 3),
     'dt_dense_workspace_bytes': (_c_i64, [_c_int] * 3),
+    'dt_dense_geometry': (_c_int, [_c_int] * 4 + [_ptr]),       # N, K, M, product, int out[8]
     'dt_dense_fwd': (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     'dt_dense_bwd': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # the same Dense on K- and M-independent tiles, for the shapes dt_dense_supported refuses (csrc/dense_tiled.hip)

@@ -15,6 +15,9 @@
 // The [rows x K] slab bounds these kernels (dt_dense_supported: 150 KB of LDS, i.e. K <= ~1198 at M >= 97, ~598 at
 // 33 <= M <= 96, ~298 below; the same with K and M swapped for grad_x).  Shapes beyond it run on dense_tiled.hip, whose
 // tiles depend on neither K nor M: ops.dense asks dt_dense_supported first, so every shape accepted here stays here.
+// 16-byte loads (the MFMA kernel's staging, the Dense(1) backward's columns) are taken only where the row length is a
+// multiple of 4 AND the pointers they go through are 16-byte aligned; the host decides and passes a flag.  The grids, the
+// LDS size and the batch split come from small helpers that dt_dense_geometry reports as well (tests/dense_support.py).
 #include "common.h"
 
 namespace dt {
@@ -26,15 +29,26 @@ __device__ __forceinline__ float dact(float g, float y, int act) {
     return (act == DT_ACT_RELU && !(y > 0.f)) ? 0.f : g;
 }
 
+// The numbers a kernel derives from its arguments and dt_dense_geometry reports: written once, for both.
+//   k_dense_mfma: MFMA steps over Kd (k = 2 st + s; an odd Kd ends on a half-empty step) and the 16-step operand chunks
+//   of its register pipeline;  k_dense_wgrad: the rows of one batch split, rounded up to 8 so that the 4 waves' quarters
+//   begin on even rows.
+__host__ __device__ __forceinline__ int mfma_steps(int Kd) { return (Kd + 1) >> 1; }
+__host__ __device__ __forceinline__ int mfma_chunks(int Kd) { return (Kd >> 1) / kDCH; }
+__host__ __device__ __forceinline__ int64_t wgrad_rows_per_split(int N, int row_splits) {
+    return (((int64_t)N + row_splits - 1) / row_splits + 7) & ~(int64_t)7;
+}
+
 // ---------------------------------------------------------------------------------------------
 // out[N, Mo] = act( A[N, Kd] . Bm[Kd, Mo] + bias )   with A optionally masked: A = ga * act'(ya)
 //   block: 4 waves = NBW waves along the output columns x RW row tiles of 32 rows.
+//   vec4: Kd % 4 == 0 and A (and ya) 16-byte aligned, the host's to establish: the tile is then staged with 16-byte loads.
 // ---------------------------------------------------------------------------------------------
 template <bool MASKED>
 __global__ __launch_bounds__(256) void k_dense_mfma(const float* __restrict__ A, const float* __restrict__ ya,
                                                     int mask_act, const float* __restrict__ Bm,
                                                     const float* __restrict__ bias, int act, int N, int Kd, int Mo,
-                                                    int NBW, float* __restrict__ out) {
+                                                    int NBW, float* __restrict__ out, int vec4) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int RW = 4 / NBW;
     const int rows_blk = 32 * RW;
@@ -45,7 +59,7 @@ __global__ __launch_bounds__(256) void k_dense_mfma(const float* __restrict__ A,
     const int64_t m0 = (int64_t)blockIdx.x * rows_blk;
 
     // ---- stage the A tile (coalesced along K), zero padded ----
-    if ((Kd & 3) == 0) {   // 16-byte loads: 4 consecutive k per thread
+    if (vec4) {   // 16-byte loads: 4 consecutive k per thread
         const int q4 = Kd >> 2;
         for (int e = threadIdx.x; e < rows_blk * q4; e += blockDim.x) {
             const int r = e / q4, q = e - r * q4;
@@ -80,8 +94,7 @@ __global__ __launch_bounds__(256) void k_dense_mfma(const float* __restrict__ A,
 
     const float* arow = lds + (wr * 32 + c) * KS + s;
     const int nblocks = (Mo + 31) >> 5;
-    const int steps = (Kd + 1) >> 1;         // k = 2 st + s; odd Kd: the last s = 1 operand is the zero pad / guarded
-    const int full = (Kd >> 1);              // steps whose both k are < Kd
+    const int steps = mfma_steps(Kd);        // k = 2 st + s; odd Kd: the last s = 1 operand is the zero pad / guarded
     for (int nb = wn; nb < nblocks; nb += NBW) {
         const int col = 32 * nb + c;
         const bool cok = col < Mo;
@@ -90,7 +103,7 @@ __global__ __launch_bounds__(256) void k_dense_mfma(const float* __restrict__ A,
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
         int st = 0;
-        const int nch = full / kDCH;
+        const int nch = mfma_chunks(Kd);     // chunks of steps whose both k are < Kd
         if (nch > 0) {
             float a0[kDCH], b0[kDCH], a1[kDCH], b1[kDCH];
 #pragma unroll
@@ -272,7 +285,7 @@ __global__ __launch_bounds__(256) void k_dense_wgrad(const float* __restrict__ x
     const int kb = blockIdx.x / nbm, nb = blockIdx.x % nbm;
     const int kcol = 32 * kb + c, ncol = 32 * nb + c;
     const bool kok = kcol < K, nok = ncol < M;
-    const int64_t rows_per_split = (((int64_t)N + row_splits - 1) / row_splits + 7) & ~(int64_t)7;
+    const int64_t rows_per_split = wgrad_rows_per_split(N, row_splits);
     const int64_t rq = rows_per_split >> 2;
     const int64_t r_begin = (int64_t)blockIdx.y * rows_per_split + wave * rq;
     const int64_t r_end = min((int64_t)N, r_begin + rq);
@@ -334,6 +347,53 @@ static int dense_nbw(int M) {
     return nb >= 4 ? 4 : (nb >= 2 ? 2 : 1);
 }
 static size_t dense_lds(int K, int nbw) { return (size_t)(32 * (4 / nbw)) * ((K + 1) | 1) * sizeof(float); }
+constexpr size_t kDenseLdsLimit = 150 * 1024;
+
+// One launch of k_dense_mfma: out [N, Mo] from A [N, Kd].  The launchers and dt_dense_geometry both read it.
+struct MfmaLaunch {
+    int nbw, rows_blk, grid;
+    size_t lds;
+};
+static MfmaLaunch mfma_launch(int N, int Kd, int Mo) {
+    MfmaLaunch g;
+    g.nbw = dense_nbw(Mo);
+    g.rows_blk = 32 * (4 / g.nbw);
+    g.grid = ceil_div(N, g.rows_blk);
+    g.lds = dense_lds(Kd, g.nbw);
+    return g;
+}
+// the 16-byte staging loads need rows of whole float4s that begin on a 16-byte boundary: A, and ya where it is read
+static int mfma_vec4(int Kd, const void* A, const void* ya) {
+    return (Kd % 4 == 0) && (((uintptr_t)A | (uintptr_t)ya) % 16 == 0);
+}
+
+// k_dense_wgrad's grid: enough (tile, batch-split) blocks for ~4 waves per SIMD; each wave keeps >= 64 rows of work
+struct WgradLaunch {
+    int tiles, splits;
+};
+static WgradLaunch wgrad_launch(int N, int K, int M) {
+    WgradLaunch g;
+    g.tiles = ceil_div(K, 32) * ceil_div(M, 32);
+    g.splits = 1024 / g.tiles;
+    if (g.splits < 1) g.splits = 1;
+    if (g.splits > 512) g.splits = 512;
+    while (g.splits > 1 && N / g.splits < 256) g.splits >>= 1;
+    return g;
+}
+
+static int dense1_fwd_grid(int N) {      // 4 rows (waves) per block, grid-stride beyond 4096 blocks
+    int blocks = ceil_div(N, 4);
+    if (blocks > 4096) blocks = 4096;
+    return blocks;
+}
+static int dense1_rows(int N) {          // rows per block of the Dense(1) backward: ~1024 blocks, 32..64 rows each
+    int rpb = ceil_div(N, 1024);
+    if (rpb < 32) rpb = 32;
+    if (rpb > kD1Rows) rpb = kD1Rows;
+    return rpb;
+}
+static int dense1_blocks(int N) { return ceil_div(N > 0 ? N : 1, dense1_rows(N)); }
+static int dense1_reduce_grid(int K) { return ceil_div(K + 1, 64); }   // 64 columns per block; column K is the bias
 
 }  // namespace dt
 
@@ -342,19 +402,37 @@ using namespace dt;
 extern "C" int dt_dense_supported(int N, int K, int M) {
     if (N <= 0 || K <= 0 || M <= 0) return 0;
     if (M == 1) return 1;
-    return dense_lds(K, dense_nbw(M)) <= 150 * 1024 && dense_lds(M, dense_nbw(K)) <= 150 * 1024;
-}
-
-static int dense1_rows(int N) {          // rows per block of the Dense(1) backward: ~1024 blocks, 32..64 rows each
-    int rpb = ceil_div(N, 1024);
-    if (rpb < 32) rpb = 32;
-    if (rpb > kD1Rows) rpb = kD1Rows;
-    return rpb;
+    return dense_lds(K, dense_nbw(M)) <= kDenseLdsLimit && dense_lds(M, dense_nbw(K)) <= kDenseLdsLimit;
 }
 
 extern "C" int64_t dt_dense_workspace_bytes(int N, int K, int M) {
-    if (M == 1) return (int64_t)sizeof(float) * ceil_div(N > 0 ? N : 1, dense1_rows(N)) * (K + 4);   // per-block column sums
+    if (M == 1) return (int64_t)sizeof(float) * dense1_blocks(N) * (K + 4);   // per-block column sums
     return (int64_t)sizeof(float) * K * M;   // W^T for grad_x
+}
+
+extern "C" int dt_dense_geometry(int N, int K, int M, int product, int* out) {
+    DT_REQUIRE(product >= 0 && product <= 4,
+               "dt_dense_geometry: product %d (0 forward, 1 grad_x, 2 grad_W, 3 Dense(1) forward, 4 Dense(1) backward)", product);
+    DT_REQUIRE(out, "dt_dense_geometry: null out");
+    DT_UNSUPPORTED(!dt_dense_supported(N, K, M), "dt_dense_geometry: N=%d K=%d M=%d", N, K, M);
+    DT_UNSUPPORTED((M == 1) != (product >= 3), "dt_dense_geometry: product %d at M=%d (3, 4: M == 1; 0..2: M >= 2)", product, M);
+    int v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (product <= 1) {
+        const int Kd = product == 0 ? K : M, Mo = product == 0 ? M : K;
+        const MfmaLaunch g = mfma_launch(N, Kd, Mo);
+        v[0] = g.nbw; v[1] = g.rows_blk; v[2] = g.grid; v[3] = (int)g.lds;
+        v[4] = mfma_chunks(Kd); v[5] = mfma_steps(Kd) - kDCH * mfma_chunks(Kd);
+        v[6] = mfma_vec4(Kd, nullptr, nullptr);
+    } else if (product == 2) {
+        const WgradLaunch g = wgrad_launch(N, K, M);
+        v[0] = g.tiles; v[1] = g.splits; v[2] = (int)wgrad_rows_per_split(N, g.splits);
+    } else if (product == 3) {
+        v[0] = dense1_fwd_grid(N);
+    } else {
+        v[0] = dense1_rows(N); v[1] = dense1_blocks(N); v[2] = dense1_reduce_grid(K);
+    }
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return DT_OK;
 }
 
 extern "C" int dt_dense_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M,
@@ -365,55 +443,47 @@ extern "C" int dt_dense_fwd(const float* x, const float* W, const float* bias, i
     DT_REQUIRE(x && W && y, "dt_dense_fwd: null pointer");
     hipStream_t st = as_stream(stream);
     if (M == 1) {
-        int blocks = ceil_div(N, 4);
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(k_dense1_fwd, dim3(blocks), dim3(256), 0, st, x, W, bias, act, N, K, y);
+        hipLaunchKernelGGL(k_dense1_fwd, dim3(dense1_fwd_grid(N)), dim3(256), 0, st, x, W, bias, act, N, K, y);
         return launch_status("dt_dense_fwd(gemv)");
     }
-    const int nbw = dense_nbw(M);
-    const size_t lds = dense_lds(K, nbw);
-    DT_UNSUPPORTED(lds > 150 * 1024, "dt_dense_fwd: K=%d too large for the LDS row tile", K);
-    hipFuncSetAttribute((const void*)k_dense_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_dense_mfma<false>), dim3(ceil_div(N, 32 * (4 / nbw))), dim3(256), lds, st, x, nullptr, 0, W,
-                       bias, act, N, K, M, nbw, y);
+    const MfmaLaunch g = mfma_launch(N, K, M);
+    DT_UNSUPPORTED(g.lds > kDenseLdsLimit, "dt_dense_fwd: K=%d too large for the LDS row tile", K);
+    hipFuncSetAttribute((const void*)k_dense_mfma<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+    hipLaunchKernelGGL((k_dense_mfma<false>), dim3(g.grid), dim3(256), g.lds, st, x, nullptr, 0, W, bias, act, N, K, M,
+                       g.nbw, y, mfma_vec4(K, x, nullptr));
     return launch_status("dt_dense_fwd");
 }
 
 extern "C" int dt_dense_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N,
                             int K, int M, float* grad_x, float* grad_W, float* grad_b, void* ws, void* stream) {
-    DT_REQUIRE(N >= 0 && K > 0 && M > 0, "dt_dense_bwd: bad sizes");
+    DT_REQUIRE(N >= 0 && K > 0 && M > 0, "dt_dense_bwd: bad sizes N=%d K=%d M=%d", N, K, M);
+    DT_REQUIRE(act == DT_ACT_LINEAR || act == DT_ACT_RELU, "dt_dense_bwd: act %d", act);
     if (N == 0) return DT_OK;
     DT_REQUIRE(x && W && y && grad_y && grad_W, "dt_dense_bwd: null pointer");
     hipStream_t st = as_stream(stream);
     if (M == 1) {
         DT_REQUIRE(ws, "dt_dense_bwd: null workspace");
-        const int rpb = dense1_rows(N), blocks = ceil_div(N, rpb);
+        const int rpb = dense1_rows(N), blocks = dense1_blocks(N);
         const int vec4 = (K % 4 == 0) && (((uintptr_t)x | (uintptr_t)W | (uintptr_t)grad_x | (uintptr_t)ws) % 16 == 0);
         float* part = reinterpret_cast<float*>(ws);
         hipLaunchKernelGGL(k_dense1_bwd, dim3(blocks), dim3(256), 0, st, x, W, y, grad_y, act, N, K, rpb, grad_x, part,
                            vec4);
-        hipLaunchKernelGGL(k_dense1_reduce, dim3(ceil_div(K + 1, 64)), dim3(256), 0, st, part, blocks, K, grad_W,
+        hipLaunchKernelGGL(k_dense1_reduce, dim3(dense1_reduce_grid(K)), dim3(256), 0, st, part, blocks, K, grad_W,
                            grad_b);
         return launch_status("dt_dense_bwd(gemv)");
     }
     if (grad_x) {
         DT_REQUIRE(ws, "dt_dense_bwd: null workspace");
+        const MfmaLaunch g = mfma_launch(N, M, K);
+        DT_UNSUPPORTED(g.lds > kDenseLdsLimit, "dt_dense_bwd: M=%d too large for the LDS row tile", M);
         float* WT = reinterpret_cast<float*>(ws);
         hipLaunchKernelGGL(k_transpose, dim3(ceil_div((int64_t)K * M, 256)), dim3(256), 0, st, W, K, M, WT);
-        const int nbw = dense_nbw(K);
-        const size_t lds = dense_lds(M, nbw);
-        DT_UNSUPPORTED(lds > 150 * 1024, "dt_dense_bwd: M=%d too large for the LDS row tile", M);
-        hipFuncSetAttribute((const void*)k_dense_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_dense_mfma<true>), dim3(ceil_div(N, 32 * (4 / nbw))), dim3(256), lds, st, grad_y, y, act,
-                           WT, nullptr, DT_ACT_LINEAR, N, M, K, nbw, grad_x);
+        hipFuncSetAttribute((const void*)k_dense_mfma<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
+        hipLaunchKernelGGL((k_dense_mfma<true>), dim3(g.grid), dim3(256), g.lds, st, grad_y, y, act, WT, nullptr,
+                           DT_ACT_LINEAR, N, M, K, g.nbw, grad_x, mfma_vec4(M, grad_y, y));
     }
-    const int tiles = ceil_div(K, 32) * ceil_div(M, 32);
-    // enough (tile, batch-split) blocks for ~4 waves per SIMD; each wave keeps >= 64 rows of work
-    int splits = 1024 / tiles;
-    if (splits < 1) splits = 1;
-    if (splits > 512) splits = 512;
-    while (splits > 1 && N / splits < 256) splits >>= 1;
-    hipLaunchKernelGGL(k_dense_wgrad, dim3(tiles, splits), dim3(256), 0, st, x, y, grad_y, act, N, K, M, splits,
+    const WgradLaunch g = wgrad_launch(N, K, M);
+    hipLaunchKernelGGL(k_dense_wgrad, dim3(g.tiles, g.splits), dim3(256), 0, st, x, y, grad_y, act, N, K, M, g.splits,
                        grad_W, grad_b);
     return launch_status("dt_dense_bwd");
 }

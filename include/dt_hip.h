@@ -433,6 +433,14 @@ int dt_ftrl_rows_step(float* table, float* accum, float* linear, const int64_t* 
  *   grad_b += colsum(G) are ACCUMULATED (zero them first); ws: dt_dense_workspace_bytes(N,K,M) bytes.        */
 int dt_dense_supported(int N, int K, int M);
 int64_t dt_dense_workspace_bytes(int N, int K, int M);
+/* the launch geometry, for tests and tools that have to reach one launch path, from the helpers the launches use.  product:
+ *   0 forward, 1 grad_x (M >= 2): out = {column waves NBW, rows per block, grid, dynamic LDS bytes, pipelined 16-step chunks,
+ *     trips of the guarded remainder loop (an odd row length's last step included), 1 where the row length permits 16-byte
+ *     staging loads (the launch also asks for 16-byte aligned pointers), 0};
+ *   2 grad_W (M >= 2): out = {32 x 32 tiles, batch splits, rows per split, 0...};
+ *   3 Dense(1) forward: out = {grid, 0...};   4 Dense(1) backward: out = {rows per block, blocks, blocks of the reduce, 0...}.
+ * out: HOST int[8]; no launch; DT_ERR_UNSUPPORTED outside dt_dense_supported or for a product of the other M */
+int dt_dense_geometry(int N, int K, int M, int product, int* out);
 int dt_dense_fwd(const float* x, const float* W, const float* bias, int act, int N, int K, int M, float* y,
                  void* stream);
 int dt_dense_bwd(const float* x, const float* W, const float* y, const float* grad_y, int act, int N, int K,
