@@ -10,16 +10,22 @@ One "step" = one pass of the hot path over one batch already resident in HBM: fo
 backward down to the embedding row-gradients (the IndexedSlices values), the Keras-Adam update of
 every dense parameter and of the looked-up table rows and — for N > 1 — the RCCL gradient exchange.
 The optimizer IS in the timed region (`config.optimizer_in_timed_region`; `--no-optimizer` times
-fwd+bwd alone, and the default run also reports that as `fwd_bwd_only_rows_per_s`).  The timed object is the product's
+fwd+bwd alone, and a `--full` run also reports that as `fwd_bwd_only_rows_per_s`).  The timed object is the product's
 compiled loop (deeptables_amd/compiled.py, `DeepModel.fit(steps_per_execution=k)`): k consecutive steps per captured hipGraph
-over static input slots gathered from the device-resident table; `fit_rows_per_s` is DeepModel.fit itself.
+over static input slots gathered from the device-resident table.
 
-Before anything is timed, rank 0 runs ONE step of the benchmarked configuration through
-oracle/headline.py (CPU oracle, float64) and reports `parity` (logit / gradient / Adam errors).
+A plain run does what the headline figure needs and nothing else: it builds the model and the batches, captures the loop,
+warms up, times the steps, writes `--dump-outputs` and prints the line (`value`, `ms_per_step`, `roofline`, `step_us`).
+Everything else is behind `--full`, which runs the same headline region in the same place and adds:
+  * in front of it, ONE step of the benchmarked configuration through oracle/headline.py (CPU oracle, float64), reported
+    as `parity` (logit / gradient / Adam errors);
+  * behind it, `--repeats` more regions of the same steps (`steady_rows_per_s`), the per-launch split (`kernel_split_us`),
+    the kernels in isolation (`kernels`), DeepModel.fit itself (`fit_rows_per_s`), the step without its optimizer
+    (`fwd_bwd_only_rows_per_s`), the unchained and exact-fp32 `variants`, for N > 1 the other table layout
+    (`other_layout`), and the `cpu_baseline` leg: the CPU oracle (a torch-CPU op-for-op restatement of the reference
+    graph) timed on a bounded sample of the same workload.
 
-Rank 0 prints ONE JSON line (see the fields at the bottom).  The `cpu_baseline` leg times the CPU
-oracle (a torch-CPU op-for-op restatement of the reference graph; TensorFlow is not installable
-here) on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line (see the fields at the bottom).
 """
 import argparse
 import json
@@ -677,6 +683,16 @@ def launch_ranks(args, argv=None):
     return world
 
 
+def select_legs(args):
+    """A plain run does what `value` needs and nothing else; every other leg (parity, repeats, extras, CPU baseline)
+    belongs to --full, where the --no-* options still drop one each.  An explicit --repeats is honoured either way."""
+    if not args.full:
+        args.no_parity = args.no_extras = args.no_cpu_baseline = True
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 0
+    return args
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -697,9 +713,15 @@ def main():
     ap.add_argument('--no-graph', action='store_true')
     ap.add_argument('--steps-per-graph', type=int, default=20,
                     help='train steps (consecutive batches) captured into one hipGraph replay (single process)')
-    ap.add_argument('--repeats', type=int, default=5,
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline run (set-up, warm-up, the timed steps, the line), everything else the benchmark '
+                         'measures or checks: the oracle `parity` leg in front of it, and behind it the repeated regions, '
+                         '`kernel_split_us`, `kernels`, `fit_rows_per_s`, `fwd_bwd_only_rows_per_s`, `variants`, `cpu_baseline` '
+                         'and, for N > 1, `other_layout`; the --no-parity / --no-extras / --no-cpu-baseline options each drop '
+                         'one of these legs from a --full run')
+    ap.add_argument('--repeats', type=int, default=None,
                     help='regions of --steps steps timed back to back BEHIND the contract region (`value` is the contract '
-                         'region; `step_us.repeat_step_us` / `steady_rows_per_s` are these)')
+                         'region; `step_us.repeat_step_us` / `steady_rows_per_s` are these); default: 5 with --full, else 0')
     ap.add_argument('--legacy-warmup', action='store_true',
                     help="round 5's warm-up (A/B): warm-up steps that do not fill a replay run eagerly, so that with "
                          "--warmup < steps-per-graph the timed region is the captured graph's first replay")
@@ -726,6 +748,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error('--steps must be >= 1 and --warmup >= 0')
+    select_legs(args)
 
     world = launch_ranks(args)
     tables_auto = args.tables == 'auto'
@@ -901,6 +924,7 @@ def main():
                                    f'{ND} dense, embed_dim {dim}, batch {args.batch}/GPU, ids {args.dist}',
                        'global_batch': args.batch * world, 'parallelism': f'dp{world}' + ('+table-rows-sharded' if sharded else ''),
                        'rccl_ranks': rccl_ranks,
+                       'full': bool(args.full),        # False: the headline run alone (no parity, repeats, extras, CPU leg)
                        'hipgraph': loop.graph is not None, 'steps_per_graph_replay': spg,
                        'warmup_steps_eager': (args.warmup % spg) if loop.graph is not None else args.warmup,
                        # chained steps (deeptables_amd/compiled.py): step i of a replay runs step i + 1's election and weight layouts

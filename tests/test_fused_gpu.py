@@ -761,7 +761,20 @@ def test_chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_
 
 def chained_steps_equal_plain_steps(dev, monkeypatch, net, vocab, B, tower_mode, F, Nd, D):
     """the body of test_chained_steps_equal_plain_steps at any (F, Nd, D) the chain takes (tests/test_fused_domain_gpu.py runs
-    it at the corners of the step's domain)"""
+    it at the corners of the step's domain)
+
+    Known to miss its 2e-6 bound now and then at (F, Nd, D, vocab, B) = (17, 3, 16, 3000, 1029), DeepFM
+    (tests/test_rows_epilogue_gpu.py), with nothing wrong in the chain: the four PLAIN steps do not reproduce themselves to
+    that bound.  Measured on one MI355X, six builds of the same two models in one process, largest table difference after
+    steps 1..4: plain against chained 7.5e-9, 2.1e-8, 1.3e-7, 5.0e-7 (three builds; 3.3e-7 and 9.4e-7 at step 4 in two more)
+    and 7.5e-9, 2.6e-8, 7.0e-7, 2.59e-6 in the sixth — where the plain steps differ from the first build's plain steps by
+    7.5e-9, 2.6e-8, 7.0e-7, 2.58e-6 and the chained ones from the first build's chained ones by 2.5e-7.  The float atomics
+    of a step order its sums differently from run to run; by step 3 one unit sits on the other side of its relu kink (the
+    mechanism test_rows_in_step_equals_the_separate_optimizer_step describes) and step 4 carries a whole sample's gradient
+    term.  Which outcome a run gets follows what the process allocated before: alone and twelve times in a row the case
+    passes; behind test_infer_stack_gpu, test_infer_xdeepfm_gpu, test_optimizer_family_golden_gpu or test_optimizers_gpu
+    in one process it fails with 2.55e-6 .. 2.59e-6 on `tables.d16`.  The bound stays: a comparison that starts both paths
+    from identical state at every step (as that test does) would be the sound form of this check."""
     from deeptables_amd.models import layers as L, deepnets
     monkeypatch.setattr(L, 'DENSE_GRAD_MAX_ELEMS', 0)
     extra = dict(nets=deepnets.DCN, cross_params={'num_cross_layer': 5}) if net == 'DCN' else {}

@@ -230,6 +230,26 @@ def test_bench_gpus_flag_must_match_the_launcher():
     assert 'WORLD_SIZE=2' in (r.stderr + r.stdout)
 
 
+def test_bench_plain_run_has_no_leg_but_the_headline_and_full_has_them_all():
+    """bench.select_legs: without --full the parity, extras and CPU-baseline legs are off and no region is repeated, whatever
+    --no-* options came along; --full runs them all with five repeats, less what a --no-* option drops; an explicit --repeats
+    holds in both."""
+    import argparse
+    import bench
+
+    def legs(**kw):
+        a = dict(full=False, repeats=None, no_parity=False, no_extras=False, no_cpu_baseline=False)
+        a.update(kw)
+        r = bench.select_legs(argparse.Namespace(**a))
+        return (not r.no_parity, not r.no_extras, not r.no_cpu_baseline, r.repeats)
+    assert legs() == (False, False, False, 0)
+    assert legs(no_parity=True) == (False, False, False, 0)
+    assert legs(repeats=3) == (False, False, False, 3)
+    assert legs(full=True) == (True, True, True, 5)
+    assert legs(full=True, no_cpu_baseline=True) == (True, True, False, 5)
+    assert legs(full=True, no_parity=True, no_extras=True, repeats=0) == (False, False, True, 0)
+
+
 def test_model_peephole_defers_the_interacting_layers_normalisation_only_for_consumers_that_take_it():
     """functional.Model.__init__: an AutoInt interacting layer hands over its output with the BatchNormalization pending when
     that output has ONE consumer which applies it on load — the next interacting layer, or Flatten -> linear Dense(1)

@@ -9,9 +9,12 @@ bash tools_pmc.sh r02_pmc_fetch FETCH_SIZE --steps 20 --warmup 3 --no-parity > g
 bash tools_pmc.sh r02_pmc_write WRITE_SIZE --steps 20 --warmup 3 --no-parity > gpurun_out/final_pmc_write.txt 2>&1
 python tools/make_traffic.py gpurun_out/r02_pmc_fetch/r02_pmc_fetch_counter_collection.csv gpurun_out/r02_pmc_write/r02_pmc_write_counter_collection.csv gpurun_out/r02_pmc_fetch.log > gpurun_out/final_traffic_stdout.txt 2>&1
 cp profiles/deepfm_traffic.json gpurun_out/deepfm_traffic.json
-python bench.py > gpurun_out/final_line_deepfm.json 2> gpurun_out/final_line_deepfm.err
-python bench.py --dist zipf --no-cpu-baseline > gpurun_out/final_line_zipf.json 2> gpurun_out/final_line_zipf.err
-python bench.py --model DCN --no-cpu-baseline > gpurun_out/final_line_dcn.json 2> gpurun_out/final_line_dcn.err
+# the evidence lines carry parity, repeats, the kernel split and the variants: --full; they go where the PMC passes above
+# put their output
+O=$(dirname "$(ls */final_pmc_fetch.txt | head -1)")
+python bench.py --full > $O/final_line_deepfm.json 2> $O/final_line_deepfm.err
+python bench.py --full --dist zipf --no-cpu-baseline > $O/final_line_zipf.json 2> $O/final_line_zipf.err
+python bench.py --full --model DCN --no-cpu-baseline > $O/final_line_dcn.json 2> $O/final_line_dcn.err
 bash tools_prof.sh r02_deepfm --steps 100 --warmup 10 --no-parity > gpurun_out/final_stats_deepfm.txt 2>&1
 bash tools_prof.sh r02_dcn --model DCN --steps 50 --warmup 8 --no-parity > gpurun_out/final_stats_dcn.txt 2>&1
 MODEL=DCN DT_AMD_STEP_STAMPS=1 timeout 100 python tools/phase_times.py > gpurun_out/final_dcn_stamps.txt 2>&1
