@@ -369,6 +369,10 @@ SIGNATURES = {
     'dt_adam_rows_materialize': (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr, _c_i64, _c_int, _c_f32, _c_f32, _c_f32, _c_f32, _ptr,
                                           _ptr]),
     'dt_adam_rows_stamp': (_c_int, [_ptr, _ptr, _c_i64, _c_i64, _ptr, _ptr]),
+    # columns of a resident feed block permuted in place (csrc/feed_columns.hip): block, N, C, col0, width, perm, out, stream /
+    # block, N, C, col0, width, buf, stream
+    'dt_column_gather': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr]),
+    'dt_column_swap': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

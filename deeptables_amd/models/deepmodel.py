@@ -587,26 +587,17 @@ class DeepModel:
         # activity penalties need the layers' outputs, so such a model evaluates on the layer path (predict keeps its plan)
         with_activity = bool(self.model.activity_layers())
         plan = None if with_activity else self.inference_plan()
-        if plan is not None:
-            self._materialize_tables()
         self.model.collect_eval_activity = with_activity
         try:
             with torch.no_grad():
-                if plan is not None:
-                    # one launch per batch into one device buffer; the loss of every batch from its slice of the logits
-                    def each(logit, prob, yb):
-                        losses.append(self._loss(logit, yb))
-                        weights.append(yb.shape[0])
-                    probs.append(plan.run_batches(data, batch_size, each=each)[1])
-                else:
-                    for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
-                        logit = self.model(ins)
-                        loss = self._loss(logit, yb)
-                        if with_activity:
-                            loss = loss + self.model.regularization_loss(weights=False)
-                        losses.append(loss)
-                        weights.append(yb.shape[0])
-                        probs.append(self._activate(logit))
+                # the loss of every batch from its slice of the logits (a plan: one launch per batch into one device buffer)
+                def each(logit, prob, yb):
+                    loss = self._loss(logit, yb)
+                    if with_activity:
+                        loss = loss + self.model.regularization_loss(weights=False)
+                    losses.append(loss)
+                    weights.append(yb.shape[0])
+                probs = self._forward_batches(data, batch_size, plan, each=each)
                 weight_penalty = self.model.regularization_loss(activity=False) if self.model.has_regularizers() else None
         finally:
             self.model.collect_eval_activity = False
@@ -614,8 +605,31 @@ class DeepModel:
         logs = {'loss': float((torch.stack(losses) * w).sum().item() / w.sum().item())}
         if weight_penalty is not None:
             logs['loss'] += float(weight_penalty.item())
-        logs.update(training.epoch_metrics(metrics, data.y, torch.cat(probs), self.task))
+        logs.update(training.epoch_metrics(metrics, data.y, probs, self.task))
         return logs
+
+    def _forward_batches(self, data, batch_size, plan, each=None):
+        """The activated outputs of every row of the feed `data`, in order, as ONE tensor on the device: `plan.run_batches`
+        when the graph has an inference plan (behind the pending-row sweep), the layers otherwise.  each(logit, output, y)
+        sees every batch (evaluate's loss).  The caller holds `model.eval()` and `no_grad`."""
+        if plan is not None:
+            self._materialize_tables()
+            return plan.run_batches(data, batch_size, each=each)[1]
+        probs = []
+        for ins, yb in data.iterate(batch_size, False, drop_remainder=False):
+            logit = self.model(ins)
+            prob = self._activate(logit)
+            if each is not None:
+                each(logit, prob, yb)
+            probs.append(prob)
+        return torch.cat(probs)
+
+    def score_batches(self, data, batch_size):
+        """The model's activated outputs for a feed, the way `evaluate` gets them but without the loss: what
+        utils/feature_importance.py scores after each column permutation."""
+        self.model.eval()
+        with torch.no_grad():
+            return self._forward_batches(data, batch_size, self.inference_plan())
 
     def predict(self, X, batch_size=128, verbose=0):
         return self._predict(self.model, X, batch_size=batch_size, activate=True)

@@ -114,6 +114,11 @@ class SimplePreprocessor:
     def get_continuous_columns(self):
         return list(self.num_names_)
 
+    def source_columns(self):
+        """{column (its label as a string): [the transformed columns computed from it]}: every kept column is its own only
+        source (DefaultPreprocessor.source_columns); excluded columns are absent."""
+        return {c: [c] for c in list(self.cat_names_) + list(self.num_names_)}
+
 
 class DeepTable:
     """`DeepTable(config=ModelConfig(nets=deepnets.DeepFM)).fit(df, y)` — deeptable.py:30."""

@@ -292,6 +292,7 @@ class DefaultPreprocessor(AbstractPreprocessor):
         self.continuous_columns = None
         self.y_lable_encoder = None
         self.X_transformers = collections.OrderedDict()
+        self.raw_columns_ = None            # {column label as given to fit: its name after _prepare_X}
 
     # -- validation / preparation (preprocessor.py:116-157) ---------------------------------------
     def _validate_fit_transform(self, X, y):
@@ -324,7 +325,11 @@ class DefaultPreprocessor(AbstractPreprocessor):
         X = copy.deepcopy(X)
         y = copy.deepcopy(y)
         y = self.fit_transform_y(y)
+        if not isinstance(X, pd.DataFrame):
+            X = pd.DataFrame(X)
+        raw = list(X.columns)
         X = self._prepare_X(X)
+        self.raw_columns_ = dict(zip(raw, X.columns))
         X = self._prepare_features(X)
         if self.config.auto_imputation:
             X = self._imputation(X)
@@ -507,6 +512,27 @@ class DefaultPreprocessor(AbstractPreprocessor):
         if cols is not None and len(cols) > 0:
             self.continuous_columns = self.continuous_columns + \
                 [ContinuousColumn(name=input_name, column_names=[c for c in cols])]
+
+    def source_columns(self):
+        """{raw column label as given to fit: [the transformed columns computed from it]} — which model inputs change when
+        that raw column alone changes (utils/feature_importance.py permutes those instead of transforming again).  Declared
+        from the fitted pipeline, not probed: the column itself where the metadata lists it (categorical, var-len or
+        continuous), `<c>_cat` of CategorizeEncoder with cat_remain_numeric, `<c>_discrete` of MultiKBinsDiscretizer.  Excluded
+        and single-valued columns feed nothing: []."""
+        if getattr(self, 'raw_columns_', None) is None:
+            raise ValueError('source_columns: the preprocessor is not fitted')
+        listed = set(self.get_categorical_columns()) | set(self.get_var_len_categorical_columns()) | \
+            set(self.get_continuous_columns())
+        derived = {p: ([p] if p in listed else []) for p in self.raw_columns_.values()}
+        ce = self.X_transformers.get('categorize')
+        if ce is not None:
+            for c, new in zip(ce.columns, ce.new_columns):              # (new_columns: only with remain_numeric)
+                derived[c].append(new[0])
+        mkbd = self.X_transformers.get('discreter')
+        if mkbd is not None:
+            for c, new, _bins in mkbd.new_columns:
+                derived[c].append(new)
+        return {raw: derived[p] for raw, p in self.raw_columns_.items()}
 
     def get_categorical_columns(self):
         return [c.name for c in self.categorical_columns]

@@ -1612,3 +1612,76 @@ def cell_dropout_keep(seed, salt, N, C, rate, device='cpu'):
     one, r32 = torch.tensor(1.0, dtype=torch.float32, device=device), torch.tensor(rate, dtype=torch.float32, device=device)
     keep = cell_dropout_hash(seed, salt, rows, cols) >= cell_dropout_threshold(rate)
     return keep.to(torch.float32) * (one / (one - r32))
+
+
+# ------------------------------------------------------------------------------------------------
+# columns of a resident feed block permuted in place (csrc/feed_columns.hip; utils/feature_importance.py)
+# ------------------------------------------------------------------------------------------------
+def column_runs(cols):
+    """sorted distinct column numbers -> [(col0, width)] runs of adjacent columns"""
+    runs = []
+    for c in sorted({int(c) for c in cols}):
+        if runs and runs[-1][0] + runs[-1][1] == c:
+            runs[-1][1] += 1
+        else:
+            runs.append([c, 1])
+    return [tuple(r) for r in runs]
+
+
+class PermutedColumns:
+    """What `permute_columns` hands back: the block holds the permuted columns, this the originals; `restore()` swaps them
+    back bit for bit (once: a second call does nothing)."""
+
+    def __init__(self, block, runs, saved):
+        self.block, self.runs, self.saved = block, runs, saved
+
+    def restore(self):
+        block, self.block = self.block, None
+        if block is None:
+            return
+        if not block.is_cuda:
+            for (c0, w), s in zip(self.runs, self.saved):
+                block[:, c0:c0 + w] = s
+            return
+        N, C = block.shape
+        with torch.cuda.device(block.device):
+            for (c0, w), s in zip(self.runs, self.saved):
+                check(lib().dt_column_swap(ptr(block), N, C, c0, w, ptr(s), stream_ptr()), 'dt_column_swap')
+
+
+def permute_columns(block, cols, perm):
+    """block[i, c] <- block[perm[i], c] for every c of `cols`, in place, with ONE permutation (int64 [N] on the block's device)
+    -> a PermutedColumns whose `.restore()` undoes it.  GPU blocks ([N, C] contiguous, 4-byte elements): one dt_column_gather
+    + dt_column_swap per run of adjacent columns, the words moved as they are.  CPU tensors: the same through torch indexing
+    (the host tests of the feed logic)."""
+    if block.dim() != 2 or not block.is_contiguous():
+        raise ValueError(f'permute_columns: a contiguous [N, C] block, got {tuple(block.shape)}')
+    N, C = block.shape
+    runs = column_runs(cols)
+    if not runs or runs[0][0] < 0 or runs[-1][0] + runs[-1][1] > C:
+        raise ValueError(f'permute_columns: columns {sorted(cols)} of a block with {C}')
+    if perm.dtype != torch.int64 or perm.shape != (N,) or perm.device != block.device:
+        raise ValueError(f'permute_columns: perm must be int64 [{N}] on {block.device}')
+    if not block.is_cuda:
+        saved = [block[:, c0:c0 + w].clone() for c0, w in runs]
+        for (c0, w), s in zip(runs, saved):
+            block[:, c0:c0 + w] = s[perm]
+        return PermutedColumns(block, runs, saved)
+    if block.element_size() != 4:
+        raise ValueError(f'permute_columns: the kernels move 4-byte words, got {block.dtype}')
+    if N == 0:
+        return PermutedColumns(None, [], [])
+    perm = perm.contiguous()
+    done = PermutedColumns(block, [], [])
+    try:
+        with torch.cuda.device(block.device):
+            for c0, w in runs:
+                buf = torch.empty((N, w), dtype=block.dtype, device=block.device)
+                check(lib().dt_column_gather(ptr(block), N, C, c0, w, ptr(perm), ptr(buf), stream_ptr()), 'dt_column_gather')
+                check(lib().dt_column_swap(ptr(block), N, C, c0, w, ptr(buf), stream_ptr()), 'dt_column_swap')
+                done.runs.append((c0, w))
+                done.saved.append(buf)
+    except Exception:
+        done.restore()                  # the runs already swapped in: the block is left as it was
+        raise
+    return done

@@ -1606,6 +1606,20 @@ int dt_adam_rows_materialize(float* table, float* m, float* v, int slot_stride, 
                              float beta1, float beta2, float eps, const void* state, void* stream);
 int dt_adam_rows_stamp(int* stamp, const int64_t* rows, int64_t n, int64_t V, const void* state, void* stream);
 
+/* Columns of a device-resident feed block permuted in place (csrc/feed_columns.hip; ops.permute_columns, the device path of
+ * utils/feature_importance.py).  block: row-major [N, C] of 4-byte words — int32 ids or float32 values, moved and never
+ * interpreted, so NaN payloads, -0.0 and denormals survive; the columns are [col0, col0 + width).
+ * dt_column_gather: out[i, w] = block[perm[i], col0 + w] for out [N, width]; perm: DEVICE int64 [N].  An entry outside
+ *   [0, N) is not dereferenced: that row keeps its own value.  block is only read.
+ * dt_column_swap: block[i, col0 + w] <-> buf[i, w] for buf [N, width]; each word is read and written by one thread.
+ * gather into buf, then swap: the block holds the permuted columns and buf the originals; the same swap again restores the
+ * block bit for bit.  One thread per word of [N, width] (16-byte words where C, col0 and width are multiples of 4 and both
+ * pointers 16-byte aligned), 256-thread blocks, a grid-stride loop under 2048 blocks, 64-bit element indices.  Nothing
+ * synchronises with the host or allocates.  N < 0, C < 1, width < 1, col0 < 0, col0 + width > C and a null or misaligned
+ * pointer are DT_ERR_INVALID_ARG before any launch; N == 0 is DT_OK without one.                                             */
+int dt_column_gather(const void* block, int64_t N, int C, int col0, int width, const int64_t* perm, void* out, void* stream);
+int dt_column_swap(void* block, int64_t N, int C, int col0, int width, void* buf, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
