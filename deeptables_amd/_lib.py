@@ -373,6 +373,11 @@ SIGNATURES = {
     # block, N, C, col0, width, buf, stream
     'dt_column_gather': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr]),
     'dt_column_swap': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    # KernelSHAP on a resident feed (csrc/coalition.hip): x, bg, Nb, C, masks, S, M, s0, s1, group, group_host, out, stream /
+    # out, nseg, Nb, O, ey, stream / P, masks, S, M, ey, fx, e0, R, O, phi, stream
+    'dt_coalition_fill': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr]),
+    'dt_coalition_mean': (_c_int, [_ptr, _c_i64, _c_i64, _c_int, _ptr, _ptr]),
+    'dt_shap_solve': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

@@ -5,8 +5,10 @@ Each Function is the forward+backward of one reference `Layer.call` in
 deeptables/models/layers.py; torch is only the carrier of device memory, streams and the
 autograd tape.  All functions require CUDA(HIP) tensors — no CPU fallback.
 """
+import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1685,3 +1687,116 @@ def permute_columns(block, cols, perm):
         done.restore()                  # the runs already swapped in: the block is left as it was
         raise
     return done
+
+
+# ------------------------------------------------------------------------------------------------
+# KernelSHAP on a resident feed (csrc/coalition.hip; utils/shap.py)
+# ------------------------------------------------------------------------------------------------
+def pack_coalitions(masks):
+    """bool [S, M] (numpy) -> int32 [S, ceil(M / 32)] CPU tensor: bit g % 32 of word g / 32 holds player g"""
+    masks = np.asarray(masks, dtype=bool)
+    S, M = masks.shape
+    W = (M + 31) // 32
+    padded = np.zeros((S, W * 32), dtype=np.uint64)
+    padded[:, :M] = masks
+    words = (padded.reshape(S, W, 32) << np.arange(32, dtype=np.uint64)).sum(axis=2)
+    return torch.from_numpy(words.astype(np.uint32).view(np.int32).reshape(S, W).copy())
+
+
+def _coalition_bits(masks, g):
+    """masks int32 [S, W], g int64 [K] (every entry inside the coalitions' players) -> bool [S, K]"""
+    return ((masks.to(torch.int64)[:, g >> 5] >> (g & 31)[None, :]) & 1).bool()
+
+
+def _check_masks(who, masks, M):
+    if masks.dtype != torch.int32 or masks.dim() != 2 or masks.shape[1] != (M + 31) // 32 or not masks.is_contiguous():
+        raise ValueError(f'{who}: masks must be a contiguous int32 [S, {(M + 31) // 32}] for {M} players, got '
+                         f'{masks.dtype} {tuple(masks.shape)}')
+
+
+def coalition_fill(x, bg, masks, M, s0, s1, group, group_host=None, out=None):
+    """out[(s - s0) Nb + b, c] = bit(masks[s], group[c]) ? x[c] : bg[b, c] for the coalitions [s0, s1) -> out [(s1 - s0) Nb, C].
+    x [C] and bg [Nb, C]: one feed block's explained row and background rows (the same 4-byte dtype); masks: int32 [S, W] from
+    `pack_coalitions`; group: int32 [C] on the block's device, the player owning each column or -1; group_host: the same
+    numbers on the host (None: read back from `group`).  GPU tensors: one dt_coalition_fill launch, the words moved as they
+    are.  CPU tensors: the same through torch.where on int32 views (the host tests of the path)."""
+    who = 'coalition_fill'
+    M, s0, s1 = int(M), int(s0), int(s1)
+    if bg.dim() != 2 or not bg.is_contiguous() or bg.element_size() != 4:
+        raise ValueError(f'{who}: a contiguous [Nb, C] block of 4-byte words, got {bg.dtype} {tuple(bg.shape)}')
+    Nb, C = bg.shape
+    x = x.reshape(-1)
+    if x.shape[0] != C or x.dtype != bg.dtype or x.device != bg.device or not x.is_contiguous():
+        raise ValueError(f'{who}: x must be a contiguous {bg.dtype} [{C}] on {bg.device}')
+    _check_masks(who, masks, M)
+    if M < 1 or not 0 <= s0 <= s1 <= masks.shape[0]:
+        raise ValueError(f'{who}: coalitions [{s0}, {s1}) of {masks.shape[0]}, {M} players')
+    if group.dtype != torch.int32 or group.shape != (C,) or group.device != bg.device or not group.is_contiguous():
+        raise ValueError(f'{who}: group must be a contiguous int32 [{C}] on {bg.device}')
+    gh = np.ascontiguousarray(group.cpu().numpy() if group_host is None else np.asarray(group_host), dtype=np.int32)
+    if gh.shape != (C,) or ((gh < -1) | (gh >= M)).any():
+        raise ValueError(f'{who}: group entries must be -1 or a player in [0, {M}), got {gh.tolist()}')
+    rows = (s1 - s0) * Nb
+    if out is None:
+        out = torch.empty((rows, C), dtype=bg.dtype, device=bg.device)
+    elif out.shape != (rows, C) or out.dtype != bg.dtype or out.device != bg.device or not out.is_contiguous():
+        raise ValueError(f'{who}: out must be a contiguous {bg.dtype} [{rows}, {C}] on {bg.device}')
+    if rows == 0 or C == 0:
+        return out
+    if not bg.is_cuda:
+        g = torch.from_numpy(gh).to(torch.int64)
+        take = _coalition_bits(masks[s0:s1], g.clamp(min=0)) & (g >= 0)[None, :]                    # [Sc, C]
+        words = torch.where(take[:, None, :], x.view(torch.int32)[None, None, :], bg.view(torch.int32)[None, :, :])
+        out.view(torch.int32).copy_(words.reshape(rows, C))
+        return out
+    require_cuda(x, masks, group, out)
+    with torch.cuda.device(bg.device):
+        check(lib().dt_coalition_fill(ptr(x), ptr(bg), Nb, C, ptr(masks), masks.shape[0], M, s0, s1, ptr(group),
+                                      ctypes.c_void_p(gh.ctypes.data), ptr(out), stream_ptr()), 'dt_coalition_fill')
+    return out
+
+
+def coalition_mean(out, Nb):
+    """out float32 [nseg Nb, O] -> float64 [nseg, O], the mean of every run of Nb rows (GPU: dt_coalition_mean, a fixed
+    summation order; CPU: torch's float64 sum over the run)"""
+    Nb = int(Nb)
+    if out.dim() != 2 or out.dtype != torch.float32 or not out.is_contiguous() or Nb < 1 or out.shape[0] % Nb:
+        raise ValueError(f'coalition_mean: a contiguous float32 [nseg * {Nb}, O], got {out.dtype} {tuple(out.shape)}')
+    nseg, O = out.shape[0] // Nb, out.shape[1]
+    if not out.is_cuda:
+        return out.double().view(nseg, Nb, O).sum(1) / Nb
+    ey = torch.empty((nseg, O), dtype=torch.float64, device=out.device)
+    with torch.cuda.device(out.device):
+        check(lib().dt_coalition_mean(ptr(out), nseg, Nb, O, ptr(ey), stream_ptr()), 'dt_coalition_mean')
+    return ey
+
+
+def shap_solve(P, masks, M, ey, fx, e0):
+    """P float64 [M - 1, S], masks int32 [S, W], ey float64 [R, S, O], fx float64 [R, O], e0 float64 [O] -> phi float64
+    [R, O, M]: y'_s = ey_s - e0 - z_{s, M-1} (fx - e0), phi_j = sum_s P[j, s] y'_s, phi_{M-1} = (fx - e0) - sum_j phi_j
+    (GPU: dt_shap_solve; CPU: the same in torch)"""
+    who = 'shap_solve'
+    M = int(M)
+    _check_masks(who, masks, M)
+    S = masks.shape[0]
+    if M < 2 or S < 1 or P.shape != (M - 1, S) or ey.dim() != 3 or ey.shape[1] != S:
+        raise ValueError(f'{who}: P [{M - 1}, {S}] and ey [R, {S}, O] for {M} >= 2 players, got {tuple(P.shape)}, '
+                         f'{tuple(ey.shape)}')
+    R, _, O = ey.shape
+    if fx.shape != (R, O) or e0.shape != (O,):
+        raise ValueError(f'{who}: fx [{R}, {O}] and e0 [{O}], got {tuple(fx.shape)}, {tuple(e0.shape)}')
+    for name, t in (('P', P), ('ey', ey), ('fx', fx), ('e0', e0)):
+        if t.dtype != torch.float64 or not t.is_contiguous() or t.device != masks.device:
+            raise ValueError(f'{who}: {name} must be a contiguous float64 tensor on {masks.device}')
+    if not ey.is_cuda:
+        last = torch.tensor([M - 1], dtype=torch.int64)
+        z = _coalition_bits(masks, last)[:, 0].double()                                                # [S]
+        delta = fx - e0[None, :]
+        y = (ey - e0[None, None, :]) - z[None, :, None] * delta[:, None, :]
+        head = torch.einsum('js,rso->roj', P, y)
+        return torch.cat([head, (delta - head.sum(-1))[..., None]], -1).contiguous()
+    phi = torch.empty((R, O, M), dtype=torch.float64, device=ey.device)
+    with torch.cuda.device(ey.device):
+        check(lib().dt_shap_solve(ptr(P), ptr(masks), S, M, ptr(ey), ptr(fx), ptr(e0), R, O, ptr(phi), stream_ptr()),
+              'dt_shap_solve')
+    return phi

@@ -1620,6 +1620,35 @@ int dt_adam_rows_stamp(int* stamp, const int64_t* rows, int64_t n, int64_t V, co
 int dt_column_gather(const void* block, int64_t N, int C, int col0, int width, const int64_t* perm, void* out, void* stream);
 int dt_column_swap(void* block, int64_t N, int C, int col0, int width, void* buf, void* stream);
 
+/* KernelSHAP on a device-resident feed (csrc/coalition.hip; ops.coalition_fill / coalition_mean / shap_solve, the device path of
+ * utils/shap.py).  Replaces deeptables/utils/shap.py:11-29 (DeepTablesExplainer: shap.KernelExplainer over `model_fn`, which
+ * builds a DataFrame of hybrid rows per call and runs DeepTable.predict on it): the hybrid rows are written into feed blocks on
+ * the device, the model's outputs are averaged over the background there and the constrained regression is a product with a
+ * matrix the host computes once per coalition plan.
+ * masks: DEVICE uint32 [S, W], W = (M + 31) / 32: bit g % 32 of word g / 32 of coalition s holds player g of M.
+ * dt_coalition_fill (replaces shap.py:23-25, the frame of hybrid rows): x [C], bg [Nb, C], out [(s1 - s0) Nb, C] are 4-byte
+ *   words (int32 ids or float32 values, moved and never interpreted);
+ *   out[(s - s0) Nb + b, c] = bit(masks[s], group[c]) ? x[c] : bg[b, c] for s in [s0, s1).  group: DEVICE int32 [C], the player
+ *   that owns column c, or -1 for a column that always takes the background word; group_host: a HOST copy of it, checked
+ *   against [-1, M) before the launch (the kernel itself treats a value outside [0, M) as -1, so it cannot index past a
+ *   coalition's words).  One thread per word (16-byte words where C % 4 == 0 and x, bg, out are 16-byte aligned), 256-thread
+ *   blocks, a grid-stride loop under 2048 blocks, 64-bit element indices.
+ * dt_coalition_mean (replaces the mean over the background inside shap.py:28, KernelExplainer's `eyVal`):
+ *   ey[seg, o] = (1 / Nb) sum_b out[seg Nb + b, o] for out float32 [nseg Nb, O], ey float64 [nseg, O]; one wave per sum, lane l
+ *   adds rows l, l + 64, ... in order, then a fixed six-step butterfly: no atomics, the same bits on every run; NaN propagates.
+ * dt_shap_solve (replaces the weighted regression inside shap.py:28, KernelExplainer.solve, without its L1 selection):
+ *   for ey float64 [R, S, O], fx float64 [R, O], e0 float64 [O], P float64 [M - 1, S]:
+ *   y'_s = ey_s - e0 - bit(masks[s], M - 1) (fx - e0); phi[r, o, j] = sum_s P[j, s] y'_s for j < M - 1 (the order of
+ *   dt_coalition_mean); phi[r, o, M - 1] = (fx - e0) - sum_j phi[r, o, j].  phi: float64 [R, O, M].
+ * Nothing synchronises with the host or allocates.  Negative sizes, M < 1 (solve: M < 2, S < 1), Nb < 1 for the mean, s0 > s1
+ * or s1 > S, a null or misaligned pointer and a group_host entry outside [-1, M) are DT_ERR_INVALID_ARG before any launch;
+ * empty sizes (s0 == s1, Nb == 0 or C == 0 for the fill; nseg == 0 or O == 0; R == 0 or O == 0) are DT_OK without one.       */
+int dt_coalition_fill(const void* x, const void* bg, int64_t Nb, int C, const uint32_t* masks, int64_t S, int M, int64_t s0,
+                      int64_t s1, const int32_t* group, const int32_t* group_host, void* out, void* stream);
+int dt_coalition_mean(const float* out, int64_t nseg, int64_t Nb, int O, double* ey, void* stream);
+int dt_shap_solve(const double* P, const uint32_t* masks, int64_t S, int M, const double* ey, const double* fx, const double* e0,
+                  int64_t R, int O, double* phi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
