@@ -378,6 +378,11 @@ SIGNATURES = {
     'dt_coalition_fill': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _c_i64, _c_int, _c_i64, _c_i64, _ptr, _ptr, _ptr, _ptr]),
     'dt_coalition_mean': (_c_int, [_ptr, _c_i64, _c_i64, _c_int, _ptr, _ptr]),
     'dt_shap_solve': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _c_i64, _c_int, _ptr, _ptr]),
+    # rows of a resident feed block gathered / scattered, the mean of K output buffers (csrc/feed_rows.hip): block, N, C, idx, n,
+    # out, stream / block, N, C, idx, n, src, stream / parts_host, K, total, mode, out, stream
+    'dt_rows_take': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _c_i64, _ptr, _ptr]),
+    'dt_rows_put': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _c_i64, _ptr, _ptr]),
+    'dt_ensemble_mean': (_c_int, [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1

@@ -403,7 +403,8 @@ class DeepModel:
         """deepmodel.py:114-129 (`model.fit`).  steps_per_execution (Keras' `model.compile` argument, deepmodel.py:319-346):
         k > 1 trains through compiled.CompiledTrainLoop — k consecutive train steps captured into ONE hipGraph over static
         input slots the device-resident feed fills, replayed steps_per_epoch // k times per epoch; None: the module default
-        (`training.DEFAULT_STEPS_PER_EXECUTION`, 'auto' = compiled when the graph has a fused whole-step plan); 1: eager."""
+        (`training.DEFAULT_STEPS_PER_EXECUTION`, 'auto' = compiled when the graph has a fused whole-step plan); 1: eager.
+        validation_data: an (X, y) pair, or a ready `training.TableBatches` carrying its own y and no weight column."""
         feed = X if isinstance(X, training.TableBatches) else None    # a ready (device-resident) feed: trained on as it is
         if feed is not None:
             if validation_data is None:
@@ -411,7 +412,13 @@ class DeepModel:
             if class_weight is not None or sample_weight is not None:
                 raise ValueError('fit(feed): per-row weights belong into the feed (TableBatches(sample_weight=...))')
         n_fit_rows, tr_i = (feed.n if feed is not None else len(X)), None
-        if validation_data is None:
+        # a ready validation feed carrying its own labels (models/cross_validation.py cuts it out of a resident feed)
+        val_feed = validation_data if isinstance(validation_data, training.TableBatches) else None
+        if val_feed is not None:
+            if val_feed.y is None or val_feed.weighted:
+                raise ValueError('fit(validation_data=feed): the feed must carry its labels and no weight column')
+            X_val, y_val = None, None
+        elif validation_data is None:
             n = n_fit_rows
             n_val = int(math.ceil(n * validation_split)) if validation_split else 0
             if n_val > 0:
@@ -469,7 +476,7 @@ class DeepModel:
                                   self.task, self.num_classes,
                                   var_len_categorical_columns=self.var_len_categorical_columns,
                                   resident=getattr(self, 'feed_resident', None), sample_weight=weights)
-        val = None
+        val = val_feed if val_feed is not None and val_feed.n > 0 else None
         if X_val is not None and len(X_val) > 0:
             val = training.TableBatches(X_val, y_val, self.categorical_columns, self.continuous_columns,
                                         self.device, self.task, self.num_classes,
@@ -703,6 +710,21 @@ class DeepModel:
         else:
             checkpoint.load_model(model, filepath, optimizer=self.optimizer)
         return model
+
+    def release_training_state(self):
+        """Keep the weights, drop what only training needs: the optimizer with its slots and gradient buffers, the captured
+        k-step loop and the whole-step plan's workspace (models/cross_validation.py keeps its fold models this way).  The
+        parameters a plan re-homed stay where they are; predict, evaluate, apply and save go on working, fit does not."""
+        info = self.model_desc.optimizer_info()
+        self.model_desc.optimizer = info if info is None or isinstance(info, str) else type(info).__name__
+        self.optimizer = None
+        self.model._dt_flat_grad = None
+        self.compiled_loop = None
+        if hasattr(self, '_fused_plan'):
+            del self._fused_plan
+        self._generic_flat_grad = None
+        for p in self.model.parameters():
+            p.grad = None
 
     def release(self):
         self.model = None

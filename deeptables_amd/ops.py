@@ -1800,3 +1800,111 @@ def shap_solve(P, masks, M, ey, fx, e0):
         check(lib().dt_shap_solve(ptr(P), ptr(masks), S, M, ptr(ey), ptr(fx), ptr(e0), R, O, ptr(phi), stream_ptr()),
               'dt_shap_solve')
     return phi
+
+
+# ------------------------------------------------------------------------------------------------
+# rows of a resident feed gathered / scattered, the mean of K output buffers (csrc/feed_rows.hip; models/cross_validation.py)
+# ------------------------------------------------------------------------------------------------
+def _row_words(who, t):
+    """a contiguous tensor of 4-byte elements whose first dimension counts rows -> (N, C words per row)"""
+    if t.dim() < 1 or not t.is_contiguous() or t.element_size() != 4:
+        raise ValueError(f'{who}: a contiguous [N, ...] tensor of 4-byte elements, got {t.dtype} {tuple(t.shape)}')
+    N = int(t.shape[0])
+    C = 1
+    for s in t.shape[1:]:
+        C *= int(s)
+    if C < 1:
+        raise ValueError(f'{who}: rows without words, got {tuple(t.shape)}')
+    return N, C
+
+
+def _row_index(who, idx, device):
+    if idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != device:
+        raise ValueError(f'{who}: idx must be int64 [n] on {device}, got {idx.dtype} {tuple(idx.shape)} on {idx.device}')
+    return idx.contiguous()
+
+
+def take_rows(block, idx):
+    """out[i] = block[idx[i]] for idx int64 [n] on the block's device -> a new [n, ...] tensor of the block's dtype.  Repeats are
+    allowed, n may exceed N; an entry outside [0, N) gives a row of zero words.  GPU blocks: one dt_rows_take launch, the words
+    moved as they are.  CPU tensors: the same through torch indexing on int32 views (the host tests of the fold logic)."""
+    who = 'take_rows'
+    N, C = _row_words(who, block)
+    idx = _row_index(who, idx, block.device)
+    n = int(idx.shape[0])
+    out = torch.empty((n,) + tuple(block.shape[1:]), dtype=block.dtype, device=block.device)
+    if not block.is_cuda:
+        ok = (idx >= 0) & (idx < N)
+        words = out.view(torch.int32).view(n, C)
+        words.zero_()
+        words[ok] = block.view(torch.int32).view(N, C)[idx[ok]]
+        return out
+    if n == 0:
+        return out
+    if N == 0:                          # no row to read (and no pointer to pass): every entry is out of range
+        return out.zero_()
+    with torch.cuda.device(block.device):
+        check(lib().dt_rows_take(ptr(block), N, C, ptr(idx), n, ptr(out), stream_ptr()), 'dt_rows_take')
+    return out
+
+
+def put_rows(block, idx, src):
+    """block[idx[i]] = src[i] in place, for idx int64 [n] and src [n, ...] of the block's dtype and row shape; rows idx does not
+    name keep their bits, an entry outside [0, N) is skipped, duplicate entries are the caller's error.  GPU blocks: one
+    dt_rows_put launch.  CPU tensors: torch indexing on int32 views.  -> block"""
+    who = 'put_rows'
+    N, C = _row_words(who, block)
+    idx = _row_index(who, idx, block.device)
+    n = int(idx.shape[0])
+    if src.dtype != block.dtype or src.device != block.device or not src.is_contiguous() or \
+            tuple(src.shape) != (n,) + tuple(block.shape[1:]):
+        raise ValueError(f'{who}: src must be a contiguous {block.dtype} {(n,) + tuple(block.shape[1:])} on {block.device}, got '
+                         f'{src.dtype} {tuple(src.shape)}')
+    if not block.is_cuda:
+        ok = (idx >= 0) & (idx < N)
+        block.view(torch.int32).view(N, C)[idx[ok]] = src.view(torch.int32).view(n, C)[ok]
+        return block
+    if n == 0 or N == 0:
+        return block
+    with torch.cuda.device(block.device):
+        check(lib().dt_rows_put(ptr(block), N, C, ptr(idx), n, ptr(src), stream_ptr()), 'dt_rows_put')
+    return block
+
+
+ENSEMBLE_MAX_PARTS = 64
+
+
+def ensemble_mean(parts, mode=0):
+    """The mean of K float32 tensors of one shape, element by element in the order of `parts`.  mode 0: float64
+    (sum_k (double)p_k) / K — numpy's `acc = zeros(float64); acc += p; acc /= K`; mode 1: float32 sum_k (p_k / float32(K)) —
+    numpy's running `mean = p_0 / K; mean += p_k / K` on float32.  GPU tensors: one dt_ensemble_mean launch (1 <= K <= 64).  CPU tensors: torch."""
+    who = 'ensemble_mean'
+    parts = list(parts)
+    K = len(parts)
+    if K < 1 or K > ENSEMBLE_MAX_PARTS:
+        raise ValueError(f'{who}: {K} parts, 1 to {ENSEMBLE_MAX_PARTS} are served')
+    if mode not in (0, 1):
+        raise ValueError(f'{who}: unknown mode {mode!r} (0: float64 mean, 1: float32 running mean)')
+    first = parts[0]
+    for p in parts:
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.shape != first.shape or p.device != first.device:
+            raise ValueError(f'{who}: every part must be a contiguous float32 {tuple(first.shape)} on {first.device}, got '
+                             f'{p.dtype} {tuple(p.shape)} on {p.device}')
+    if not first.is_cuda:
+        if mode == 0:
+            acc = torch.zeros(first.shape, dtype=torch.float64)
+            for p in parts:
+                acc += p.double()
+            return acc / K
+        fk = torch.tensor(float(K), dtype=torch.float32)
+        acc = first / fk
+        for p in parts[1:]:
+            acc += p / fk
+        return acc
+    out = torch.empty(first.shape, dtype=torch.float64 if mode == 0 else torch.float32, device=first.device)
+    if first.numel() == 0:
+        return out
+    table = (ctypes.c_void_p * K)(*[p.data_ptr() for p in parts])
+    with torch.cuda.device(first.device):
+        check(lib().dt_ensemble_mean(table, K, first.numel(), mode, ptr(out), stream_ptr()), 'dt_ensemble_mean')
+    return out

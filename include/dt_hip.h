@@ -1649,6 +1649,29 @@ int dt_coalition_mean(const float* out, int64_t nseg, int64_t Nb, int O, double*
 int dt_shap_solve(const double* P, const uint32_t* masks, int64_t S, int M, const double* ey, const double* fx, const double* e0,
                   int64_t R, int O, double* phi, void* stream);
 
+/* Rows of a device-resident feed block gathered and scattered, and the mean of K output buffers (csrc/feed_rows.hip;
+ * ops.take_rows / put_rows / ensemble_mean, the device path of models/cross_validation.py).  block: row-major [N, C] of 4-byte
+ * words — int32 ids or float32 values, moved and never interpreted; idx: DEVICE int64 [n].
+ * dt_rows_take (replaces deeptables/models/deeptable.py:449, `tb.select_df(X, train_idx)`, `y[train_idx]` and their validation
+ *   twins, a pandas slice per fold): out[i, :] = block[idx[i], :] for out [n, C], i < n.  Repeats are allowed and n may exceed N;
+ *   block is only read.  An entry outside [0, N) is not dereferenced: its row of out is zero words.
+ * dt_rows_put (replaces deeptable.py:455, `oof_proba[idx] = fold_oof_proba` on the host): block[idx[i], :] = src[i, :] for src
+ *   [n, C].  A row idx does not name keeps its bits; an entry outside [0, N) is skipped; duplicate entries are a caller error
+ *   (one of them wins, nothing faults).
+ * dt_ensemble_mean (replaces deeptable.py:456-465, the running `proba_mean += fold_proba / num_folds`, and deeptable.py:549-552,
+ *   predict_proba's `proba_avg += proba; proba_avg /= len(models)`): parts_host is a HOST array of K DEVICE pointers to float32
+ *   [total], 1 <= K <= 64, which travel in the kernel's argument struct (no table copy: the launch can be captured).
+ *   mode 0: out float64 [total] = (sum_k (double)p_k) / K; mode 1: out float32 [total] = sum_k (p_k / (float)K) in float32 with a
+ *   correctly rounded division.  Each thread sums its element in the order k = 0..K-1 (mode 0 from +0, mode 1 from its first
+ *   quotient): no atomics, the same bits on every run.  Parts may alias each other.
+ * One thread per word (16-byte words where C % 4 == 0 and both pointers are 16-byte aligned), 256-thread blocks, a grid-stride
+ * loop under 2048 blocks, 64-bit element indices.  Nothing synchronises with the host or allocates.  N < 0, C < 1, n < 0,
+ * K outside [1, 64], total < 0, an unknown mode and a null or misaligned pointer are DT_ERR_INVALID_ARG before any launch;
+ * n == 0 (put: N == 0 as well) and total == 0 are DT_OK without one.                                                         */
+int dt_rows_take(const void* block, int64_t N, int C, const int64_t* idx, int64_t n, void* out, void* stream);
+int dt_rows_put(void* block, int64_t N, int C, const int64_t* idx, int64_t n, const void* src, void* stream);
+int dt_ensemble_mean(const void* const* parts_host, int K, int64_t total, int mode, void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
