@@ -383,6 +383,8 @@ SIGNATURES = {
     'dt_rows_take': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _c_i64, _ptr, _ptr]),
     'dt_rows_put': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _c_i64, _ptr, _ptr]),
     'dt_ensemble_mean': (_c_int, [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
+    # the fitted preprocessor's transform on the device (csrc/prep_transform.hip): N, cols, cols_host, C, out_kind, out, stream
+    'dt_prep_transform': (_c_int, [_c_i64, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -421,6 +423,13 @@ DT_LOSS_MAX_CLASSES = 4096
 DT_GHMC_MAX_BINS = 256
 DT_CLIP_VALUE, DT_CLIP_NORM, DT_CLIP_GLOBAL_NORM = 0, 1, 2
 DT_FIELD_SUMSQ_PARTS = 32
+# dt_prep_transform: source dtype codes, operations, flags, output kinds and the kernel's tile geometry (include/dt_hip.h)
+DT_PREP_BOOL, DT_PREP_I8, DT_PREP_I16, DT_PREP_I32, DT_PREP_I64 = 0, 1, 2, 3, 4
+DT_PREP_U8, DT_PREP_U16, DT_PREP_U32, DT_PREP_U64, DT_PREP_F32, DT_PREP_F64, DT_PREP_DTYPE_COUNT = 5, 6, 7, 8, 9, 10, 11
+DT_PREP_LOOKUP, DT_PREP_CONT, DT_PREP_BIN, DT_PREP_COPY = 0, 1, 2, 3
+DT_PREP_IMPUTE, DT_PREP_SCALE = 0x1, 0x2
+DT_PREP_OUT_I32, DT_PREP_OUT_F32 = 0, 1
+DT_PREP_TILE_ROWS, DT_PREP_CHUNK_COLS, DT_PREP_MAX_BLOCKS, DT_PREP_COL_BYTES = 256, 32, 1024, 80
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

@@ -639,6 +639,11 @@ class DeepModel:
             return self._forward_batches(data, batch_size, self.inference_plan())
 
     def predict(self, X, batch_size=128, verbose=0):
+        """X: a transformed frame, or a ready `training.TableBatches` (`DeepTable.make_feed`), scored as it is"""
+        if isinstance(X, training.TableBatches):
+            if X.n == 0:
+                return np.zeros((0, 1), dtype=np.float32)
+            return self.score_batches(X, batch_size).cpu().numpy()
         return self._predict(self.model, X, batch_size=batch_size, activate=True)
 
     def _predict(self, model, X, batch_size=128, activate=True):
@@ -677,10 +682,19 @@ class DeepModel:
             return [transformer.fit_transform(o.reshape((o.shape[0], -1))) for o in output]
         return transformer.fit_transform(output)
 
-    def evaluate(self, X_test, y_test, batch_size=256, verbose=0, return_dict=True):
-        data = training.TableBatches(X_test, y_test, self.categorical_columns, self.continuous_columns, self.device,
-                                     self.task, self.num_classes,
-                                     var_len_categorical_columns=self.var_len_categorical_columns)
+    def evaluate(self, X_test, y_test=None, batch_size=256, verbose=0, return_dict=True):
+        """X_test, y_test: a transformed frame and its encoded targets, or X_test a ready `training.TableBatches` carrying its
+        own y and no weight column"""
+        if isinstance(X_test, training.TableBatches):
+            if y_test is not None:
+                raise ValueError('evaluate(feed): the targets belong into the feed')
+            if X_test.y is None or X_test.weighted:
+                raise ValueError('evaluate(feed): the feed must carry y and no weight column')
+            data = X_test
+        else:
+            data = training.TableBatches(X_test, y_test, self.categorical_columns, self.continuous_columns, self.device,
+                                         self.task, self.num_classes,
+                                         var_len_categorical_columns=self.var_len_categorical_columns)
         result = self._evaluate_batches(data, batch_size, list(self.config.metrics or []))
         return IgnoreCaseDict(inputs=result) if return_dict else list(result.values())
 

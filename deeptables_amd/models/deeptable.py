@@ -270,8 +270,29 @@ class DeepTable:
                 raise ValueError('Model set is empty.')
             return cross_validation.predict_proba_mean(self, X, models, batch_size, auto_transform_data)
         model = self.get_model(model_selector)
-        proba = model.predict(self.preprocessor.transform_X(X) if auto_transform_data else X, batch_size=batch_size)
+        proba = model.predict(self._feed_of(model, X) if auto_transform_data else X, batch_size=batch_size)
         return cross_validation.fix_binary(self, proba)             # fix_binary_predict_proba_result
+
+    def _feed_of(self, model, X, y=None, device=None):
+        """The raw frame (and raw y) as the model's input feed: `preprocessor.transform_feed` — on a GPU the numeric columns are
+        transformed by one kernel launch per block, on the host otherwise — or, for a preprocessor without it, the frame
+        `transform_X` makes (and the encoded y), which `DeepModel` turns into a feed itself"""
+        pp = self.preprocessor
+        if not callable(getattr(pp, 'transform_feed', None)):
+            return pp.transform_X(X) if y is None else (pp.transform_X(X), pp.transform_y(y))
+        return pp.transform_feed(X, y, device=model.device if device is None else device, task=model.task,
+                                 num_classes=model.num_classes)
+
+    def make_feed(self, X, y=None, device='auto'):
+        """A raw frame (and raw y) as a device-resident `training.TableBatches` of the current model's inputs: what `predict`,
+        `evaluate` and `DeepModel.fit` / `predict` / `evaluate` take in place of a frame.  device 'auto': the model's.
+        `feed.transform_path` says whether the kernel ('device') or pandas ('host') made it."""
+        self._require_model()
+        model = self._one_model(consts.MODEL_SELECTOR_CURRENT)
+        pp = self.preprocessor
+        if not callable(getattr(pp, 'transform_feed', None)):
+            raise ValueError(f'make_feed: {type(pp).__name__} has no transform_feed')
+        return self._feed_of(model, X, y, None if device == 'auto' else device)
 
     def predict_proba_all(self, X, batch_size=128, verbose=0, auto_transform_data=True):
         """{name: proba} of every model of the set"""
@@ -308,8 +329,10 @@ class DeepTable:
 
     def evaluate(self, X_test, y_test, batch_size=256, verbose=0, model_selector=consts.MODEL_SELECTOR_CURRENT, **kwargs):
         model = self._one_model(model_selector)
-        return model.evaluate(self.preprocessor.transform_X(X_test), self.preprocessor.transform_y(y_test),
-                              batch_size=batch_size)
+        feed = self._feed_of(model, X_test, y_test)
+        if isinstance(feed, tuple):
+            return model.evaluate(feed[0], feed[1], batch_size=batch_size)
+        return model.evaluate(feed, batch_size=batch_size)
 
     def apply(self, X, output_layers, concat_outputs=False, batch_size=128, verbose=0, transformer=None,
               model_selector=consts.MODEL_SELECTOR_CURRENT, auto_transform_data=True):

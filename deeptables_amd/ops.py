@@ -1908,3 +1908,152 @@ def ensemble_mean(parts, mode=0):
     with torch.cuda.device(first.device):
         check(lib().dt_ensemble_mean(table, K, first.numel(), mode, ptr(out), stream_ptr()), 'dt_ensemble_mean')
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# the fitted preprocessor's transform: raw columns -> one block of a resident feed (csrc/prep_transform.hip;
+# models/preprocessor.py DefaultPreprocessor.transform_feed)
+# ------------------------------------------------------------------------------------------------
+PREP_DTYPES = {'bool': _lib.DT_PREP_BOOL, 'int8': _lib.DT_PREP_I8, 'int16': _lib.DT_PREP_I16, 'int32': _lib.DT_PREP_I32,
+               'int64': _lib.DT_PREP_I64, 'uint8': _lib.DT_PREP_U8, 'uint16': _lib.DT_PREP_U16, 'uint32': _lib.DT_PREP_U32,
+               'uint64': _lib.DT_PREP_U64, 'float32': _lib.DT_PREP_F32, 'float64': _lib.DT_PREP_F64}
+PREP_DTYPE_NAMES = {v: k for k, v in PREP_DTYPES.items()}
+PREP_LOOKUP, PREP_CONT, PREP_BIN, PREP_COPY = _lib.DT_PREP_LOOKUP, _lib.DT_PREP_CONT, _lib.DT_PREP_BIN, _lib.DT_PREP_COPY
+PREP_IMPUTE, PREP_SCALE = _lib.DT_PREP_IMPUTE, _lib.DT_PREP_SCALE
+PREP_TILE_ROWS, PREP_CHUNK_COLS, PREP_MAX_BLOCKS = _lib.DT_PREP_TILE_ROWS, _lib.DT_PREP_CHUNK_COLS, _lib.DT_PREP_MAX_BLOCKS
+PREP_NAN_KEY32, PREP_NAN_KEY64 = 0x7FC00000, 0x7FF8000000000000
+
+
+class PrepCol(ctypes.Structure):
+    """include/dt_hip.h dt_prep_col"""
+    _fields_ = [('src', ctypes.c_void_p), ('keys', ctypes.c_void_p), ('ids', ctypes.c_void_p), ('edges', ctypes.c_void_p),
+                ('fill', ctypes.c_double), ('min', ctypes.c_double), ('range', ctypes.c_double),
+                ('dtype', ctypes.c_int32), ('op', ctypes.c_int32), ('n_keys', ctypes.c_int32), ('n_edges', ctypes.c_int32),
+                ('miss', ctypes.c_int32), ('flags', ctypes.c_int32)]
+
+
+assert ctypes.sizeof(PrepCol) == _lib.DT_PREP_COL_BYTES
+
+
+class PrepColumn:
+    """One output column of `prep_transform`.  src: a 1-D uint8 tensor, the bytes of the raw column [N] in dtype `dtype` (a name
+    of PREP_DTYPES); op: PREP_LOOKUP (keys: int64 tensor holding the uint64 keys ascending, ids: int32 tensor, miss), PREP_CONT
+    (flags, fill, min, range), PREP_BIN (CONT's constants and edges: float64 tensor ascending) or PREP_COPY.  All tensors of a
+    column live on one device."""
+    __slots__ = ('src', 'dtype', 'op', 'keys', 'ids', 'edges', 'fill', 'min', 'range', 'miss', 'flags')
+
+    def __init__(self, src, dtype, op, keys=None, ids=None, edges=None, fill=0.0, min=0.0, range=1.0, miss=0, flags=0):
+        self.src, self.dtype, self.op, self.keys, self.ids, self.edges = src, dtype, op, keys, ids, edges
+        self.fill, self.min, self.range, self.miss, self.flags = float(fill), float(min), float(range), int(miss), int(flags)
+
+
+def prep_source(array, device):
+    """a raw numpy column (any PREP_DTYPES dtype) -> its bytes on `device`, the `src` of a PrepColumn: one copy, no conversion"""
+    a = np.ascontiguousarray(array)
+    if a.dtype.name not in PREP_DTYPES or a.ndim != 1:
+        raise ValueError(f'prep_source: a 1-D array of {sorted(PREP_DTYPES)}, got {a.dtype} {a.shape}')
+    return torch.from_numpy(a.view(np.uint8)).to(device)
+
+
+def prep_keys(values):
+    """numpy values of one PREP_DTYPES dtype -> their uint64 LOOKUP keys (include/dt_hip.h DT_PREP_LOOKUP)"""
+    a = np.asarray(values)
+    name = a.dtype.name
+    if name == 'float32':
+        k = a.view(np.uint32).astype(np.uint64)
+        k[np.isnan(a)] = PREP_NAN_KEY32
+        return k
+    if name == 'float64':
+        k = a.view(np.uint64).copy()
+        k[np.isnan(a)] = PREP_NAN_KEY64
+        return k
+    if name == 'bool' or name.startswith('uint'):
+        return a.astype(np.uint64)
+    return a.astype(np.int64).view(np.uint64)
+
+
+def _prep_host_word(c, N):
+    """column c of the block in numpy, by the definitions of include/dt_hip.h -> int32 or float32 [N]"""
+    a = c.src.numpy().view(np.dtype(c.dtype))
+    if a.shape[0] != N:
+        raise ValueError(f'prep_transform: a source of {a.shape[0]} elements for N={N}')
+    if c.op == PREP_LOOKUP:
+        k = prep_keys(a)
+        n = 0 if c.keys is None else int(c.keys.shape[0])
+        if n == 0:
+            return np.full(N, c.miss, dtype=np.int32)
+        keys, ids = c.keys.numpy().view(np.uint64), c.ids.numpy()
+        p = np.minimum(np.searchsorted(keys, k, side='left'), n - 1)
+        return np.where(keys[p] == k, ids[p], np.int32(c.miss)).astype(np.int32)
+    if c.op == PREP_COPY:
+        return prep_keys(a).astype(np.uint32).view(np.int32)
+    with np.errstate(all='ignore'):
+        v = a.astype(np.float64)
+        if c.flags & PREP_IMPUTE:
+            v = np.where(np.isnan(v), np.float64(c.fill), v)
+        if c.flags & PREP_SCALE:
+            v = (v - np.float64(c.min)) / np.float64(c.range)
+        if c.op == PREP_CONT:
+            return v.astype(np.float32)
+    edges = np.zeros(0) if c.edges is None else c.edges.numpy()
+    return np.where(np.isnan(v), len(edges), np.searchsorted(edges, v, side='right')).astype(np.int32)
+
+
+def prep_transform(N, cols, kind, out=None):
+    """One block of a feed from raw columns: out[i, j] = what PrepColumn cols[j] makes of row i, for i < N -> `out`, a contiguous
+    [N, len(cols)] tensor, int32 for kind 'cat' (LOOKUP, BIN and COPY columns) or float32 for kind 'cont' (CONT columns), created
+    on the sources' device unless given.  GPU tensors: one dt_prep_transform launch; the descriptors travel as one small upload.
+    CPU tensors: the same definitions in numpy (the host tests of the plan)."""
+    who = 'prep_transform'
+    cols = list(cols)
+    C, N = len(cols), int(N)
+    if kind not in ('cat', 'cont'):
+        raise ValueError(f"{who}: kind must be 'cat' or 'cont', got {kind!r}")
+    if C < 1 or N < 0:
+        raise ValueError(f'{who}: bad sizes N={N} C={C}')
+    dtype = torch.int32 if kind == 'cat' else torch.float32
+    device = cols[0].src.device
+    for j, c in enumerate(cols):
+        if c.dtype not in PREP_DTYPES:
+            raise ValueError(f'{who}: column {j}: unknown dtype {c.dtype!r}')
+        if c.op not in ((PREP_CONT,) if kind == 'cont' else (PREP_LOOKUP, PREP_BIN, PREP_COPY)):
+            raise ValueError(f'{who}: column {j}: op {c.op!r} does not write a {kind} block')
+        if c.op == PREP_COPY and c.dtype.startswith('float'):
+            raise ValueError(f'{who}: column {j}: COPY of a float source')
+        if c.src.dtype != torch.uint8 or c.src.dim() != 1 or not c.src.is_contiguous() or \
+                c.src.numel() != N * np.dtype(c.dtype).itemsize:
+            raise ValueError(f'{who}: column {j}: src must be the {N * np.dtype(c.dtype).itemsize} bytes of a {c.dtype} [{N}] column')
+        tables = [('keys', c.keys, torch.int64), ('ids', c.ids, torch.int32), ('edges', c.edges, torch.float64)]
+        for name, t, want in tables:
+            if t is not None and (t.dtype != want or t.dim() != 1 or not t.is_contiguous() or t.device != device):
+                raise ValueError(f'{who}: column {j}: {name} must be a contiguous 1-D {want} tensor on {device}')
+        if c.src.device != device:
+            raise ValueError(f'{who}: column {j}: src on {c.src.device}, column 0 on {device}')
+        if c.op == PREP_LOOKUP and ((c.keys is None) != (c.ids is None) or
+                                    (c.keys is not None and c.keys.shape[0] != c.ids.shape[0])):
+            raise ValueError(f'{who}: column {j}: keys and ids must have one length')
+    if out is None:
+        out = torch.empty((N, C), dtype=dtype, device=device)
+    elif out.dtype != dtype or tuple(out.shape) != (N, C) or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'{who}: out must be a contiguous {dtype} {(N, C)} on {device}')
+    if device.type != 'cuda':
+        if N:
+            host = out.numpy()
+            for j, c in enumerate(cols):
+                host[:, j] = _prep_host_word(c, N)
+        return out
+    if N == 0:
+        return out
+    table = (PrepCol * C)()
+    for j, c in enumerate(cols):
+        n_keys = 0 if c.keys is None else int(c.keys.shape[0])
+        n_edges = 0 if c.edges is None else int(c.edges.shape[0])
+        table[j] = PrepCol(c.src.data_ptr(), c.keys.data_ptr() if n_keys else None, c.ids.data_ptr() if n_keys else None,
+                           c.edges.data_ptr() if n_edges else None, c.fill, c.min, c.range, PREP_DTYPES[c.dtype], c.op,
+                           n_keys, n_edges, c.miss, c.flags)
+    packed = torch.from_numpy(np.frombuffer(table, dtype=np.uint8).copy()).to(device)
+    with torch.cuda.device(device):
+        check(lib().dt_prep_transform(N, ptr(packed), ctypes.cast(table, ctypes.c_void_p), C,
+                                      _lib.DT_PREP_OUT_I32 if kind == 'cat' else _lib.DT_PREP_OUT_F32, ptr(out), stream_ptr()),
+              'dt_prep_transform')
+    return out              # (`packed` goes back to the caching allocator, which reuses it in stream order: after the kernel)

@@ -1911,6 +1911,24 @@ class History:
 # ---------------------------------------------------------------------------------------------
 # data feed (replaces utils/dataset_generator.py:36-72 for in-memory frames)
 # ---------------------------------------------------------------------------------------------
+def host_targets(y, task=None, num_classes=None, sample_weight=None):
+    """y as a feed carries it, on the host: float32, one-hot for integer multiclass labels, the per-row weights as the LAST
+    column -> (tensor or None, y's own rank without the weight column)"""
+    if y is None:
+        return None, None
+    y = np.asarray(y)
+    if task == consts.TASK_MULTICLASS and y.ndim == 1:
+        y = np.eye(num_classes, dtype=np.float32)[y.astype(np.int64)]
+    y_host = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
+    y_ndim = y_host.dim()                      # weights ride as an extra column: remember y's own rank
+    if sample_weight is not None:
+        w = torch.as_tensor(np.ascontiguousarray(np.asarray(sample_weight).reshape(-1), dtype=np.float32))
+        if w.shape[0] != y_host.shape[0]:
+            raise ValueError(f'sample_weight has {w.shape[0]} entries for {y_host.shape[0]} rows')
+        y_host = torch.cat([y_host.reshape(y_host.shape[0], -1), w[:, None]], 1).contiguous()
+    return y_host, y_ndim
+
+
 class TableBatches:
     """Input feed for in-memory frames (replaces `to_dataset`, utils/dataset_generator.py:36-72, which
     converts whole frames through `.tolist()` into tf.constants and feeds float32 ids).
@@ -1943,18 +1961,7 @@ class TableBatches:
         for c in continuous_columns or []:
             arr = get(list(c.column_names)) if get else np.asarray(X[c.name])
             host.append(('cont', torch.as_tensor(np.ascontiguousarray(arr, dtype=np.float32))))
-        y_host = None
-        if y is not None:
-            y = np.asarray(y)
-            if task == consts.TASK_MULTICLASS and y.ndim == 1:
-                y = np.eye(num_classes, dtype=np.float32)[y.astype(np.int64)]
-            y_host = torch.as_tensor(np.ascontiguousarray(y, dtype=np.float32))
-            self.y_ndim = y_host.dim()                 # weights ride as an extra column: remember y's own rank
-            if sample_weight is not None:
-                w = torch.as_tensor(np.ascontiguousarray(np.asarray(sample_weight).reshape(-1), dtype=np.float32))
-                if w.shape[0] != y_host.shape[0]:
-                    raise ValueError(f'sample_weight has {w.shape[0]} entries for {y_host.shape[0]} rows')
-                y_host = torch.cat([y_host.reshape(y_host.shape[0], -1), w[:, None]], 1).contiguous()
+        y_host, self.y_ndim = host_targets(y, task, num_classes, sample_weight)
         nbytes = sum(t.numel() * t.element_size() for _, t in host) + (0 if y_host is None else y_host.numel() * 4)
         self.resident = (nbytes <= max_resident_bytes) if resident is None else bool(resident)
         self.kinds = [k for k, _ in host]

@@ -72,8 +72,14 @@ def _derived(source_map, raw):
 
 
 def make_feed(dt_model, X, y_encoded, cat_dtype=torch.int32, resident=None):
-    """`preprocessor.transform_X` once -> ONE feed with the encoded labels on the model's device"""
+    """The raw frame once -> ONE feed with the encoded labels on the model's device: `preprocessor.transform_feed` (on a GPU the
+    numeric columns go through one kernel launch per block), `transform_X` for a preprocessor without it or a feed that is
+    asked not to be resident"""
     dm = dt_model.model
+    pp = dt_model.preprocessor
+    if callable(getattr(pp, 'transform_feed', None)) and resident is not False:
+        return pp.transform_feed(X, y_encoded, device=dm.device, task=dm.task, num_classes=dm.num_classes, cat_dtype=cat_dtype,
+                                 y_encoded=True)
     return training.TableBatches(dt_model.preprocessor.transform_X(X), y_encoded, dm.categorical_columns,
                                  dm.continuous_columns, dm.device, dm.task, dm.num_classes, cat_dtype=cat_dtype,
                                  var_len_categorical_columns=dm.var_len_categorical_columns, resident=resident)

@@ -1672,6 +1672,64 @@ int dt_rows_take(const void* block, int64_t N, int C, const int64_t* idx, int64_
 int dt_rows_put(void* block, int64_t N, int C, const int64_t* idx, int64_t n, const void* src, void* stream);
 int dt_ensemble_mean(const void* const* parts_host, int K, int64_t total, int mode, void* out, void* stream);
 
+/* The fitted preprocessor's transform on the device (csrc/prep_transform.hip; ops.prep_transform, the device path of
+ * models/preprocessor.py DefaultPreprocessor.transform_feed; replaces deeptables/models/preprocessor.py:249-260, `transform_X`'s
+ * pandas steps, and utils/dataset_generator.py:36-72 on numeric columns).  Sources are column-major, one contiguous DEVICE array
+ * [N] per raw column in the column's own dtype; the output is one row-major [N, C] block of a resident feed, int32
+ * (DT_PREP_OUT_I32) or float32 (DT_PREP_OUT_F32).  Column j of the block is what cols[j] describes:
+ *   DT_PREP_LOOKUP  the raw value widened to a 64-bit key — ints sign-extended, uints and bool zero-extended, float32 bits
+ *     zero-extended, float64 bits, every NaN the canonical quiet NaN (0x7FC00000 / 0x7FF8000000000000) — searched in
+ *     keys (uint64 [n_keys], ascending); a hit at p gives ids[p], a miss gives `miss`.  n_keys may be 0.
+ *   DT_PREP_CONT    v = (double)x; flags & DT_PREP_IMPUTE and v is NaN: v = fill; flags & DT_PREP_SCALE: v = (v - min) / range
+ *     in float64, each operation correctly rounded; the word is (float)v.  Integers go int -> double -> float.
+ *   DT_PREP_BIN     v as for CONT before its last cast; the word is the number of edges (float64 [n_edges], ascending) <= v,
+ *     n_edges for a NaN — np.searchsorted(edges, v, side='right').  n_edges may be 0.
+ *   DT_PREP_COPY    the low 32 bits of an integer (or bool) source: `.astype(int64)` followed by `.to(int32)`.
+ * An int32 block takes LOOKUP, BIN and COPY columns, a float32 block CONT columns.
+ * cols is the DEVICE copy of the descriptors the kernel reads, cols_host the HOST copy the entry validates (the same C
+ * descriptors; the pointers inside both are device pointers).  One launch per block: 256-thread blocks, a tile of
+ * DT_PREP_TILE_ROWS rows by DT_PREP_CHUNK_COLS columns staged through LDS so that sources are read and rows are written
+ * coalesced (16-byte stores where C % 4 == 0 and out is 16-byte aligned), a grid-stride loop under DT_PREP_MAX_BLOCKS blocks,
+ * 64-bit row indices, a fixed-trip binary search, no atomics: the same bits on every run.  Nothing synchronises with the host
+ * or allocates.  N < 0, C < 1, an unknown out_kind, a null or misaligned pointer, and in cols_host an unknown dtype or op code,
+ * an op that does not fit out_kind, COPY of a float source, unknown flags, n_keys < 0 or n_edges < 0, a null source (N > 0), a
+ * null or misaligned table of a non-empty LOOKUP / BIN are DT_ERR_INVALID_ARG before any launch; N == 0 is DT_OK without one.
+ * The kernel itself gives a zero word for a dtype or op code it does not know and treats a null or negative table as empty. */
+#define DT_PREP_BOOL 0
+#define DT_PREP_I8 1
+#define DT_PREP_I16 2
+#define DT_PREP_I32 3
+#define DT_PREP_I64 4
+#define DT_PREP_U8 5
+#define DT_PREP_U16 6
+#define DT_PREP_U32 7
+#define DT_PREP_U64 8
+#define DT_PREP_F32 9
+#define DT_PREP_F64 10
+#define DT_PREP_DTYPE_COUNT 11
+#define DT_PREP_LOOKUP 0
+#define DT_PREP_CONT 1
+#define DT_PREP_BIN 2
+#define DT_PREP_COPY 3
+#define DT_PREP_IMPUTE 0x1
+#define DT_PREP_SCALE 0x2
+#define DT_PREP_OUT_I32 0
+#define DT_PREP_OUT_F32 1
+#define DT_PREP_TILE_ROWS 256
+#define DT_PREP_CHUNK_COLS 32
+#define DT_PREP_MAX_BLOCKS 1024
+#define DT_PREP_COL_BYTES 80
+typedef struct dt_prep_col {
+    const void* src;        /* device [N] of `dtype` */
+    const uint64_t* keys;   /* LOOKUP: device uint64 [n_keys], ascending */
+    const int32_t* ids;     /* LOOKUP: device int32 [n_keys] */
+    const double* edges;    /* BIN: device float64 [n_edges], ascending */
+    double fill, min, range;
+    int32_t dtype, op, n_keys, n_edges, miss, flags;
+} dt_prep_col;
+int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* cols_host, int C, int out_kind, void* out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
