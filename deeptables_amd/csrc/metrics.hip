@@ -18,9 +18,10 @@
 // AUC (k_auc_*): keys = order-preserving uint32 of the score (-0.0 -> +0.0 first), values = 1 for label 1, else 0; after the
 //   sort a reduce-then-scan over tiles (three launches) gives, for every group of equal keys, where it starts and how many
 //   negatives precede it; one thread per group then adds pos_g * (2 * negs_before_g + neg_g) into U2 (64-bit integers).
-// Scores (k_score_*, k_ap_*; dt_score_*): log loss with the precision / recall counts, MSLE / MAPE, top-k hits with the
-//   categorical cross-entropy, and average precision from the AUC's group arrays — float64 from the float32 inputs, every sum
-//   a per-block partial added by one block in a fixed order.
+// Sums (k_sums_partial, k_score_*, k_ap_partial; dt_metric_sums, dt_score_*): the hit count with the squared and absolute
+//   errors, log loss with the precision / recall counts, MSLE / MAPE, top-k hits with the categorical cross-entropy, and
+//   average precision from the AUC's group arrays — float64 from the float32 inputs.  One scheme for all of them: a block
+//   writes its partial words behind the result words (score_partial), and k_score_final, one block, adds them in block order.
 #include "common.h"
 
 namespace dt {
@@ -334,106 +335,27 @@ __global__ __launch_bounds__(kThreads) void k_auc_u2(const uint32_t* __restrict_
 
 int64_t auc_ws_bytes(int64_t n) { return 2 * a256(4 * n) + sort_ws_bytes(n) + a256(8 * tiles_of(n)) + 256; }
 
-// ---- accuracy / MSE / MAE -------------------------------------------------------------------------------------------------
-constexpr int kSumsBlocks = DT_METRIC_SUMS_BLOCKS;
-static_assert(kSumsBlocks <= kThreads && DT_METRIC_SUMS_WORDS == 3 + 3 * kSumsBlocks, "k_sums_final: one thread per partial");
-
-// out (8-byte words): [0] hits (int64) [1] sum (p-y)^2 (double) [2] sum |p-y| (double), then 3 words per block of partials
-__global__ __launch_bounds__(kThreads) void k_sums_partial(const float* __restrict__ y_true, const float* __restrict__ y_prob,
-                                                           int64_t n, u64* __restrict__ out) {
-    __shared__ u64 shi[kWaves];
-    __shared__ double shd[kWaves];
-    u64 hits = 0;
-    double se = 0.0, ae = 0.0;
-    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
-        const float p = y_prob[i], y = y_true[i];
-        hits += (long long)(p > 0.5f) == (long long)y;
-        const double d = (double)p - (double)y;
-        se += d * d;
-        ae += fabs(d);
-    }
-    hits = block_sum<u64>(hits, shi);
-    se = block_sum<double>(se, shd);
-    ae = block_sum<double>(ae, shd);
-    if (threadIdx.x == 0) {
-        u64* part = out + 3 + 3 * blockIdx.x;
-        part[0] = hits;
-        part[1] = (u64)__double_as_longlong(se);
-        part[2] = (u64)__double_as_longlong(ae);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void k_sums_final(u64* __restrict__ out, int blocks) {
-    __shared__ u64 shi[kWaves];
-    __shared__ double shd[kWaves];
-    const bool live = (int)threadIdx.x < blocks;          // blocks <= kSumsBlocks = kThreads
-    const u64* part = out + 3 + 3 * threadIdx.x;
-    const u64 hits = block_sum<u64>(live ? part[0] : 0, shi);
-    const double se = block_sum<double>(live ? __longlong_as_double((long long)part[1]) : 0.0, shd);
-    const double ae = block_sum<double>(live ? __longlong_as_double((long long)part[2]) : 0.0, shd);
-    if (threadIdx.x == 0) {
-        out[0] = hits;
-        out[1] = (u64)__double_as_longlong(se);
-        out[2] = (u64)__double_as_longlong(ae);
-    }
-}
-
-// rows whose argmax (first maximum, as numpy.argmax) equals the label; ONEHOT: the label is the argmax of the y_true row
-template <int KIND>
-__global__ __launch_bounds__(kThreads) void k_argmax_hits(const float* __restrict__ y_prob, const float* __restrict__ y_true,
-                                                          int64_t n, int C, u64* __restrict__ out) {
-    __shared__ uint32_t sh[kWaves];
-    uint32_t hits = 0;
-    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < n; r += (int64_t)gridDim.x * kThreads) {
-        const float* p = y_prob + r * C;
-        int best = 0;
-        float bv = p[0];
-        for (int c = 1; c < C; ++c) {
-            const float v = p[c];
-            if (v > bv) { bv = v; best = c; }
-        }
-        if (KIND == DT_METRIC_Y_ONEHOT) {
-            const float* t = y_true + r * C;
-            int tb = 0;
-            float tv = t[0];
-            for (int c = 1; c < C; ++c) {
-                const float v = t[c];
-                if (v > tv) { tv = v; tb = c; }
-            }
-            hits += best == tb;
-        } else {
-            hits += (float)best == y_true[r];
-        }
-    }
-    hits = block_sum<uint32_t>(hits, sh);
-    if (threadIdx.x == 0 && hits) atomicAdd(out, (u64)hits);
-}
-
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline unsigned stride_blocks(int64_t n) {
     const int64_t b = (n + kThreads - 1) / kThreads;
     return (unsigned)(b < kMaxBlocks ? b : kMaxBlocks);
 }
 
-// ---- scores: log loss, precision / recall counts, top-k hits, MSLE / MAPE, average precision -------------------------------
-// Every pass below is k_sums_partial's scheme: a block adds what it saw in a fixed order and writes its partial words behind
-// the result words of `out` (W result words, then W words per block); k_score_final, one block, adds the partials in block
-// order.  The block count is a function of the shape alone, so the same input gives the same bits.
+// ---- the partial / final scheme of every float64 sum below -----------------------------------------------------------------
+// A block adds what it saw in a fixed order and writes its partial words behind the result words of `out` (W result words,
+// then W words per block); k_score_final, one block, adds the partials in block order.  The block count is a function of the
+// shape alone, so the same input gives the same bits.
 constexpr int kScoreBlocks = DT_SCORE_BLOCKS;
 static_assert(kScoreBlocks <= kThreads, "k_score_final: one thread per partial");
-static_assert(DT_SCORE_BINARY_WORDS == 5 + 5 * kScoreBlocks && DT_SCORE_REGRESSION_WORDS == 2 + 2 * kScoreBlocks &&
+static_assert(DT_METRIC_SUMS_BLOCKS == DT_SCORE_BLOCKS && DT_METRIC_SUMS_WORDS == 3 + 3 * kScoreBlocks &&
+              DT_SCORE_BINARY_WORDS == 5 + 5 * kScoreBlocks && DT_SCORE_REGRESSION_WORDS == 2 + 2 * kScoreBlocks &&
               DT_SCORE_CATEGORICAL_WORDS == 2 + 2 * kScoreBlocks && DT_SCORE_RANKING_WORDS == 6 + kScoreBlocks, "out layouts");
-constexpr int kThreadRowMaxC = DT_SCORE_THREAD_ROW_MAX_C;     // a thread per row up to here, a wave per row beyond
-constexpr double kClipLo = (double)1e-7f;                     // Keras' epsilon as float32 ...
-constexpr double kClipHi = (double)(1.0f - 1e-7f);            // ... and 1 - epsilon, subtracted in float32 (0.99999988...)
 
-// numpy.clip(p, lo, hi): a NaN fails both comparisons and comes out as it went in (fmin / fmax would drop it)
-__device__ __forceinline__ double clip_prob(double p) { return p < kClipLo ? kClipLo : (p > kClipHi ? kClipHi : p); }
-// numpy.maximum(x, lo), NaN kept
-__device__ __forceinline__ double at_least_lo(double x) { return x < kClipLo ? kClipLo : x; }
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-// the class a float label names, -1 when it names none of [0, C) (a NaN too)
-__device__ __forceinline__ int label_class(float y, int C) { return (y >= 0.0f && (double)y < (double)C) ? (int)y : -1; }
+// ceil(work / per_block) blocks, at most kScoreBlocks
+inline int score_blocks(int64_t work, int64_t per_block) {
+    const int64_t b = (work + per_block - 1) / per_block;
+    return (int)(b < kScoreBlocks ? b : kScoreBlocks);
+}
 
 __device__ __forceinline__ void score_partial(u64* __restrict__ out, int W, int k, u64 v) { out[W + W * blockIdx.x + k] = v; }
 __device__ __forceinline__ void score_partial(u64* __restrict__ out, int W, int k, double v) {
@@ -459,6 +381,72 @@ __global__ __launch_bounds__(kThreads) void k_score_final(u64* __restrict__ out,
         if (threadIdx.x == 0) out[k] = (u64)__double_as_longlong(s);
     }
 }
+
+// the class a `v > best` scan from class 0 ends on: the first maximum, as numpy.argmax (class 0 when the row leads with a NaN)
+__device__ __forceinline__ int first_max(const float* __restrict__ row, int C) {
+    int best = 0;
+    float bv = row[0];
+    for (int c = 1; c < C; ++c) {
+        const float v = row[c];
+        if (v > bv) { bv = v; best = c; }
+    }
+    return best;
+}
+
+// ---- accuracy / MSE / MAE -------------------------------------------------------------------------------------------------
+// out: hits (int64), sum (p-y)^2, sum |p-y| (double)
+__global__ __launch_bounds__(kThreads) void k_sums_partial(const float* __restrict__ y_true, const float* __restrict__ y_prob,
+                                                           int64_t n, u64* __restrict__ out) {
+    __shared__ u64 shi[kWaves];
+    __shared__ double shd[kWaves];
+    u64 hits = 0;
+    double se = 0.0, ae = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kThreads) {
+        const float p = y_prob[i], y = y_true[i];
+        hits += (long long)(p > 0.5f) == (long long)y;
+        const double d = (double)p - (double)y;
+        se += d * d;
+        ae += fabs(d);
+    }
+    hits = block_sum<u64>(hits, shi);
+    se = block_sum<double>(se, shd);
+    ae = block_sum<double>(ae, shd);
+    if (threadIdx.x == 0) {
+        score_partial(out, 3, 0, hits);
+        score_partial(out, 3, 1, se);
+        score_partial(out, 3, 2, ae);
+    }
+}
+
+// rows whose argmax (first_max) equals the label; ONEHOT: the label is the argmax of the y_true row
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void k_argmax_hits(const float* __restrict__ y_prob, const float* __restrict__ y_true,
+                                                          int64_t n, int C, u64* __restrict__ out) {
+    __shared__ uint32_t sh[kWaves];
+    uint32_t hits = 0;
+    for (int64_t r = (int64_t)blockIdx.x * kThreads + threadIdx.x; r < n; r += (int64_t)gridDim.x * kThreads) {
+        const int best = first_max(y_prob + r * C, C);
+        if (KIND == DT_METRIC_Y_ONEHOT)
+            hits += best == first_max(y_true + r * C, C);
+        else
+            hits += (float)best == y_true[r];
+    }
+    hits = block_sum<uint32_t>(hits, sh);
+    if (threadIdx.x == 0 && hits) atomicAdd(out, (u64)hits);
+}
+
+// ---- scores: log loss, precision / recall counts, top-k hits, MSLE / MAPE, average precision -------------------------------
+constexpr int kThreadRowMaxC = DT_SCORE_THREAD_ROW_MAX_C;     // a thread per row up to here, a wave per row beyond
+constexpr double kClipLo = (double)1e-7f;                     // Keras' epsilon as float32 ...
+constexpr double kClipHi = (double)(1.0f - 1e-7f);            // ... and 1 - epsilon, subtracted in float32 (0.99999988...)
+
+// numpy.clip(p, lo, hi): a NaN fails both comparisons and comes out as it went in (fmin / fmax would drop it)
+__device__ __forceinline__ double clip_prob(double p) { return p < kClipLo ? kClipLo : (p > kClipHi ? kClipHi : p); }
+// numpy.maximum(x, lo), NaN kept
+__device__ __forceinline__ double at_least_lo(double x) { return x < kClipLo ? kClipLo : x; }
+__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
+// the class a float label names, -1 when it names none of [0, C) (a NaN too)
+__device__ __forceinline__ int label_class(float y, int C) { return (y >= 0.0f && (double)y < (double)C) ? (int)y : -1; }
 
 // out: TP, FP, FN, TN (int64), sum of -(y log q + (1 - y) log(1 - q)) (double); LABELS: y = (class of the row == column)
 template <int KIND>
@@ -524,7 +512,7 @@ __global__ __launch_bounds__(kThreads) void k_score_regression(const float* __re
 }
 
 // the row pass: out = rows whose target class is among the k best (int64), sum of the rows' categorical cross-entropy.
-// target: the label, or the first maximum of the one-hot row found by `v > best` from class 0 on (k_argmax_hits' scan).
+// target: the label, or the first_max of the one-hot row.
 // A thread per row: every sum over the classes runs in class order.
 template <int KIND>
 __global__ __launch_bounds__(kThreads) void k_score_rows_thread(const float* __restrict__ y_prob, const float* __restrict__ y_true,
@@ -538,17 +526,7 @@ __global__ __launch_bounds__(kThreads) void k_score_rows_thread(const float* __r
         const float* t = y_true + r * C;                 // (ONEHOT only)
         double s = 0.0;
         for (int c = 0; c < C; ++c) s += (double)p[c];
-        int target;
-        if (KIND == DT_METRIC_Y_ONEHOT) {
-            target = 0;
-            float tv = t[0];
-            for (int c = 1; c < C; ++c) {
-                const float v = t[c];
-                if (v > tv) { tv = v; target = c; }
-            }
-        } else {
-            target = label_class(y_true[r], C);
-        }
+        const int target = KIND == DT_METRIC_Y_ONEHOT ? first_max(t, C) : label_class(y_true[r], C);
         if (target >= 0) {
             const float pt = p[target];
             int above = 0;
@@ -655,7 +633,7 @@ __global__ __launch_bounds__(kThreads) void k_score_rows_wave(const float* __res
 
 // average precision over the groups k_auc_groups compacted (ascending score): group g holds pos_g positives, TPcum = the
 // positives at or above it, n - start = everything at or above it.  out6: dt_metric_auc's five words (P is complete: an
-// earlier launch counted it), then the sum of pos_g * TPcum / (n - start); partials behind.
+// earlier launch counted it), then from word 5 on the scheme's one float64 word: the sum of pos_g * TPcum / (n - start).
 __global__ __launch_bounds__(kThreads) void k_ap_partial(const uint32_t* __restrict__ group_start, const uint32_t* __restrict__ group_negs_before,
                                                          const uint32_t* __restrict__ meta, int64_t n, u64* __restrict__ out6) {
     __shared__ double shd[kWaves];
@@ -672,20 +650,7 @@ __global__ __launch_bounds__(kThreads) void k_ap_partial(const uint32_t* __restr
         if (pos) acc += (double)pos * (double)(P - (s - nb)) / (double)(n - s);
     }
     acc = block_sum<double>(acc, shd);
-    if (threadIdx.x == 0) out6[6 + blockIdx.x] = (u64)__double_as_longlong(acc);
-}
-
-__global__ __launch_bounds__(kThreads) void k_ap_final(u64* __restrict__ out6, int blocks) {
-    __shared__ double shd[kWaves];
-    const double v = (int)threadIdx.x < blocks ? __longlong_as_double((long long)out6[6 + threadIdx.x]) : 0.0;
-    const double s = block_sum<double>(v, shd);
-    if (threadIdx.x == 0) out6[5] = (u64)__double_as_longlong(s);
-}
-
-// ceil(work / per_block) blocks, at most kScoreBlocks
-inline int score_blocks(int64_t work, int64_t per_block) {
-    const int64_t b = (work + per_block - 1) / per_block;
-    return (int)(b < kScoreBlocks ? b : kScoreBlocks);
+    if (threadIdx.x == 0) score_partial(out6 + 5, 1, 0, acc);
 }
 
 struct AucArrays {
@@ -744,59 +709,66 @@ extern "C" int dt_metric_sort_pairs(const uint32_t* keys, const uint32_t* vals, 
     return sort_pairs(keys, vals, n, keys_out, vals_out, ws, as_stream(stream), "dt_metric_sort_pairs");
 }
 
-extern "C" int64_t dt_metric_auc_workspace_bytes(int64_t n) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_metric_auc_workspace_bytes: n = %lld outside [0, 2^31)", (long long)n);
-    return auc_ws_bytes(n);
+// ---- the argument checks of the passes, in one order: n, then (n > 0) null pointers, then alignments -------------------------
+static int check_n(const char* what, int64_t n) {
+    DT_REQUIRE(n >= 0 && n < kMaxN, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
+    return DT_OK;
 }
 
-extern "C" int dt_metric_auc(const float* score, const float* label, int64_t n, void* ws, int64_t* out5, void* stream) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_metric_auc: n = %lld outside [0, 2^31)", (long long)n);
+// a, b: the two float arrays, `names` in the message; has_ws: the pass takes the workspace <what>_workspace_bytes sizes.
+// Nothing is looked at when n == 0: the call is a no-op.
+static int check_pointers(const char* what, int64_t n, const void* a, const void* b, const char* names, const void* out,
+                          const char* out_name, bool has_ws = false, const void* ws = nullptr) {
     if (n == 0) return DT_OK;
-    DT_REQUIRE(score && label && out5, "dt_metric_auc: null pointer");
-    DT_REQUIRE(ws, "dt_metric_auc: null workspace (dt_metric_auc_workspace_bytes)");
-    DT_REQUIRE(aligned(score, 4) && aligned(label, 4), "dt_metric_auc: score / label are not 4-byte aligned");
-    DT_REQUIRE(aligned(out5, 8), "dt_metric_auc: out5 is not 8-byte aligned");
-    DT_REQUIRE(aligned(ws, 16), "dt_metric_auc: the workspace is not 16-byte aligned");
+    DT_REQUIRE(a && b && out, "%s: null pointer", what);
+    if (has_ws) DT_REQUIRE(ws, "%s: null workspace (%s_workspace_bytes)", what, what);
+    DT_REQUIRE(aligned(a, 4) && aligned(b, 4), "%s: %s are not 4-byte aligned", what, names);
+    DT_REQUIRE(aligned(out, 8), "%s: %s is not 8-byte aligned", what, out_name);
+    if (has_ws) DT_REQUIRE(aligned(ws, 16), "%s: the workspace is not 16-byte aligned", what);
+    return DT_OK;
+}
+
+// the element-wise and row passes; on success *total = n * C
+static int score_args(const char* what, const void* y_true, const void* y_prob, int64_t n, int C, int min_C, const void* out,
+                      int64_t* total) {
+    int rc = check_n(what, n);
+    if (rc != DT_OK) return rc;
+    DT_REQUIRE(C >= min_C, "%s: C = %d, at least %d here", what, C, min_C);
+    DT_REQUIRE(n * (int64_t)C < kMaxN, "%s: n * C = %lld x %d overflows 2^31 elements", what, (long long)n, C);
+    *total = n * (int64_t)C;
+    return check_pointers(what, n, y_true, y_prob, "y_true / y_prob", out, "out");
+}
+
+// the two ranking passes, which share a workspace size
+static int64_t ranking_ws_bytes(const char* what, int64_t n) { return check_n(what, n) == DT_OK ? auc_ws_bytes(n) : DT_ERR_INVALID_ARG; }
+static int ranking_args(const char* what, const void* score, const void* label, int64_t n, const void* ws, const void* out,
+                        const char* out_name) {
+    int rc = check_n(what, n);
+    return rc != DT_OK ? rc : check_pointers(what, n, score, label, "score / label", out, out_name, true, ws);
+}
+
+extern "C" int64_t dt_metric_auc_workspace_bytes(int64_t n) { return ranking_ws_bytes("dt_metric_auc_workspace_bytes", n); }
+extern "C" int64_t dt_score_ranking_workspace_bytes(int64_t n) { return ranking_ws_bytes("dt_score_ranking_workspace_bytes", n); }
+
+extern "C" int dt_metric_auc(const float* score, const float* label, int64_t n, void* ws, int64_t* out5, void* stream) {
+    int rc = ranking_args("dt_metric_auc", score, label, n, ws, out5, "out5");
+    if (rc != DT_OK || n == 0) return rc;
     AucArrays arrays;
     return auc_launches(score, label, n, ws, reinterpret_cast<u64*>(out5), as_stream(stream), "dt_metric_auc", &arrays);
 }
 
-extern "C" int64_t dt_score_ranking_workspace_bytes(int64_t n) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_score_ranking_workspace_bytes: n = %lld outside [0, 2^31)", (long long)n);
-    return auc_ws_bytes(n);
-}
-
 extern "C" int dt_score_ranking(const float* score, const float* label, int64_t n, void* ws, void* out, void* stream) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_score_ranking: n = %lld outside [0, 2^31)", (long long)n);
-    if (n == 0) return DT_OK;
-    DT_REQUIRE(score && label && out, "dt_score_ranking: null pointer");
-    DT_REQUIRE(ws, "dt_score_ranking: null workspace (dt_score_ranking_workspace_bytes)");
-    DT_REQUIRE(aligned(score, 4) && aligned(label, 4), "dt_score_ranking: score / label are not 4-byte aligned");
-    DT_REQUIRE(aligned(out, 8), "dt_score_ranking: out is not 8-byte aligned");
-    DT_REQUIRE(aligned(ws, 16), "dt_score_ranking: the workspace is not 16-byte aligned");
+    int rc = ranking_args("dt_score_ranking", score, label, n, ws, out, "out");
+    if (rc != DT_OK || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     u64* o = reinterpret_cast<u64*>(out);
     AucArrays a;
-    int rc = auc_launches(score, label, n, ws, o, st, "dt_score_ranking", &a);
+    rc = auc_launches(score, label, n, ws, o, st, "dt_score_ranking", &a);
     if (rc != DT_OK) return rc;
     const int blocks = score_blocks(n, 4 * kThreads);        // (the number of groups is the device's to know: at most n)
     hipLaunchKernelGGL(k_ap_partial, dim3((unsigned)blocks), dim3(kThreads), 0, st, a.group_start, a.group_negs, a.meta, n, o);
-    hipLaunchKernelGGL(k_ap_final, dim3(1), dim3(kThreads), 0, st, o, blocks);
+    hipLaunchKernelGGL((k_score_final<0, 1>), dim3(1), dim3(kThreads), 0, st, o + 5, blocks);
     return launch_status("dt_score_ranking");
-}
-
-// the checks the three passes share; on success *total = n * C
-static int score_args(const char* what, const void* y_true, const void* y_prob, int64_t n, int C, int min_C, const void* out,
-                      int64_t* total) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "%s: n = %lld outside [0, 2^31)", what, (long long)n);
-    DT_REQUIRE(C >= min_C, "%s: C = %d, at least %d here", what, C, min_C);
-    DT_REQUIRE(n * (int64_t)C < kMaxN, "%s: n * C = %lld x %d overflows 2^31 elements", what, (long long)n, C);
-    *total = n * (int64_t)C;
-    if (n == 0) return DT_OK;
-    DT_REQUIRE(y_true && y_prob && out, "%s: null pointer", what);
-    DT_REQUIRE(aligned(y_true, 4) && aligned(y_prob, 4), "%s: y_true / y_prob are not 4-byte aligned", what);
-    DT_REQUIRE(aligned(out, 8), "%s: out is not 8-byte aligned", what);
-    return DT_OK;
 }
 
 extern "C" int dt_score_binary(const float* y_true, const float* y_prob, int y_kind, int64_t n, int C, void* out, void* stream) {
@@ -852,29 +824,25 @@ extern "C" int dt_score_categorical(const float* y_prob, const float* y_true, in
 }
 
 extern "C" int dt_metric_sums(const float* y_true, const float* y_prob, int64_t n, void* out, void* stream) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_metric_sums: n = %lld outside [0, 2^31)", (long long)n);
-    if (n == 0) return DT_OK;
-    DT_REQUIRE(y_true && y_prob && out, "dt_metric_sums: null pointer");
-    DT_REQUIRE(aligned(y_true, 4) && aligned(y_prob, 4), "dt_metric_sums: y_true / y_prob are not 4-byte aligned");
-    DT_REQUIRE(aligned(out, 8), "dt_metric_sums: out is not 8-byte aligned");
-    // the block count depends on n alone, and both stages add in a fixed order: the same n gives the same bits
-    int64_t blocks = (n + 4 * kThreads - 1) / (4 * kThreads);
-    if (blocks > kSumsBlocks) blocks = kSumsBlocks;
-    hipLaunchKernelGGL(k_sums_partial, dim3((unsigned)blocks), dim3(kThreads), 0, as_stream(stream), y_true, y_prob, n,
-                       reinterpret_cast<u64*>(out));
-    hipLaunchKernelGGL(k_sums_final, dim3(1), dim3(kThreads), 0, as_stream(stream), reinterpret_cast<u64*>(out), (int)blocks);
+    int64_t total;
+    int rc = score_args("dt_metric_sums", y_true, y_prob, n, 1, 1, out, &total);
+    if (rc != DT_OK || n == 0) return rc;
+    hipStream_t st = as_stream(stream);
+    u64* o = reinterpret_cast<u64*>(out);
+    const int blocks = score_blocks(n, 4 * kThreads);
+    hipLaunchKernelGGL(k_sums_partial, dim3((unsigned)blocks), dim3(kThreads), 0, st, y_true, y_prob, n, o);
+    hipLaunchKernelGGL((k_score_final<1, 2>), dim3(1), dim3(kThreads), 0, st, o, blocks);
     return launch_status("dt_metric_sums");
 }
 
 extern "C" int dt_metric_argmax_hits(const float* y_prob, const float* y_true, int y_kind, int64_t n, int C, int64_t* out,
                                      void* stream) {
-    DT_REQUIRE(n >= 0 && n < kMaxN, "dt_metric_argmax_hits: n = %lld outside [0, 2^31)", (long long)n);
+    int rc = check_n("dt_metric_argmax_hits", n);
+    if (rc != DT_OK) return rc;
     DT_REQUIRE(C >= 2, "dt_metric_argmax_hits: C = %d, a multiclass output has at least 2 columns", C);
     DT_REQUIRE(y_kind == DT_METRIC_Y_LABELS || y_kind == DT_METRIC_Y_ONEHOT, "dt_metric_argmax_hits: unknown y_kind %d", y_kind);
-    if (n == 0) return DT_OK;
-    DT_REQUIRE(y_prob && y_true && out, "dt_metric_argmax_hits: null pointer");
-    DT_REQUIRE(aligned(y_prob, 4) && aligned(y_true, 4), "dt_metric_argmax_hits: y_prob / y_true are not 4-byte aligned");
-    DT_REQUIRE(aligned(out, 8), "dt_metric_argmax_hits: out is not 8-byte aligned");
+    rc = check_pointers("dt_metric_argmax_hits", n, y_prob, y_true, "y_prob / y_true", out, "out");
+    if (rc != DT_OK || n == 0) return rc;
     hipStream_t st = as_stream(stream);
     if (hipMemsetAsync(out, 0, sizeof(int64_t), st) != hipSuccess) return launch_status("dt_metric_argmax_hits");
     u64* o = reinterpret_cast<u64*>(out);

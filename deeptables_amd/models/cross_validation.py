@@ -19,7 +19,7 @@ Deviations from the reference, all declared: no CSV file is written; `n_jobs` is
 on the one device; dask inputs are refused; no early-stopping callback is injected; `sample_weight` (length n) is sliced to
 each fold's training rows (the reference passes it whole, which fails); the means divide by the number of folds the iterator
 yields (the reference by `num_folds`, which is the same number for its own iterators); `oof_metrics` are this project's metric
-names (`training.epoch_metrics`), one dict per fold."""
+names (`metrics.epoch_metrics`), one dict per fold."""
 import os
 import time
 import types
@@ -29,7 +29,7 @@ import torch
 
 from . import deepmodel
 from .modelset import ModelInfo
-from .. import ops, training
+from .. import metrics, ops, training
 from ..utils import consts
 from ..utils import feature_importance as FI
 
@@ -191,7 +191,7 @@ def host_cross_validation(dt, X_t, y_t, folds, X_eval, X_test, fit_kwargs, class
             with _Phase('mean'):
                 means[key] = p / K if means[key] is None else means[key] + p / K
         if scores is not None:
-            scores.append({training.metric_name(m): training.compute_metric(m, y_va, p_va, dt.task) for m in oof_metrics})
+            scores.append({metrics.metric_name(m): metrics.compute_metric(m, y_va, p_va, dt.task) for m in oof_metrics})
         _keep(dt, dm, history, fold)
     return oof, means['eval'], means['test'], scores
 
@@ -249,7 +249,7 @@ def device_cross_validation(dt, feed, folds, eval_feed, test_feed, fit_kwargs, o
                 if f is not None:
                     parts[key].append(dm.score_batches(f, bs).reshape(f.n, -1).contiguous())
             if scores is not None:
-                scores.append(training.epoch_metrics(list(oof_metrics), val.y, p_va, dt.task))
+                scores.append(metrics.epoch_metrics(list(oof_metrics), val.y, p_va, dt.task))
         _keep(dt, dm, history, fold)
     with _Phase('mean', dev):
         means = {k: ops.ensemble_mean(v, mode=1) if v else None for k, v in parts.items()}

@@ -16,6 +16,7 @@ from . import deepnets
 from .layers import BinaryFocalLoss, CategoricalFocalLoss, GHMCLoss, MultiColumnEmbedding, VarLenColumnEmbedding, dt_custom_objects
 from .. import functional as F
 from .. import _lib, losses, training
+from ..metrics import epoch_metrics
 from ..functional import Dense, Concatenate, Flatten, Input, Add, BatchNormalization, Dropout, Model
 from ..utils import consts
 
@@ -549,8 +550,8 @@ class DeepModel:
                 self._fused_plan.check_dedupe()        # batches beyond 8192 rows: an election table that overflowed (fused.py)
             logs = {'loss': float(torch.cat([l.reshape(-1) for l in losses]).mean().item()) if losses else float('nan')}
             if probs:
-                # on the device when the HIP metric kernels cover every metric (training.epoch_metrics), else on the host
-                logs.update(training.epoch_metrics(metrics, torch.cat(ys), torch.cat(probs), self.task))
+                # on the device when the HIP metric kernels cover every metric (metrics.epoch_metrics), else on the host
+                logs.update(epoch_metrics(metrics, torch.cat(ys), torch.cat(probs), self.task))
             if val is not None and (epoch + 1) % max(validation_freq, 1) == 0:
                 self._sync_sharded_tables()        # table rows owned by other ranks: fetch their current values
                 vlogs = self._evaluate_batches(val, batch_size, metrics)
@@ -612,7 +613,7 @@ class DeepModel:
         logs = {'loss': float((torch.stack(losses) * w).sum().item() / w.sum().item())}
         if weight_penalty is not None:
             logs['loss'] += float(weight_penalty.item())
-        logs.update(training.epoch_metrics(metrics, data.y, probs, self.task))
+        logs.update(epoch_metrics(metrics, data.y, probs, self.task))
         return logs
 
     def _forward_batches(self, data, batch_size, plan, each=None):

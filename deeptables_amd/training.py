@@ -1,7 +1,7 @@
 # -*- coding:utf-8 -*-
 """Train-step glue around the layers hot path: losses, Keras-semantics Adam
-(dense + row-sparse embedding update, HIP kernels), metrics, batching, and the data-parallel
-gradient exchange hook.  This is what `keras.Model.fit` does for the reference
+(dense + row-sparse embedding update, HIP kernels), batching, and the data-parallel
+gradient exchange hook (epoch metrics: metrics.py).  This is what `keras.Model.fit` does for the reference
 (deeptables/models/deepmodel.py:114-129, :319-346)."""
 import ctypes
 import math
@@ -1547,354 +1547,6 @@ def flatten_dense_parameters(model, optimizer, exclude=()):
             p.data = flat_param[o:o + n].view(p.shape)
     optimizer.register_flat_group(flat_param, flat_grad, members, off, grad_views=True)
     return flat_param, flat_grad
-
-
-# ---------------------------------------------------------------------------------------------
-# metrics (host side, outside any timed region)
-# ---------------------------------------------------------------------------------------------
-def metric_name(m):
-    if isinstance(m, str):
-        return m
-    return getattr(m, 'name', None) or getattr(m, '__name__', str(m))
-
-
-# Keras 3's definitions (average precision: sklearn's) in float64 from the float32 values, sums exact (math.fsum), counts
-# integers.  Keras clips probabilities to [epsilon, 1 - epsilon] with both bounds formed in float32; numpy.clip and
-# numpy.maximum keep a NaN, as Keras' ops do.
-_BCE_KEYS = ('binary_crossentropy', 'binarycrossentropy')
-_CCE_KEYS = ('categorical_crossentropy', 'categoricalcrossentropy')
-_LOGLOSS_KEYS = ('logloss', 'log_loss')                   # the task's cross-entropy
-_PRECISION_KEYS, _RECALL_KEYS = ('precision',), ('recall',)
-_TOPK_KEYS = ('top_k_categorical_accuracy', 'topkcategoricalaccuracy')
-_MSLE_KEYS = ('msle', 'mean_squared_logarithmic_error', 'meansquaredlogarithmicerror')
-_MAPE_KEYS = ('mape', 'mean_absolute_percentage_error', 'meanabsolutepercentageerror')
-_AP_KEYS = ('average_precision', 'pr_auc')
-CLIP_LO = float(np.float32(1e-7))
-CLIP_HI = float(np.float32(1) - np.float32(1e-7))
-TOP_K = 5
-
-
-def score_kind(key, task):
-    """'bce' / 'cce' / 'precision' / 'recall' / 'topk' / 'msle' / 'mape' / 'ap' for a lower-case metric name, else None"""
-    if key in _LOGLOSS_KEYS:
-        return 'cce' if task == consts.TASK_MULTICLASS else 'bce'
-    for kind, keys in (('bce', _BCE_KEYS), ('cce', _CCE_KEYS), ('precision', _PRECISION_KEYS), ('recall', _RECALL_KEYS),
-                       ('topk', _TOPK_KEYS), ('msle', _MSLE_KEYS), ('mape', _MAPE_KEYS), ('ap', _AP_KEYS)):
-        if key in keys:
-            return kind
-    return None
-
-
-def _exact_sum(a):
-    a = np.asarray(a, dtype=np.float64).reshape(-1)
-    return math.fsum(a.tolist()) if np.isfinite(a).all() else float(a.sum())      # (NaN / Inf: what numpy gives)
-
-
-def label_classes(y, C):
-    """the class a float label names ((int) label when 0 <= label < C), -1 where it names none (a NaN too)"""
-    y = np.asarray(y, dtype=np.float32).reshape(-1)
-    ok = (y >= 0) & (y.astype(np.float64) < C)
-    return np.where(ok, np.where(ok, y, 0).astype(np.int64), -1)
-
-
-def first_max(t):
-    """per row of t [n, C]: the class a `v > best` scan from class 0 ends on (numpy.argmax when the row holds no NaN)"""
-    best, idx = t[:, 0].copy(), np.zeros(t.shape[0], dtype=np.int64)
-    for c in range(1, t.shape[1]):
-        m = t[:, c] > best
-        best, idx = np.where(m, t[:, c], best), np.where(m, c, idx)
-    return idx
-
-
-def _elementwise_labels(y_true, y_prob, name, expand):
-    """y as float64 and p as float32, both flat: y_true as it is when it has y_prob's size, [n] labels against [n, C]
-    expanded to one-hot when `expand`"""
-    p = np.asarray(y_prob, dtype=np.float32)
-    if y_true.size == p.size:
-        return np.asarray(y_true, dtype=np.float32).astype(np.float64).reshape(-1), p.reshape(-1)
-    if expand and p.ndim == 2 and p.shape[1] > 1 and y_true.size == p.shape[0]:
-        y = label_classes(y_true, p.shape[1])[:, None] == np.arange(p.shape[1])[None, :]
-        return y.astype(np.float64).reshape(-1), p.reshape(-1)
-    raise ValueError(f'{name}: y_true {y_true.shape} does not match y_prob {p.shape}')
-
-
-def confusion_counts(y, p):
-    """(TP, FP, FN, TN): predicted positive is p > 0.5 (strict; a NaN is not), label positive is y != 0"""
-    pp, yp = p > np.float32(0.5), y != 0
-    return int((pp & yp).sum()), int((pp & ~yp).sum()), int((~pp & yp).sum()), int((~pp & ~yp).sum())
-
-
-def _rows_and_targets(y_true, y_prob, name):
-    p = np.asarray(y_prob, dtype=np.float32)
-    if p.ndim != 2 or p.shape[1] < 2:
-        raise ValueError(f'{name} needs y_prob [n, C] with C >= 2, got {p.shape}')
-    y = np.asarray(y_true, dtype=np.float32)
-    if y.shape == p.shape:
-        return p, y, first_max(y)
-    if y.size == p.shape[0]:
-        return p, None, label_classes(y, p.shape[1])
-    raise ValueError(f'{name}: y_true {y.shape} does not match y_prob {p.shape}')
-
-
-def _new_metric(kind, name, y_true, y_prob):
-    with np.errstate(all='ignore'):
-        if kind in ('bce', 'precision', 'recall'):
-            y, p = _elementwise_labels(y_true, y_prob, name, expand=kind != 'bce')
-            if kind == 'bce':
-                q = np.clip(p.astype(np.float64), CLIP_LO, CLIP_HI)
-                return _exact_sum(-(y * np.log(q) + (1.0 - y) * np.log(1.0 - q))) / p.size
-            tp, fp, fn, _ = confusion_counts(y, p)
-            den = tp + (fp if kind == 'precision' else fn)
-            return tp / den if den else 0.0
-        if kind in ('cce', 'topk'):
-            p32, onehot, target = _rows_and_targets(y_true, y_prob, name)
-            n, C = p32.shape
-            rows, valid = np.arange(n), target >= 0
-            if kind == 'topk':
-                pt = p32[rows, np.maximum(target, 0)]
-                above = (p32 > pt[:, None]).sum(1)
-                return int((valid & (pt == pt) & (above < TOP_K)).sum()) / n
-            p = p32.astype(np.float64)
-            s = np.zeros(n)
-            for c in range(C):                                  # (class order)
-                s += p[:, c]
-            q = np.clip(p / s[:, None], CLIP_LO, CLIP_HI)
-            if onehot is None:
-                loss = np.where(valid, -np.log(q[rows, np.maximum(target, 0)]), np.nan)
-            else:
-                acc = np.zeros(n)
-                for c in range(C):
-                    acc += onehot[:, c].astype(np.float64) * np.log(q[:, c])
-                loss = -acc
-            return _exact_sum(loss) / n
-        y = np.asarray(y_true, dtype=np.float32).astype(np.float64).reshape(-1)
-        p = np.asarray(y_prob, dtype=np.float32).astype(np.float64).reshape(-1)
-        if y.size != p.size:
-            raise ValueError(f'{name}: y_true {np.shape(y_true)} does not match y_prob {np.shape(y_prob)}')
-        if kind == 'msle':
-            d = np.log(np.maximum(p, CLIP_LO) + 1.0) - np.log(np.maximum(y, CLIP_LO) + 1.0)
-            return _exact_sum(d * d) / p.size
-        if kind == 'mape':
-            return 100.0 * (_exact_sum(np.abs(y - p) / np.maximum(np.abs(y), CLIP_LO)) / p.size)
-    from sklearn.metrics import average_precision_score            # 'ap'
-    if np.ndim(y_prob) == 2 and np.shape(y_prob)[1] > 1:
-        raise ValueError(f'{name} takes binary scores, got y_prob {np.shape(y_prob)}')
-    if not (y == 1).any():
-        return float('nan')
-    try:
-        return float(average_precision_score(y, p))
-    except ValueError:
-        return float('nan')
-
-
-def compute_metric(m, y_true, y_prob, task):
-    name = metric_name(m)
-    key = name.lower()
-    y_true = np.asarray(y_true)
-    y_prob = np.asarray(y_prob)
-    if callable(m) and not isinstance(m, str):
-        return float(m(y_true, y_prob))
-    kind = score_kind(key, task)
-    if kind is not None:
-        return float(_new_metric(kind, name, y_true, y_prob))
-    if key in ('accuracy', 'acc'):
-        if task == consts.TASK_MULTICLASS and y_prob.ndim == 2 and y_prob.shape[1] > 1:
-            yt = y_true.argmax(-1) if y_true.ndim == 2 else y_true
-            return float((y_prob.argmax(-1) == yt).mean())
-        return float(((y_prob.reshape(-1) > 0.5).astype(np.int64) == y_true.reshape(-1).astype(np.int64)).mean())
-    if key == 'auc':
-        from sklearn.metrics import roc_auc_score
-        try:
-            if y_prob.ndim == 2 and y_prob.shape[1] > 1:
-                return float(roc_auc_score(y_true, y_prob, multi_class='ovr'))
-            return float(roc_auc_score(y_true.reshape(-1), y_prob.reshape(-1)))
-        except ValueError:
-            return float('nan')
-    if key in ('mse', 'mean_squared_error'):
-        return float(((y_prob.reshape(-1) - y_true.reshape(-1)) ** 2).mean())
-    if key in ('rmse', 'rootmeansquarederror', 'root_mean_squared_error'):
-        return float(np.sqrt(((y_prob.reshape(-1) - y_true.reshape(-1)) ** 2).mean()))
-    if key in ('mae', 'mean_absolute_error'):
-        return float(np.abs(y_prob.reshape(-1) - y_true.reshape(-1)).mean())
-    raise ValueError(f'Unsupported metric: {name}')
-
-
-# ---------------------------------------------------------------------------------------------
-# metrics on the device (csrc/metrics.hip): the same values, computed where the outputs already are
-# ---------------------------------------------------------------------------------------------
-_AUC_KEYS = ('auc',)
-_ACC_KEYS = ('accuracy', 'acc')
-_MSE_KEYS = ('mse', 'mean_squared_error')
-_RMSE_KEYS = ('rmse', 'rootmeansquarederror', 'root_mean_squared_error')
-_MAE_KEYS = ('mae', 'mean_absolute_error')
-_metric_buffers = {}        # device -> {'ws': uint8 workspace (grown on demand), 'out': int64 result words}
-_OUT_AUC, _OUT_SUMS, _OUT_ARGMAX = 0, 8, 8 + _lib.DT_METRIC_SUMS_WORDS         # word offsets inside 'out'
-_OUT_RANKING = _OUT_ARGMAX + 1                                                  # ... the dt_score_* results behind them
-_OUT_BINARY = _OUT_RANKING + _lib.DT_SCORE_RANKING_WORDS
-_OUT_CATEGORICAL = _OUT_BINARY + _lib.DT_SCORE_BINARY_WORDS
-_OUT_REGRESSION = _OUT_CATEGORICAL + _lib.DT_SCORE_CATEGORICAL_WORDS
-_OUT_WORDS = _OUT_REGRESSION + _lib.DT_SCORE_REGRESSION_WORDS
-
-
-def _is_argmax_accuracy(y_prob, task):
-    return task == consts.TASK_MULTICLASS and y_prob.dim() == 2 and y_prob.shape[1] > 1
-
-
-def _rows_against_labels(y_true, y_prob):
-    """y_prob [n, C >= 2] against y_true [n] class numbers"""
-    return y_prob.dim() == 2 and y_prob.shape[1] > 1 and y_true.numel() == y_prob.shape[0]
-
-
-def device_metrics_supported(metrics, y_true, y_prob, task):
-    """True when compute_metrics_device serves every one of `metrics`: float32 tensors on the GPU, metric names it knows
-    (by name only, a callable is the host's), shapes the kernels cover, and DT_AMD_DEVICE_METRICS not '0'."""
-    if os.environ.get('DT_AMD_DEVICE_METRICS', '1') == '0' or not metrics:
-        return False
-    if not (torch.is_tensor(y_true) and torch.is_tensor(y_prob) and y_true.is_cuda and y_prob.is_cuda and
-            y_true.dtype == torch.float32 and y_prob.dtype == torch.float32 and y_prob.numel() > 0):
-        return False
-    flat = y_true.numel() == y_prob.numel()
-    rows = y_prob.dim() == 2 and y_prob.shape[1] > 1 and \
-        (y_true.numel() == y_prob.shape[0] or (y_true.dim() == 2 and y_true.shape == y_prob.shape))
-    for m in metrics:
-        if not isinstance(m, str):
-            return False
-        key = m.lower()
-        kind = score_kind(key, task)
-        if key in _ACC_KEYS:
-            if _is_argmax_accuracy(y_prob, task):
-                if not rows:
-                    return False
-            elif not flat:
-                return False
-        elif key in _AUC_KEYS or kind == 'ap':
-            if not flat or (y_prob.dim() == 2 and y_prob.shape[1] > 1):       # multiclass one-vs-rest AUC: the host's
-                return False
-        elif key in _MSE_KEYS + _RMSE_KEYS + _MAE_KEYS or kind in ('bce', 'msle', 'mape'):
-            if not flat:
-                return False
-        elif kind in ('precision', 'recall'):
-            if not (flat or _rows_against_labels(y_true, y_prob)):
-                return False
-        elif kind in ('cce', 'topk'):
-            if not rows:
-                return False
-        else:
-            return False
-    return True
-
-
-def compute_metrics_device(metrics, y_true, y_prob, task):
-    """{name: value} for metrics that device_metrics_supported accepts, from device tensors: at most one radix sort (AUC,
-    average precision), one reduction (accuracy / mse / rmse / mae), one element-wise pass (log loss, precision, recall), one
-    row pass (categorical cross-entropy, top-k accuracy) and one regression pass (msle, mape) whatever the number of metrics,
-    and one small device-to-host read.  The values are compute_metric's: AUC is the exact ROC AUC U2 / (2 P N) in integers
-    and average precision the groups' sum / P (both nan where sklearn raises or has no positive: one class only, a NaN / Inf
-    score); labels other than 0 / 1 send both to compute_metric on the host."""
-    if not device_metrics_supported(metrics, y_true, y_prob, task):
-        raise ValueError(f'compute_metrics_device does not cover {[metric_name(m) for m in metrics]} for these outputs')
-    h = lib()
-    y_true, y_prob = y_true.detach().contiguous(), y_prob.detach().contiguous()
-    n = y_prob.numel()
-    keys = [m.lower() for m in metrics]
-    kinds = [score_kind(k, task) for k in keys]
-    want_auc = any(k in _AUC_KEYS for k in keys)
-    want_ap = 'ap' in kinds
-    argmax_acc = _is_argmax_accuracy(y_prob, task) and any(k in _ACC_KEYS for k in keys)
-    want_sums = any(k in _MSE_KEYS + _RMSE_KEYS + _MAE_KEYS for k in keys) or \
-        (any(k in _ACC_KEYS for k in keys) and not argmax_acc)
-    want_binary = any(k in ('bce', 'precision', 'recall') for k in kinds)
-    want_rows = any(k in ('cce', 'topk') for k in kinds)
-    want_regression = any(k in ('msle', 'mape') for k in kinds)
-    buf = _metric_buffers.setdefault(y_prob.device, {})
-    if 'out' not in buf:
-        buf['out'] = torch.zeros(_OUT_WORDS, dtype=torch.int64, device=y_prob.device)
-    out = buf['out']
-    word = lambda k: ctypes.c_void_p(out.data_ptr() + 8 * k)
-    labels_kind = _lib.DT_METRIC_Y_ONEHOT if y_true.dim() == 2 and y_true.shape == y_prob.shape else _lib.DT_METRIC_Y_LABELS
-    auc_at = _OUT_RANKING if want_ap else _OUT_AUC          # dt_score_ranking's first five words are dt_metric_auc's
-    with torch.cuda.device(y_prob.device):
-        if want_auc or want_ap:
-            need = h.dt_score_ranking_workspace_bytes(n) if want_ap else h.dt_metric_auc_workspace_bytes(n)
-            if need < 0:
-                check(int(need), 'dt_metric_auc_workspace_bytes')
-            if buf.get('ws') is None or buf['ws'].numel() < need:
-                buf['ws'] = None                                    # (release before the larger one is allocated)
-                buf['ws'] = torch.empty(int(need), dtype=torch.uint8, device=y_prob.device)
-            if want_ap:                                             # one sort serves both
-                check(h.dt_score_ranking(ptr(y_prob), ptr(y_true), n, ptr(buf['ws']), word(_OUT_RANKING), stream_ptr()),
-                      'dt_score_ranking')
-            else:
-                check(h.dt_metric_auc(ptr(y_prob), ptr(y_true), n, ptr(buf['ws']), word(_OUT_AUC), stream_ptr()), 'dt_metric_auc')
-        if want_sums:
-            check(h.dt_metric_sums(ptr(y_true), ptr(y_prob), n, word(_OUT_SUMS), stream_ptr()), 'dt_metric_sums')
-        if argmax_acc:
-            check(h.dt_metric_argmax_hits(ptr(y_prob), ptr(y_true), labels_kind, y_prob.shape[0], y_prob.shape[1],
-                                          word(_OUT_ARGMAX), stream_ptr()), 'dt_metric_argmax_hits')
-        if want_binary:
-            if y_true.numel() == n:                                 # element against element, whatever the two shapes
-                args = (_lib.DT_METRIC_Y_ONEHOT, n, 1)
-            else:
-                args = (_lib.DT_METRIC_Y_LABELS, y_prob.shape[0], y_prob.shape[1])
-            check(h.dt_score_binary(ptr(y_true), ptr(y_prob), *args, word(_OUT_BINARY), stream_ptr()), 'dt_score_binary')
-        if want_rows:
-            check(h.dt_score_categorical(ptr(y_prob), ptr(y_true), labels_kind, y_prob.shape[0], y_prob.shape[1], TOP_K,
-                                         word(_OUT_CATEGORICAL), stream_ptr()), 'dt_score_categorical')
-        if want_regression:
-            check(h.dt_score_regression(ptr(y_true), ptr(y_prob), n, word(_OUT_REGRESSION), stream_ptr()),
-                  'dt_score_regression')
-        host = out.cpu()                                            # the one read: 27 KB
-    f64 = lambda k: float(host[k:k + 1].view(torch.float64))
-    u2, pos, neg, nonfinite, bad_label = (int(v) for v in host[auc_at:auc_at + 5])
-    hits = int(host[_OUT_SUMS])
-    sq, ab = (float(v) for v in host[_OUT_SUMS + 1:_OUT_SUMS + 3].view(torch.float64))
-    tp, fp, fn = (int(v) for v in host[_OUT_BINARY:_OUT_BINARY + 3])
-    res = {}
-    for m, key, kind in zip(metrics, keys, kinds):
-        if key in _AUC_KEYS or kind == 'ap':
-            if bad_label > 0:
-                v = compute_metric(m, y_true.cpu().numpy(), y_prob.cpu().numpy(), task)
-            elif kind == 'ap':
-                v = float('nan') if pos == 0 or nonfinite > 0 else f64(_OUT_RANKING + 5) / pos
-            elif pos == 0 or neg == 0 or nonfinite > 0:
-                v = float('nan')
-            else:
-                v = u2 / (2 * pos * neg)
-        elif key in _ACC_KEYS:
-            v = int(host[_OUT_ARGMAX]) / y_prob.shape[0] if argmax_acc else hits / n
-        elif key in _MSE_KEYS:
-            v = sq / n
-        elif key in _RMSE_KEYS:
-            v = math.sqrt(sq / n)
-        elif key in _MAE_KEYS:
-            v = ab / n
-        elif kind == 'bce':
-            v = f64(_OUT_BINARY + 4) / n
-        elif kind == 'precision':
-            v = tp / (tp + fp) if tp + fp else 0.0
-        elif kind == 'recall':
-            v = tp / (tp + fn) if tp + fn else 0.0
-        elif kind == 'topk':
-            v = int(host[_OUT_CATEGORICAL]) / y_prob.shape[0]
-        elif kind == 'cce':
-            v = f64(_OUT_CATEGORICAL + 1) / y_prob.shape[0]
-        elif kind == 'msle':
-            v = f64(_OUT_REGRESSION) / n
-        else:
-            v = 100.0 * (f64(_OUT_REGRESSION + 1) / n)
-        res[metric_name(m)] = float(v)
-    return res
-
-
-def epoch_metrics(metrics, y_true, y_prob, task):
-    """{name: value} for an epoch's concatenated labels and outputs (tensors): on the device when
-    device_metrics_supported, else exactly the host path — copy both to the host and compute_metric each."""
-    if not metrics:
-        return {}
-    if device_metrics_supported(metrics, y_true, y_prob, task):
-        return compute_metrics_device(metrics, y_true, y_prob, task)
-    yt, yp = y_true.cpu().numpy(), y_prob.cpu().numpy()
-    return {metric_name(m): compute_metric(m, yt, yp, task) for m in metrics}
 
 
 class History:

@@ -10,11 +10,11 @@ definition the quantity hypernets' `calc_score` gives on `predict` / `predict_pr
 Two paths compute it:
   * device: the frame is transformed ONCE into a resident `training.TableBatches`; every pass permutes the model inputs a raw
     column feeds inside the feed's blocks (`ops.permute_columns`: csrc/feed_columns.hip), scores the way `DeepModel.evaluate`
-    does (`DeepModel.score_batches`, `training.epoch_metrics`) and swaps the original values back.  Which inputs a raw column
+    does (`DeepModel.score_batches`, `metrics.epoch_metrics`) and swaps the original values back.  Which inputs a raw column
     feeds is declared by the preprocessor (`source_columns()`); every fitted transformer works row by row, so permuting the
     raw column and transforming equals transforming and permuting those inputs with the same permutation.
   * host: per pass copy the frame, permute the raw column(s), `preprocessor.transform_X`, `DeepModel.predict`,
-    `training.compute_metric`.  Any preprocessor, any device.
+    `metrics.compute_metric`.  Any preprocessor, any device.
 
 One permutation per (iteration, entry of `columns`), iteration-major, from `torch.randperm` with a `torch.Generator` on the
 model's device seeded by `random_state` — for every entry, also one that is skipped, so both paths consume the same
@@ -25,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from .. import ops, training
+from .. import metrics, ops, training
 
 HOST_BATCH_SIZE = 128           # the reference's predict_proba default
 DEVICE_BATCH_SIZE = 8192
@@ -167,7 +167,7 @@ def feed_scores(dt_model, feed, entries, metric, n_iter, sign, generator, batch_
     if reason is not None:
         raise ValueError(f'feature importance on the device: {reason}')
     dm = dt_model.model
-    name = training.metric_name(metric)
+    name = metrics.metric_name(metric)
     source_map = _source_map(dt_model.preprocessor)
     targets = [feed_targets(dm, feed, source_map, members) for _, members in entries]
 
@@ -175,7 +175,7 @@ def feed_scores(dt_model, feed, entries, metric, n_iter, sign, generator, batch_
         out = dm.score_batches(feed, batch_size)
         if on_pass is not None:
             on_pass(i, c, out)
-        return sign * training.epoch_metrics([metric], feed.y, out, dm.task)[name]
+        return sign * metrics.epoch_metrics([metric], feed.y, out, dm.task)[name]
 
     base = score(None, None)
     dec = np.zeros((n_iter, len(entries)), dtype=np.float64)
@@ -197,7 +197,7 @@ def feed_scores(dt_model, feed, entries, metric, n_iter, sign, generator, batch_
 
 def host_scores(dt_model, X, y_encoded, entries, metric, n_iter, sign, generator, batch_size, on_pass=None):
     """The loop a user writes by hand: per pass copy the frame, permute the raw column(s), transform_X, DeepModel.predict,
-    training.compute_metric -> (base_score, score_decreases).  A raw column the preprocessor declares to feed nothing is 0.0
+    metrics.compute_metric -> (base_score, score_decreases).  A raw column the preprocessor declares to feed nothing is 0.0
     without a pass (its permutation is drawn all the same)."""
     dm, pp = dt_model.model, dt_model.preprocessor
     source_map = _source_map(pp)
@@ -206,7 +206,7 @@ def host_scores(dt_model, X, y_encoded, entries, metric, n_iter, sign, generator
         out = dm.predict(pp.transform_X(frame), batch_size=batch_size)
         if on_pass is not None:
             on_pass(i, c, out)
-        return sign * training.compute_metric(metric, y_encoded, out, dm.task)
+        return sign * metrics.compute_metric(metric, y_encoded, out, dm.task)
 
     base = score(X, None, None)
     dec = np.zeros((n_iter, len(entries)), dtype=np.float64)

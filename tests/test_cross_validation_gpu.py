@@ -344,7 +344,7 @@ def test_fold_feeds_equal_the_feeds_of_frame_slices(run, dev):
 def test_out_of_fold_rows_sit_against_their_own_labels(run, dev):
     """the project's metric of oof_proba[idx_valid] against y[idx_valid] is the fold's last val_<metric> of its history exactly:
     the same weights in eval mode on the same rows at the same batch size, scored by the same code"""
-    from deeptables_amd import training
+    from deeptables_amd import metrics, training
     dt, oof = run['dt'], run['out'][0]
     y_t = np.asarray(run['pps'].y_t)
     metric = run['spec']['metrics'][0]
@@ -353,8 +353,8 @@ def test_out_of_fold_rows_sit_against_their_own_labels(run, dev):
         p = p[:, 1:] if dt.task == 'binary' else p.reshape(len(va), -1)
         val = training.TableBatches(run['pps'].X_t.iloc[va], y_t[va], dt.preprocessor.categorical_columns,
                                     dt.preprocessor.continuous_columns, dev, dt.task, dt.num_classes)
-        got = training.epoch_metrics([metric], val.y, torch.from_numpy(p.astype(np.float32)).to(dev), dt.task)
-        assert got[training.metric_name(metric)] == mi.meta['history'][f'val_{metric}'][-1], (mi.name, got)
+        got = metrics.epoch_metrics([metric], val.y, torch.from_numpy(p.astype(np.float32)).to(dev), dt.task)
+        assert got[metrics.metric_name(metric)] == mi.meta['history'][f'val_{metric}'][-1], (mi.name, got)
 
 
 def test_device_results_equal_the_host_restatement(run):
@@ -367,11 +367,11 @@ def test_device_results_equal_the_host_restatement(run):
     nan_rows = np.flatnonzero(np.isnan(oof.reshape(N_ROWS, -1)).any(1))
     assert np.array_equal(nan_rows, LEFT_OUT if run['name'] == 'dnn_multiclass' else [])
     if run['name'] == 'dnn_multiclass':
-        from deeptables_amd import training
+        from deeptables_amd import metrics
         scores, y_t = run['out'][3], np.asarray(run['pps'].y_t)
         assert len(scores) == FOLDS
         for (tr, va), s in zip(_folds(run), scores):
-            assert s['accuracy'] == training.compute_metric('accuracy', y_t[va], oof[va].astype(np.float32), dt.task)
+            assert s['accuracy'] == metrics.compute_metric('accuracy', y_t[va], oof[va].astype(np.float32), dt.task)
     if dt.task == 'binary':
         assert oof.shape == (N_ROWS, 2) and ev.shape == (150, 2) and np.array_equal(te[:, 0], 1.0 - te[:, 1])
     if dt.task == 'regression':

@@ -276,10 +276,10 @@ def test_left_out_rows_are_nan_and_scores_per_fold(_cpu):
     assert ev is None and te.shape == (30, 2)
     assert np.array_equal(np.flatnonzero(np.isnan(oof).any(1)), left) and np.isnan(oof[left]).all()
     assert len(scores) == FOLDS and all(set(s) == {'auc', 'accuracy'} for s in scores)
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y_enc = dt.preprocessor.transform_y(y)
     for (tr, va), s in zip(CS.LeaveOut(FOLDS, left).split(df), scores):
-        assert s['auc'] == training.compute_metric('auc', y_enc[va], oof[va][:, 1:].astype(np.float32), 'binary')
+        assert s['auc'] == metrics.compute_metric('auc', y_enc[va], oof[va][:, 1:].astype(np.float32), 'binary')
     with pytest.raises(ValueError, match='sample_weight'):
         dt.fit_cross_validation(df, y, num_folds=FOLDS, sample_weight=w[:-1], verbose=0)
 

@@ -251,7 +251,7 @@ def _same_bits(feed, before):
 
 
 def test_feed_is_bit_identical_afterwards_also_when_a_pass_raises(deepfm, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     dt, df, y = deepfm
     feed = F.make_feed(dt, df, dt.preprocessor.transform_y(y))
     assert F.device_refusal(dt, feed) is None and all(b.is_cuda for b in feed.blocks)
@@ -259,7 +259,7 @@ def test_feed_is_bit_identical_afterwards_also_when_a_pass_raises(deepfm, monkey
     entries = F._entries(df, None)
     F.feed_scores(dt, feed, entries, 'auc', 2, 1.0, F._generator(dt.model.device, 1), 256)
     assert _same_bits(feed, before)
-    real, calls, seen = training.epoch_metrics, [0], []
+    real, calls, seen = metrics.epoch_metrics, [0], []
 
     def third_pass_raises(metrics, y_true, y_prob, task):
         calls[0] += 1
@@ -268,7 +268,7 @@ def test_feed_is_bit_identical_afterwards_also_when_a_pass_raises(deepfm, monkey
             raise RuntimeError('metric failed')
         return real(metrics, y_true, y_prob, task)
 
-    monkeypatch.setattr(training, 'epoch_metrics', third_pass_raises)
+    monkeypatch.setattr(metrics, 'epoch_metrics', third_pass_raises)
     with pytest.raises(RuntimeError, match='metric failed'):
         F.feed_scores(dt, feed, entries, 'auc', 2, 1.0, F._generator(dt.model.device, 1), 256)
     assert seen == [True] and _same_bits(feed, before)
@@ -277,14 +277,14 @@ def test_feed_is_bit_identical_afterwards_also_when_a_pass_raises(deepfm, monkey
 # ---- 4. nothing large crosses -----------------------------------------------------------------------------------------------
 def test_no_row_sized_tensor_crosses_to_the_host_in_a_pass(deepfm, monkeypatch):
     """Tensor.cpu / .numpy / .tolist on a tensor of n or more elements, counted while the passes run.  The metric's own result
-    buffer (training._OUT_WORDS words, read once per pass) must stay below n for the count to mean what it says: the 600-row
+    buffer (metrics._OUT_WORDS words, read once per pass) must stay below n for the count to mean what it says: the 600-row
     frame is scored six times over."""
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     dt, df, y = deepfm
     df = pd.concat([df] * 6, ignore_index=True)
     y = np.concatenate([y] * 6)
     n = len(df)
-    assert training._OUT_WORDS < n
+    assert metrics._OUT_WORDS < n
     big = [0]
 
     def counting(name):

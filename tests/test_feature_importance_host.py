@@ -166,11 +166,11 @@ def test_feed_path_on_cpu_tensors_is_the_host_path(fitted, task, metric, mode):
 
 
 def test_feed_is_restored_when_a_pass_raises(fitted, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     dt, df, y = fitted['binary']
     feed = F.make_feed(dt, df, dt.preprocessor.transform_y(y))
     before = _feed_bits(feed)
-    real, calls, seen = training.epoch_metrics, [0], []
+    real, calls, seen = metrics.epoch_metrics, [0], []
 
     def third_pass_raises(metrics, y_true, y_prob, task):
         calls[0] += 1
@@ -179,7 +179,7 @@ def test_feed_is_restored_when_a_pass_raises(fitted, monkeypatch):
             raise RuntimeError('metric failed')
         return real(metrics, y_true, y_prob, task)
 
-    monkeypatch.setattr(training, 'epoch_metrics', third_pass_raises)
+    monkeypatch.setattr(metrics, 'epoch_metrics', third_pass_raises)
     with pytest.raises(RuntimeError, match='metric failed'):
         F.feed_scores(dt, feed, F._entries(df, None), 'auc', 2, 1.0, F._generator('cpu', 3), 128)
     assert seen == [True] and _same_bits(feed, before)
@@ -320,10 +320,10 @@ def test_a_group_is_permuted_with_one_permutation(fitted):
     assert res['columns'] == [('age', 'job'), 'rate']
     # by hand: the same stream, ONE permutation for both members
     pp, dm = dt.preprocessor, dt.model
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     g = torch.Generator().manual_seed(4)
     y_enc = pp.transform_y(y)
-    score = lambda f: training.compute_metric('auc', y_enc, dm.predict(pp.transform_X(f), batch_size=128), dm.task)
+    score = lambda f: metrics.compute_metric('auc', y_enc, dm.predict(pp.transform_X(f), batch_size=128), dm.task)
     base, want = score(df), np.zeros((2, 2))
     for i in range(2):
         for c, members in enumerate((['age', 'job'], ['rate'])):

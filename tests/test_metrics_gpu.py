@@ -191,17 +191,17 @@ def test_auc_counts_nonfinite_scores_and_bad_labels(dev):
 
 
 def _device_metrics(names, y, p, task, dev):
-    from deeptables_amd import training
-    return training.compute_metrics_device(names, torch.from_numpy(np.array(y)).to(dev), torch.from_numpy(np.array(p)).to(dev), task)
+    from deeptables_amd import metrics
+    return metrics.compute_metrics_device(names, torch.from_numpy(np.array(y)).to(dev), torch.from_numpy(np.array(p)).to(dev), task)
 
 
 def test_auc_through_compute_metrics_device(dev, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     n = 2 * _tile() + 3
     score, label, words = _auc_case('rare_positives', n)
     got = _device_metrics(['AUC'], label, score.reshape(-1, 1), 'binary', dev)
     assert got == {'AUC': words[0] / (2 * words[1] * words[2])}
-    assert abs(got['AUC'] - training.compute_metric('AUC', label, score, 'binary')) <= 1e-12
+    assert abs(got['AUC'] - metrics.compute_metric('AUC', label, score, 'binary')) <= 1e-12
     # one class only, a NaN, an Inf: nan, as the host path (roc_auc_score raises there)
     assert np.isnan(_device_metrics(['auc'], np.zeros(n, dtype=np.float32), score, 'binary', dev)['auc'])
     assert np.isnan(_device_metrics(['auc'], np.ones(n, dtype=np.float32), score, 'binary', dev)['auc'])
@@ -209,14 +209,14 @@ def test_auc_through_compute_metrics_device(dev, monkeypatch):
         s = np.array(score)
         s[n // 2] = bad
         assert np.isnan(_device_metrics(['AUC'], label, s, 'binary', dev)['AUC'])
-        assert np.isnan(training.compute_metric('AUC', label, s, 'binary'))
+        assert np.isnan(metrics.compute_metric('AUC', label, s, 'binary'))
     # a label 2.0: the host path's value, whatever it is (here: roc_auc_score takes 2 for the positive class)
     y2 = np.array(label) * 2
-    want = training.compute_metric('AUC', y2, score, 'binary')
+    want = metrics.compute_metric('AUC', y2, score, 'binary')
     assert np.isfinite(want) and _device_metrics(['AUC'], y2, score, 'binary', dev)['AUC'] == want
     y3 = np.array(label)
     y3[5] = 2.0
-    assert np.isnan(training.compute_metric('AUC', y3, score, 'binary')) and np.isnan(_device_metrics(['AUC'], y3, score, 'binary', dev)['AUC'])
+    assert np.isnan(metrics.compute_metric('AUC', y3, score, 'binary')) and np.isnan(_device_metrics(['AUC'], y3, score, 'binary', dev)['AUC'])
 
 
 # ---- accuracy / MSE / MAE --------------------------------------------------------------------------------------------------
@@ -267,7 +267,7 @@ def test_sums_hits_exact_and_float64_sums_within_the_rounding_bound(dev, kind, s
 @pytest.mark.parametrize('size', SIZE_INDEX, ids=SIZE_IDS)
 @pytest.mark.parametrize('C', [3, 10])
 def test_multiclass_hits_exact(dev, C, size):
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, metrics
     h = _lib.lib()
     n = _sizes()[size]
     rng = np.random.default_rng(4000 + n + C)
@@ -283,8 +283,8 @@ def test_multiclass_hits_exact(dev, C, size):
         _lib.check(h.dt_metric_argmax_hits(_lib.ptr(pd_), _lib.ptr(yd), kind, n, C, _lib.ptr(out), _lib.stream_ptr()),
                    'dt_metric_argmax_hits')
         assert int(out[0]) == want and bool((out[1:] == -7).all())
-        got = training.compute_metrics_device(['accuracy'], yd, pd_, 'multiclass')
-        assert got == {'accuracy': training.compute_metric('accuracy', y, p, 'multiclass')} == {'accuracy': want / n}
+        got = metrics.compute_metrics_device(['accuracy'], yd, pd_, 'multiclass')
+        assert got == {'accuracy': metrics.compute_metric('accuracy', y, p, 'multiclass')} == {'accuracy': want / n}
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------
@@ -316,17 +316,17 @@ def _model(task, metrics):
 
 def _forbid_the_host_path(monkeypatch):
     import sklearn.metrics
-    from deeptables_amd import training
+    from deeptables_amd import metrics
 
     def forbidden(*a, **k):
         raise AssertionError('the host metric path was taken')
 
     monkeypatch.setattr(sklearn.metrics, 'roc_auc_score', forbidden)
-    monkeypatch.setattr(training, 'compute_metric', forbidden)
+    monkeypatch.setattr(metrics, 'compute_metric', forbidden)
 
 
 def test_fit_and_evaluate_score_on_the_device_binary(dev, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     df, y = _frame('binary')
     dm = _model('binary', ['AUC', 'accuracy'])
     with monkeypatch.context() as mp:
@@ -338,8 +338,8 @@ def test_fit_and_evaluate_score_on_the_device_binary(dev, monkeypatch):
     assert all(k in ev for k in ('loss', 'AUC', 'accuracy'))
     again = dm.evaluate(df, y, batch_size=64)
     prob = dm.predict(df, batch_size=64)
-    assert abs(again['AUC'] - training.compute_metric('AUC', y, prob, 'binary')) <= 1e-12
-    assert again['accuracy'] == training.compute_metric('accuracy', y, prob, 'binary')
+    assert abs(again['AUC'] - metrics.compute_metric('AUC', y, prob, 'binary')) <= 1e-12
+    assert again['accuracy'] == metrics.compute_metric('accuracy', y, prob, 'binary')
     assert again['AUC'] == ev['AUC'] and again['accuracy'] == ev['accuracy']
 
 

@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """CPU: the device metrics' reference (tests/metrics_reference.py) against a brute-force pair count and sklearn, the C-ABI
-surface and argument checks of the dt_metric_* entry points (no launch), and the routing of training.epoch_metrics."""
+surface and argument checks of the dt_metric_* entry points (no launch), and the routing of metrics.epoch_metrics."""
 import ctypes
 import os
 import re
@@ -184,87 +184,87 @@ class _FakeCuda:
 
 @pytest.fixture
 def host_calls(monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     calls = []
 
     def fake(m, y_true, y_prob, task):
         assert isinstance(y_true, np.ndarray) and isinstance(y_prob, np.ndarray)
-        calls.append(training.metric_name(m))
+        calls.append(metrics.metric_name(m))
         return 0.25
 
-    monkeypatch.setattr(training, 'compute_metric', fake)
-    monkeypatch.setattr(training, 'compute_metrics_device', lambda *a, **k: pytest.fail('device path taken'))
+    monkeypatch.setattr(metrics, 'compute_metric', fake)
+    monkeypatch.setattr(metrics, 'compute_metrics_device', lambda *a, **k: pytest.fail('device path taken'))
     monkeypatch.setattr(torch, 'is_tensor', lambda t: isinstance(t, (torch.Tensor, _FakeCuda)))
     monkeypatch.delenv('DT_AMD_DEVICE_METRICS', raising=False)
     return calls
 
 
 def test_routing_takes_the_host_path_for_cpu_tensors(host_calls):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p = torch.tensor([0., 1, 1, 0]), torch.tensor([[.2], [.7], [.6], [.4]])
-    assert not training.device_metrics_supported(['AUC'], y, p, 'binary')
-    assert training.epoch_metrics(['AUC', 'accuracy'], y, p, 'binary') == {'AUC': 0.25, 'accuracy': 0.25}
+    assert not metrics.device_metrics_supported(['AUC'], y, p, 'binary')
+    assert metrics.epoch_metrics(['AUC', 'accuracy'], y, p, 'binary') == {'AUC': 0.25, 'accuracy': 0.25}
     assert host_calls == ['AUC', 'accuracy']
 
 
 def test_routing_takes_the_host_path_when_switched_off(host_calls, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p = _FakeCuda(torch.tensor([0., 1, 1, 0])), _FakeCuda(torch.tensor([[.2], [.7], [.6], [.4]]))
-    assert training.device_metrics_supported(['AUC', 'acc', 'mse', 'RMSE', 'mae'], y, p, 'binary')   # (the tensors qualify)
+    assert metrics.device_metrics_supported(['AUC', 'acc', 'mse', 'RMSE', 'mae'], y, p, 'binary')   # (the tensors qualify)
     monkeypatch.setenv('DT_AMD_DEVICE_METRICS', '0')
-    assert not training.device_metrics_supported(['AUC'], y, p, 'binary')
-    assert training.epoch_metrics(['AUC'], y, p, 'binary') == {'AUC': 0.25}
+    assert not metrics.device_metrics_supported(['AUC'], y, p, 'binary')
+    assert metrics.epoch_metrics(['AUC'], y, p, 'binary') == {'AUC': 0.25}
     assert host_calls == ['AUC']
 
 
 def test_routing_takes_the_host_path_for_a_callable_metric(host_calls):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
 
     def my_metric(y_true, y_prob):
         return 1.0
 
     y, p = _FakeCuda(torch.tensor([0., 1, 1, 0])), _FakeCuda(torch.tensor([[.2], [.7], [.6], [.4]]))
-    assert not training.device_metrics_supported(['AUC', my_metric], y, p, 'binary')
-    assert training.epoch_metrics(['AUC', my_metric], y, p, 'binary') == {'AUC': 0.25, 'my_metric': 0.25}
+    assert not metrics.device_metrics_supported(['AUC', my_metric], y, p, 'binary')
+    assert metrics.epoch_metrics(['AUC', my_metric], y, p, 'binary') == {'AUC': 0.25, 'my_metric': 0.25}
     assert host_calls == ['AUC', 'my_metric']
 
 
 def test_routing_takes_the_host_path_for_multiclass_auc(host_calls):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     p = _FakeCuda(torch.tensor([[.2, .5, .3], [.7, .2, .1], [.1, .1, .8], [.3, .4, .3]]))
     y = _FakeCuda(torch.eye(3)[[1, 0, 2, 1]])
-    assert training.device_metrics_supported(['accuracy'], y, p, 'multiclass')
-    assert training.device_metrics_supported(['accuracy'], _FakeCuda(torch.tensor([1., 0, 2, 1])), p, 'multiclass')
-    assert not training.device_metrics_supported(['AUC'], y, p, 'multiclass')
-    assert training.epoch_metrics(['AUC', 'accuracy'], y, p, 'multiclass') == {'AUC': 0.25, 'accuracy': 0.25}
+    assert metrics.device_metrics_supported(['accuracy'], y, p, 'multiclass')
+    assert metrics.device_metrics_supported(['accuracy'], _FakeCuda(torch.tensor([1., 0, 2, 1])), p, 'multiclass')
+    assert not metrics.device_metrics_supported(['AUC'], y, p, 'multiclass')
+    assert metrics.epoch_metrics(['AUC', 'accuracy'], y, p, 'multiclass') == {'AUC': 0.25, 'accuracy': 0.25}
     assert host_calls == ['AUC', 'accuracy']
 
 
 def test_routing_keeps_other_dtypes_and_no_metrics_on_the_host(host_calls):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p = _FakeCuda(torch.tensor([0., 1, 1, 0]).double()), _FakeCuda(torch.tensor([[.2], [.7], [.6], [.4]]))
-    assert not training.device_metrics_supported(['mse'], y, p, 'regression')
-    assert training.epoch_metrics([], y, p, 'regression') == {} and host_calls == []
+    assert not metrics.device_metrics_supported(['mse'], y, p, 'regression')
+    assert metrics.epoch_metrics([], y, p, 'regression') == {} and host_calls == []
 
 
 def test_an_unknown_metric_name_still_raises():
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p = torch.tensor([0., 1, 1, 0]), torch.tensor([[.2], [.7], [.6], [.4]])
     with pytest.raises(ValueError, match='Unsupported metric'):
-        training.epoch_metrics(['AUC', 'f1'], y, p, 'binary')
+        metrics.epoch_metrics(['AUC', 'f1'], y, p, 'binary')
     with pytest.raises(ValueError, match='Unsupported metric'):
-        training.compute_metric('f1', y.numpy(), p.numpy(), 'binary')
+        metrics.compute_metric('f1', y.numpy(), p.numpy(), 'binary')
     yc, pc = _FakeCuda(y), _FakeCuda(p)
-    assert not training.device_metrics_supported(['f1'], yc, pc, 'binary')
+    assert not metrics.device_metrics_supported(['f1'], yc, pc, 'binary')
 
 
 def test_host_path_values_are_unchanged():
     """epoch_metrics on CPU tensors is compute_metric on their arrays, value for value"""
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     rng = np.random.default_rng(5)
     y = (rng.random(500) < 0.3).astype(np.float32)
     p = rng.random((500, 1)).astype(np.float32)
     names = ['AUC', 'accuracy', 'mse', 'rmse', 'mae']
-    got = training.epoch_metrics(names, torch.from_numpy(y), torch.from_numpy(p), 'binary')
-    assert got == {m: training.compute_metric(m, y, p, 'binary') for m in names}
+    got = metrics.epoch_metrics(names, torch.from_numpy(y), torch.from_numpy(p), 'binary')
+    assert got == {m: metrics.compute_metric(m, y, p, 'binary') for m in names}
     assert abs(got['AUC'] - R.auc(p, y)) <= 1e-12

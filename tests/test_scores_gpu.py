@@ -1,7 +1,7 @@
 # -*- coding:utf-8 -*-
 """GPU: the dt_score_* entry points of csrc/metrics.hip — log loss + precision / recall counts, MSLE / MAPE, top-k hits +
 categorical cross-entropy, AUC + average precision — called through the C-ABI against tests/scores_reference.py: integers
-exactly, float64 sums within the bounds derived there; then training.compute_metrics_device and fit / evaluate on top."""
+exactly, float64 sums within the bounds derived there; then metrics.compute_metrics_device and fit / evaluate on top."""
 import functools
 import math
 
@@ -410,15 +410,15 @@ def test_ranking_counts_nonfinite_scores_and_bad_labels(dev):
 
 # ---- compute_metrics_device ------------------------------------------------------------------------------------------------
 def _device_and_host(names, y, p, task, dev, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     yd, pd_ = _dev(y, dev), _dev(p, dev)
-    assert training.device_metrics_supported(names, yd, pd_, task)
-    got = training.compute_metrics_device(names, yd, pd_, task)
-    assert training.epoch_metrics(names, yd, pd_, task) == got
+    assert metrics.device_metrics_supported(names, yd, pd_, task)
+    got = metrics.compute_metrics_device(names, yd, pd_, task)
+    assert metrics.epoch_metrics(names, yd, pd_, task) == got
     with monkeypatch.context() as mp:
         mp.setenv('DT_AMD_DEVICE_METRICS', '0')
-        mp.setattr(training, 'compute_metrics_device', lambda *a, **k: pytest.fail('device path taken'))
-        host = training.epoch_metrics(names, yd, pd_, task)
+        mp.setattr(metrics, 'compute_metrics_device', lambda *a, **k: pytest.fail('device path taken'))
+        host = metrics.epoch_metrics(names, yd, pd_, task)
     assert list(got) == list(names) == list(host)
     return got, host
 
@@ -430,13 +430,13 @@ def _within(what, got, want, rel):
 
 
 def test_compute_metrics_device_binary_set(dev, monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     n = 2 * _lib().lib().dt_metric_sort_tile() + 3
     score, label, want = _rank_case('rare_positives', n)
     p = score.reshape(-1, 1)
     names = ['AUC', 'average_precision', 'binary_crossentropy', 'Precision', 'Recall', 'accuracy']
     got, host = _device_and_host(names, label, p, 'binary', dev, monkeypatch)
-    two = training.compute_metrics_device(['AUC', 'accuracy'], _dev(label, dev), _dev(p, dev), 'binary')
+    two = metrics.compute_metrics_device(['AUC', 'accuracy'], _dev(label, dev), _dev(p, dev), 'binary')
     assert two == {'AUC': got['AUC'], 'accuracy': got['accuracy']}                  # bit-equal: the same integers
     assert got['Precision'] == host['Precision'] and got['Recall'] == host['Recall'] and got['accuracy'] == host['accuracy']
     assert abs(got['AUC'] - host['AUC']) <= 1e-12
@@ -448,21 +448,21 @@ def test_compute_metrics_device_binary_set(dev, monkeypatch):
     _within('binary_crossentropy', got['binary_crossentropy'], host['binary_crossentropy'], S.sum_bound(n, S.E_BCE))
     # where AUC is nan, average precision is: no positive, a NaN, an Inf; with positives only it is 1.0
     yd, pd_ = _dev(np.zeros(n, np.float32), dev), _dev(p, dev)
-    r = training.compute_metrics_device(['pr_auc', 'precision', 'recall'], yd, pd_, 'binary')
+    r = metrics.compute_metrics_device(['pr_auc', 'precision', 'recall'], yd, pd_, 'binary')
     assert math.isnan(r['pr_auc']) and r['precision'] == 0.0 and r['recall'] == 0.0
-    r = training.compute_metrics_device(['pr_auc', 'AUC'], _dev(np.ones(n, np.float32), dev), pd_, 'binary')
+    r = metrics.compute_metrics_device(['pr_auc', 'AUC'], _dev(np.ones(n, np.float32), dev), pd_, 'binary')
     assert abs(r['pr_auc'] - 1.0) <= S.sum_bound(n, S.E_AP) and math.isnan(r['AUC'])
     for bad in (np.nan, np.inf):
         s = np.array(p)
         s[n // 2] = bad
-        r = training.compute_metrics_device(['average_precision'], _dev(label, dev), _dev(s, dev), 'binary')
-        assert math.isnan(r['average_precision']) and math.isnan(training.compute_metric('average_precision', label, s, 'binary'))
+        r = metrics.compute_metrics_device(['average_precision'], _dev(label, dev), _dev(s, dev), 'binary')
+        assert math.isnan(r['average_precision']) and math.isnan(metrics.compute_metric('average_precision', label, s, 'binary'))
     # labels 2 and 0.5: average precision is the host's value, precision counts them positive
     for other in (2.0, 0.5):
         y2 = np.array(label)
         y2[y2 == 1] = other
-        r = training.compute_metrics_device(['average_precision', 'precision'], _dev(y2, dev), pd_, 'binary')
-        h = training.compute_metric('average_precision', y2, p, 'binary')
+        r = metrics.compute_metrics_device(['average_precision', 'precision'], _dev(y2, dev), pd_, 'binary')
+        h = metrics.compute_metric('average_precision', y2, p, 'binary')
         assert (math.isnan(h) and math.isnan(r['average_precision'])) or r['average_precision'] == h
         assert r['precision'] == got['Precision']
 
@@ -537,12 +537,12 @@ def _model(task, num_classes, metrics):
 @pytest.mark.parametrize('task', list(TASKS))
 def test_fit_and_evaluate_report_the_new_metrics(dev, monkeypatch, task):
     """fit(metrics=['AUC', 'binary_crossentropy', 'Precision', 'Recall']) raised 'Unsupported metric' before these kernels"""
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     num_classes, names = TASKS[task]
     df, y = _frame(task)
     dm = _model(task, num_classes, names)
     with monkeypatch.context() as mp:
-        mp.setattr(training, 'compute_metric', lambda *a, **k: pytest.fail('the host metric path was taken'))
+        mp.setattr(metrics, 'compute_metric', lambda *a, **k: pytest.fail('the host metric path was taken'))
         hist = dm.fit(df, y, batch_size=64, epochs=2, verbose=0, validation_split=0.2)
         on = dm.evaluate(df, y, batch_size=64)
     for k in names:
@@ -557,7 +557,7 @@ def test_fit_and_evaluate_report_the_new_metrics(dev, monkeypatch, task):
     rel = {'bce': S.sum_bound(n_out, S.E_BCE), 'cce': S.sum_bound(ROWS + num_classes, S.E_CCE),
            'ap': S.sum_bound(ROWS, S.E_AP), 'mape': S.sum_bound(ROWS, S.E_MAPE)}
     for k in names:
-        kind = training.score_kind(k.lower(), task)
+        kind = metrics.score_kind(k.lower(), task)
         print(f'{task} {k}: device {on[k]!r} host {off[k]!r}')
         if k.lower() in EXACT:
             assert on[k] == off[k], k

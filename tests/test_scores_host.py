@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """CPU: the reference of the dt_score_* kernels (tests/scores_reference.py) against sklearn where the definitions coincide
-and against brute force where they do not; training.compute_metric / epoch_metrics for the new metric names; their routing;
+and against brute force where they do not; metrics.compute_metric / epoch_metrics for the new metric names; their routing;
 and the C-ABI surface and argument checks of the dt_score_* entry points (no launch)."""
 import ctypes
 import math
@@ -214,7 +214,7 @@ def _reference_value(kind, y, p):
                                         ('onehot', ['cce', 'topk', 'precision', 'recall', 'bce']),
                                         ('regression', ['msle', 'mape'])])
 def test_compute_metric_serves_every_name_in_any_case(case, kinds):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p, task = _cases()[case]
     for kind in kinds:
         want = _reference_value(kind, y, p)
@@ -222,46 +222,46 @@ def test_compute_metric_serves_every_name_in_any_case(case, kinds):
             if alias in ('logloss', 'log_loss') and (kind == 'cce') != (task == 'multiclass'):
                 continue
             for name in (alias, alias.upper(), alias.title()):
-                got = training.compute_metric(name, y, p, task)
+                got = metrics.compute_metric(name, y, p, task)
                 assert isinstance(got, float)
                 assert got == want or abs(got - want) <= 1e-13 * abs(want), (name, got, want)
-                assert training.epoch_metrics([name], torch.from_numpy(y), torch.from_numpy(p), task) == {name: got}
+                assert metrics.epoch_metrics([name], torch.from_numpy(y), torch.from_numpy(p), task) == {name: got}
     with pytest.raises(ValueError, match='Unsupported metric'):
-        training.compute_metric('f1', y, p, task)
+        metrics.compute_metric('f1', y, p, task)
     with pytest.raises(ValueError, match='Unsupported metric'):
-        training.compute_metric('r2', y, p, task)
+        metrics.compute_metric('r2', y, p, task)
 
 
 def test_compute_metric_special_values():
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     y, p, _ = _cases()['binary']
     n = y.shape[0]
-    assert math.isnan(training.compute_metric('average_precision', np.zeros(n, np.float32), p, 'binary'))
-    assert training.compute_metric('average_precision', np.ones(n, np.float32), p, 'binary') == 1.0
+    assert math.isnan(metrics.compute_metric('average_precision', np.zeros(n, np.float32), p, 'binary'))
+    assert metrics.compute_metric('average_precision', np.ones(n, np.float32), p, 'binary') == 1.0
     bad = p.copy()
     bad[3] = np.nan
-    assert math.isnan(training.compute_metric('pr_auc', y, bad, 'binary'))
-    assert math.isnan(training.compute_metric('binary_crossentropy', y, bad, 'binary'))        # the clip keeps the NaN
+    assert math.isnan(metrics.compute_metric('pr_auc', y, bad, 'binary'))
+    assert math.isnan(metrics.compute_metric('binary_crossentropy', y, bad, 'binary'))        # the clip keeps the NaN
     bad[3] = np.inf
-    assert math.isfinite(training.compute_metric('binary_crossentropy', y, bad, 'binary'))     # ... and clips an Inf
-    assert training.compute_metric('precision', np.zeros(n, np.float32), p, 'binary') == 0.0
-    assert training.compute_metric('recall', np.zeros(n, np.float32), p, 'binary') == 0.0
-    assert training.compute_metric('precision', y, np.zeros_like(p), 'binary') == 0.0
+    assert math.isfinite(metrics.compute_metric('binary_crossentropy', y, bad, 'binary'))     # ... and clips an Inf
+    assert metrics.compute_metric('precision', np.zeros(n, np.float32), p, 'binary') == 0.0
+    assert metrics.compute_metric('recall', np.zeros(n, np.float32), p, 'binary') == 0.0
+    assert metrics.compute_metric('precision', y, np.zeros_like(p), 'binary') == 0.0
     y2 = y.copy()
     y2[y2 == 1] = 0.5                                          # precision counts any y != 0 as positive
-    assert training.compute_metric('precision', y2, p, 'binary') == training.compute_metric('precision', y, p, 'binary')
+    assert metrics.compute_metric('precision', y2, p, 'binary') == metrics.compute_metric('precision', y, p, 'binary')
     with pytest.raises(ValueError):
-        training.compute_metric('average_precision', *_cases()['onehot'][:2], 'multiclass')
+        metrics.compute_metric('average_precision', *_cases()['onehot'][:2], 'multiclass')
     with pytest.raises(ValueError):
-        training.compute_metric('categorical_crossentropy', y, p, 'binary')                    # one column
+        metrics.compute_metric('categorical_crossentropy', y, p, 'binary')                    # one column
 
 
 # ---- routing ---------------------------------------------------------------------------------------------------------------
 def test_routing_accepts_the_new_names_where_the_kernels_cover_them(monkeypatch):
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     monkeypatch.setattr(torch, 'is_tensor', lambda t: isinstance(t, (torch.Tensor, _FakeCuda)))
     monkeypatch.delenv('DT_AMD_DEVICE_METRICS', raising=False)
-    ok = training.device_metrics_supported
+    ok = metrics.device_metrics_supported
     y, p = _FakeCuda(torch.tensor([0., 1, 1, 0])), _FakeCuda(torch.tensor([[.2], [.7], [.6], [.4]]))
     assert ok(['AUC', 'average_precision', 'binary_crossentropy', 'Precision', 'Recall', 'accuracy', 'LogLoss', 'pr_auc'], y, p, 'binary')
     assert ok(['mse', 'msle', 'MAPE', 'mean_squared_logarithmic_error'], y, p, 'regression')
@@ -285,6 +285,45 @@ def test_routing_accepts_the_new_names_where_the_kernels_cover_them(monkeypatch)
     assert not ok(['precision'], torch.tensor([0., 1, 1, 0]), torch.tensor([[.2], [.7], [.6], [.4]]), 'binary')     # CPU tensors
     monkeypatch.setenv('DT_AMD_DEVICE_METRICS', '0')
     assert not ok(['precision'], y, p, 'binary')
+
+
+def test_every_name_reaches_the_same_table_row_on_the_host_and_the_device_path(monkeypatch):
+    """compute_metric and device_metrics_supported look a name up in metrics.KINDS: for every name of metrics.NAMES in
+    lower, upper and mixed case and every task, on one column and on [n, C], both take the same row; a name the table does not
+    hold is refused by both"""
+    from deeptables_amd import metrics
+    monkeypatch.setattr(torch, 'is_tensor', lambda t: isinstance(t, (torch.Tensor, _FakeCuda)))
+    monkeypatch.delenv('DT_AMD_DEVICE_METRICS', raising=False)
+    seen = []
+
+    class Spy(dict):
+        def __getitem__(self, kind):
+            seen.append(kind)
+            return dict.__getitem__(self, kind)._replace(host=lambda name, y_true, y_prob: 0.5)
+
+    monkeypatch.setattr(metrics, 'KINDS', Spy(metrics.KINDS))
+    y = torch.tensor([0., 1, 1, 0])
+    column, wide = torch.tensor([[.2], [.7], [.6], [.4]]), torch.tensor([[.2, .5, .3], [.7, .2, .1], [.1, .1, .8], [.3, .4, .3]])
+    assert len(metrics.NAMES) == 28 and set(metrics.NAMES.values()) - {'logloss'} <= set(metrics.KINDS)
+    rows = set()
+    for key in metrics.NAMES:
+        for name in (key, key.upper(), key.title()):
+            for task in ('binary', 'multiclass', 'regression'):
+                for p in (column, wide):
+                    del seen[:]
+                    assert metrics.compute_metric(name, y.numpy(), p.numpy(), task) == 0.5
+                    host_row = list(seen)
+                    del seen[:]
+                    metrics.device_metrics_supported([name], _FakeCuda(y), _FakeCuda(p), task)
+                    assert len(host_row) == 1 and seen == host_row and host_row[0] in metrics.KINDS, (name, task, host_row, seen)
+                    rows.add(host_row[0])
+    assert rows == set(metrics.KINDS)                              # (every row is some name's)
+    for name in ('f1', 'r2', 'logloss_', 'argmax_accuracy', ''):
+        for task in ('binary', 'multiclass', 'regression'):
+            del seen[:]
+            with pytest.raises(ValueError, match='Unsupported metric'):
+                metrics.compute_metric(name, y.numpy(), column.numpy(), task)
+            assert metrics.device_metrics_supported([name], _FakeCuda(y), _FakeCuda(column), task) is False and seen == []
 
 
 # ---- the C-ABI surface -----------------------------------------------------------------------------------------------------

@@ -1,6 +1,6 @@
 # -*- coding:utf-8 -*-
 """Times an epoch's AUC on resident outputs both ways (GPU, not a test): (i) the host path — copy scores and labels to the
-host, `training.compute_metric('AUC', ...)` = sklearn.metrics.roc_auc_score — and (ii) `training.compute_metrics_device`,
+host, `metrics.compute_metric('AUC', ...)` = sklearn.metrics.roc_auc_score — and (ii) `metrics.compute_metrics_device`,
 which ends in its small device-to-host read.  Seeded scores and labels, 3 % positives; both paths are warmed up, then
 alternated; a host clock around work that ends in a synchronise.  Prints ONE JSON line (profiles/metrics_bench.jsonl).
 
@@ -10,7 +10,7 @@ alternated; a host clock around work that ends in a synchronise.  Prints ONE JSO
     python tools/metrics_bench.py --bench scores       # log loss, precision / recall, average precision: one line per leg
 
 `--bench scores` times the metric names csrc/metrics.hip serves beyond AUC against what a user had before them: a callable
-metric wrapping sklearn.metrics.log_loss / precision_score / average_precision_score, which `training.epoch_metrics` sends to
+metric wrapping sklearn.metrics.log_loss / precision_score / average_precision_score, which `metrics.epoch_metrics` sends to
 the host path, copies included.  The same data, the same protocol, one JSON line per leg.
 
 The yardstick is the project's own step: the DeepFM step trains 8192 rows in 95.7 us, these rows in 98 ms."""
@@ -61,11 +61,11 @@ def bench_scores(args, base, label, score):
     """one JSON line per leg: the device call against the callable on the host path, warmed up, alternated, a host clock around
     work that ends in a synchronise (the host path ends in numpy, the device path in its read)"""
     import torch
-    from deeptables_amd import training
+    from deeptables_amd import metrics
     for leg, names, fn in score_legs():
-        run = {'device': lambda: training.compute_metrics_device(names, label, score, 'binary')}
+        run = {'device': lambda: metrics.compute_metrics_device(names, label, score, 'binary')}
         if fn is not None and 'host' in args.paths.split(','):
-            run['host'] = lambda: training.epoch_metrics([fn], label, score, 'binary')
+            run['host'] = lambda: metrics.epoch_metrics([fn], label, score, 'binary')
         times, values = {p: [] for p in run}, {}
         for p in run:
             for _ in range(args.warmup):
@@ -104,7 +104,7 @@ def main():
     import numpy as np
     import torch
     import __graft_entry__ as g
-    from deeptables_amd import _lib, training
+    from deeptables_amd import _lib, metrics
     tile = _lib.lib().dt_metric_sort_tile()
     n = args.rows
     res = {'bench': 'metrics_auc', 'rows': n, 'positives': 0.03, 'source_hash': g.source_hash(), 'sort_tile': tile,
@@ -134,10 +134,10 @@ def main():
 
     def host():
         yp, yt = score.cpu().numpy(), label.cpu().numpy()
-        return training.compute_metric('AUC', yt, yp, 'binary')
+        return metrics.compute_metric('AUC', yt, yp, 'binary')
 
     def device():
-        return training.compute_metrics_device(['AUC'], label, score, 'binary')['AUC']
+        return metrics.compute_metrics_device(['AUC'], label, score, 'binary')['AUC']
 
     run = {'host': host, 'device': device}
     times, values = {p: [] for p in paths}, {}
