@@ -385,6 +385,17 @@ SIGNATURES = {
     'dt_ensemble_mean': (_c_int, [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
     # the fitted preprocessor's transform on the device (csrc/prep_transform.hip): N, cols, cols_host, C, out_kind, out, stream
     'dt_prep_transform': (_c_int, [_c_i64, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
+    # histogram gradient-boosted trees for the GBM leaf features (csrc/gbdt.hip); `ws` is a host dt_gbdt_ws (ops.GbdtWs)
+    'dt_gbdt_bin': (_c_int, [_ptr, _c_int, _c_i64, _ptr, _c_int, _ptr, _ptr]),            # src, dtype, N, edges, n_edges, out, stream
+    'dt_gbdt_pack': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _ptr]),                         # bins, N, P, packed, stream
+    'dt_gbdt_grad': (_c_int, [_c_int, _ptr, _ptr, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),  # objective, scores, y, N, max_slot, sexp, qg, qh
+    'dt_gbdt_tree_begin': (_c_int, [_ptr, _ptr]),
+    'dt_gbdt_hist': (_c_int, [_ptr, _c_int, _ptr]),                                       # ws, root, stream
+    'dt_gbdt_split': (_c_int, [_ptr, _c_int, _ptr]),
+    'dt_gbdt_grow': (_c_int, [_ptr, _ptr]),
+    'dt_gbdt_leaf_update': (_c_int, [_ptr, _ptr, _ptr, _ptr]),                            # ws, scores, row_leaf, stream
+    # packed, N, P, T, L, node_feat, node_bin, node_child, n_nodes, out, stream
+    'dt_gbdt_predict_leaves': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -430,6 +441,11 @@ DT_PREP_LOOKUP, DT_PREP_CONT, DT_PREP_BIN, DT_PREP_COPY = 0, 1, 2, 3
 DT_PREP_IMPUTE, DT_PREP_SCALE = 0x1, 0x2
 DT_PREP_OUT_I32, DT_PREP_OUT_F32 = 0, 1
 DT_PREP_TILE_ROWS, DT_PREP_CHUNK_COLS, DT_PREP_MAX_BLOCKS, DT_PREP_COL_BYTES = 256, 32, 1024, 80
+# dt_gbdt_*: objectives, the histogram / partition geometry and the sizes of the workspace tables (include/dt_hip.h)
+DT_GBDT_BINARY, DT_GBDT_REGRESSION = 0, 1
+DT_GBDT_BINS, DT_GBDT_HIST_GROUP, DT_GBDT_HIST_ROWS, DT_GBDT_PART_CHUNK = 256, 8, 4096, 2048
+DT_GBDT_MAX_ROWS, DT_GBDT_MAX_FEATURES, DT_GBDT_MAX_LEAVES = 2147483647, 4096, 1024
+DT_GBDT_STATE_WORDS, DT_GBDT_LEAF_WORDS, DT_GBDT_WS_BYTES = 16, 12, 184
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

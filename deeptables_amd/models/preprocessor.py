@@ -10,7 +10,8 @@ Step order of `fit_transform` (preprocessor.py:165-204): y label-encode -> featu
 Where the reference defers to `hypernets.tabular.sklearn_ex` (absent here) the behaviour assumed is written next
 to the transformer: it only has to be self-consistent between fit and transform — the embedding gather sees ids in
 `[0, vocabulary_size)` either way (vocabulary_size = nunique + 2, preprocessor.py:333).
-GBM leaf features (`apply_gbm_features`, needs lightgbm) and the fit cache are not provided.
+GBM leaf features (`apply_gbm_features`) come from `GbmLeavesEncoder`, a histogram GBDT trained by this library's own HIP
+kernels (csrc/gbdt.hip) in place of hypernets' LgbmLeavesEncoder; the fit cache is not provided.
 """
 import collections
 import copy
@@ -203,6 +204,141 @@ class MultiVarLenFeatureEncoder:
 
     def vocabulary_size(self, name):
         return len(self.maps_[name]) + 1
+
+
+GBM_DEFAULTS = {'n_estimators': 100, 'num_leaves': 31, 'learning_rate': 0.1, 'max_bin': 255, 'min_child_samples': 20,
+                'reg_lambda': 0.0, 'min_split_gain': 0.0}
+
+
+def gbm_bin_edges(values, max_bin):
+    """The ascending float64 bin edges of one feature (bin = the number of edges <= x, NaN -> the last bin): with at most
+    `max_bin` distinct finite values the midpoints between neighbours (a midpoint that rounds onto its lower neighbour is moved to
+    the upper one, so neighbours always part), otherwise the max_bin - 1 quantiles k / max_bin, deduplicated."""
+    v = np.asarray(values, dtype=np.float64)
+    u = np.unique(v[np.isfinite(v)])
+    if len(u) <= max_bin:
+        mid = (u[:-1] + u[1:]) / 2
+        return np.where(mid > u[:-1], mid, u[1:])
+    return np.unique(np.quantile(v[np.isfinite(v)], np.arange(1, max_bin) / max_bin))
+
+
+class GbmLeavesEncoder:
+    """Stand-in for hypernets' LgbmLeavesEncoder (preprocessor.py:431-438): a gradient-boosted tree ensemble is fitted on the
+    prepared categorical and continuous columns and every tree's leaf index becomes a new column `gbm_leaf_<t>`.  The trees are
+    grown by this library's histogram GBDT on the GPU (ops.gbdt_*, csrc/gbdt.hip): LightGBM's algorithm in outline, NOT LightGBM
+    and not compared with it.  Deviations: categorical codes are binned as ordinal integers (LightGBM partitions the categories);
+    no row or column subsampling and no max_depth; binary log loss and L2 regression only.  The fitted state is numpy only."""
+
+    def __init__(self, cat_vars, cont_vars, task, **gbm_params):
+        unknown = sorted(set(gbm_params) - set(GBM_DEFAULTS))
+        if unknown:
+            raise ValueError(f'gbm_params: unsupported key(s) {unknown}; GbmLeavesEncoder takes {sorted(GBM_DEFAULTS)}')
+        if task not in (consts.TASK_BINARY, consts.TASK_REGRESSION):
+            raise ValueError(f'apply_gbm_features: task {task!r} is not supported yet; multiclass and multilabel boosting are a '
+                             f'follow-up, the GBM leaf features take binary and regression')
+        self.cat_vars, self.cont_vars, self.task = list(cat_vars), list(cont_vars), task
+        self.params = dict(GBM_DEFAULTS, **gbm_params)
+        p = self.params
+        if not 2 <= int(p['max_bin']) <= 255:
+            raise ValueError(f"gbm_params: max_bin must be in [2, 255], got {p['max_bin']}")
+        if int(p['n_estimators']) < 1 or int(p['num_leaves']) < 2 or int(p['min_child_samples']) < 0 or \
+                float(p['reg_lambda']) < 0 or float(p['min_split_gain']) < 0:
+            raise ValueError(f'gbm_params: n_estimators >= 1, num_leaves >= 2, min_child_samples, reg_lambda and min_split_gain >= 0: {p}')
+        self.columns = self.cat_vars + self.cont_vars
+        self.new_columns = []
+        self.edges_ = None
+        self.timings = None         # a dict: seconds per kernel role of the next fit (tools/gbm_bench.py)
+
+    @staticmethod
+    def _device():
+        import torch
+        from .._lib import DtHipError
+        if not torch.cuda.is_available():
+            raise DtHipError('deeptables_amd kernels run on the GPU only (apply_gbm_features fits its trees there); '
+                             'there is deliberately no CPU fallback for the hot path.')
+        return torch.device('cuda', torch.cuda.current_device())
+
+    def _upload(self, X, device):
+        """the feature columns as device tensors the binning kernel reads: int32 / int64 / float32 / float64 as they are,
+        every other numeric dtype as float64"""
+        import torch
+        cols = []
+        for c in self.columns:
+            a = np.asarray(X[c].values)
+            if a.dtype.kind not in 'biuf':
+                raise ValueError(f'apply_gbm_features: column {c!r} has dtype {a.dtype}; the trees need numeric columns '
+                                 f'(auto_encode_label encodes the categorical ones)')
+            if a.dtype.name not in ('int32', 'int64', 'float32', 'float64'):
+                a = a.astype(np.float64)
+            cols.append(torch.from_numpy(np.ascontiguousarray(a)).to(device))
+        return cols
+
+    def _append(self, X, leaves):
+        return pd.concat([X, pd.DataFrame(leaves, columns=self.new_columns, index=X.index)], axis=1)
+
+    def fit_transform(self, X, y):
+        import torch
+        from .. import ops
+        device = self._device()
+        p = self.params
+        T, L, N = int(p['n_estimators']), int(p['num_leaves']), len(X)
+        if not self.columns or N < 1:
+            raise ValueError('apply_gbm_features: no categorical or continuous column to fit the trees on')
+        objective = 'binary' if self.task == consts.TASK_BINARY else 'regression'
+        yv = np.asarray(y, dtype=np.float64).reshape(-1)
+        if objective == 'binary':
+            pbar = min(max(float(yv.mean()), 1e-15), 1 - 1e-15)
+            init = np.float32(np.log(pbar / (1 - pbar)))
+        else:
+            init = np.float32(yv.mean())
+        self.edges_ = [gbm_bin_edges(X[c].values, int(p['max_bin'])) for c in self.columns]
+        bins = ops.gbdt_bin(self._upload(X, device), self.edges_)
+        ws = ops.GbdtWorkspace(bins, L)
+        yd = torch.from_numpy(yv.astype(np.float32)).to(device)
+        scores = torch.full((N,), float(init), dtype=torch.float32, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        trees = {'node_feat': torch.empty((T, L - 1), **i32), 'node_bin': torch.empty((T, L - 1), **i32),
+                 'node_child': torch.empty((T, L - 1, 2), **i32), 'n_nodes': torch.empty(T, **i32),
+                 'leaf_value': torch.empty((T, L), dtype=torch.float32, device=device)}
+        leaves = torch.empty((T, N), **i32)
+        sexp = torch.empty((T, 2), **i32)
+        max_bits = torch.zeros(T, dtype=torch.int64, device=device)
+        grads = (torch.empty(N, **i32), torch.empty(N, **i32))
+        grow = {k: p[k] for k in ('num_leaves', 'min_child_samples', 'reg_lambda', 'min_split_gain', 'learning_rate')}
+        for t in range(T):              # launches only: the scale and the choice of leaves stay on the device
+            qg, qh, s = ops.gbdt_gradients(scores, yd, objective, max_slot=max_bits[t:t + 1], out=grads + (sexp[t],))
+            out = {k: (v[t:t + 1] if k == 'n_nodes' else v[t]) for k, v in trees.items()}
+            out['row_leaf'] = leaves[t]
+            ops.gbdt_grow_tree(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=self.timings)
+        for k, v in trees.items():
+            setattr(self, k + '_', v.cpu().numpy())
+        self.scale_exponents_ = sexp.cpu().numpy()
+        self.init_score_ = init
+        self.new_columns = [f'gbm_leaf_{t}' for t in range(T)]
+        return self._append(X, leaves.t().contiguous().cpu().numpy())
+
+    def fit(self, X, y):
+        self.fit_transform(X, y)
+        return self
+
+    def transform(self, X):
+        import torch
+        from .. import ops
+        if self.edges_ is None:
+            raise ValueError('GbmLeavesEncoder is not fitted')
+        device = self._device()
+        if len(X) == 0:
+            return self._append(X, np.zeros((0, len(self.new_columns)), dtype=np.int32))
+        packed = ops.gbdt_pack(ops.gbdt_bin(self._upload(X, device), self.edges_))
+        trees = {k: torch.from_numpy(getattr(self, k + '_')).to(device) for k in ('node_feat', 'node_bin', 'node_child', 'n_nodes')}
+        return self._append(X, ops.gbdt_predict_leaves(packed, trees, int(self.params['num_leaves'])).cpu().numpy())
+
+    def raw_scores(self, leaves):
+        """the ensemble's raw scores (logits / predictions) float32 [N] of rows whose leaf ids [N, T] are given"""
+        s = np.full(len(leaves), self.init_score_, dtype=np.float32)
+        for t in range(leaves.shape[1]):
+            s = s + self.leaf_value_[t][np.asarray(leaves)[:, t]]
+        return s
 
 
 class LabelEncoder:
@@ -448,7 +584,7 @@ class DefaultPreprocessor(AbstractPreprocessor):
         if self.config.auto_discrete:
             X = self._discretization(X)
         if self.config.apply_gbm_features:
-            raise NotImplementedError('apply_gbm_features needs lightgbm, which this environment does not have')
+            X = self._apply_gbm_features(X, y)
         var_len = self.config.var_len_categorical_columns
         if var_len is not None and len(var_len) > 0:
             X = self._var_len_encoder(X, var_len)
@@ -577,6 +713,19 @@ class DefaultPreprocessor(AbstractPreprocessor):
         X = mkbd.fit_transform(X)
         self._append_categorical_cols([(new_name, bins + 1) for name, new_name, bins in mkbd.new_columns])
         self.X_transformers['discreter'] = mkbd
+        return X
+
+    def _apply_gbm_features(self, X, y):
+        """preprocessor.py:431-445 with GbmLeavesEncoder: the leaf columns join the categorical columns (vocabulary max + 1) or
+        form one continuous block"""
+        enc = GbmLeavesEncoder(self.get_categorical_columns(), self.get_continuous_columns(), self.task_,
+                               **(self.config.gbm_params or {}))
+        X = enc.fit_transform(X, y)
+        self.X_transformers['gbm_features'] = enc
+        if self.config.gbm_feature_type == consts.GBM_FEATURE_TYPE_EMB:
+            self._append_categorical_cols([(name, int(X[name].max()) + 1) for name in enc.new_columns])
+        else:
+            self._append_continuous_cols(enc.new_columns, consts.INPUT_PREFIX_NUM + 'gbm_leaves')
         return X
 
     def _var_len_encoder(self, X, var_len_categorical_columns):
@@ -788,6 +937,8 @@ class DefaultPreprocessor(AbstractPreprocessor):
         st = self.config.distribute_strategy
         if st is not None and getattr(st, 'world_size', 1) > 1:
             return 'a multi-rank distribute_strategy is active'
+        if 'gbm_features' in self.X_transformers:
+            return 'a gbm_features step'
         if cat_dtype is not None and cat_dtype != torch.int32:
             return f'cat_dtype is {cat_dtype}, the kernel writes int32 ids'
         plan = self.device_plan()

@@ -7,6 +7,7 @@ autograd tape.  All functions require CUDA(HIP) tensors — no CPU fallback.
 """
 import ctypes
 import os
+import time
 
 import numpy as np
 import torch
@@ -2057,3 +2058,171 @@ def prep_transform(N, cols, kind, out=None):
                                       _lib.DT_PREP_OUT_I32 if kind == 'cat' else _lib.DT_PREP_OUT_F32, ptr(out), stream_ptr()),
               'dt_prep_transform')
     return out              # (`packed` goes back to the caching allocator, which reuses it in stream order: after the kernel)
+
+
+# ------------------------------------------------------------------------------------------------
+# histogram gradient-boosted trees: the GBM leaf features (csrc/gbdt.hip; models/preprocessor.py GbmLeavesEncoder)
+# ------------------------------------------------------------------------------------------------
+GBDT_OBJECTIVES = {'binary': _lib.DT_GBDT_BINARY, 'regression': _lib.DT_GBDT_REGRESSION}
+_GBDT_DTYPES = {torch.int32: _lib.DT_PREP_I32, torch.int64: _lib.DT_PREP_I64, torch.float32: _lib.DT_PREP_F32,
+                torch.float64: _lib.DT_PREP_F64}
+
+
+class GbdtWs(ctypes.Structure):
+    """include/dt_hip.h dt_gbdt_ws"""
+    _fields_ = [(n, ctypes.c_void_p) for n in ('bins', 'packed', 'qg', 'qh', 'sexp', 'idx', 'hg', 'hh', 'hc', 'leaf', 'state', 'part',
+                                               'node_feat', 'node_bin', 'node_child', 'leaf_value', 'n_nodes')] + \
+               [('N', ctypes.c_int64), ('P', ctypes.c_int32), ('L', ctypes.c_int32), ('min_child', ctypes.c_int32),
+                ('reserved', ctypes.c_int32), ('reg_lambda', ctypes.c_double), ('min_gain', ctypes.c_double), ('lr', ctypes.c_double)]
+
+
+assert ctypes.sizeof(GbdtWs) == _lib.DT_GBDT_WS_BYTES
+
+
+def gbdt_bin(columns, edges):
+    """columns: P device tensors [N] (int32 / int64 / float32 / float64), edges: P ascending float64 numpy arrays of at most 255
+    edges -> the feature-major bin matrix uint8 [P, N]: bin = the number of edges <= x, len(edges) for a NaN.  One launch per
+    feature."""
+    P, N = len(columns), int(columns[0].shape[0])
+    require_cuda(*columns)
+    device = columns[0].device
+    bins = torch.empty((P, N), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        for f, (c, e) in enumerate(zip(columns, edges)):
+            if c.dtype not in _GBDT_DTYPES or c.dim() != 1 or c.shape[0] != N or not c.is_contiguous():
+                raise ValueError(f'gbdt_bin: column {f} must be a contiguous [{N}] int32 / int64 / float32 / float64 tensor')
+            e = torch.from_numpy(np.ascontiguousarray(e, dtype=np.float64)).to(device)
+            check(lib().dt_gbdt_bin(ptr(c), _GBDT_DTYPES[c.dtype], N, ptr(e) if e.numel() else None, int(e.numel()), ptr(bins[f]),
+                                    stream_ptr()), 'dt_gbdt_bin')
+    return bins
+
+
+def gbdt_pack(bins):
+    """feature-major bins uint8 [P, N] -> the row-major copy uint8 [N, P8] (P8 = P rounded up to 8, zero padded)"""
+    require_cuda(bins)
+    if bins.dtype != torch.uint8 or bins.dim() != 2 or not bins.is_contiguous():
+        raise ValueError('gbdt_pack: bins must be a contiguous uint8 [P, N] tensor')
+    P, N = bins.shape
+    packed = torch.empty((N, (P + 7) // 8 * 8), dtype=torch.uint8, device=bins.device)
+    with torch.cuda.device(bins.device):
+        check(lib().dt_gbdt_pack(ptr(bins), N, P, ptr(packed), stream_ptr()), 'dt_gbdt_pack')
+    return packed
+
+
+def gbdt_gradients(scores, y, objective, max_slot=None, out=None):
+    """float32 scores and y [N] -> (qg int32 [N], qh int32 [N], sexp int32 [2]): the gradients and hessians of `objective`
+    ('binary': log loss, 'regression': L2) quantised as rint(v * 2^S), sexp = (Sg, Sh); see include/dt_hip.h dt_gbdt_grad.
+    max_slot: a ZEROED int64 [1] tensor that receives the bits of max |g| in regression mode (a fresh one unless given)."""
+    require_cuda(scores, y)
+    if scores.dtype != torch.float32 or y.dtype != torch.float32 or scores.shape != y.shape or scores.dim() != 1 or \
+            not (scores.is_contiguous() and y.is_contiguous()):
+        raise ValueError('gbdt_gradients: scores and y must be contiguous float32 [N] tensors')
+    if objective not in GBDT_OBJECTIVES:
+        raise ValueError(f'gbdt_gradients: objective must be one of {sorted(GBDT_OBJECTIVES)}, got {objective!r}')
+    N, device = scores.shape[0], scores.device
+    qg, qh, sexp = out if out is not None else (torch.empty(N, dtype=torch.int32, device=device),
+                                                torch.empty(N, dtype=torch.int32, device=device),
+                                                torch.empty(2, dtype=torch.int32, device=device))
+    if max_slot is None:
+        max_slot = torch.zeros(1, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        check(lib().dt_gbdt_grad(GBDT_OBJECTIVES[objective], ptr(scores), ptr(y), N, ptr(max_slot), ptr(sexp), ptr(qg), ptr(qh),
+                                 stream_ptr()), 'dt_gbdt_grad')
+    return qg, qh, sexp
+
+
+class GbdtWorkspace:
+    """The device buffers one tree needs (include/dt_hip.h dt_gbdt_ws) for a bin matrix [P, N] and `num_leaves`: the row-major
+    copy of the bins, both index buffers, the histograms of every leaf, the leaf table.  Reused by every tree of a fit."""
+
+    def __init__(self, bins, num_leaves):
+        self.bins, self.packed = bins, gbdt_pack(bins)
+        P, N = bins.shape
+        L, dev = int(num_leaves), bins.device
+        self.N, self.P, self.L = N, P, L
+        self.idx = torch.empty((2, N), dtype=torch.int32, device=dev)
+        self.hg = torch.empty((L, P, _lib.DT_GBDT_BINS), dtype=torch.int64, device=dev)
+        self.hh = torch.empty_like(self.hg)
+        self.hc = torch.empty((L, P, _lib.DT_GBDT_BINS), dtype=torch.int32, device=dev)
+        self.leaf = torch.empty((L, _lib.DT_GBDT_LEAF_WORDS), dtype=torch.int64, device=dev)
+        self.state = torch.empty(_lib.DT_GBDT_STATE_WORDS, dtype=torch.int32, device=dev)
+        self.part = torch.empty((N + _lib.DT_GBDT_PART_CHUNK - 1) // _lib.DT_GBDT_PART_CHUNK, dtype=torch.int32, device=dev)
+
+
+def gbdt_grow_tree(bins, qg, qh, params, workspace=None, scores=None, out=None, timings=None):
+    """One leaf-wise tree on the feature-major bin matrix uint8 [P, N] and the quantised gradients int32 [N].
+    params: num_leaves, min_child_samples, reg_lambda, min_split_gain, learning_rate and sexp (the (Sg, Sh) of gbdt_gradients:
+    an int32 [2] device tensor or two ints).  -> {'node_feat', 'node_bin' int32 [L-1], 'node_child' int32 [L-1, 2] (>= 0: node,
+    < 0: ~leaf id), 'n_nodes' int32 [1], 'leaf_value' float32 [L], 'row_leaf' int32 [N]}, all on the device; `scores` (float32
+    [N]) gets the leaf values added.  The host only issues launches: 2 + 4 per possible split, none reads anything back.
+    out: views to write the tree into (the keys above; a fit keeps [T, ...] arrays); timings: a dict that collects seconds
+    per kernel role, the device drained around every call (tools/gbm_bench.py)."""
+    require_cuda(bins, qg, qh)
+    P, N = bins.shape
+    L = int(params.get('num_leaves', 31))
+    if not 2 <= L <= _lib.DT_GBDT_MAX_LEAVES:
+        raise ValueError(f'gbdt_grow_tree: num_leaves must be in [2, {_lib.DT_GBDT_MAX_LEAVES}], got {L}')
+    if qg.dtype != torch.int32 or qh.dtype != torch.int32 or qg.shape != (N,) or qh.shape != (N,):
+        raise ValueError(f'gbdt_grow_tree: qg and qh must be int32 [{N}] tensors')
+    dev = bins.device
+    ws = workspace if workspace is not None else GbdtWorkspace(bins, L)
+    if (ws.N, ws.P, ws.L) != (N, P, L) or ws.bins.data_ptr() != bins.data_ptr():
+        raise ValueError('gbdt_grow_tree: the workspace was made for another bin matrix or num_leaves')
+    sexp = params.get('sexp', (0, 0))
+    if not torch.is_tensor(sexp):
+        sexp = torch.tensor([int(sexp[0]), int(sexp[1])], dtype=torch.int32, device=dev)
+    if out is None:
+        out = {'node_feat': torch.empty(L - 1, dtype=torch.int32, device=dev), 'node_bin': torch.empty(L - 1, dtype=torch.int32, device=dev),
+               'node_child': torch.empty((L - 1, 2), dtype=torch.int32, device=dev), 'n_nodes': torch.empty(1, dtype=torch.int32, device=dev),
+               'leaf_value': torch.empty(L, dtype=torch.float32, device=dev), 'row_leaf': torch.empty(N, dtype=torch.int32, device=dev)}
+    if scores is None:
+        scores = torch.zeros(N, dtype=torch.float32, device=dev)
+    d = GbdtWs(bins.data_ptr(), ws.packed.data_ptr(), qg.data_ptr(), qh.data_ptr(), sexp.data_ptr(), ws.idx.data_ptr(),
+               ws.hg.data_ptr(), ws.hh.data_ptr(), ws.hc.data_ptr(), ws.leaf.data_ptr(), ws.state.data_ptr(), ws.part.data_ptr(),
+               out['node_feat'].data_ptr(), out['node_bin'].data_ptr(), out['node_child'].data_ptr(), out['leaf_value'].data_ptr(),
+               out['n_nodes'].data_ptr(), N, P, L, int(params.get('min_child_samples', 20)), 0, float(params.get('reg_lambda', 0.0)),
+               float(params.get('min_split_gain', 0.0)), float(params.get('learning_rate', 0.1)))
+    h, dp = lib(), ctypes.byref(d)
+
+    def run(role, fn, *args):
+        if timings is None:
+            check(fn(*args), role)
+            return
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        check(fn(*args), role)
+        torch.cuda.synchronize(dev)
+        timings[role] = timings.get(role, 0.0) + time.perf_counter() - t0
+
+    with torch.cuda.device(dev):
+        s = stream_ptr()
+        run('tree_begin', h.dt_gbdt_tree_begin, dp, s)
+        run('hist', h.dt_gbdt_hist, dp, 1, s)
+        run('split', h.dt_gbdt_split, dp, 1, s)
+        for _ in range(L - 1):
+            run('grow', h.dt_gbdt_grow, dp, s)
+            run('hist', h.dt_gbdt_hist, dp, 0, s)
+            run('split', h.dt_gbdt_split, dp, 0, s)
+        run('leaf_update', h.dt_gbdt_leaf_update, dp, ptr(scores), ptr(out['row_leaf']), s)
+    return out
+
+
+def gbdt_predict_leaves(packed, trees, num_leaves):
+    """the row-major bin matrix uint8 [N, P8] (gbdt_pack) and T trees — `trees` holds node_feat, node_bin int32 [T, L-1],
+    node_child int32 [T, L-1, 2], n_nodes int32 [T] on the device — -> int32 [N, T] leaf ids.  P is the feature count the
+    trees were grown on (any value with the same P8)."""
+    require_cuda(packed)
+    L = int(num_leaves)
+    nf, nb, nc, nn = (trees[k].contiguous() for k in ('node_feat', 'node_bin', 'node_child', 'n_nodes'))
+    T = int(nn.shape[0])
+    if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[1] % 8 or not packed.is_contiguous():
+        raise ValueError('gbdt_predict_leaves: packed must be the contiguous uint8 [N, P8] matrix of gbdt_pack')
+    if tuple(nf.shape) != (T, L - 1) or tuple(nb.shape) != (T, L - 1) or tuple(nc.shape) != (T, L - 1, 2) or \
+            any(t.dtype != torch.int32 or t.device != packed.device for t in (nf, nb, nc, nn)):
+        raise ValueError(f'gbdt_predict_leaves: the tree arrays must be int32 [{T}, {L - 1}] (node_child [.., 2]) on {packed.device}')
+    N, P8 = packed.shape
+    out = torch.empty((N, T), dtype=torch.int32, device=packed.device)
+    with torch.cuda.device(packed.device):
+        check(lib().dt_gbdt_predict_leaves(ptr(packed), N, P8, T, L, ptr(nf), ptr(nb), ptr(nc), ptr(nn), ptr(out), stream_ptr()),
+              'dt_gbdt_predict_leaves')
+    return out

@@ -1730,6 +1730,89 @@ typedef struct dt_prep_col {
 int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* cols_host, int C, int out_kind, void* out,
                       void* stream);
 
+/* Histogram gradient-boosted trees for the GBM leaf features (csrc/gbdt.hip; ops.gbdt_gradients / gbdt_grow_tree /
+ * gbdt_predict_leaves, models/preprocessor.py GbmLeavesEncoder; replaces deeptables/models/preprocessor.py:431-452, hypernets'
+ * LgbmLeavesEncoder).  LightGBM's algorithm in outline, not compared with a LightGBM run.  Binary log loss and L2 regression.
+ * dt_gbdt_bin: one raw DEVICE column [N] (dtype DT_PREP_I32 / I64 / F32 / F64) and its ascending float64 edges (n_edges <= 255)
+ *   -> uint8 [N]: the number of edges <= x, n_edges for a NaN (DT_PREP_BIN's rule).  Called once per feature on the rows of the
+ *   feature-major bin matrix uint8 [P][N].
+ * dt_gbdt_pack: the bin matrix [P][N] -> its row-major copy uint8 [N][P8], P8 = P rounded up to 8, zero padded; what the
+ *   histogram and prediction kernels read (a row's features in one place: 8 features per 8-byte load).
+ * dt_gbdt_grad: float32 scores and y [N] -> int32 qg, qh [N] = rint(g 2^Sg), rint(h 2^Sh) and sexp int32 [2] = {Sg, Sh}.
+ *   DT_GBDT_BINARY: p = 1 / (1 + exp(-s)) in float64, g = p - y, h = p (1 - p), Sg = 23, Sh = 25.  DT_GBDT_REGRESSION:
+ *   g = s - y in float64, qh = 1, Sh = 0, Sg = 23 - e where max |g| = f 2^e with f in [0.5, 1) (0 when the max is 0): a first
+ *   launch reduces the max into *max_slot (uint64, the bits of the float64; an integer atomicMax), which the caller gives
+ *   zeroed and may read back afterwards.  |q| < 2^24 either way.
+ * One tree (dt_gbdt_ws describes the buffers; every launch of a tree takes the same descriptor, passed by value to the kernels):
+ *   dt_gbdt_tree_begin  idx = 0 .. N-1, histograms cleared, leaf table = the root, the tree's arrays reset
+ *   dt_gbdt_hist        root != 0: the histogram of all rows; otherwise the histogram of the SMALLER child of the last split
+ *     over its segment of idx, and the sibling as parent - child.  A block takes DT_GBDT_HIST_ROWS rows and a group of
+ *     DT_GBDT_HIST_GROUP features (40 KiB of LDS), accumulates with LDS integer atomics and flushes with 64-bit global integer
+ *     adds.  Entries are (sum qg int64, sum qh int64, count int32): integer sums, the same on every run.
+ *   dt_gbdt_split       the best split of the root (root != 0) or of the two leaves of the last split: per feature a wave scans
+ *     the 256 bins; gain = GL^2 / (HL + lambda) + GR^2 / (HR + lambda) - G^2 / (H + lambda) on G 2^-Sg, H 2^-Sh in float64,
+ *     every operation correctly rounded, in that order; valid when both children have >= max(min_child, 1) rows, the three
+ *     denominators are positive and gain > min_gain; ties go to the lower feature, then the lower bin.
+ *   dt_gbdt_grow        the leaf with the largest gain (ties: the lower id) is split on the device: node k = (feature, bin;
+ *     rows with bins[feature] <= bin go left), the left child keeps the leaf's id, the right child takes the next free id, its
+ *     segment of idx is partitioned by a stable two-pass count-and-scatter into the other index buffer.  Nothing happens once
+ *     num_leaves is reached or no leaf has a valid split; nothing is read back.
+ *   dt_gbdt_leaf_update leaf_value[l] = (float)(-(lr * (G / (H + lambda)))) in float64, scores[r] += leaf_value (float32),
+ *     row_leaf[r] = l for every row.
+ *   A tree is node_feat / node_bin int32 [L-1], node_child int32 [2 (L-1)] (>= 0: a node, < 0: ~leaf id), n_nodes int32 [1],
+ *   leaf_value float32 [L]; a tree without a node has the single leaf 0.
+ * dt_gbdt_predict_leaves: the row-major bin matrix [N][P8] and T trees ([T][L-1] node arrays, n_nodes [T]) -> int32 [N][T] leaf
+ *   ids; one thread walks one (row, tree), the node arrays of a tile of trees sit in LDS.
+ * Nothing synchronises with the host or allocates.  Sizes outside the limits below, a null or misaligned pointer, a negative
+ * lambda or min_gain are DT_ERR_INVALID_ARG before any launch.                                                                */
+#define DT_GBDT_BINARY 0
+#define DT_GBDT_REGRESSION 1
+#define DT_GBDT_BINS 256
+#define DT_GBDT_HIST_GROUP 8
+#define DT_GBDT_HIST_ROWS 4096
+#define DT_GBDT_PART_CHUNK 2048
+#define DT_GBDT_PREDICT_ROWS 64
+#define DT_GBDT_PREDICT_LDS_BYTES 49152
+#define DT_GBDT_MAX_ROWS 2147483647
+#define DT_GBDT_MAX_FEATURES 4096
+#define DT_GBDT_MAX_LEAVES 1024
+#define DT_GBDT_STATE_WORDS 16
+#define DT_GBDT_LEAF_WORDS 12
+#define DT_GBDT_WS_BYTES 184
+typedef struct dt_gbdt_ws {
+    const uint8_t* bins;      /* [P][N] */
+    const uint32_t* packed;   /* [N][P8 / 4] */
+    const int32_t* qg;        /* [N] */
+    const int32_t* qh;        /* [N] */
+    const int32_t* sexp;      /* [2]: Sg, Sh */
+    int32_t* idx;             /* [2][N] */
+    int64_t* hg;              /* [L][P][256] */
+    int64_t* hh;              /* [L][P][256] */
+    int32_t* hc;              /* [L][P][256] */
+    int64_t* leaf;            /* [L][DT_GBDT_LEAF_WORDS] */
+    int32_t* state;           /* [DT_GBDT_STATE_WORDS] */
+    int32_t* part;            /* [ceil(N / DT_GBDT_PART_CHUNK)] */
+    int32_t* node_feat;       /* this tree: [L-1] */
+    int32_t* node_bin;        /* [L-1] */
+    int32_t* node_child;      /* [2 (L-1)] */
+    float* leaf_value;        /* [L] */
+    int32_t* n_nodes;         /* [1] */
+    int64_t N;
+    int32_t P, L, min_child, reserved;
+    double lambda, min_gain, lr;
+} dt_gbdt_ws;
+int dt_gbdt_bin(const void* src, int dtype, int64_t N, const double* edges, int n_edges, void* out, void* stream);
+int dt_gbdt_pack(const void* bins, int64_t N, int P, void* packed, void* stream);
+int dt_gbdt_grad(int objective, const float* scores, const float* y, int64_t N, void* max_slot, int32_t* sexp, int32_t* qg,
+                 int32_t* qh, void* stream);
+int dt_gbdt_tree_begin(const dt_gbdt_ws* ws, void* stream);
+int dt_gbdt_hist(const dt_gbdt_ws* ws, int root, void* stream);
+int dt_gbdt_split(const dt_gbdt_ws* ws, int root, void* stream);
+int dt_gbdt_grow(const dt_gbdt_ws* ws, void* stream);
+int dt_gbdt_leaf_update(const dt_gbdt_ws* ws, float* scores, int32_t* row_leaf, void* stream);
+int dt_gbdt_predict_leaves(const void* packed, int64_t N, int P, int T, int L, const int32_t* node_feat, const int32_t* node_bin,
+                           const int32_t* node_child, const int32_t* n_nodes, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
