@@ -394,6 +394,13 @@ SIGNATURES = {
     'dt_gbdt_split': (_c_int, [_ptr, _c_int, _ptr]),
     'dt_gbdt_grow': (_c_int, [_ptr, _ptr]),
     'dt_gbdt_leaf_update': (_c_int, [_ptr, _ptr, _ptr, _ptr]),                            # ws, scores, row_leaf, stream
+    # softmax boosting: scores, y, N, K, sexp, qg, qh, stream; `m` is a host dt_gbdt_mc (ops.GbdtMc), K trees per launch
+    'dt_gbdt_grad_softmax': (_c_int, [_ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _ptr]),
+    'dt_gbdt_mc_tree_begin': (_c_int, [_ptr, _ptr]),
+    'dt_gbdt_mc_hist': (_c_int, [_ptr, _c_int, _ptr]),                                    # m, root, stream
+    'dt_gbdt_mc_split': (_c_int, [_ptr, _c_int, _ptr]),
+    'dt_gbdt_mc_grow': (_c_int, [_ptr, _ptr]),
+    'dt_gbdt_mc_leaf_update': (_c_int, [_ptr, _ptr, _ptr, _ptr]),                         # m, scores, row_leaf, stream
     # packed, N, P, T, L, node_feat, node_bin, node_child, n_nodes, out, stream
     'dt_gbdt_predict_leaves': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
 }
@@ -446,6 +453,7 @@ DT_GBDT_BINARY, DT_GBDT_REGRESSION = 0, 1
 DT_GBDT_BINS, DT_GBDT_HIST_GROUP, DT_GBDT_HIST_ROWS, DT_GBDT_PART_CHUNK = 256, 8, 4096, 2048
 DT_GBDT_MAX_ROWS, DT_GBDT_MAX_FEATURES, DT_GBDT_MAX_LEAVES = 2147483647, 4096, 1024
 DT_GBDT_STATE_WORDS, DT_GBDT_LEAF_WORDS, DT_GBDT_WS_BYTES = 16, 12, 184
+DT_GBDT_MAX_CLASSES, DT_GBDT_MC_BYTES = 64, 272
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

@@ -30,6 +30,15 @@
 //                  next launches are written to the leaf table / state
 //   k_part_count, k_part_scatter   stable two-pass partition of the chosen segment by bins[f][row] <= bin
 //   k_leaf_update  leaf values -lr * G / (H + lambda) (float64, rounded once to float32), scores += value, row -> leaf id
+//
+// Multiclass (softmax boosting, ops.gbdt_gradients_softmax / gbdt_grow_trees).  The K class trees of a round share the bin
+// matrix, the packed rows and the launch sequence; only gradients, partitions and decisions differ.  So every kernel body above
+// is a __device__ function of a dt_gbdt_ws, the single-tree kernels and the k_*_mc kernels are thin wrappers over it, and the
+// _mc wrappers take the class from blockIdx.z and form that class's view of a dt_gbdt_mc (class 0's dt_gbdt_ws plus the
+// element strides between classes; 272 bytes, passed by value).  All K trees grow in lock-step: a round costs the launches of
+// ONE tree plus one k_gbdt_grad_softmax, a class that is finished returns at once while the others go on, and the host still
+// reads nothing back.  Memory for K classes: 8 N K bytes of row indices and K L P 256 20 bytes of histograms (K = 10, 31
+// leaves, 39 features: 62 MB), 8 N K bytes of quantised gradients.
 #include "common.h"
 #include "optim_dev.h"
 
@@ -46,6 +55,7 @@ constexpr int kPartChunk = DT_GBDT_PART_CHUNK;
 static_assert(kPartChunk == kThreads * kPartPer, "a partition chunk is one block");
 static_assert(kGroup == 8, "a feature group is one 8-byte load of the packed matrix");
 static_assert(sizeof(dt_gbdt_ws) == DT_GBDT_WS_BYTES, "ops.py packs the workspace descriptor by this layout");
+static_assert(sizeof(dt_gbdt_mc) == DT_GBDT_MC_BYTES && offsetof(dt_gbdt_mc, base) == 0, "ops.py packs the class-batched descriptor too");
 
 // state words
 enum { S_NLEAVES, S_DONE, S_LEAF, S_NEW, S_FEAT, S_BIN, S_BEGIN, S_COUNT, S_BUF, S_CL, S_SMALL, S_NNODES };
@@ -166,8 +176,39 @@ __global__ __launch_bounds__(kThreads) void k_gbdt_grad(int objective, const flo
     }
 }
 
+// softmax cross-entropy, K class-major score rows [K][N]: one thread per row, its K scores read with stride N (the lanes of a
+// wave read consecutive rows of one class, so every load and store coalesces).  The scores are read three times (max, sum,
+// write) and the exponentials formed twice instead of holding K values per thread: K is a run-time number up to 64, 64 float64
+// in registers are 128 VGPRs and need a compile-time K, while the re-reads hit the cache and the kernel is one launch of a
+// round that issues ~180 more.  float64 in the written order: m = max, e = exp(s - m), Z = sum in class order, p = e / Z,
+// g = p - [y == k], h = (K / (K - 1)) (p (1 - p)) (LightGBM's factor); h <= 0.375 for K >= 3, so |qh| < 2^24.
+__global__ __launch_bounds__(kThreads) void k_gbdt_grad_softmax(const float* __restrict__ s, const float* __restrict__ y, int64_t N,
+                                                                 int K, int32_t* __restrict__ sexp, int32_t* __restrict__ qg,
+                                                                 int32_t* __restrict__ qh) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) { sexp[0] = 23; sexp[1] = 25; }
+    const double kg = pow2(23), kh = pow2(25), factor = (double)K / (double)(K - 1);
+    for (int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kThreads) {
+        double m = (double)s[i];
+        for (int k = 1; k < K; ++k) {
+            const double v = (double)s[(int64_t)k * N + i];
+            if (v > m) m = v;
+        }
+        double Z = 0.0;
+        for (int k = 0; k < K; ++k) Z += exp((double)s[(int64_t)k * N + i] - m);
+        const float label = y[i];                         // a NaN or a value outside [0, K) equals no class number
+        for (int k = 0; k < K; ++k) {
+            const double p = exp((double)s[(int64_t)k * N + i] - m) / Z;
+            const double g = p - (label == (float)k ? 1.0 : 0.0);
+            const double h = factor * (p * (1.0 - p));
+            const double a = rint(g * kg), b = rint(h * kh);
+            qg[(int64_t)k * N + i] = a == a ? (int32_t)a : 0;
+            qh[(int64_t)k * N + i] = b == b ? (int32_t)b : 0;
+        }
+    }
+}
+
 // ---- one tree --------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void k_tree_begin(dt_gbdt_ws ws) {
+__device__ __forceinline__ void tree_begin_body(const dt_gbdt_ws& ws) {
     const int64_t stride = (int64_t)gridDim.x * kThreads, t0 = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     for (int64_t i = t0; i < ws.N; i += stride) ws.idx[i] = (int32_t)i;
     const int64_t entries = (int64_t)ws.L * ws.P * kBins;
@@ -189,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void k_tree_begin(dt_gbdt_ws ws) {
 }
 
 // grid (row chunks, feature groups).  root: the whole of buffer 0 into slot 0; otherwise the smaller child into slot S_NEW
-__global__ __launch_bounds__(kThreads) void k_hist(dt_gbdt_ws ws, int root) {
+__device__ __forceinline__ void hist_body(const dt_gbdt_ws& ws, int root) {
     __shared__ unsigned long long lg[kGroup * kBins], lh[kGroup * kBins];
     __shared__ unsigned int lc[kGroup * kBins];
     int64_t begin = 0, count = ws.N;
@@ -236,7 +277,7 @@ __global__ __launch_bounds__(kThreads) void k_hist(dt_gbdt_ws ws, int root) {
 }
 
 // slot S_NEW holds the smaller child.  It is the right child: parent slot -= it.  It is the left child: swap roles.
-__global__ __launch_bounds__(kThreads) void k_hist_sub(dt_gbdt_ws ws) {
+__device__ __forceinline__ void hist_sub_body(const dt_gbdt_ws& ws) {
     if (ws.state[S_DONE]) return;
     const int64_t n = (int64_t)ws.P * kBins;
     const int64_t pa = (int64_t)ws.state[S_LEAF] * n, nw = (int64_t)ws.state[S_NEW] * n;
@@ -271,7 +312,7 @@ struct SplitGain {
 };
 
 // one block per leaf to evaluate (root: leaf 0; otherwise S_LEAF and S_NEW); wave w takes features w, w + 4, ...
-__global__ __launch_bounds__(kThreads) void k_split(dt_gbdt_ws ws, int root) {
+__device__ __forceinline__ void split_body(const dt_gbdt_ws& ws, int root) {
     __shared__ double w_gain[kThreads / kWave];
     __shared__ int w_feat[kThreads / kWave], w_bin[kThreads / kWave], w_cl[kThreads / kWave];
     __shared__ int64_t w_tot[2];
@@ -333,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void k_split(dt_gbdt_ws ws, int root) {
 }
 
 // one wave: choose the leaf, append the node, describe the two children and the job of the next launches
-__global__ __launch_bounds__(kWave) void k_grow_pick(dt_gbdt_ws ws) {
+__device__ __forceinline__ void grow_pick_body(const dt_gbdt_ws& ws) {
     if (ws.state[S_DONE]) return;
     const int lane = threadIdx.x, n = ws.state[S_NLEAVES];
     double best = 0.0;
@@ -378,7 +419,7 @@ __device__ __forceinline__ int block_sum(int v, int* red) {
 }
 
 // chunk c = rows [c * kPartChunk, ...) of the chosen segment, thread t its rows t * 8 .. t * 8 + 7: part[c] = lefts of the chunk
-__global__ __launch_bounds__(kThreads) void k_part_count(dt_gbdt_ws ws) {
+__device__ __forceinline__ void part_count_body(const dt_gbdt_ws& ws) {
     __shared__ int red[kThreads / kWave];
     if (ws.state[S_DONE]) return;
     const int64_t count = ws.state[S_COUNT], base = (int64_t)blockIdx.x * kPartChunk;
@@ -395,7 +436,7 @@ __global__ __launch_bounds__(kThreads) void k_part_count(dt_gbdt_ws ws) {
     if (threadIdx.x == 0) ws.part[blockIdx.x] = total;
 }
 
-__global__ __launch_bounds__(kThreads) void k_part_scatter(dt_gbdt_ws ws) {
+__device__ __forceinline__ void part_scatter_body(const dt_gbdt_ws& ws) {
     __shared__ int red[kThreads / kWave], wave_tot[kThreads / kWave];
     if (ws.state[S_DONE]) return;
     const int64_t count = ws.state[S_COUNT], base = (int64_t)blockIdx.x * kPartChunk;
@@ -438,7 +479,7 @@ __global__ __launch_bounds__(kThreads) void k_part_scatter(dt_gbdt_ws ws) {
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_leaf_update(dt_gbdt_ws ws, float* __restrict__ scores, int32_t* __restrict__ row_leaf) {
+__device__ __forceinline__ void leaf_update_body(const dt_gbdt_ws& ws, float* __restrict__ scores, int32_t* __restrict__ row_leaf) {
     extern __shared__ int64_t tab[];                      // per leaf: begin, end, buf, value bits
     const int n = ws.state[S_NLEAVES];
     const double sg = pow2(-ws.sexp[0]), sh = pow2(-ws.sexp[1]);
@@ -462,6 +503,46 @@ __global__ __launch_bounds__(kThreads) void k_leaf_update(dt_gbdt_ws ws, float* 
             }
         }
     }
+}
+
+// ---- the launches: one tree, or the K class trees of a softmax round in lock-step --------------------------------------------
+// class c's view of a class-batched workspace: the shared bins / packed / sexp / sizes / parameters, its own everything else
+__device__ __forceinline__ dt_gbdt_ws class_view(const dt_gbdt_mc& m, int c) {
+    dt_gbdt_ws ws = m.base;
+    ws.qg += c * m.q_stride; ws.qh += c * m.q_stride;
+    ws.idx += c * m.idx_stride;
+    ws.hg += c * m.hist_stride; ws.hh += c * m.hist_stride; ws.hc += c * m.hist_stride;
+    ws.leaf += c * m.leaf_stride;
+    ws.state += c * m.state_stride;
+    ws.part += c * m.part_stride;
+    ws.node_feat += c * m.node_stride; ws.node_bin += c * m.node_stride; ws.node_child += 2 * c * m.node_stride;
+    ws.leaf_value += c * m.value_stride;
+    ws.n_nodes += c * m.nn_stride;
+    return ws;
+}
+
+__global__ __launch_bounds__(kThreads) void k_tree_begin(dt_gbdt_ws ws) { tree_begin_body(ws); }
+__global__ __launch_bounds__(kThreads) void k_hist(dt_gbdt_ws ws, int root) { hist_body(ws, root); }
+__global__ __launch_bounds__(kThreads) void k_hist_sub(dt_gbdt_ws ws) { hist_sub_body(ws); }
+__global__ __launch_bounds__(kThreads) void k_split(dt_gbdt_ws ws, int root) { split_body(ws, root); }
+__global__ __launch_bounds__(kWave) void k_grow_pick(dt_gbdt_ws ws) { grow_pick_body(ws); }
+__global__ __launch_bounds__(kThreads) void k_part_count(dt_gbdt_ws ws) { part_count_body(ws); }
+__global__ __launch_bounds__(kThreads) void k_part_scatter(dt_gbdt_ws ws) { part_scatter_body(ws); }
+__global__ __launch_bounds__(kThreads) void k_leaf_update(dt_gbdt_ws ws, float* __restrict__ scores, int32_t* __restrict__ row_leaf) {
+    leaf_update_body(ws, scores, row_leaf);
+}
+
+// the same bodies with the class as blockIdx.z: x and y keep their single-tree meaning, a finished class's blocks return at once
+__global__ __launch_bounds__(kThreads) void k_tree_begin_mc(dt_gbdt_mc m) { tree_begin_body(class_view(m, blockIdx.z)); }
+__global__ __launch_bounds__(kThreads) void k_hist_mc(dt_gbdt_mc m, int root) { hist_body(class_view(m, blockIdx.z), root); }
+__global__ __launch_bounds__(kThreads) void k_hist_sub_mc(dt_gbdt_mc m) { hist_sub_body(class_view(m, blockIdx.z)); }
+__global__ __launch_bounds__(kThreads) void k_split_mc(dt_gbdt_mc m, int root) { split_body(class_view(m, blockIdx.z), root); }
+__global__ __launch_bounds__(kWave) void k_grow_pick_mc(dt_gbdt_mc m) { grow_pick_body(class_view(m, blockIdx.z)); }
+__global__ __launch_bounds__(kThreads) void k_part_count_mc(dt_gbdt_mc m) { part_count_body(class_view(m, blockIdx.z)); }
+__global__ __launch_bounds__(kThreads) void k_part_scatter_mc(dt_gbdt_mc m) { part_scatter_body(class_view(m, blockIdx.z)); }
+__global__ __launch_bounds__(kThreads) void k_leaf_update_mc(dt_gbdt_mc m, float* __restrict__ scores, int32_t* __restrict__ row_leaf) {
+    const int64_t c = blockIdx.z;
+    leaf_update_body(class_view(m, blockIdx.z), scores + c * m.row_stride, row_leaf + c * m.row_stride);
 }
 
 // ---- prediction ------------------------------------------------------------------------------------------------------------
@@ -515,6 +596,21 @@ static int check_ws(const char* who, const dt_gbdt_ws* ws) {
     DT_REQUIRE(aligned_to(ws->packed, 8) && aligned_to(ws->hg, 8) && aligned_to(ws->hh, 8) && aligned_to(ws->leaf, 8) &&
                aligned_to(ws->qg, 4) && aligned_to(ws->qh, 4) && aligned_to(ws->idx, 4) && aligned_to(ws->hc, 4),
                "%s: misaligned pointer in the workspace descriptor", who);
+    return DT_OK;
+}
+
+// the class-batched descriptor: class 0's view passes check_ws, and no class's tables reach into the next class's
+static int check_mc(const char* who, const dt_gbdt_mc* m) {
+    DT_REQUIRE(m, "%s: null workspace descriptor", who);
+    const int rc = check_ws(who, &m->base);
+    if (rc != DT_OK) return rc;
+    const dt_gbdt_ws& ws = m->base;
+    DT_REQUIRE(m->K >= 1 && m->K <= DT_GBDT_MAX_CLASSES, "%s: K=%d outside [1, %d]", who, m->K, DT_GBDT_MAX_CLASSES);
+    const int64_t hist = (int64_t)ws.L * ws.P * kBins, chunks = (ws.N + kPartChunk - 1) / kPartChunk;
+    DT_REQUIRE(m->q_stride >= ws.N && m->idx_stride >= 2 * ws.N && m->hist_stride >= hist &&
+               m->leaf_stride >= (int64_t)ws.L * DT_GBDT_LEAF_WORDS && m->state_stride >= DT_GBDT_STATE_WORDS &&
+               m->part_stride >= chunks && m->node_stride >= ws.L - 1 && m->value_stride >= ws.L && m->nn_stride >= 1 &&
+               m->row_stride >= ws.N, "%s: a class stride is smaller than one class's table", who);
     return DT_OK;
 }
 
@@ -623,6 +719,79 @@ extern "C" int dt_gbdt_leaf_update(const dt_gbdt_ws* ws, float* scores, int32_t*
     DT_REQUIRE(scores && row_leaf && aligned_to(scores, 4) && aligned_to(row_leaf, 4), "%s: null or misaligned pointer", who);
     hipLaunchKernelGGL(k_leaf_update, dim3(grid_for(ws->N, kThreads, 2048)), dim3(kThreads), (size_t)ws->L * 4 * sizeof(int64_t),
                        as_stream(stream), *ws, scores, row_leaf);
+    return launch_status(who);
+}
+
+extern "C" int dt_gbdt_grad_softmax(const float* scores, const float* y, int64_t N, int K, int32_t* sexp, int32_t* qg, int32_t* qh,
+                                    void* stream) {
+    const char* who = "dt_gbdt_grad_softmax";
+    DT_UNSUPPORTED(K < 3 || K > DT_GBDT_MAX_CLASSES, "%s: K=%d outside [3, %d] (two classes are the binary objective)", who, K,
+                   DT_GBDT_MAX_CLASSES);
+    DT_REQUIRE(N >= 1 && N <= DT_GBDT_MAX_ROWS, "%s: N=%lld", who, (long long)N);
+    DT_REQUIRE(scores && y && sexp && qg && qh, "%s: null pointer", who);
+    DT_REQUIRE(aligned_to(scores, 4) && aligned_to(y, 4) && aligned_to(sexp, 4) && aligned_to(qg, 4) && aligned_to(qh, 4),
+               "%s: misaligned pointer", who);
+    hipLaunchKernelGGL(k_gbdt_grad_softmax, dim3(grid_for(N, kThreads, 2048)), dim3(kThreads), 0, as_stream(stream), scores, y, N, K,
+                       sexp, qg, qh);
+    return launch_status(who);
+}
+
+// the class-batched launches: the grids of the single-tree entry points with K as the z dimension
+extern "C" int dt_gbdt_mc_tree_begin(const dt_gbdt_mc* m, void* stream) {
+    const char* who = "dt_gbdt_mc_tree_begin";
+    const int rc = check_mc(who, m);
+    if (rc != DT_OK) return rc;
+    const dt_gbdt_ws* ws = &m->base;
+    const int64_t items = ws->N > (int64_t)ws->L * ws->P * kBins ? ws->N : (int64_t)ws->L * ws->P * kBins;
+    hipLaunchKernelGGL(k_tree_begin_mc, dim3(grid_for(items, kThreads, 2048), 1, m->K), dim3(kThreads), 0, as_stream(stream), *m);
+    return launch_status(who);
+}
+
+extern "C" int dt_gbdt_mc_hist(const dt_gbdt_mc* m, int root, void* stream) {
+    const char* who = "dt_gbdt_mc_hist";
+    const int rc = check_mc(who, m);
+    if (rc != DT_OK) return rc;
+    const dt_gbdt_ws* ws = &m->base;
+    const int64_t rows = root ? ws->N : ws->N / 2;
+    if (rows > 0) {
+        hipLaunchKernelGGL(k_hist_mc, dim3(grid_for(rows, kHistRows, INT32_MAX), (ws->P + kGroup - 1) / kGroup, m->K), dim3(kThreads), 0,
+                           as_stream(stream), *m, root ? 1 : 0);
+        const int rc2 = launch_status(who);
+        if (rc2 != DT_OK) return rc2;
+    }
+    if (!root) hipLaunchKernelGGL(k_hist_sub_mc, dim3(grid_for((int64_t)ws->P * kBins, kThreads, 1024), 1, m->K), dim3(kThreads), 0,
+                                  as_stream(stream), *m);
+    return launch_status(who);
+}
+
+extern "C" int dt_gbdt_mc_split(const dt_gbdt_mc* m, int root, void* stream) {
+    const char* who = "dt_gbdt_mc_split";
+    const int rc = check_mc(who, m);
+    if (rc != DT_OK) return rc;
+    hipLaunchKernelGGL(k_split_mc, dim3(root ? 1 : 2, 1, m->K), dim3(kThreads), 0, as_stream(stream), *m, root ? 1 : 0);
+    return launch_status(who);
+}
+
+extern "C" int dt_gbdt_mc_grow(const dt_gbdt_mc* m, void* stream) {
+    const char* who = "dt_gbdt_mc_grow";
+    int rc = check_mc(who, m);
+    if (rc != DT_OK) return rc;
+    hipLaunchKernelGGL(k_grow_pick_mc, dim3(1, 1, m->K), dim3(kWave), 0, as_stream(stream), *m);
+    if ((rc = launch_status(who)) != DT_OK) return rc;
+    const unsigned chunks = grid_for(m->base.N, kPartChunk, INT32_MAX);
+    hipLaunchKernelGGL(k_part_count_mc, dim3(chunks, 1, m->K), dim3(kThreads), 0, as_stream(stream), *m);
+    if ((rc = launch_status(who)) != DT_OK) return rc;
+    hipLaunchKernelGGL(k_part_scatter_mc, dim3(chunks, 1, m->K), dim3(kThreads), 0, as_stream(stream), *m);
+    return launch_status(who);
+}
+
+extern "C" int dt_gbdt_mc_leaf_update(const dt_gbdt_mc* m, float* scores, int32_t* row_leaf, void* stream) {
+    const char* who = "dt_gbdt_mc_leaf_update";
+    const int rc = check_mc(who, m);
+    if (rc != DT_OK) return rc;
+    DT_REQUIRE(scores && row_leaf && aligned_to(scores, 4) && aligned_to(row_leaf, 4), "%s: null or misaligned pointer", who);
+    hipLaunchKernelGGL(k_leaf_update_mc, dim3(grid_for(m->base.N, kThreads, 2048), 1, m->K), dim3(kThreads),
+                       (size_t)m->base.L * 4 * sizeof(int64_t), as_stream(stream), *m, scores, row_leaf);
     return launch_status(who);
 }
 

@@ -227,16 +227,27 @@ class GbmLeavesEncoder:
     prepared categorical and continuous columns and every tree's leaf index becomes a new column `gbm_leaf_<t>`.  The trees are
     grown by this library's histogram GBDT on the GPU (ops.gbdt_*, csrc/gbdt.hip): LightGBM's algorithm in outline, NOT LightGBM
     and not compared with it.  Deviations: categorical codes are binned as ordinal integers (LightGBM partitions the categories);
-    no row or column subsampling and no max_depth; binary log loss and L2 regression only.  The fitted state is numpy only."""
+    no row or column subsampling and no max_depth; binary log loss, L2 regression and, with `num_classes` = K in [3, 64], softmax
+    cross-entropy with LightGBM's K / (K - 1) hessian factor: round t grows one tree per class, stored at index t K + c, and the
+    new columns gbm_leaf_0 .. gbm_leaf_{T K - 1} are in that order (LightGBM's pred_leaf order).  The fitted state is numpy only."""
 
-    def __init__(self, cat_vars, cont_vars, task, **gbm_params):
+    MAX_CLASSES = 64                    # include/dt_hip.h DT_GBDT_MAX_CLASSES
+
+    def __init__(self, cat_vars, cont_vars, task, num_classes=None, **gbm_params):
         unknown = sorted(set(gbm_params) - set(GBM_DEFAULTS))
         if unknown:
             raise ValueError(f'gbm_params: unsupported key(s) {unknown}; GbmLeavesEncoder takes {sorted(GBM_DEFAULTS)}')
-        if task not in (consts.TASK_BINARY, consts.TASK_REGRESSION):
-            raise ValueError(f'apply_gbm_features: task {task!r} is not supported yet; multiclass and multilabel boosting are a '
-                             f'follow-up, the GBM leaf features take binary and regression')
+        if task == consts.TASK_MULTICLASS and num_classes is None:
+            raise ValueError(f'apply_gbm_features: task {task!r} needs num_classes (3 to {self.MAX_CLASSES}) to size one tree per '
+                             f'class and round; only multilabel boosting remains a follow-up')
+        if task not in (consts.TASK_BINARY, consts.TASK_REGRESSION, consts.TASK_MULTICLASS):
+            raise ValueError(f'apply_gbm_features: task {task!r} is not supported; multilabel boosting is a follow-up, the GBM '
+                             f'leaf features take binary, regression and multiclass')
+        if task == consts.TASK_MULTICLASS and not 3 <= int(num_classes) <= self.MAX_CLASSES:
+            raise ValueError(f'apply_gbm_features: num_classes must be in [3, {self.MAX_CLASSES}] for a multiclass task, got '
+                             f'{num_classes} (two classes are the binary task)')
         self.cat_vars, self.cont_vars, self.task = list(cat_vars), list(cont_vars), task
+        self.num_classes = np.int64(num_classes) if task == consts.TASK_MULTICLASS else None
         self.params = dict(GBM_DEFAULTS, **gbm_params)
         p = self.params
         if not 2 <= int(p['max_bin']) <= 255:
@@ -284,19 +295,25 @@ class GbmLeavesEncoder:
         T, L, N = int(p['n_estimators']), int(p['num_leaves']), len(X)
         if not self.columns or N < 1:
             raise ValueError('apply_gbm_features: no categorical or continuous column to fit the trees on')
+        K = None if self.num_classes is None else int(self.num_classes)
         objective = 'binary' if self.task == consts.TASK_BINARY else 'regression'
         yv = np.asarray(y, dtype=np.float64).reshape(-1)
-        if objective == 'binary':
+        if K is not None:               # one score row per class from the class priors; a label outside [0, K) counts nowhere
+            prior = np.array([(yv == c).mean() for c in range(K)])
+            init = np.log(np.maximum(prior, 1e-15)).astype(np.float32)
+        elif objective == 'binary':
             pbar = min(max(float(yv.mean()), 1e-15), 1 - 1e-15)
             init = np.float32(np.log(pbar / (1 - pbar)))
         else:
             init = np.float32(yv.mean())
         self.edges_ = [gbm_bin_edges(X[c].values, int(p['max_bin'])) for c in self.columns]
         bins = ops.gbdt_bin(self._upload(X, device), self.edges_)
-        ws = ops.GbdtWorkspace(bins, L)
+        ws = ops.GbdtWorkspace(bins, L, num_classes=K)
         yd = torch.from_numpy(yv.astype(np.float32)).to(device)
-        scores = torch.full((N,), float(init), dtype=torch.float32, device=device)
         i32 = dict(dtype=torch.int32, device=device)
+        if K is not None:
+            return self._fit_softmax(X, bins, ws, yd, init, device)
+        scores = torch.full((N,), float(init), dtype=torch.float32, device=device)
         trees = {'node_feat': torch.empty((T, L - 1), **i32), 'node_bin': torch.empty((T, L - 1), **i32),
                  'node_child': torch.empty((T, L - 1, 2), **i32), 'n_nodes': torch.empty(T, **i32),
                  'leaf_value': torch.empty((T, L), dtype=torch.float32, device=device)}
@@ -317,6 +334,34 @@ class GbmLeavesEncoder:
         self.new_columns = [f'gbm_leaf_{t}' for t in range(T)]
         return self._append(X, leaves.t().contiguous().cpu().numpy())
 
+    def _fit_softmax(self, X, bins, ws, yd, init, device):
+        """the boosting loop of a multiclass task: per round one gradient launch over the class-major scores [K, N] and the
+        launches of one tree, which grow the K class trees in lock-step into rows t K .. t K + K - 1 of the tree arrays"""
+        import torch
+        from .. import ops
+        p, K, N = self.params, int(self.num_classes), len(X)
+        T, L = int(p['n_estimators']), int(p['num_leaves'])
+        i32 = dict(dtype=torch.int32, device=device)
+        scores = torch.from_numpy(init).to(device)[:, None].expand(K, N).contiguous()
+        trees = {'node_feat': torch.empty((T * K, L - 1), **i32), 'node_bin': torch.empty((T * K, L - 1), **i32),
+                 'node_child': torch.empty((T * K, L - 1, 2), **i32), 'n_nodes': torch.empty(T * K, **i32),
+                 'leaf_value': torch.empty((T * K, L), dtype=torch.float32, device=device)}
+        leaves = torch.empty((T * K, N), **i32)
+        sexp = torch.empty((T, 2), **i32)
+        grads = (torch.empty((K, N), **i32), torch.empty((K, N), **i32))
+        grow = {k: p[k] for k in ('num_leaves', 'min_child_samples', 'reg_lambda', 'min_split_gain', 'learning_rate')}
+        for t in range(T):
+            qg, qh, s = ops.gbdt_gradients_softmax(scores, yd, K, out=grads + (sexp[t],))
+            out = {k: v[t * K:(t + 1) * K] for k, v in trees.items()}
+            out['row_leaf'] = leaves[t * K:(t + 1) * K]
+            ops.gbdt_grow_trees(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=self.timings)
+        for k, v in trees.items():
+            setattr(self, k + '_', v.cpu().numpy())
+        self.scale_exponents_ = sexp.cpu().numpy()
+        self.init_score_ = init
+        self.new_columns = [f'gbm_leaf_{j}' for j in range(T * K)]
+        return self._append(X, leaves.t().contiguous().cpu().numpy())
+
     def fit(self, X, y):
         self.fit_transform(X, y)
         return self
@@ -334,7 +379,14 @@ class GbmLeavesEncoder:
         return self._append(X, ops.gbdt_predict_leaves(packed, trees, int(self.params['num_leaves'])).cpu().numpy())
 
     def raw_scores(self, leaves):
-        """the ensemble's raw scores (logits / predictions) float32 [N] of rows whose leaf ids [N, T] are given"""
+        """the ensemble's raw scores (logits / predictions) float32 [N] of rows whose leaf ids [N, T] are given; a multiclass
+        encoder: float32 [N, K] from the leaf ids [N, T K], tree j adding to class j mod K"""
+        if getattr(self, 'num_classes', None) is not None:
+            K = int(self.num_classes)
+            s = np.tile(np.asarray(self.init_score_, dtype=np.float32), (len(leaves), 1))
+            for j in range(leaves.shape[1]):
+                s[:, j % K] = s[:, j % K] + self.leaf_value_[j][np.asarray(leaves)[:, j]]
+            return s
         s = np.full(len(leaves), self.init_score_, dtype=np.float32)
         for t in range(leaves.shape[1]):
             s = s + self.leaf_value_[t][np.asarray(leaves)[:, t]]
@@ -719,6 +771,7 @@ class DefaultPreprocessor(AbstractPreprocessor):
         """preprocessor.py:431-445 with GbmLeavesEncoder: the leaf columns join the categorical columns (vocabulary max + 1) or
         form one continuous block"""
         enc = GbmLeavesEncoder(self.get_categorical_columns(), self.get_continuous_columns(), self.task_,
+                               num_classes=len(self.labels_) if self.task_ == consts.TASK_MULTICLASS else None,
                                **(self.config.gbm_params or {}))
         X = enc.fit_transform(X, y)
         self.X_transformers['gbm_features'] = enc

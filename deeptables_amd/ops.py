@@ -2079,6 +2079,15 @@ class GbdtWs(ctypes.Structure):
 assert ctypes.sizeof(GbdtWs) == _lib.DT_GBDT_WS_BYTES
 
 
+class GbdtMc(ctypes.Structure):
+    """include/dt_hip.h dt_gbdt_mc: class 0's descriptor and the element strides between classes"""
+    _fields_ = [('base', GbdtWs), ('K', ctypes.c_int32), ('reserved', ctypes.c_int32)] + \
+               [(n + '_stride', ctypes.c_int64) for n in ('q', 'idx', 'hist', 'leaf', 'state', 'part', 'node', 'value', 'nn', 'row')]
+
+
+assert ctypes.sizeof(GbdtMc) == _lib.DT_GBDT_MC_BYTES
+
+
 def gbdt_bin(columns, edges):
     """columns: P device tensors [N] (int32 / int64 / float32 / float64), edges: P ascending float64 numpy arrays of at most 255
     edges -> the feature-major bin matrix uint8 [P, N]: bin = the number of edges <= x, len(edges) for a NaN.  One launch per
@@ -2131,22 +2140,84 @@ def gbdt_gradients(scores, y, objective, max_slot=None, out=None):
     return qg, qh, sexp
 
 
+def gbdt_gradients_softmax(scores, y, num_classes, out=None):
+    """float32 class-major scores [K, N] and y [N] holding class numbers -> (qg int32 [K, N], qh int32 [K, N], sexp int32 [2] =
+    (23, 25)): the softmax cross-entropy gradients p - [y == k] and LightGBM's hessians K / (K - 1) * p (1 - p), float64,
+    quantised as rint(v * 2^S); see include/dt_hip.h dt_gbdt_grad_softmax.  3 <= K <= 64."""
+    require_cuda(scores, y)
+    K = int(num_classes)
+    if scores.dtype != torch.float32 or y.dtype != torch.float32 or scores.dim() != 2 or tuple(scores.shape) != (K, y.numel()) or \
+            y.dim() != 1 or not (scores.is_contiguous() and y.is_contiguous()):
+        raise ValueError(f'gbdt_gradients_softmax: scores must be a contiguous float32 [{K}, N] tensor and y float32 [N]')
+    N, device = y.shape[0], scores.device
+    qg, qh, sexp = out if out is not None else (torch.empty((K, N), dtype=torch.int32, device=device),
+                                                torch.empty((K, N), dtype=torch.int32, device=device),
+                                                torch.empty(2, dtype=torch.int32, device=device))
+    if tuple(qg.shape) != (K, N) or tuple(qh.shape) != (K, N) or not (qg.is_contiguous() and qh.is_contiguous()):
+        raise ValueError(f'gbdt_gradients_softmax: out must hold contiguous int32 [{K}, {N}] qg and qh')
+    with torch.cuda.device(device):
+        check(lib().dt_gbdt_grad_softmax(ptr(scores), ptr(y), N, K, ptr(sexp), ptr(qg), ptr(qh), stream_ptr()), 'dt_gbdt_grad_softmax')
+    return qg, qh, sexp
+
+
 class GbdtWorkspace:
     """The device buffers one tree needs (include/dt_hip.h dt_gbdt_ws) for a bin matrix [P, N] and `num_leaves`: the row-major
-    copy of the bins, both index buffers, the histograms of every leaf, the leaf table.  Reused by every tree of a fit."""
+    copy of the bins, both index buffers, the histograms of every leaf, the leaf table.  Reused by every tree of a fit.
+    num_classes = K: the buffers of K trees grown in lock-step (gbdt_grow_trees), every table with a leading [K] — 8 N K bytes
+    of indices and K * num_leaves * P * 256 * 20 bytes of histograms; the bins and their row-major copy stay shared."""
 
-    def __init__(self, bins, num_leaves):
+    def __init__(self, bins, num_leaves, num_classes=None):
         self.bins, self.packed = bins, gbdt_pack(bins)
         P, N = bins.shape
         L, dev = int(num_leaves), bins.device
-        self.N, self.P, self.L = N, P, L
-        self.idx = torch.empty((2, N), dtype=torch.int32, device=dev)
-        self.hg = torch.empty((L, P, _lib.DT_GBDT_BINS), dtype=torch.int64, device=dev)
+        self.N, self.P, self.L, self.K = N, P, L, None if num_classes is None else int(num_classes)
+        if self.K is not None and not 2 <= self.K <= _lib.DT_GBDT_MAX_CLASSES:
+            raise ValueError(f'GbdtWorkspace: num_classes must be in [2, {_lib.DT_GBDT_MAX_CLASSES}] (None: one tree), got {num_classes}')
+        k = () if self.K is None else (self.K,)
+        self.idx = torch.empty(k + (2, N), dtype=torch.int32, device=dev)
+        self.hg = torch.empty(k + (L, P, _lib.DT_GBDT_BINS), dtype=torch.int64, device=dev)
         self.hh = torch.empty_like(self.hg)
-        self.hc = torch.empty((L, P, _lib.DT_GBDT_BINS), dtype=torch.int32, device=dev)
-        self.leaf = torch.empty((L, _lib.DT_GBDT_LEAF_WORDS), dtype=torch.int64, device=dev)
-        self.state = torch.empty(_lib.DT_GBDT_STATE_WORDS, dtype=torch.int32, device=dev)
-        self.part = torch.empty((N + _lib.DT_GBDT_PART_CHUNK - 1) // _lib.DT_GBDT_PART_CHUNK, dtype=torch.int32, device=dev)
+        self.hc = torch.empty(k + (L, P, _lib.DT_GBDT_BINS), dtype=torch.int32, device=dev)
+        self.leaf = torch.empty(k + (L, _lib.DT_GBDT_LEAF_WORDS), dtype=torch.int64, device=dev)
+        self.state = torch.empty(k + (_lib.DT_GBDT_STATE_WORDS,), dtype=torch.int32, device=dev)
+        self.part = torch.empty(k + ((N + _lib.DT_GBDT_PART_CHUNK - 1) // _lib.DT_GBDT_PART_CHUNK,), dtype=torch.int32, device=dev)
+
+
+def _gbdt_descriptor(bins, qg, qh, sexp, ws, out, params):
+    """the dt_gbdt_ws of one tree (class 0's, when the tensors carry a leading class dimension)"""
+    P, N = bins.shape
+    return GbdtWs(bins.data_ptr(), ws.packed.data_ptr(), qg.data_ptr(), qh.data_ptr(), sexp.data_ptr(), ws.idx.data_ptr(),
+                  ws.hg.data_ptr(), ws.hh.data_ptr(), ws.hc.data_ptr(), ws.leaf.data_ptr(), ws.state.data_ptr(), ws.part.data_ptr(),
+                  out['node_feat'].data_ptr(), out['node_bin'].data_ptr(), out['node_child'].data_ptr(), out['leaf_value'].data_ptr(),
+                  out['n_nodes'].data_ptr(), N, P, ws.L, int(params.get('min_child_samples', 20)), 0, float(params.get('reg_lambda', 0.0)),
+                  float(params.get('min_split_gain', 0.0)), float(params.get('learning_rate', 0.1)))
+
+
+def _gbdt_launch_tree(prefix, d, L, scores, row_leaf, dev, timings):
+    """the launch sequence of one tree through the entry points `prefix`_tree_begin, _hist, ...: 2 + 4 per possible split"""
+    h, dp = lib(), ctypes.byref(d)
+    begin, hist, split, grow, update = (getattr(h, f'{prefix}_{n}') for n in ('tree_begin', 'hist', 'split', 'grow', 'leaf_update'))
+
+    def run(role, fn, *args):
+        if timings is None:
+            check(fn(*args), role)
+            return
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        check(fn(*args), role)
+        torch.cuda.synchronize(dev)
+        timings[role] = timings.get(role, 0.0) + time.perf_counter() - t0
+
+    with torch.cuda.device(dev):
+        s = stream_ptr()
+        run('tree_begin', begin, dp, s)
+        run('hist', hist, dp, 1, s)
+        run('split', split, dp, 1, s)
+        for _ in range(L - 1):
+            run('grow', grow, dp, s)
+            run('hist', hist, dp, 0, s)
+            run('split', split, dp, 0, s)
+        run('leaf_update', update, dp, ptr(scores), ptr(row_leaf), s)
 
 
 def gbdt_grow_tree(bins, qg, qh, params, workspace=None, scores=None, out=None, timings=None):
@@ -2166,8 +2237,8 @@ def gbdt_grow_tree(bins, qg, qh, params, workspace=None, scores=None, out=None, 
         raise ValueError(f'gbdt_grow_tree: qg and qh must be int32 [{N}] tensors')
     dev = bins.device
     ws = workspace if workspace is not None else GbdtWorkspace(bins, L)
-    if (ws.N, ws.P, ws.L) != (N, P, L) or ws.bins.data_ptr() != bins.data_ptr():
-        raise ValueError('gbdt_grow_tree: the workspace was made for another bin matrix or num_leaves')
+    if (ws.N, ws.P, ws.L, ws.K) != (N, P, L, None) or ws.bins.data_ptr() != bins.data_ptr():
+        raise ValueError('gbdt_grow_tree: the workspace was made for another bin matrix, num_leaves or for several classes')
     sexp = params.get('sexp', (0, 0))
     if not torch.is_tensor(sexp):
         sexp = torch.tensor([int(sexp[0]), int(sexp[1])], dtype=torch.int32, device=dev)
@@ -2177,33 +2248,51 @@ def gbdt_grow_tree(bins, qg, qh, params, workspace=None, scores=None, out=None, 
                'leaf_value': torch.empty(L, dtype=torch.float32, device=dev), 'row_leaf': torch.empty(N, dtype=torch.int32, device=dev)}
     if scores is None:
         scores = torch.zeros(N, dtype=torch.float32, device=dev)
-    d = GbdtWs(bins.data_ptr(), ws.packed.data_ptr(), qg.data_ptr(), qh.data_ptr(), sexp.data_ptr(), ws.idx.data_ptr(),
-               ws.hg.data_ptr(), ws.hh.data_ptr(), ws.hc.data_ptr(), ws.leaf.data_ptr(), ws.state.data_ptr(), ws.part.data_ptr(),
-               out['node_feat'].data_ptr(), out['node_bin'].data_ptr(), out['node_child'].data_ptr(), out['leaf_value'].data_ptr(),
-               out['n_nodes'].data_ptr(), N, P, L, int(params.get('min_child_samples', 20)), 0, float(params.get('reg_lambda', 0.0)),
-               float(params.get('min_split_gain', 0.0)), float(params.get('learning_rate', 0.1)))
-    h, dp = lib(), ctypes.byref(d)
+    _gbdt_launch_tree('dt_gbdt', _gbdt_descriptor(bins, qg, qh, sexp, ws, out, params), L, scores, out['row_leaf'], dev, timings)
+    return out
 
-    def run(role, fn, *args):
-        if timings is None:
-            check(fn(*args), role)
-            return
-        torch.cuda.synchronize(dev)
-        t0 = time.perf_counter()
-        check(fn(*args), role)
-        torch.cuda.synchronize(dev)
-        timings[role] = timings.get(role, 0.0) + time.perf_counter() - t0
 
-    with torch.cuda.device(dev):
-        s = stream_ptr()
-        run('tree_begin', h.dt_gbdt_tree_begin, dp, s)
-        run('hist', h.dt_gbdt_hist, dp, 1, s)
-        run('split', h.dt_gbdt_split, dp, 1, s)
-        for _ in range(L - 1):
-            run('grow', h.dt_gbdt_grow, dp, s)
-            run('hist', h.dt_gbdt_hist, dp, 0, s)
-            run('split', h.dt_gbdt_split, dp, 0, s)
-        run('leaf_update', h.dt_gbdt_leaf_update, dp, ptr(scores), ptr(out['row_leaf']), s)
+def gbdt_grow_trees(bins, qg, qh, params, workspace=None, scores=None, out=None, timings=None):
+    """The K class trees of one softmax round, grown in lock-step: gbdt_grow_tree's arguments with a leading class dimension —
+    qg, qh int32 [K, N] (gbdt_gradients_softmax), scores float32 [K, N], the returned arrays [K, ...] ('n_nodes' int32 [K]);
+    `workspace` is a GbdtWorkspace(bins, num_leaves, num_classes=K).  Class c's tree is bit for bit gbdt_grow_tree's on
+    (qg[c], qh[c]).  The host issues the launches of ONE tree (the class is a grid dimension) and reads nothing back; a class
+    whose tree is finished idles while the others grow on.  out: [K, ...] views whose rows are contiguous (a fit hands
+    [t K : (t + 1) K] of its [T K, ...] arrays); timings as in gbdt_grow_tree."""
+    require_cuda(bins, qg, qh)
+    P, N = bins.shape
+    L = int(params.get('num_leaves', 31))
+    if not 2 <= L <= _lib.DT_GBDT_MAX_LEAVES:
+        raise ValueError(f'gbdt_grow_trees: num_leaves must be in [2, {_lib.DT_GBDT_MAX_LEAVES}], got {L}')
+    if qg.dtype != torch.int32 or qh.dtype != torch.int32 or qg.dim() != 2 or qg.shape[1] != N or qh.shape != qg.shape or \
+            not 2 <= qg.shape[0] <= _lib.DT_GBDT_MAX_CLASSES or not (qg.is_contiguous() and qh.is_contiguous()):
+        raise ValueError(f'gbdt_grow_trees: qg and qh must be contiguous int32 [K, {N}] tensors, 2 <= K <= {_lib.DT_GBDT_MAX_CLASSES} '
+                         f'(one class is gbdt_grow_tree)')
+    K, dev = int(qg.shape[0]), bins.device
+    ws = workspace if workspace is not None else GbdtWorkspace(bins, L, num_classes=K)
+    if (ws.N, ws.P, ws.L, ws.K) != (N, P, L, K) or ws.bins.data_ptr() != bins.data_ptr():
+        raise ValueError('gbdt_grow_trees: the workspace was made for another bin matrix, num_leaves or num_classes')
+    sexp = params.get('sexp', (0, 0))
+    if not torch.is_tensor(sexp):
+        sexp = torch.tensor([int(sexp[0]), int(sexp[1])], dtype=torch.int32, device=dev)
+    i32 = dict(dtype=torch.int32, device=dev)
+    shapes = {'node_feat': (K, L - 1), 'node_bin': (K, L - 1), 'node_child': (K, L - 1, 2), 'n_nodes': (K,), 'leaf_value': (K, L),
+              'row_leaf': (K, N)}
+    if out is None:
+        out = {k: torch.empty(v, **(dict(i32, dtype=torch.float32) if k == 'leaf_value' else i32)) for k, v in shapes.items()}
+    if scores is None:
+        scores = torch.zeros((K, N), dtype=torch.float32, device=dev)
+    for k, v in dict(out, scores=scores).items():
+        want = torch.float32 if k in ('leaf_value', 'scores') else torch.int32
+        if tuple(v.shape) != shapes.get(k, (K, N)) or v.dtype != want or not v[0].is_contiguous() or v.device != dev:
+            raise ValueError(f'gbdt_grow_trees: {k} must be a {want} {shapes.get(k, (K, N))} tensor on {dev} with contiguous rows')
+    if out['node_feat'].stride(0) != out['node_bin'].stride(0) or 2 * out['node_feat'].stride(0) != out['node_child'].stride(0) or \
+            scores.stride(0) != out['row_leaf'].stride(0):
+        raise ValueError('gbdt_grow_trees: node_feat / node_bin / node_child (and scores / row_leaf) must share one class stride')
+    d = GbdtMc(_gbdt_descriptor(bins, qg, qh, sexp, ws, out, params), K, 0, qg.stride(0), ws.idx.stride(0), ws.hg.stride(0),
+               ws.leaf.stride(0), ws.state.stride(0), ws.part.stride(0), out['node_feat'].stride(0),
+               out['leaf_value'].stride(0), out['n_nodes'].stride(0), scores.stride(0))
+    _gbdt_launch_tree('dt_gbdt_mc', d, L, scores, out['row_leaf'], dev, timings)
     return out
 
 

@@ -1732,7 +1732,8 @@ int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* col
 
 /* Histogram gradient-boosted trees for the GBM leaf features (csrc/gbdt.hip; ops.gbdt_gradients / gbdt_grow_tree /
  * gbdt_predict_leaves, models/preprocessor.py GbmLeavesEncoder; replaces deeptables/models/preprocessor.py:431-452, hypernets'
- * LgbmLeavesEncoder).  LightGBM's algorithm in outline, not compared with a LightGBM run.  Binary log loss and L2 regression.
+ * LgbmLeavesEncoder).  LightGBM's algorithm in outline, not compared with a LightGBM run.  Binary log loss, L2 regression and
+ * softmax cross-entropy over 3 .. 64 classes.
  * dt_gbdt_bin: one raw DEVICE column [N] (dtype DT_PREP_I32 / I64 / F32 / F64) and its ascending float64 edges (n_edges <= 255)
  *   -> uint8 [N]: the number of edges <= x, n_edges for a NaN (DT_PREP_BIN's rule).  Called once per feature on the rows of the
  *   feature-major bin matrix uint8 [P][N].
@@ -1763,6 +1764,19 @@ int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* col
  *   leaf_value float32 [L]; a tree without a node has the single leaf 0.
  * dt_gbdt_predict_leaves: the row-major bin matrix [N][P8] and T trees ([T][L-1] node arrays, n_nodes [T]) -> int32 [N][T] leaf
  *   ids; one thread walks one (row, tree), the node arrays of a tile of trees sit in LDS.
+ * Multiclass, softmax boosting: round t grows one tree per class, all K of them in lock-step.
+ *   dt_gbdt_grad_softmax  float32 scores [K][N] (class-major: class k's scores are contiguous) and y [N] holding class numbers
+ *     -> int32 qg, qh [K][N], sexp = {23, 25}.  Per row, float64, in this order: m = max_k s_k, e_k = exp(s_k - m), Z = sum_k e_k
+ *     in class order, p_k = e_k / Z, g_k = p_k - [y == k], h_k = (K / (K - 1)) (p_k (1 - p_k)) (LightGBM's factor).  A label
+ *     outside [0, K) or a NaN names no class; a NaN result quantises to 0.  3 <= K <= DT_GBDT_MAX_CLASSES: then h <= 0.375 and
+ *     |qh| < 2^24 (K = 2 would reach 2^24; two classes are DT_GBDT_BINARY).  Any other K is DT_ERR_UNSUPPORTED before any launch.
+ *   dt_gbdt_mc_tree_begin / _hist / _split / _grow / _leaf_update: the launches of ONE tree, for K trees.  dt_gbdt_mc is class
+ *     0's dt_gbdt_ws plus the distance in ELEMENTS from a class's table to the next class's; bins, packed, sexp, N, P, L and
+ *     the parameters are shared.  The kernels run the single-tree code on class blockIdx.z's view (grid z = K; x and y as in
+ *     the single-tree launch), so every class's tree is bit for bit what dt_gbdt_* grow from its qg / qh.  A class whose tree
+ *     is finished returns at once while the others go on.  dt_gbdt_mc_leaf_update takes scores float32 and row_leaf int32
+ *     [K][row_stride].  Memory: 8 N K bytes of idx, K L P 256 20 bytes of histograms (K = 10, L = 31, P = 39: 62 MB).
+ *     1 <= K <= DT_GBDT_MAX_CLASSES and every stride at least one class's table, otherwise DT_ERR_INVALID_ARG.
  * Nothing synchronises with the host or allocates.  Sizes outside the limits below, a null or misaligned pointer, a negative
  * lambda or min_gain are DT_ERR_INVALID_ARG before any launch.                                                                */
 #define DT_GBDT_BINARY 0
@@ -1779,6 +1793,8 @@ int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* col
 #define DT_GBDT_STATE_WORDS 16
 #define DT_GBDT_LEAF_WORDS 12
 #define DT_GBDT_WS_BYTES 184
+#define DT_GBDT_MAX_CLASSES 64
+#define DT_GBDT_MC_BYTES 272
 typedef struct dt_gbdt_ws {
     const uint8_t* bins;      /* [P][N] */
     const uint32_t* packed;   /* [N][P8 / 4] */
@@ -1801,6 +1817,20 @@ typedef struct dt_gbdt_ws {
     int32_t P, L, min_child, reserved;
     double lambda, min_gain, lr;
 } dt_gbdt_ws;
+typedef struct dt_gbdt_mc {
+    dt_gbdt_ws base;          /* class 0's tables; class c's are base + c * stride (in elements of each table) */
+    int32_t K, reserved;
+    int64_t q_stride;         /* qg, qh: >= N */
+    int64_t idx_stride;       /* idx: >= 2 N */
+    int64_t hist_stride;      /* hg, hh, hc: >= L P 256 */
+    int64_t leaf_stride;      /* leaf: >= L DT_GBDT_LEAF_WORDS */
+    int64_t state_stride;     /* state: >= DT_GBDT_STATE_WORDS */
+    int64_t part_stride;      /* part: >= ceil(N / DT_GBDT_PART_CHUNK) */
+    int64_t node_stride;      /* node_feat, node_bin: >= L - 1; node_child moves by twice this */
+    int64_t value_stride;     /* leaf_value: >= L */
+    int64_t nn_stride;        /* n_nodes: >= 1 */
+    int64_t row_stride;       /* scores, row_leaf of dt_gbdt_mc_leaf_update: >= N */
+} dt_gbdt_mc;
 int dt_gbdt_bin(const void* src, int dtype, int64_t N, const double* edges, int n_edges, void* out, void* stream);
 int dt_gbdt_pack(const void* bins, int64_t N, int P, void* packed, void* stream);
 int dt_gbdt_grad(int objective, const float* scores, const float* y, int64_t N, void* max_slot, int32_t* sexp, int32_t* qg,
@@ -1812,6 +1842,13 @@ int dt_gbdt_grow(const dt_gbdt_ws* ws, void* stream);
 int dt_gbdt_leaf_update(const dt_gbdt_ws* ws, float* scores, int32_t* row_leaf, void* stream);
 int dt_gbdt_predict_leaves(const void* packed, int64_t N, int P, int T, int L, const int32_t* node_feat, const int32_t* node_bin,
                            const int32_t* node_child, const int32_t* n_nodes, int32_t* out, void* stream);
+int dt_gbdt_grad_softmax(const float* scores, const float* y, int64_t N, int K, int32_t* sexp, int32_t* qg, int32_t* qh,
+                         void* stream);
+int dt_gbdt_mc_tree_begin(const dt_gbdt_mc* m, void* stream);
+int dt_gbdt_mc_hist(const dt_gbdt_mc* m, int root, void* stream);
+int dt_gbdt_mc_split(const dt_gbdt_mc* m, int root, void* stream);
+int dt_gbdt_mc_grow(const dt_gbdt_mc* m, void* stream);
+int dt_gbdt_mc_leaf_update(const dt_gbdt_mc* m, float* scores, int32_t* row_leaf, void* stream);
 
 #ifdef __cplusplus
 }
