@@ -385,6 +385,11 @@ SIGNATURES = {
     'dt_ensemble_mean': (_c_int, [_ptr, _c_int, _c_i64, _c_int, _ptr, _ptr]),
     # the fitted preprocessor's transform on the device (csrc/prep_transform.hip): N, cols, cols_host, C, out_kind, out, stream
     'dt_prep_transform': (_c_int, [_c_i64, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
+    # the preprocessor's fit on the device (csrc/prep_fit.hip): srcs, dtypes, srcs_host, dtypes_host, N, C, cap, stats,
+    # distinct_keys, distinct_counts, ws, stream | ws, dtypes, dtypes_host, N, C, stats, ranks, fills, out, stream
+    'dt_column_profile_workspace_bytes': (_c_i64, [_c_i64, _c_int, _c_int]),
+    'dt_column_profile': (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_i64, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    'dt_column_order_stats': (_c_int, [_ptr, _ptr, _ptr, _c_i64, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr]),
     # histogram gradient-boosted trees for the GBM leaf features (csrc/gbdt.hip); `ws` is a host dt_gbdt_ws (ops.GbdtWs)
     'dt_gbdt_bin': (_c_int, [_ptr, _c_int, _c_i64, _ptr, _c_int, _ptr, _ptr]),            # src, dtype, N, edges, n_edges, out, stream
     'dt_gbdt_pack': (_c_int, [_ptr, _c_i64, _c_int, _ptr, _ptr]),                         # bins, N, P, packed, stream
@@ -448,6 +453,8 @@ DT_PREP_LOOKUP, DT_PREP_CONT, DT_PREP_BIN, DT_PREP_COPY = 0, 1, 2, 3
 DT_PREP_IMPUTE, DT_PREP_SCALE = 0x1, 0x2
 DT_PREP_OUT_I32, DT_PREP_OUT_F32 = 0, 1
 DT_PREP_TILE_ROWS, DT_PREP_CHUNK_COLS, DT_PREP_MAX_BLOCKS, DT_PREP_COL_BYTES = 256, 32, 1024, 80
+# dt_column_profile: the sort's tile, the words of a column's stats row, ranks and columns per call (include/dt_hip.h)
+DT_PROFILE_TILE, DT_PROFILE_STAT_WORDS, DT_PROFILE_MAX_RANKS, DT_PROFILE_MAX_COLS = 4096, 8, 32, 1024
 # dt_gbdt_*: objectives, the histogram / partition geometry and the sizes of the workspace tables (include/dt_hip.h)
 DT_GBDT_BINARY, DT_GBDT_REGRESSION = 0, 1
 DT_GBDT_BINS, DT_GBDT_HIST_GROUP, DT_GBDT_HIST_ROWS, DT_GBDT_PART_CHUNK = 256, 8, 4096, 2048

@@ -7,11 +7,14 @@ and the hypernets toolbox are outside the accelerated hot path (SURVEY §2 row 8
 `preprocessor.DefaultPreprocessor` (the TF/hypernets-free restatement of the reference's pipeline);
 `SimplePreprocessor` below is a smaller impute + label-encode variant kept for callers that want ids with 0
 reserved for unseen values."""
+import math
 import os
 import pickle
+import types
 
 import numpy as np
 import pandas as pd
+import torch
 
 from . import cross_validation, deepmodel
 from .config import ModelConfig
@@ -227,6 +230,50 @@ class DeepTable:
                             initial_epoch=initial_epoch, steps_per_epoch=steps_per_epoch,
                             validation_steps=validation_steps, validation_freq=validation_freq)
         self._modelset.clear()                                      # reference deeptable.py:369-370, :695-697
+        self._push_model('val', '+'.join(self.nets), model, history.history)
+        self._models['dt-1'] = model
+        return model, history
+
+    def fit_feed(self, X=None, y=None, batch_size=128, epochs=1, verbose=1, callbacks=None, validation_split=0.2,
+                 validation_data=None, shuffle=True, class_weight=None, sample_weight=None, initial_epoch=0,
+                 steps_per_epoch=None, validation_steps=None, validation_freq=1, device='auto', mode='auto'):
+        """`fit` with the preprocessor fitted by `DefaultPreprocessor.fit_feed` (the numeric columns profiled on the device,
+        csrc/prep_fit.hip) and the model trained on the resident feed it returns: no transformed pandas frame is made.  The
+        validation rows are cut out of the feed with `ops.take_rows` (the random split of `DeepModel.fit`), `validation_data`
+        goes through `transform_feed`; class and sample weights travel as the feed's weight column.  Same return value as
+        `fit`, and the model enters the set as `fit` leaves it.  device 'auto': where a fresh model is built; mode as
+        `DefaultPreprocessor.fit_feed`; `fit_path` / `fit_refusal` say how the preprocessor was fitted."""
+        if X is None or len(X) == 0:
+            raise ValueError('X can not be empty.')
+        pp = self.preprocessor
+        if not callable(getattr(pp, 'fit_feed', None)):
+            raise ValueError(f'fit_feed: {type(pp).__name__} has no fit_feed')
+        dev = cross_validation.target_device(self) if device == 'auto' else torch.device(device)
+
+        def weights(y_t):                   # class weights need the fitted label encoder: computed on the encoded y
+            cw = class_weight
+            if cw is None and self.config.apply_class_weight and self.task != consts.TASK_REGRESSION:
+                cw = self.get_class_weight(y_t)
+            return cross_validation.row_weights(y_t, cw, sample_weight)
+
+        feed = pp.fit_feed(X, y, device=dev, mode=mode, sample_weight=weights)
+        self.fit_path, self.fit_refusal = feed.fit_path, feed.fit_refusal
+        if len(pp.categorical_columns) == 0 and len(pp.continuous_columns) == 0:
+            raise ValueError('No valid input columns.')
+        if validation_data is not None:
+            val = self._feed_of(types.SimpleNamespace(device=dev, task=self.task, num_classes=self.num_classes),
+                                validation_data[0], validation_data[1])
+        else:
+            n_val = int(math.ceil(feed.n * validation_split)) if validation_split else 0
+            val = None
+            if n_val > 0:
+                perm = torch.from_numpy(np.random.permutation(feed.n)).to(feed.device)
+                feed, val = cross_validation.fold_feeds(feed, perm[n_val:].contiguous(), perm[:n_val].contiguous())
+        model = cross_validation.new_model(self)
+        history = model.fit(feed, batch_size=batch_size, epochs=epochs, verbose=verbose, callbacks=callbacks,
+                            validation_data=val, shuffle=shuffle, initial_epoch=initial_epoch, steps_per_epoch=steps_per_epoch,
+                            validation_steps=validation_steps, validation_freq=validation_freq)
+        self._modelset.clear()
         self._push_model('val', '+'.join(self.nets), model, history.history)
         self._models['dt-1'] = model
         return model, history

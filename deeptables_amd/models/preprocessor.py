@@ -50,10 +50,11 @@ class CategorizeEncoder:
         self.new_columns = []
 
     def fit(self, X, y=None):
-        self.new_columns = []
-        if self.remain_numeric:
-            for c in self.columns:
-                self.new_columns.append((c + '_cat', 'str', int(X[c].nunique())))
+        return self.fit_counts({c: X[c].nunique() for c in self.columns} if self.remain_numeric else {})
+
+    def fit_counts(self, nuniques):
+        """`fit` from the columns' nunique alone"""
+        self.new_columns = [(c + '_cat', 'str', int(nuniques[c])) for c in self.columns] if self.remain_numeric else []
         return self
 
     def transform(self, X):
@@ -688,8 +689,9 @@ class DefaultPreprocessor(AbstractPreprocessor):
         return y_indicator
 
     # -- steps ----------------------------------------------------------------------------------------
-    def _prepare_features(self, X):
-        """Column typing, preprocessor.py:267-336."""
+    def _prepare_features(self, X, nuniques=None):
+        """Column typing, preprocessor.py:267-336.  nuniques ({column: nunique}, the device fit): the counts are taken from
+        it and the CategorizeEncoder is sized without being run on X."""
         num_vars, convert2cat_vars, cat_vars = [], [], []
         if self.config.cat_exponent >= 1:
             raise ValueError(f'"cat_exponent" must be less than 1, not {self.config.cat_exponent} .')
@@ -702,7 +704,7 @@ class DefaultPreprocessor(AbstractPreprocessor):
                 var_len_sep[v[0]] = v[1]
         unique_upper_limit = round(X.shape[0] ** self.config.cat_exponent)
         for c in X.columns:
-            nunique = X[c].nunique()
+            nunique = X[c].nunique() if nuniques is None else int(nuniques[c])
             dtype = str(X[c].dtype)
             if nunique <= 1 and self.config.auto_discard_unique:
                 continue
@@ -726,7 +728,10 @@ class DefaultPreprocessor(AbstractPreprocessor):
                     num_vars.append((c, dtype, nunique))
         if len(convert2cat_vars) > 0:
             ce = CategorizeEncoder([c for c, d, n in convert2cat_vars], self.config.cat_remain_numeric)
-            X = ce.fit_transform(X)
+            if nuniques is None:
+                X = ce.fit_transform(X)
+            else:
+                ce.fit_counts(nuniques)
             self.X_transformers['categorize'] = ce
             if self.config.cat_remain_numeric:
                 cat_vars = cat_vars + ce.new_columns
@@ -1004,10 +1009,11 @@ class DefaultPreprocessor(AbstractPreprocessor):
                 return f'the feed ({4 * words * int(n_rows)} bytes) would exceed max_resident_bytes={max_resident_bytes}'
         return None
 
-    def feed_blocks(self, X, device):
+    def feed_blocks(self, X, device, sources=None):
         """The blocks of a feed for the prepared frame X on `device`, by the plan: one upload per raw column, one
         `ops.prep_transform` per id / continuous block; host-served columns go through `_replay_host` and enter as plain
         copies.  A CPU `device` runs the same plan through the numpy branch of ops.prep_transform.
+        sources: {raw column: its bytes already on `device`} (fit_feed uploaded them for the profile) are not uploaded again.
         -> (blocks, kinds, host-served raw columns)"""
         import torch
         from .. import ops
@@ -1015,7 +1021,7 @@ class DefaultPreprocessor(AbstractPreprocessor):
         dev_cols, host_cols = plan.partition(X)
         N = len(X)
         with _Phase('upload', device):
-            src = {c: ops.prep_source(X[c].values, device) for c in dev_cols}
+            src = {c: sources[c] if sources and c in sources else ops.prep_source(X[c].values, device) for c in dev_cols}
             tabs = plan.resident(device)
         blocks, kinds, var_blocks, host_src = [], [], [], {}
         with _Phase('host_columns', device):
@@ -1097,6 +1103,251 @@ class DefaultPreprocessor(AbstractPreprocessor):
                                                  weighted=sample_weight is not None)
         feed.transform_path, feed.host_columns, feed.transform_refusal = 'device', list(host_cols), None
         return feed
+
+    # -- the device path of fit: column profiles (ops.column_profile, csrc/prep_fit.hip), then transform_feed ---------------------
+    def device_fit_refusal(self, device):
+        """None when `fit_feed` can fit on the device, else the failing condition in words"""
+        import torch
+        if torch.device(device).type != 'cuda':
+            return f'the target device is {torch.device(device)}, not a GPU'
+        st = self.config.distribute_strategy
+        if st is not None and getattr(st, 'world_size', 1) > 1:
+            return 'a multi-rank distribute_strategy is active'
+        if self.config.apply_gbm_features:
+            return 'apply_gbm_features fits its trees on the transformed frame'
+        return None
+
+    def fit_feed(self, X, y, *, device, mode='auto', sample_weight=None, cat_dtype=None, max_resident_bytes=32 << 30):
+        """`fit_transform` with the numeric columns' statistics taken on the device, and the training rows turned into a
+        resident `training.TableBatches` by `transform_feed` — no transformed pandas frame is made.  Every numeric column
+        (`served_dtype`) is uploaded as it is and profiled by `ops.column_profile`: nunique, the distinct values of the columns a
+        label encoder sees, min, max, the fixed-order float64 sum behind the mean, and the few order statistics np.quantile's
+        formula reads.  Other columns (strings, categories, var-len) are fitted by the host steps on a sub-frame of themselves.
+        The fitted state is `fit_transform`'s, attribute for attribute; `means_` is sum / count of the exact-order device sum
+        (pandas' own summation order differs by rounding on general data).  mode as `transform_feed`; False, DT_AMD_DEVICE_FIT=0
+        or a refusal (`feed.fit_refusal`) take `fit_transform` + `transform_feed`.  -> the feed; `feed.fit_path` says which.
+        sample_weight: per-row weights, or a function of the encoded y returning them (class weights need the fitted label
+        encoder).  The raw columns are uploaded once and serve the profile and the transform.  max_resident_bytes bounds the
+        profile's workspace (16 bytes per numeric element, checked before anything is fitted) and the feed; the feed's size is
+        known only after typing, so a feed beyond the bound is refused AFTER the device fit: 'auto' then fits again on the
+        host, mode=True raises and leaves the object device-fitted.  `apply_gbm_features` is refused as a whole — a narrower
+        reading than "the GBM step keeps its own fit": its trees are fitted on the transformed pandas frame, which this path
+        never makes (and `transform_feed` refuses a gbm_features step)."""
+        import torch
+        from .. import training
+        if mode not in (True, False, 'auto'):
+            raise ValueError(f"fit_feed: mode must be True, False or 'auto', got {mode!r}")
+        kw = dict(device=device, cat_dtype=cat_dtype, max_resident_bytes=max_resident_bytes)
+        if mode is False:
+            why = 'mode=False'
+        elif os.environ.get('DT_AMD_DEVICE_FIT', '1') == '0':
+            why = 'DT_AMD_DEVICE_FIT=0'
+        else:
+            why = self.device_fit_refusal(device)
+        if why is None:
+            self._validate_fit_transform(X, y)
+            frame = X if isinstance(X, pd.DataFrame) else pd.DataFrame(X)
+            numeric = sum(served_dtype(frame[c].dtype) for c in frame.columns)
+            if 16 * numeric * len(frame) > max_resident_bytes:          # the sort's two key buffers: 2 x 8 bytes per element
+                why = f'the profile workspace ({16 * numeric * len(frame)} bytes) would exceed max_resident_bytes={max_resident_bytes}'
+        if why is None:
+            y_enc, sources = self._fit_on_device(X, copy.deepcopy(y), device)
+            weights = sample_weight(y_enc) if callable(sample_weight) else sample_weight
+            num_classes = len(self.labels_) if self.labels_ is not None and len(self.labels_) else 1
+            y_host, y_ndim = training.host_targets(y_enc, self.task_, num_classes, weights)
+            why = self.feed_refusal(device, cat_dtype, len(frame), y_host.numel() // max(1, y_host.shape[0]), max_resident_bytes)
+            if why is None:
+                Xp = self._prepare_X(frame.copy(deep=False))
+                blocks, kinds, host_cols = self.feed_blocks(Xp, torch.device(device), sources)
+                feed = training.TableBatches.from_device(blocks, kinds, y=y_host.to(device), y_ndim=y_ndim,
+                                                         weighted=weights is not None)
+                feed.transform_path, feed.host_columns, feed.transform_refusal = 'device', list(host_cols), None
+                feed.fit_path, feed.fit_refusal = 'device', None
+                return feed
+        if mode is True:
+            raise ValueError(f'fit_feed(mode=True): {why}')
+        _Xt, y_enc = self.fit_transform(X, y)
+        weights = sample_weight(y_enc) if callable(sample_weight) else sample_weight
+        feed = self.transform_feed(X, y_enc, y_encoded=True, mode='auto', sample_weight=weights, **kw)
+        feed.fit_path, feed.fit_refusal = 'host', why
+        return feed
+
+    def _fit_on_device(self, X, y, device):
+        """the steps of `fit_transform` in its order; -> (the encoded y, {numeric column: its bytes on `device`})"""
+        from .. import ops
+        self.reset()
+        y = self.fit_transform_y(y)
+        X = X.copy(deep=False) if isinstance(X, pd.DataFrame) else pd.DataFrame(X)
+        raw = list(X.columns)
+        X = self._prepare_X(X)
+        self.raw_columns_ = dict(zip(raw, X.columns))
+        self.fit_dtypes_ = {c: X[c].dtype for c in X.columns}
+        conf, N = self.config, len(X)
+        var_names = [v[0] for v in (conf.var_len_categorical_columns or [])]
+        dev_cols = [c for c in X.columns if served_dtype(X[c].dtype) and c not in var_names]
+        Xh = X[[c for c in X.columns if c not in dev_cols]].copy()            # the host sub-frame, transformed step by step
+        prof, at = None, {}
+        if dev_cols and N > 0:
+            with _Phase('fit_upload', device):
+                srcs = [ops.prep_source(X[c].values, device) for c in dev_cols]
+            names = [X[c].dtype.name for c in dev_cols]
+            cap = max(round(N ** conf.cat_exponent), MultiKBinsDiscretizer([]).max_bins + 1) if conf.cat_exponent < 1 else 0
+            with _Phase('fit_kernel', device):
+                prof = ops.column_profile(srcs, names, cap=cap)
+                prof.host()
+            at = {c: j for j, c in enumerate(dev_cols)}
+            self.last_profile_passes = list(prof.passes)        # digit passes the sort ran per column (tools/prep_fit_bench.py)
+        nuniques = {c: (prof.nunique[at[c]] if c in at else X[c].nunique()) for c in X.columns}
+        self._prepare_features(X, nuniques)
+        ce = self.X_transformers.get('categorize')
+        if ce is not None:
+            host_ce = copy.copy(ce)
+            host_ce.columns = [c for c in ce.columns if c not in at]
+            Xh = host_ce.transform(Xh)
+        # the distinct values of the columns a label encoder sees; explicit categoricals above the cap get a second, wider profile
+        wanted = [c for c in dev_cols if conf.auto_encode_label and
+                  (c in self.get_categorical_columns() or (ce is not None and c in ce.columns))]
+        distinct = {c: prof.distinct(at[c]) for c in wanted}
+        wide = [c for c in wanted if distinct[c] is None]
+        if wide:
+            with _Phase('fit_kernel', device):
+                p2 = ops.column_profile([srcs[at[c]] for c in wide], [names[at[c]] for c in wide],
+                                        cap=int(max(prof.n_distinct[at[c]] for c in wide)))
+            distinct.update({c: p2.distinct(j) for j, c in enumerate(wide)})
+        self.raw_keys_ = {}
+        for c in wanted:
+            values = distinct[c][0]
+            if prof.nan_count[at[c]]:
+                values = np.concatenate([values, np.array([np.nan], dtype=values.dtype)])
+            self.raw_keys_[c] = distinct_raw_values(values)
+        conts = self.get_continuous_columns()
+        dev_conts = [c for c in conts if c in at]
+        fill = {}                                       # what a NaN of the column becomes; no entry: it stays
+        if conf.auto_imputation:
+            cats = self.get_categorical_columns() + self.get_var_len_categorical_columns()
+            targets = set() if ce is None else {c + '_cat' if ce.remain_numeric else c for c in ce.columns}
+            is_obj = {c: c in targets or str(X[c].dtype).startswith(('obj', 'str')) or str(X[c].dtype) == 'category' for c in cats}
+            imp = ColumnImputer(conts, [c for c in cats if is_obj[c]], [c for c in cats if not is_obj[c]])
+            for c in dev_conts:
+                j = at[c]
+                count = N - int(prof.nan_count[j])
+                mean = float(prof.sums[j]) / count if count else 0.0
+                imp.means_[c] = float(np.float32(mean)) if names[j] == 'float32' else mean
+                fill[c] = imp.means_[c]
+            Xh = self._fit_host_part(imp, Xh)
+            self.X_transformers['imputation'] = imp
+        lo_hi = {}
+        for c in dev_conts:
+            j = at[c]
+            lo, hi = prof.minimum(j), prof.maximum(j)
+            lo, hi = (float('nan'), float('nan')) if lo is None else (float(lo), float(hi))
+            if c in fill and prof.nan_count[j]:
+                lo, hi = (fill[c], fill[c]) if lo != lo else (min(lo, fill[c]), max(hi, fill[c]))
+            lo_hi[c] = lo, hi
+        scale = {}
+        if conf.auto_scale:
+            ss = MinMaxScalerTransformer(conts)
+            for c in dev_conts:
+                lo, hi = lo_hi[c]
+                ss.min_[c], ss.range_[c] = lo, (hi - lo) if hi > lo else 1.0
+                scale[c] = ss.min_[c], ss.range_[c]
+            Xh = self._fit_host_part(ss, Xh)
+            self.X_transformers['standard_scale'] = ss
+
+        def final(c, values):
+            """float64 raw values of continuous column c after imputation and scaling, as the host steps compute them"""
+            v = np.asarray(values, dtype=np.float64)
+            if c in fill:
+                v = np.where(np.isnan(v), fill[c], v)
+            return (v - scale[c][0]) / scale[c][1] if c in scale else v
+
+        if conf.auto_encode_label:
+            mle = MultiLabelEncoder(self.get_categorical_columns())
+            sources = self._output_sources()
+            for name in mle.columns:
+                c = sources.get(name, name)
+                if c in at:                             # the fitted host steps on the one-column frame of distinct raw values
+                    probe = self._replay_host(pd.DataFrame({c: self.raw_keys_[c]}), [c])
+                    mle.maps_[name] = MultiLabelEncoder([name]).fit(probe).maps_[name]
+            Xh = self._fit_host_part(mle, Xh)
+            self.X_transformers['label_encoder'] = mle
+        if conf.auto_discrete:
+            mkbd = MultiKBinsDiscretizer(conts)
+            with _Phase('fit_kernel', device):
+                stats = self._quantile_edges(prof, at, dev_conts, fill, final, mkbd.max_bins, N) if dev_conts else {}
+            host_part = copy.copy(mkbd)
+            host_part.columns = [c for c in conts if c not in at]
+            host_part.fit(Xh)
+            Xh = host_part.transform(Xh)
+            host_new = {t[0]: t for t in host_part.new_columns}
+            mkbd.new_columns = []
+            for c in conts:
+                if c in at:
+                    mkbd.edges_[c], new = stats[c]
+                    mkbd.new_columns.append(new)
+                else:
+                    mkbd.new_columns.append(host_new[c])
+            self._append_categorical_cols([(new_name, bins + 1) for name, new_name, bins in mkbd.new_columns])
+            self.X_transformers['discreter'] = mkbd
+        var_len = conf.var_len_categorical_columns
+        if var_len is not None and len(var_len) > 0:
+            self._var_len_encoder(Xh, var_len)
+        self.X_transformers['last'] = PassThroughEstimator()
+        return y, ({c: srcs[at[c]] for c in dev_cols} if prof is not None else {})
+
+    @staticmethod
+    def _fit_host_part(step, Xh):
+        """fit `step` (an imputer, scaler or label encoder holding ALL its columns) on those of its columns the host sub-frame
+        Xh holds — the fitted dicts are shared with `step` — and transform Xh by it"""
+        part = copy.copy(step)
+        for attr in ('columns', 'continuous', 'obj_cats', 'num_cats'):
+            if hasattr(step, attr):
+                setattr(part, attr, [c for c in getattr(step, attr) if c in Xh.columns])
+        return part.fit_transform(Xh)
+
+    @staticmethod
+    def _quantile_edges(prof, at, columns, fill, final, max_bins, N):
+        """{c: (edges_[c], new_columns entry)} of MultiKBinsDiscretizer.fit for profiled columns: np.quantile's 'linear' rule
+        (virtual index (n - 1) q, its two neighbours, numpy's lerp) on order statistics read from the device.  The
+        imputation and scale maps are monotone, so ranks are taken on raw values and the selected values are mapped here."""
+        cols = list(columns)
+        bins, ranks, gammas = {}, np.full((len(at), 2 * (max_bins + 1)), -1, dtype=np.int64), {}
+        for c in cols:
+            j = at[c]
+            d = prof.distinct(j)
+            if d is None:
+                nunique = max_bins + 1                  # more distinct raw values than the cap >= max_bins + 1
+            else:
+                values = d[0].astype(np.float64)
+                if prof.nan_count[j]:
+                    values = np.concatenate([values, [np.nan]])
+                nunique = pd.Series(final(c, values)).nunique()
+            bins[c] = int(max(2, min(max_bins, nunique)))
+            q = np.linspace(0, 1, bins[c] + 1)
+            virtual = (N - 1) * q
+            prev = np.floor(virtual)
+            nxt = prev + 1
+            above = virtual >= N - 1
+            prev[above], nxt[above] = N - 1, N - 1
+            gammas[c] = virtual - np.floor(virtual)
+            ranks[j, :len(q)] = prev.astype(np.int64)
+            ranks[j, len(q):2 * len(q)] = nxt.astype(np.int64)
+        fills = np.array([fill.get(c, np.nan) for c in sorted(at, key=at.get)], dtype=np.float64)
+        got = prof.order_stats(ranks, fills)
+        out = {}
+        for c in cols:
+            j, n = at[c], bins[c] + 1
+            unfilled = c not in fill and prof.nan_count[j] > 0      # np.quantile of a column holding NaN: NaN
+            a, b, t = final(c, got[j, :n]), final(c, got[j, n:2 * n]), gammas[c]
+            with np.errstate(all='ignore'):
+                diff = b - a
+                quant = a + diff * t
+                quant = np.where(t >= 0.5, b - diff * (1 - t), quant)
+            if unfilled:
+                quant = np.full(n, np.nan)
+            edges = np.unique(quant)
+            out[c] = edges[1:-1], (c, c + '_discrete', len(edges) - 1 if len(edges) > 1 else 1)
+        return out
 
     def source_columns(self):
         """{raw column label as given to fit: [the transformed columns computed from it]} — which model inputs change when

@@ -2061,6 +2061,168 @@ def prep_transform(N, cols, kind, out=None):
 
 
 # ------------------------------------------------------------------------------------------------
+# the preprocessor's fit: the profile of raw numeric columns (csrc/prep_fit.hip; models/preprocessor.py
+# DefaultPreprocessor.fit_feed)
+# ------------------------------------------------------------------------------------------------
+PROFILE_MAX_RANKS, PROFILE_TILE = _lib.DT_PROFILE_MAX_RANKS, _lib.DT_PROFILE_TILE
+_PROFILE_NAN = {'float32': 0xFFC00000, 'float64': 0xFFF8000000000000}
+
+
+def profile_keys(values):
+    """numpy values of one PREP_DTYPES dtype -> their ordered uint64 keys (include/dt_hip.h, dt_column_profile): integer order
+    = numeric order, -0.0 just below +0.0, every NaN the one largest key"""
+    a = np.ascontiguousarray(values)
+    name, w = a.dtype.name, a.dtype.itemsize
+    if name not in PREP_DTYPES:
+        raise ValueError(f'profile_keys: a dtype of {sorted(PREP_DTYPES)}, got {a.dtype}')
+    if name == 'bool':
+        return a.astype(np.uint64)
+    bits = a.view(f'u{w}')
+    top = bits.dtype.type(1 << (8 * w - 1))
+    if a.dtype.kind == 'u':
+        return bits.astype(np.uint64)
+    if a.dtype.kind == 'i':
+        return (bits ^ top).astype(np.uint64)
+    k = np.where(bits & top, ~bits, bits | top).astype(np.uint64)
+    k[np.isnan(a)] = _PROFILE_NAN[name]
+    return k
+
+
+def profile_values(keys, dtype):
+    """ordered uint64 keys -> the values of numpy dtype `dtype`, exactly (the NaN key gives a NaN)"""
+    dtype = np.dtype(dtype)
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    if dtype.name == 'bool':
+        return k.astype(np.bool_)
+    u = np.dtype(f'u{dtype.itemsize}')
+    bits = k.astype(u)
+    top = u.type(1 << (8 * dtype.itemsize - 1))
+    if dtype.kind == 'u':
+        return bits
+    if dtype.kind == 'i':
+        return (bits ^ top).view(dtype)
+    return np.where(bits & top, bits ^ top, ~bits).view(dtype)
+
+
+class ColumnProfile:
+    """What `column_profile` left on the device, and its small results on the host (read on first use: one synchronising copy).
+      n_distinct, nan_count, nunique  int64 [C]   distinct non-NaN keys, NaNs, pandas' nunique
+      sums                            float64 [C] the fixed-order sum of the non-NaN values
+      passes                          [C]         how many digit passes the sort ran for the column
+      minimum(c), maximum(c)          the extreme non-NaN value in the column's dtype (None without one)
+      distinct(c)                     (values ascending by key in the column's dtype, int64 counts), None above the cap
+      sorted_keys(c)                  the device int64 tensor [N] holding the column's sorted ordered keys (uint64 bits)
+      order_stats(ranks, fills)       float64 [C, len] values at ranks of "non-NaN ascending, NaN-count fills at their rank" """
+
+    def __init__(self, names, N, cap, dtypes_dev, stats, dkeys, dcounts, ws):
+        self.dtypes, self.N, self.cap = list(names), N, cap
+        self._dtypes_dev, self._stats, self._dkeys, self._dcounts, self._ws = dtypes_dev, stats, dkeys, dcounts, ws
+        self._host = None
+
+    def host(self):
+        if self._host is None:
+            self._host = self._stats.cpu().numpy()
+        return self._host
+
+    n_distinct = property(lambda self: self.host()[:, 0])
+    nan_count = property(lambda self: self.host()[:, 1])
+    nunique = property(lambda self: self.host()[:, 2])
+    sums = property(lambda self: self.host()[:, 5].copy().view(np.float64))
+    passes = property(lambda self: [bin(int(m)).count('1') for m in self.host()[:, 6]])
+
+    def _extreme(self, c, word):
+        if self.host()[c, 0] == 0:
+            return None
+        return profile_values(self.host()[c, word:word + 1].view(np.uint64), self.dtypes[c])[0]
+
+    def minimum(self, c):
+        return self._extreme(c, 3)
+
+    def maximum(self, c):
+        return self._extreme(c, 4)
+
+    def distinct(self, c):
+        n = int(self.host()[c, 0])
+        if n > self.cap:
+            return None
+        keys = self._dkeys[c, :n].cpu().numpy().view(np.uint64)
+        return profile_values(keys, self.dtypes[c]), self._dcounts[c, :n].cpu().numpy()
+
+    def sorted_keys(self, c):
+        C, N = len(self.dtypes), self.N
+        half = (8 * N * C + 255) // 256 * 256
+        odd = bin(int(self.host()[c, 6])).count('1') & 1
+        return self._ws[odd * half:odd * half + 8 * N * C].view(torch.int64)[c * N:(c + 1) * N]
+
+    def order_stats(self, ranks, fills):
+        C = len(self.dtypes)
+        ranks = np.asarray(ranks, dtype=np.int64).reshape(C, -1)
+        R = ranks.shape[1]
+        if R > PROFILE_MAX_RANKS:
+            raise ValueError(f'order_stats: {R} ranks per column, at most {PROFILE_MAX_RANKS}')
+        if self.N == 0:
+            raise ValueError('order_stats: the columns are empty')
+        padded = np.full((C, PROFILE_MAX_RANKS), -1, dtype=np.int64)
+        padded[:, :R] = ranks
+        device = self._stats.device
+        ranks_d = torch.from_numpy(padded).to(device)
+        fills_d = torch.from_numpy(np.broadcast_to(np.asarray(fills, dtype=np.float64), (C,)).copy()).to(device)
+        out = torch.empty((C, PROFILE_MAX_RANKS), dtype=torch.float64, device=device)
+        codes = (ctypes.c_int32 * C)(*[PREP_DTYPES[d] for d in self.dtypes])
+        with torch.cuda.device(device):
+            check(lib().dt_column_order_stats(ptr(self._ws), ptr(self._dtypes_dev), ctypes.cast(codes, ctypes.c_void_p), self.N, C,
+                                              ptr(self._stats), ptr(ranks_d), ptr(fills_d), ptr(out), stream_ptr()),
+                  'dt_column_order_stats')
+        return out.cpu().numpy()[:, :R]
+
+
+def column_profile(columns, dtypes=None, cap=0):
+    """The profile of C raw device columns of one length N in a fixed number of launches (dt_column_profile): a segmented 64-bit
+    radix sort and a run-length pass -> ColumnProfile.  columns: 1-D contiguous GPU tensors in their own dtype (bool, int8..64,
+    uint8, float32, float64), or, with `dtypes` (names of PREP_DTYPES), the columns' bytes as `prep_source` uploads them.
+    cap: columns with at most `cap` distinct non-NaN values also get those values and their counts."""
+    who = 'column_profile'
+    columns = list(columns)
+    C, cap = len(columns), int(cap)
+    if C < 1 or cap < 0:
+        raise ValueError(f'{who}: {C} columns, cap={cap}')
+    require_cuda(*columns)
+    device = columns[0].device
+    names, srcs = [], []
+    for j, t in enumerate(columns):
+        name = str(t.dtype).replace('torch.', '') if dtypes is None else dtypes[j]
+        if name not in PREP_DTYPES or (dtypes is not None and t.dtype != torch.uint8):
+            raise ValueError(f'{who}: column {j}: dtype {name!r} ({t.dtype}); one of {sorted(PREP_DTYPES)}')
+        if t.dim() != 1 or not t.is_contiguous() or t.device != device:
+            raise ValueError(f'{who}: column {j} must be a contiguous 1-D tensor on {device}')
+        names.append(name)
+        srcs.append(t)
+    widths = [np.dtype(n).itemsize if dtypes is not None else 1 for n in names]
+    lengths = {t.numel() // w if dtypes is not None else t.numel() for t, w in zip(srcs, widths)}
+    if len(lengths) != 1 or any(t.numel() % w for t, w in zip(srcs, widths)):
+        raise ValueError(f'{who}: the columns must have one length, got {sorted(lengths)}')
+    N = lengths.pop()
+    table = (ctypes.c_void_p * C)(*[t.data_ptr() for t in srcs])
+    codes = (ctypes.c_int32 * C)(*[PREP_DTYPES[n] for n in names])
+    need = lib().dt_column_profile_workspace_bytes(N, C, cap)
+    if need < 0:
+        check(int(need), 'dt_column_profile_workspace_bytes')
+    srcs_d = torch.from_numpy(np.frombuffer(table, dtype=np.int64).copy()).to(device)
+    dtypes_d = torch.from_numpy(np.frombuffer(codes, dtype=np.int32).copy()).to(device)
+    stats = torch.zeros((C, _lib.DT_PROFILE_STAT_WORDS), dtype=torch.int64, device=device)
+    dkeys = torch.empty((C, cap), dtype=torch.int64, device=device)
+    dcounts = torch.empty((C, cap), dtype=torch.int64, device=device)
+    ws = torch.empty(max(int(need), 16), dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        check(lib().dt_column_profile(ptr(srcs_d), ptr(dtypes_d), ctypes.cast(table, ctypes.c_void_p),
+                                      ctypes.cast(codes, ctypes.c_void_p), N, C, cap, ptr(stats), ptr(dkeys) if cap else None,
+                                      ptr(dcounts) if cap else None, ptr(ws), stream_ptr()), 'dt_column_profile')
+    prof = ColumnProfile(names, N, cap, dtypes_d, stats, dkeys, dcounts, ws)
+    prof._keep = (srcs, srcs_d)
+    return prof
+
+
+# ------------------------------------------------------------------------------------------------
 # histogram gradient-boosted trees: the GBM leaf features (csrc/gbdt.hip; models/preprocessor.py GbmLeavesEncoder)
 # ------------------------------------------------------------------------------------------------
 GBDT_OBJECTIVES = {'binary': _lib.DT_GBDT_BINARY, 'regression': _lib.DT_GBDT_REGRESSION}

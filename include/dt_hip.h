@@ -1730,6 +1730,47 @@ typedef struct dt_prep_col {
 int dt_prep_transform(int64_t N, const dt_prep_col* cols, const dt_prep_col* cols_host, int C, int out_kind, void* out,
                       void* stream);
 
+/* The preprocessor's fit on the device: the profile of every raw numeric column of a frame (csrc/prep_fit.hip;
+ * ops.column_profile / ops.column_order_stats, models/preprocessor.py DefaultPreprocessor.fit_feed; replaces the pandas
+ * `nunique`, `pd.unique`, `mean`, `min` / `max` and `np.quantile` sorts of deeptables/models/preprocessor.py:165-204 on numeric
+ * columns).  C columns of one length N, each one contiguous DEVICE array in its own dtype (DT_PREP_* codes), go through every
+ * launch together (the column is grid dimension y).
+ * Ordered key of an element: an unsigned 64-bit word whose integer order is the column's numeric order — bool / uintW: the
+ *   value; intW: the W-byte word with its sign bit flipped, zero-extended; float32 / float64: the IEEE bits, all flipped when
+ *   negative, else the sign bit set, zero-extended.  -0.0 is the key just below +0.0; every NaN is the key 0xFFC00000 /
+ *   0xFFF8000000000000, above +inf.  A bijection on the non-NaN values, so the raw value and DT_PREP_LOOKUP's key follow from it.
+ * dt_column_profile: a stable LSD radix sort (8-bit digits, keys only) of every column, then a run-length pass.  All digit
+ *   histograms are taken while the keys are written; a digit place whose histogram has one non-empty bin is skipped for that
+ *   column (bool / int8: at most 1 pass, float32: at most 4, int64 ids below 65 536: 2), the launch count is fixed: 30 with
+ *   cap > 0, 28 with cap = 0.  No block waits for another block.  Results:
+ *   stats  int64 [C][DT_PROFILE_STAT_WORDS]: 0 distinct non-NaN keys, 1 NaN count, 2 nunique as pandas counts it (-0.0 and +0.0
+ *     one value, NaN excluded), 3 / 4 the smallest / largest non-NaN ordered key (0 when there is none), 5 the bits of the
+ *     float64 sum of the non-NaN values, each widened to float64, added in one fixed order (the same bits on every run),
+ *     6 the mask of digit places the sort ran, 7 zero.
+ *   distinct_keys uint64 [C][cap], distinct_counts int64 [C][cap]: for a column with at most cap distinct non-NaN keys, those keys
+ *     ascending and how often each occurs; rows of other columns and entries past the distinct count are not written.
+ *   The workspace (dt_column_profile_workspace_bytes(N, C, cap) bytes, 16-byte aligned) then holds the sorted keys: column c at
+ *     uint64 offset c N of its first half-pair [C][N] when stats word 6 has an even number of bits, else of the second, which
+ *     starts 8 N C bytes rounded up to 256 behind the first.
+ * dt_column_order_stats: behind dt_column_profile on the same workspace and stats.  ranks int64 [C][DT_PROFILE_MAX_RANKS] are
+ *   zero-based ranks into the column's virtual sorted sequence "the non-NaN values ascending, with NaN-count copies of fills[c]
+ *   (float64 [C]) inserted at its rank" — what np.quantile sorts after mean imputation; out float64 [C][DT_PROFILE_MAX_RANKS]
+ *   gets the values there, NaN for a rank outside [0, N).  One launch.
+ * srcs / dtypes are DEVICE arrays (C pointers / C codes) the kernels read, srcs_host / dtypes_host the HOST copies the entry
+ * validates.  Nothing synchronises with the host or allocates.  N outside [0, 2^31), C < 1, cap < 0, a null or misaligned
+ * pointer, an unknown dtype code: DT_ERR_INVALID_ARG; C > DT_PROFILE_MAX_COLS: DT_ERR_UNSUPPORTED; both before any launch.
+ * dt_column_profile with N == 0 is DT_OK without a launch (nothing is written).                                           */
+#define DT_PROFILE_TILE 4096
+#define DT_PROFILE_STAT_WORDS 8
+#define DT_PROFILE_MAX_RANKS 32
+#define DT_PROFILE_MAX_COLS 1024
+int64_t dt_column_profile_workspace_bytes(int64_t N, int C, int cap);
+int dt_column_profile(const void* const* srcs, const int32_t* dtypes, const void* const* srcs_host, const int32_t* dtypes_host,
+                      int64_t N, int C, int cap, int64_t* stats, uint64_t* distinct_keys, int64_t* distinct_counts, void* ws,
+                      void* stream);
+int dt_column_order_stats(const void* ws, const int32_t* dtypes, const int32_t* dtypes_host, int64_t N, int C,
+                          const int64_t* stats, const int64_t* ranks, const double* fills, double* out, void* stream);
+
 /* Histogram gradient-boosted trees for the GBM leaf features (csrc/gbdt.hip; ops.gbdt_gradients / gbdt_grow_tree /
  * gbdt_predict_leaves, models/preprocessor.py GbmLeavesEncoder; replaces deeptables/models/preprocessor.py:431-452, hypernets'
  * LgbmLeavesEncoder).  LightGBM's algorithm in outline, not compared with a LightGBM run.  Binary log loss, L2 regression and
