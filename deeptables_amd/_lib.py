@@ -408,6 +408,10 @@ SIGNATURES = {
     'dt_gbdt_mc_leaf_update': (_c_int, [_ptr, _ptr, _ptr, _ptr]),                         # m, scores, row_leaf, stream
     # packed, N, P, T, L, node_feat, node_bin, node_child, n_nodes, out, stream
     'dt_gbdt_predict_leaves': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # the in-feed variants (csrc/gbdt_feed.hip): ids, F, blocks, widths, n_blocks, N, edges, n_edges, bins, packed, stream
+    'dt_gbdt_bin_feed': (_c_int, [_ptr, _c_int, _ptr, _ptr, _c_int, _c_i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # packed, N, P, T, L, node_feat, node_bin, node_child, n_nodes, ids, F, mode, out, stream
+    'dt_gbdt_leaves_feed': (_c_int, [_ptr, _c_i64, _c_int, _c_int, _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
 }
 
 DT_IDX_F32, DT_IDX_I32 = 0, 1
@@ -461,6 +465,9 @@ DT_GBDT_BINS, DT_GBDT_HIST_GROUP, DT_GBDT_HIST_ROWS, DT_GBDT_PART_CHUNK = 256, 8
 DT_GBDT_MAX_ROWS, DT_GBDT_MAX_FEATURES, DT_GBDT_MAX_LEAVES = 2147483647, 4096, 1024
 DT_GBDT_STATE_WORDS, DT_GBDT_LEAF_WORDS, DT_GBDT_WS_BYTES = 16, 12, 184
 DT_GBDT_MAX_CLASSES, DT_GBDT_MC_BYTES = 64, 272
+DT_GBDT_PREDICT_ROWS, DT_GBDT_PREDICT_LDS_BYTES = 64, 49152
+DT_GBDT_FEED_ROWS, DT_GBDT_FEED_GROUP, DT_GBDT_FEED_GRID, DT_GBDT_FEED_EDGES, DT_GBDT_FEED_MAX_BLOCKS = 256, 64, 256, 255, 8
+DT_GBDT_FEED_EMBEDDING, DT_GBDT_FEED_DENSE = 0, 1
 # keras.activations names the CIN / AFM kernels fuse (include/dt_hip.h DT_ACT_*)
 ACT_CODES = {None: 0, 'linear': 0, 'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'selu': 5, 'softplus': 6, 'softsign': 7,
              'exponential': 8}

@@ -223,6 +223,56 @@ def gbm_bin_edges(values, max_bin):
     return np.unique(np.quantile(v[np.isfinite(v)], np.arange(1, max_bin) / max_bin))
 
 
+class FeedRefusal(ValueError):
+    """a condition under which a device path hands the call to the host path"""
+
+
+def gbm_feed_edges(blocks, names, max_bin):
+    """`gbm_bin_edges` of every column of the device blocks ([N, width] int32 / float32 tensors; names: one per column, for
+    messages) without bringing a column to the host -> a list of float64 arrays.  `ops.column_profile` sorts a transposed copy
+    of the blocks (the profile wants contiguous columns) with cap = max_bin + 1: one more than the rule needs, so that a column
+    whose max_bin + 1 distinct keys hold both -0.0 and +0.0 — one value to np.unique — still gets its midpoints.  Columns with
+    more values get np.quantile's 'linear' rule on order statistics (`ColumnProfile.order_stats`, 32 ranks per launch; the ranks
+    are those of the non-NaN values: NaN fills sort first, so every rank moves up by the NaN count).  The host does float64
+    arithmetic on at most 2 (max_bin - 1) values per column.  An infinite value raises and names the column: np.quantile over
+    the finite values alone has no counterpart in the profile."""
+    from .. import ops
+    columns = [col for b in blocks for col in b.t().contiguous()]
+    prof = ops.column_profile(columns, cap=max_bin + 1)
+    prof.host()
+    C, edges, wide = len(columns), [None] * len(columns), []
+    for j, name in enumerate(names):
+        lo, hi = prof.minimum(j), prof.maximum(j)
+        if lo is not None and not (np.isfinite(np.float64(lo)) and np.isfinite(np.float64(hi))):
+            raise FeedRefusal(f'apply_gbm_features: column {name!r} holds an infinite value; the in-feed fit takes finite values '
+                              f'and NaN (fit_transform bins the finite ones)')
+        d = prof.distinct(j)
+        u = None if d is None else np.unique(d[0].astype(np.float64))
+        if u is not None and len(u) <= max_bin:
+            mid = (u[:-1] + u[1:]) / 2
+            edges[j] = np.where(mid > u[:-1], mid, u[1:])
+        else:
+            wide.append(j)
+    if wide:
+        q = np.arange(1, max_bin) / max_bin
+        ranks, gamma = np.full((C, 2 * len(q)), -1, dtype=np.int64), {}
+        for j in wide:
+            nans = int(prof.nan_count[j])
+            n = prof.N - nans
+            virtual = (n - 1) * q
+            prev = np.floor(virtual)
+            gamma[j] = virtual - prev
+            ranks[j, :len(q)] = prev.astype(np.int64) + nans
+            ranks[j, len(q):] = np.minimum(prev.astype(np.int64) + 1, n - 1) + nans
+        R = ops.PROFILE_MAX_RANKS
+        got = np.concatenate([prof.order_stats(ranks[:, s:s + R], np.nan) for s in range(0, ranks.shape[1], R)], axis=1)
+        for j in wide:
+            a, b, t = got[j, :len(q)], got[j, len(q):], gamma[j]
+            diff = b - a
+            edges[j] = np.unique(np.where(t >= 0.5, b - diff * (1 - t), a + diff * t))
+    return edges
+
+
 class GbmLeavesEncoder:
     """Stand-in for hypernets' LgbmLeavesEncoder (preprocessor.py:431-438): a gradient-boosted tree ensemble is fitted on the
     prepared categorical and continuous columns and every tree's leaf index becomes a new column `gbm_leaf_<t>`.  The trees are
@@ -297,28 +347,45 @@ class GbmLeavesEncoder:
         if not self.columns or N < 1:
             raise ValueError('apply_gbm_features: no categorical or continuous column to fit the trees on')
         K = None if self.num_classes is None else int(self.num_classes)
-        objective = 'binary' if self.task == consts.TASK_BINARY else 'regression'
         yv = np.asarray(y, dtype=np.float64).reshape(-1)
-        if K is not None:               # one score row per class from the class priors; a label outside [0, K) counts nowhere
-            prior = np.array([(yv == c).mean() for c in range(K)])
-            init = np.log(np.maximum(prior, 1e-15)).astype(np.float32)
-        elif objective == 'binary':
-            pbar = min(max(float(yv.mean()), 1e-15), 1 - 1e-15)
-            init = np.float32(np.log(pbar / (1 - pbar)))
-        else:
-            init = np.float32(yv.mean())
+        init = self._init_score(yv)
         self.edges_ = [gbm_bin_edges(X[c].values, int(p['max_bin'])) for c in self.columns]
         bins = ops.gbdt_bin(self._upload(X, device), self.edges_)
         ws = ops.GbdtWorkspace(bins, L, num_classes=K)
         yd = torch.from_numpy(yv.astype(np.float32)).to(device)
+        leaves = torch.empty((T * (K or 1), N), dtype=torch.int32, device=device)
+        self._boost(bins, ws, yd, init, leaves)
+        return self._append(X, leaves.t().contiguous().cpu().numpy())
+
+    def _init_score(self, yv):
+        """the score every row starts from: the log odds, the mean, or per class the log prior (a label outside [0, K)
+        counts nowhere)"""
+        if self.num_classes is not None:
+            prior = np.array([(yv == c).mean() for c in range(int(self.num_classes))])
+            return np.log(np.maximum(prior, 1e-15)).astype(np.float32)
+        if self.task == consts.TASK_BINARY:
+            pbar = min(max(float(yv.mean()), 1e-15), 1 - 1e-15)
+            return np.float32(np.log(pbar / (1 - pbar)))
+        return np.float32(yv.mean())
+
+    def _boost(self, bins, ws, yd, init, leaves=None):
+        """the boosting loop on the bin matrix and its workspace; the fitted state becomes numpy.  leaves: int32 [T (K), N] that
+        receives every tree's leaf id per row (the host fit); None: one scratch row per class is reused (the in-feed fit walks
+        the finished trees instead)"""
+        import torch
+        from .. import ops
+        p, device, N = self.params, bins.device, bins.shape[1]
+        T, L = int(p['n_estimators']), int(p['num_leaves'])
+        objective = 'binary' if self.task == consts.TASK_BINARY else 'regression'
         i32 = dict(dtype=torch.int32, device=device)
-        if K is not None:
-            return self._fit_softmax(X, bins, ws, yd, init, device)
+        if self.num_classes is not None:
+            return self._boost_softmax(bins, ws, yd, init, leaves)
+        scratch = torch.empty(N, **i32) if leaves is None else None
+        kernel_timings = self.timings if leaves is not None else None       # the in-feed fit reports whole roles (fit_feed)
         scores = torch.full((N,), float(init), dtype=torch.float32, device=device)
         trees = {'node_feat': torch.empty((T, L - 1), **i32), 'node_bin': torch.empty((T, L - 1), **i32),
                  'node_child': torch.empty((T, L - 1, 2), **i32), 'n_nodes': torch.empty(T, **i32),
                  'leaf_value': torch.empty((T, L), dtype=torch.float32, device=device)}
-        leaves = torch.empty((T, N), **i32)
         sexp = torch.empty((T, 2), **i32)
         max_bits = torch.zeros(T, dtype=torch.int64, device=device)
         grads = (torch.empty(N, **i32), torch.empty(N, **i32))
@@ -326,42 +393,43 @@ class GbmLeavesEncoder:
         for t in range(T):              # launches only: the scale and the choice of leaves stay on the device
             qg, qh, s = ops.gbdt_gradients(scores, yd, objective, max_slot=max_bits[t:t + 1], out=grads + (sexp[t],))
             out = {k: (v[t:t + 1] if k == 'n_nodes' else v[t]) for k, v in trees.items()}
-            out['row_leaf'] = leaves[t]
-            ops.gbdt_grow_tree(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=self.timings)
+            out['row_leaf'] = scratch if leaves is None else leaves[t]
+            ops.gbdt_grow_tree(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=kernel_timings)
+        self._keep_trees(trees, sexp, init)
+
+    def _keep_trees(self, trees, sexp, init):
+        """the fitted state, numpy only (one read-back per tree array)"""
+        t0 = self._role(None, 0.0, sexp.device)
         for k, v in trees.items():
             setattr(self, k + '_', v.cpu().numpy())
         self.scale_exponents_ = sexp.cpu().numpy()
         self.init_score_ = init
-        self.new_columns = [f'gbm_leaf_{t}' for t in range(T)]
-        return self._append(X, leaves.t().contiguous().cpu().numpy())
+        self.new_columns = [f'gbm_leaf_{j}' for j in range(len(self.n_nodes_))]
+        self._role('state_readback', t0, sexp.device)
 
-    def _fit_softmax(self, X, bins, ws, yd, init, device):
+    def _boost_softmax(self, bins, ws, yd, init, leaves):
         """the boosting loop of a multiclass task: per round one gradient launch over the class-major scores [K, N] and the
         launches of one tree, which grow the K class trees in lock-step into rows t K .. t K + K - 1 of the tree arrays"""
         import torch
         from .. import ops
-        p, K, N = self.params, int(self.num_classes), len(X)
+        p, K, N, device = self.params, int(self.num_classes), bins.shape[1], bins.device
         T, L = int(p['n_estimators']), int(p['num_leaves'])
         i32 = dict(dtype=torch.int32, device=device)
         scores = torch.from_numpy(init).to(device)[:, None].expand(K, N).contiguous()
         trees = {'node_feat': torch.empty((T * K, L - 1), **i32), 'node_bin': torch.empty((T * K, L - 1), **i32),
                  'node_child': torch.empty((T * K, L - 1, 2), **i32), 'n_nodes': torch.empty(T * K, **i32),
                  'leaf_value': torch.empty((T * K, L), dtype=torch.float32, device=device)}
-        leaves = torch.empty((T * K, N), **i32)
+        scratch = torch.empty((K, N), **i32) if leaves is None else None
+        kernel_timings = self.timings if leaves is not None else None
         sexp = torch.empty((T, 2), **i32)
         grads = (torch.empty((K, N), **i32), torch.empty((K, N), **i32))
         grow = {k: p[k] for k in ('num_leaves', 'min_child_samples', 'reg_lambda', 'min_split_gain', 'learning_rate')}
         for t in range(T):
             qg, qh, s = ops.gbdt_gradients_softmax(scores, yd, K, out=grads + (sexp[t],))
             out = {k: v[t * K:(t + 1) * K] for k, v in trees.items()}
-            out['row_leaf'] = leaves[t * K:(t + 1) * K]
-            ops.gbdt_grow_trees(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=self.timings)
-        for k, v in trees.items():
-            setattr(self, k + '_', v.cpu().numpy())
-        self.scale_exponents_ = sexp.cpu().numpy()
-        self.init_score_ = init
-        self.new_columns = [f'gbm_leaf_{j}' for j in range(T * K)]
-        return self._append(X, leaves.t().contiguous().cpu().numpy())
+            out['row_leaf'] = scratch if leaves is None else leaves[t * K:(t + 1) * K]
+            ops.gbdt_grow_trees(bins, qg, qh, dict(grow, sexp=s), workspace=ws, scores=scores, out=out, timings=kernel_timings)
+        self._keep_trees(trees, sexp, init)
 
     def fit(self, X, y):
         self.fit_transform(X, y)
@@ -375,9 +443,105 @@ class GbmLeavesEncoder:
         device = self._device()
         if len(X) == 0:
             return self._append(X, np.zeros((0, len(self.new_columns)), dtype=np.int32))
-        packed = ops.gbdt_pack(ops.gbdt_bin(self._upload(X, device), self.edges_))
-        trees = {k: torch.from_numpy(getattr(self, k + '_')).to(device) for k in ('node_feat', 'node_bin', 'node_child', 'n_nodes')}
-        return self._append(X, ops.gbdt_predict_leaves(packed, trees, int(self.params['num_leaves'])).cpu().numpy())
+        cols = self._upload(X, device)
+        if getattr(self, 'feed_fitted_', False):        # the edges come from a feed's float32 values: bin what a feed would hold
+            cols = [c.to(torch.float32) if name in self.cont_vars else c for name, c in zip(self.columns, cols)]
+        packed = ops.gbdt_pack(ops.gbdt_bin(cols, self.edges_))
+        return self._append(X, ops.gbdt_predict_leaves(packed, self._device_trees(device), int(self.params['num_leaves'])).cpu().numpy())
+
+    def _device_trees(self, device):
+        import torch
+        return {k: torch.from_numpy(getattr(self, k + '_')).to(device) for k in ('node_feat', 'node_bin', 'node_child', 'n_nodes')}
+
+    # -- inside a resident feed: the features are the columns of the id block and of the continuous blocks, where they lie ----
+    def _feed_features(self, blocks, kinds):
+        ids = next((b for b, k in zip(blocks, kinds) if k == 'cat'), None)
+        conts = [b for b, k in zip(blocks, kinds) if k == 'cont']
+        if (0 if ids is None else ids.shape[1]) != len(self.cat_vars) or sum(b.shape[1] for b in conts) != len(self.cont_vars):
+            raise ValueError(f'GbmLeavesEncoder: the feed holds {0 if ids is None else ids.shape[1]} id and '
+                             f'{sum(b.shape[1] for b in conts)} continuous columns, the encoder {len(self.cat_vars)} and '
+                             f'{len(self.cont_vars)}')
+        return ids, conts
+
+    def feed_bytes(self, n_rows, feature_type):
+        """device bytes the in-feed fit and transform hold besides the feed's blocks: both bin matrices, the widened block,
+        and (fit) the profile's transposed columns with the sort's two key buffers"""
+        P, T = len(self.columns), int(self.params['n_estimators']) * int(self.num_classes or 1)
+        wide = len(self.cat_vars) + T if feature_type == consts.GBM_FEATURE_TYPE_EMB else T
+        return int(n_rows) * (2 * ((P + 7) // 8 * 8) + 4 * wide), int(n_rows) * 20 * P
+
+    def _widen(self, blocks, kinds, packed, feature_type, device):
+        """the leaf launch: the id block grows by the leaf columns, or one float block of leaf ids joins the end"""
+        from .. import ops
+        blocks, kinds = list(blocks), list(kinds)
+        L, trees = int(self.params['num_leaves']), self._device_trees(device)
+        if feature_type == consts.GBM_FEATURE_TYPE_EMB:
+            at = kinds.index('cat') if 'cat' in kinds else None
+            wide = ops.gbdt_leaves_feed(packed, trees, L, 'embedding', ids=None if at is None else blocks[at])
+            if at is None:
+                blocks.insert(0, wide)
+                kinds.insert(0, 'cat')
+            else:
+                blocks[at] = wide
+        else:
+            blocks.append(ops.gbdt_leaves_feed(packed, trees, L, 'dense'))
+            kinds.append('cont')
+        return blocks, kinds
+
+    def _role(self, role, t0, device):
+        """with `timings`: drain the device and add the seconds since t0 to `role` (None: only start the clock)"""
+        import torch
+        if getattr(self, 'timings', None) is not None:
+            torch.cuda.synchronize(device)
+            if role is not None:
+                self.timings[role] = self.timings.get(role, 0.0) + time.perf_counter() - t0
+        return time.perf_counter()
+
+    def fit_feed(self, blocks, kinds, y, feature_type=consts.GBM_FEATURE_TYPE_EMB):
+        """`fit_transform` on the blocks of a resident feed (`DefaultPreprocessor.feed_blocks`): the edges from a device profile
+        of the blocks' columns (`gbm_feed_edges`), one binning launch over the blocks (ops.gbdt_bin_feed), the boosting loop,
+        one leaf launch (ops.gbdt_leaves_feed).  y: the encoded targets (class numbers), uploaded once; nothing else of size N
+        crosses the bus and only the fitted trees come back.  -> the widened (blocks, kinds)"""
+        import torch
+        from .. import ops
+        p = self.params
+        ids, conts = self._feed_features(blocks, kinds)
+        if not self.columns or blocks[0].shape[0] < 1:
+            raise ValueError('apply_gbm_features: no categorical or continuous column to fit the trees on')
+        device = blocks[0].device
+        K = None if self.num_classes is None else int(self.num_classes)
+        yv = np.asarray(y, dtype=np.float64).reshape(-1)
+        t0 = self._role(None, 0.0, device)
+        self.edges_ = gbm_feed_edges(([ids] if ids is not None else []) + conts, self.columns, int(p['max_bin']))
+        t0 = self._role('profile_edges', t0, device)
+        bins, packed = ops.gbdt_bin_feed(ids, conts, self.edges_)
+        t0 = self._role('bin_launch', t0, device)
+        ws = ops.GbdtWorkspace(bins, int(p['num_leaves']), num_classes=K, packed=packed)
+        self._boost(bins, ws, torch.from_numpy(yv.astype(np.float32)).to(device), self._init_score(yv))
+        self.feed_fitted_ = True
+        t0 = self._role('boosting_loop', t0, device)
+        if self.timings is not None:                            # (_keep_trees timed its read-back inside the loop's span)
+            self.timings['boosting_loop'] -= self.timings.get('state_readback', 0.0)
+        out = self._widen(blocks, kinds, packed, feature_type, device)
+        self._role('leaf_launch', t0, device)
+        return out
+
+    def transform_feed(self, blocks, kinds, feature_type=consts.GBM_FEATURE_TYPE_EMB):
+        """the blocks of a feed -> the widened (blocks, kinds): one binning launch, one leaf launch"""
+        from .. import ops
+        if self.edges_ is None or not getattr(self, 'feed_fitted_', False):
+            raise ValueError('GbmLeavesEncoder.transform_feed: the encoder was not fitted by fit_feed')
+        ids, conts = self._feed_features(blocks, kinds)
+        tabs = getattr(self, '_edge_tabs', None)                # the edge tables stay on the device between calls
+        if tabs is None or tabs[0].device != blocks[0].device:
+            tabs = self._edge_tabs = ops.gbdt_edge_table(self.edges_, blocks[0].device)
+        _bins, packed = ops.gbdt_bin_feed(ids, conts, tabs[0], tabs[1])
+        return self._widen(blocks, kinds, packed, feature_type, blocks[0].device)
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state.pop('_edge_tabs', None)                           # device tensors never travel
+        return state
 
     def raw_scores(self, leaves):
         """the ensemble's raw scores (logits / predictions) float32 [N] of rows whose leaf ids [N, T] are given; a multiclass
@@ -772,12 +936,32 @@ class DefaultPreprocessor(AbstractPreprocessor):
         self.X_transformers['discreter'] = mkbd
         return X
 
+    def _gbm_encoder(self):
+        return GbmLeavesEncoder(self.get_categorical_columns(), self.get_continuous_columns(), self.task_,
+                                num_classes=len(self.labels_) if self.task_ == consts.TASK_MULTICLASS else None,
+                                **(self.config.gbm_params or {}))
+
+    def _apply_gbm_features_feed(self, enc, blocks, kinds, y):
+        """`_apply_gbm_features` on the blocks of the training feed: the same step name, column names, order and
+        gbm_feature_type handling; the vocabulary of leaf column t is its tree's leaf count n_nodes + 1 (every leaf holds a
+        training row, so this is the host's max + 1).  The step goes where fit_transform puts it: before the var-len encoder.
+        -> the widened (blocks, kinds)"""
+        kind = self.config.gbm_feature_type
+        blocks, kinds = enc.fit_feed(blocks, kinds, y, kind)
+        self.X_transformers['gbm_features'] = enc
+        for later in ('var_len_encoder', 'last'):
+            if later in self.X_transformers:
+                self.X_transformers.move_to_end(later)
+        if kind == consts.GBM_FEATURE_TYPE_EMB:
+            self._append_categorical_cols([(name, int(n) + 1) for name, n in zip(enc.new_columns, enc.n_nodes_)])
+        else:
+            self._append_continuous_cols(enc.new_columns, consts.INPUT_PREFIX_NUM + 'gbm_leaves')
+        return blocks, kinds
+
     def _apply_gbm_features(self, X, y):
         """preprocessor.py:431-445 with GbmLeavesEncoder: the leaf columns join the categorical columns (vocabulary max + 1) or
         form one continuous block"""
-        enc = GbmLeavesEncoder(self.get_categorical_columns(), self.get_continuous_columns(), self.task_,
-                               num_classes=len(self.labels_) if self.task_ == consts.TASK_MULTICLASS else None,
-                               **(self.config.gbm_params or {}))
+        enc = self._gbm_encoder()
         X = enc.fit_transform(X, y)
         self.X_transformers['gbm_features'] = enc
         if self.config.gbm_feature_type == consts.GBM_FEATURE_TYPE_EMB:
@@ -876,6 +1060,8 @@ class DefaultPreprocessor(AbstractPreprocessor):
                 s.new_columns = [t for t in step.new_columns if t[0] in cols]
             elif isinstance(step, MultiVarLenFeatureEncoder):
                 s.features = [f for f in step.features if f[0] in cols]
+            elif isinstance(step, GbmLeavesEncoder):
+                continue                                # its columns derive from ALL columns: the feed adds them (transform_feed)
             elif not isinstance(step, PassThroughEstimator):
                 raise ValueError(f'_replay_host: unknown step {type(step).__name__}')
             X = s.transform(X)
@@ -916,7 +1102,9 @@ class DefaultPreprocessor(AbstractPreprocessor):
                 kw.update(flags=kw['flags'] | 2, min=float(ss.min_[c]), range=float(ss.range_[c]))
             return kw
 
-        names = self.get_categorical_columns()
+        gbm = steps.get('gbm_features')                 # its leaf columns are made from the finished blocks, not by the plan
+        leaf_names = set(gbm.new_columns) if gbm is not None else set()
+        names = [n for n in self.get_categorical_columns() if n not in leaf_names]
         outs = []
         for name in names:
             c = sources.get(name, name)
@@ -947,6 +1135,8 @@ class DefaultPreprocessor(AbstractPreprocessor):
                     np.result_type(*kinds).kind not in 'biu':
                 plan.whole = 'auto_encode_label is off and the categorical columns have no common integer dtype'
         for cc in self.continuous_columns or []:
+            if leaf_names and set(cc.column_names) <= leaf_names:
+                continue
             blk = []
             for c in cc.column_names:
                 if not served_dtype(self.fit_dtypes_.get(c)):
@@ -983,8 +1173,12 @@ class DefaultPreprocessor(AbstractPreprocessor):
         self._device_plan = plan
         return plan
 
-    def feed_refusal(self, device, cat_dtype=None, n_rows=None, y_words=0, max_resident_bytes=32 << 30):
-        """None when `transform_feed` can take the device path for this call, else the failing condition in words"""
+    GBM_HOST_FITTED = 'a gbm_features step'
+
+    def feed_refusal(self, device, cat_dtype=None, n_rows=None, y_words=0, max_resident_bytes=32 << 30, extra_bytes=0):
+        """None when `transform_feed` can take the device path for this call, else the failing condition in words.
+        extra_bytes: per-call device bytes besides the feed (fit_feed: the GBM fit's profile); a feed-fitted gbm_features step
+        adds its bin matrices and the widened block itself"""
         import torch
         if torch.device(device).type != 'cuda':
             return f'the target device is {torch.device(device)}, not a GPU'
@@ -995,8 +1189,9 @@ class DefaultPreprocessor(AbstractPreprocessor):
         st = self.config.distribute_strategy
         if st is not None and getattr(st, 'world_size', 1) > 1:
             return 'a multi-rank distribute_strategy is active'
-        if 'gbm_features' in self.X_transformers:
-            return 'a gbm_features step'
+        gbm = self.X_transformers.get('gbm_features')
+        if gbm is not None and not getattr(gbm, 'feed_fitted_', False):
+            return self.GBM_HOST_FITTED                 # (transform_feed spells out that it is the host-fitted kind)
         if cat_dtype is not None and cat_dtype != torch.int32:
             return f'cat_dtype is {cat_dtype}, the kernel writes int32 ids'
         plan = self.device_plan()
@@ -1005,8 +1200,11 @@ class DefaultPreprocessor(AbstractPreprocessor):
         if n_rows is not None:
             words = len(plan.cat or []) + sum(len(b) for b in plan.conts) + \
                 sum(int(c.max_elements_length) for c in self.var_len_categorical_columns or []) + int(y_words)
-            if 4 * words * int(n_rows) > max_resident_bytes:
-                return f'the feed ({4 * words * int(n_rows)} bytes) would exceed max_resident_bytes={max_resident_bytes}'
+            nbytes = 4 * words * int(n_rows) + int(extra_bytes)
+            if gbm is not None:
+                nbytes += gbm.feed_bytes(n_rows, self.config.gbm_feature_type)[0]
+            if nbytes > max_resident_bytes:
+                return f'the feed ({nbytes} bytes) would exceed max_resident_bytes={max_resident_bytes}'
         return None
 
     def feed_blocks(self, X, device, sources=None):
@@ -1089,6 +1287,8 @@ class DefaultPreprocessor(AbstractPreprocessor):
             why = self.feed_refusal(device, cat_dtype, n_rows, y_words, max_resident_bytes)
         if why is not None:
             if mode is True:
+                if why == self.GBM_HOST_FITTED:
+                    why += ' fitted on the host frame (fit_transform); only fit_feed fits the trees on the blocks of a feed'
                 raise ValueError(f'transform_feed(mode=True): {why}')
             feed = training.TableBatches(self.transform_X(X), y, self.categorical_columns, self.continuous_columns, device, task,
                                          num_classes, cat_dtype=cat_dtype,
@@ -1099,6 +1299,9 @@ class DefaultPreprocessor(AbstractPreprocessor):
         X = X.copy(deep=False) if isinstance(X, pd.DataFrame) else X
         X = self._prepare_X(X)
         blocks, kinds, host_cols = self.feed_blocks(X, torch.device(device))
+        if 'gbm_features' in self.X_transformers:
+            with _Phase('gbm', device):
+                blocks, kinds = self.X_transformers['gbm_features'].transform_feed(blocks, kinds, self.config.gbm_feature_type)
         feed = training.TableBatches.from_device(blocks, kinds, y=None if y_host is None else y_host.to(device), y_ndim=y_ndim,
                                                  weighted=sample_weight is not None)
         feed.transform_path, feed.host_columns, feed.transform_refusal = 'device', list(host_cols), None
@@ -1113,8 +1316,6 @@ class DefaultPreprocessor(AbstractPreprocessor):
         st = self.config.distribute_strategy
         if st is not None and getattr(st, 'world_size', 1) > 1:
             return 'a multi-rank distribute_strategy is active'
-        if self.config.apply_gbm_features:
-            return 'apply_gbm_features fits its trees on the transformed frame'
         return None
 
     def fit_feed(self, X, y, *, device, mode='auto', sample_weight=None, cat_dtype=None, max_resident_bytes=32 << 30):
@@ -1130,9 +1331,11 @@ class DefaultPreprocessor(AbstractPreprocessor):
         encoder).  The raw columns are uploaded once and serve the profile and the transform.  max_resident_bytes bounds the
         profile's workspace (16 bytes per numeric element, checked before anything is fitted) and the feed; the feed's size is
         known only after typing, so a feed beyond the bound is refused AFTER the device fit: 'auto' then fits again on the
-        host, mode=True raises and leaves the object device-fitted.  `apply_gbm_features` is refused as a whole — a narrower
-        reading than "the GBM step keeps its own fit": its trees are fitted on the transformed pandas frame, which this path
-        never makes (and `transform_feed` refuses a gbm_features step)."""
+        host, mode=True raises and leaves the object device-fitted.  `apply_gbm_features`: the trees are fitted on the blocks of
+        the feed (`GbmLeavesEncoder.fit_feed`: the id block and the float32 continuous blocks are exactly the columns the host
+        fit sees, the continuous ones rounded to float32) and the leaf columns are written into the widened blocks; the bound
+        also covers the two bin matrices, the widened block and the profile of the blocks' columns.  A column holding an
+        infinite value is a refusal that names it."""
         import torch
         from .. import training
         if mode not in (True, False, 'auto'):
@@ -1155,10 +1358,20 @@ class DefaultPreprocessor(AbstractPreprocessor):
             weights = sample_weight(y_enc) if callable(sample_weight) else sample_weight
             num_classes = len(self.labels_) if self.labels_ is not None and len(self.labels_) else 1
             y_host, y_ndim = training.host_targets(y_enc, self.task_, num_classes, weights)
-            why = self.feed_refusal(device, cat_dtype, len(frame), y_host.numel() // max(1, y_host.shape[0]), max_resident_bytes)
+            enc = self._gbm_encoder() if self.config.apply_gbm_features else None
+            gbm_bytes = sum(enc.feed_bytes(len(frame), self.config.gbm_feature_type)) if enc is not None else 0
+            why = self.feed_refusal(device, cat_dtype, len(frame), y_host.numel() // max(1, y_host.shape[0]), max_resident_bytes,
+                                    extra_bytes=gbm_bytes)
             if why is None:
                 Xp = self._prepare_X(frame.copy(deep=False))
                 blocks, kinds, host_cols = self.feed_blocks(Xp, torch.device(device), sources)
+                if enc is not None:
+                    try:
+                        with _Phase('fit_gbm', device):
+                            blocks, kinds = self._apply_gbm_features_feed(enc, blocks, kinds, y_enc)
+                    except FeedRefusal as e:            # (a column the in-feed fit does not take: 'auto' fits on the host)
+                        why = str(e)
+            if why is None:
                 feed = training.TableBatches.from_device(blocks, kinds, y=y_host.to(device), y_ndim=y_ndim,
                                                          weighted=weights is not None)
                 feed.transform_path, feed.host_columns, feed.transform_refusal = 'device', list(host_cols), None

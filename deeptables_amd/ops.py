@@ -2326,11 +2326,15 @@ class GbdtWorkspace:
     """The device buffers one tree needs (include/dt_hip.h dt_gbdt_ws) for a bin matrix [P, N] and `num_leaves`: the row-major
     copy of the bins, both index buffers, the histograms of every leaf, the leaf table.  Reused by every tree of a fit.
     num_classes = K: the buffers of K trees grown in lock-step (gbdt_grow_trees), every table with a leading [K] — 8 N K bytes
-    of indices and K * num_leaves * P * 256 * 20 bytes of histograms; the bins and their row-major copy stay shared."""
+    of indices and K * num_leaves * P * 256 * 20 bytes of histograms; the bins and their row-major copy stay shared.
+    packed: the row-major copy where it exists already (gbdt_bin_feed writes both); otherwise gbdt_pack makes it."""
 
-    def __init__(self, bins, num_leaves, num_classes=None):
-        self.bins, self.packed = bins, gbdt_pack(bins)
+    def __init__(self, bins, num_leaves, num_classes=None, packed=None):
         P, N = bins.shape
+        if packed is not None and (packed.dtype != torch.uint8 or tuple(packed.shape) != (N, (P + 7) // 8 * 8) or
+                                   not packed.is_contiguous() or packed.device != bins.device):
+            raise ValueError(f'GbdtWorkspace: packed must be the contiguous uint8 [{N}, {(P + 7) // 8 * 8}] copy of bins (gbdt_bin_feed)')
+        self.bins, self.packed = bins, gbdt_pack(bins) if packed is None else packed
         L, dev = int(num_leaves), bins.device
         self.N, self.P, self.L, self.K = N, P, L, None if num_classes is None else int(num_classes)
         if self.K is not None and not 2 <= self.K <= _lib.DT_GBDT_MAX_CLASSES:
@@ -2476,4 +2480,124 @@ def gbdt_predict_leaves(packed, trees, num_leaves):
     with torch.cuda.device(packed.device):
         check(lib().dt_gbdt_predict_leaves(ptr(packed), N, P8, T, L, ptr(nf), ptr(nb), ptr(nc), ptr(nn), ptr(out), stream_ptr()),
               'dt_gbdt_predict_leaves')
+    return out
+
+
+GBDT_FEED_ROWS, GBDT_FEED_GROUP, GBDT_FEED_MAX_BLOCKS = _lib.DT_GBDT_FEED_ROWS, _lib.DT_GBDT_FEED_GROUP, _lib.DT_GBDT_FEED_MAX_BLOCKS
+GBDT_FEED_MODES = {'embedding': _lib.DT_GBDT_FEED_EMBEDDING, 'dense': _lib.DT_GBDT_FEED_DENSE}
+
+
+def _feed_sources(who, ids, conts):
+    """the id block (or None) and the float blocks of a feed, checked -> (device, N, F, [widths])"""
+    conts = list(conts)
+    first = ids if ids is not None else (conts[0] if conts else None)
+    if first is None:
+        raise ValueError(f'{who}: neither an id block nor a continuous block')
+    device, N = first.device, int(first.shape[0])
+    if len(conts) > GBDT_FEED_MAX_BLOCKS:
+        raise ValueError(f'{who}: {len(conts)} continuous blocks, at most {GBDT_FEED_MAX_BLOCKS}')
+    for name, t, want in [('ids', ids, torch.int32)] + [(f'block {b}', t, torch.float32) for b, t in enumerate(conts)]:
+        if t is not None and (t.dtype != want or t.dim() != 2 or t.shape[0] != N or not t.is_contiguous() or t.device != device):
+            raise ValueError(f'{who}: {name} must be a contiguous {want} [{N}, width] tensor on {device}')
+    return device, N, 0 if ids is None else int(ids.shape[1]), [int(t.shape[1]) for t in conts]
+
+
+def gbdt_edge_table(edges, device):
+    """P ascending float64 edge lists of at most 255 edges -> (float64 [P, 255] zero padded, int32 [P] counts) on `device`: the
+    tables of gbdt_bin_feed, one small upload each"""
+    P = len(edges)
+    table, counts = np.zeros((P, _lib.DT_GBDT_FEED_EDGES), dtype=np.float64), np.zeros(P, dtype=np.int32)
+    for f, e in enumerate(edges):
+        e = np.asarray(e, dtype=np.float64).reshape(-1)
+        if len(e) > _lib.DT_GBDT_FEED_EDGES:
+            raise ValueError(f'gbdt_edge_table: feature {f} has {len(e)} edges, at most {_lib.DT_GBDT_FEED_EDGES}')
+        table[f, :len(e)], counts[f] = e, len(e)
+    return torch.from_numpy(table).to(device), torch.from_numpy(counts).to(device)
+
+
+def gbdt_bin_feed(ids, conts, edges, n_edges=None):
+    """The blocks of a feed -> (bins uint8 [P, N] feature-major, packed uint8 [N, P8] row-major zero padded), the two matrices
+    the grower reads, in ONE launch (dt_gbdt_bin_feed).  ids: the int32 id block [N, F] or None; conts: up to 8 float32 blocks
+    [N, Nd_b]; feature f is column f of `ids`, then the columns of the blocks in order, P = F + sum Nd_b.  edges: P ascending
+    float64 numpy lists of at most 255 edges, or, with n_edges, the tables of gbdt_edge_table already on the device.  bin = the
+    number of edges <= (double)x, len(edges) for a NaN.  CPU tensors: the same rule in numpy."""
+    who = 'gbdt_bin_feed'
+    device, N, F, widths = _feed_sources(who, ids, conts)
+    P = F + sum(widths)
+    if P < 1 or P > _lib.DT_GBDT_MAX_FEATURES:
+        raise ValueError(f'{who}: P={P} features outside [1, {_lib.DT_GBDT_MAX_FEATURES}]')
+    table, counts = gbdt_edge_table(edges, device) if n_edges is None else (edges, n_edges)
+    if table.dtype != torch.float64 or tuple(table.shape) != (P, _lib.DT_GBDT_FEED_EDGES) or counts.dtype != torch.int32 or \
+            tuple(counts.shape) != (P,) or not (table.is_contiguous() and counts.is_contiguous()) or \
+            table.device != device or counts.device != device:
+        raise ValueError(f'{who}: the edge tables must be float64 [{P}, {_lib.DT_GBDT_FEED_EDGES}] and int32 [{P}] on {device}')
+    P8 = (P + 7) // 8 * 8
+    bins = torch.empty((P, N), dtype=torch.uint8, device=device)
+    packed = torch.empty((N, P8), dtype=torch.uint8, device=device)
+    if device.type != 'cuda':
+        x = np.concatenate([t.numpy().astype(np.float64) for t in ([ids] if ids is not None else []) + list(conts)], axis=1)
+        host, e, n = packed.numpy(), table.numpy(), counts.numpy().clip(0, _lib.DT_GBDT_FEED_EDGES)
+        host[:] = 0
+        for f in range(P):
+            host[:, f] = np.where(np.isnan(x[:, f]), n[f], np.searchsorted(e[f, :n[f]], x[:, f], side='right'))
+        bins.numpy()[:] = host[:, :P].T
+        return bins, packed
+    if N == 0:
+        return bins, packed
+    blocks = (ctypes.c_void_p * max(1, len(widths)))(*[t.data_ptr() for t in conts])
+    wtab = (ctypes.c_int32 * max(1, len(widths)))(*widths)
+    with torch.cuda.device(device):
+        check(lib().dt_gbdt_bin_feed(ptr(ids), F, ctypes.cast(blocks, ctypes.c_void_p), ctypes.cast(wtab, ctypes.c_void_p), len(widths),
+                                     N, ptr(table), ptr(counts), ptr(bins), ptr(packed), stream_ptr()), 'dt_gbdt_bin_feed')
+    return bins, packed
+
+
+def gbdt_leaves_feed(packed, trees, num_leaves, mode, ids=None):
+    """gbdt_predict_leaves written as a block of a feed (dt_gbdt_leaves_feed).  mode 'embedding': -> int32 [N, F + T], columns
+    0 .. F-1 the id block `ids` int32 [N, F] (None: F = 0) copied in the same launch, columns F .. the leaf ids; mode 'dense': ->
+    float32 [N, T], the leaf ids as floats.  CPU tensors: the same walk in numpy."""
+    who = 'gbdt_leaves_feed'
+    if mode not in GBDT_FEED_MODES:
+        raise ValueError(f'{who}: mode must be one of {sorted(GBDT_FEED_MODES)}, got {mode!r}')
+    L = int(num_leaves)
+    nf, nb, nc, nn = (trees[k].contiguous() for k in ('node_feat', 'node_bin', 'node_child', 'n_nodes'))
+    T, device = int(nn.shape[0]), packed.device
+    if packed.dtype != torch.uint8 or packed.dim() != 2 or packed.shape[1] % 8 or not packed.is_contiguous():
+        raise ValueError(f'{who}: packed must be the contiguous uint8 [N, P8] matrix of gbdt_bin_feed / gbdt_pack')
+    if T < 1 or tuple(nf.shape) != (T, L - 1) or tuple(nb.shape) != (T, L - 1) or tuple(nc.shape) != (T, L - 1, 2) or \
+            any(t.dtype != torch.int32 or t.device != device for t in (nf, nb, nc, nn)):
+        raise ValueError(f'{who}: the tree arrays must be int32 [{T}, {L - 1}] (node_child [.., 2]) on {device}')
+    N, P8 = packed.shape
+    if mode == 'dense':
+        ids = None
+    if ids is not None and (ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != N or not ids.is_contiguous() or
+                            ids.device != device):
+        raise ValueError(f'{who}: ids must be a contiguous int32 [{N}, F] tensor on {device}')
+    F = 0 if ids is None else int(ids.shape[1])
+    out = torch.empty((N, T), dtype=torch.float32, device=device) if mode == 'dense' else \
+        torch.empty((N, F + T), dtype=torch.int32, device=device)
+    if device.type != 'cuda':
+        x, feat, thr, child, cnt = packed.numpy(), nf.numpy(), nb.numpy(), nc.numpy(), nn.numpy()
+        leaves = np.zeros((N, T), dtype=np.int32)
+        for t in range(T):
+            cur = np.where(cnt[t] > 0, 0, -1) * np.ones(N, dtype=np.int64)
+            for _ in range(L - 1):
+                live = np.flatnonzero(cur >= 0)
+                if not len(live):
+                    break
+                c = cur[live]
+                cur[live] = child[t, c, (x[live, feat[t, c]] > thr[t, c]).astype(np.int64)]
+            leaves[:, t] = np.where(cur < 0, ~cur, 0)
+        if mode == 'dense':
+            out.numpy()[:] = leaves
+        else:
+            out.numpy()[:, F:] = leaves
+            if F:
+                out.numpy()[:, :F] = ids.numpy()
+        return out
+    if N == 0:
+        return out
+    with torch.cuda.device(device):
+        check(lib().dt_gbdt_leaves_feed(ptr(packed), N, P8, T, L, ptr(nf), ptr(nb), ptr(nc), ptr(nn), ptr(ids), F, GBDT_FEED_MODES[mode],
+                                        ptr(out), stream_ptr()), 'dt_gbdt_leaves_feed')
     return out

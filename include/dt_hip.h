@@ -1818,6 +1818,21 @@ int dt_column_order_stats(const void* ws, const int32_t* dtypes, const int32_t* 
  *     is finished returns at once while the others go on.  dt_gbdt_mc_leaf_update takes scores float32 and row_leaf int32
  *     [K][row_stride].  Memory: 8 N K bytes of idx, K L P 256 20 bytes of histograms (K = 10, L = 31, P = 39: 62 MB).
  *     1 <= K <= DT_GBDT_MAX_CLASSES and every stride at least one class's table, otherwise DT_ERR_INVALID_ARG.
+ * In-feed variants (csrc/gbdt_feed.hip; ops.gbdt_bin_feed / gbdt_leaves_feed, GbmLeavesEncoder.fit_feed / transform_feed): the
+ * features are the columns of a resident feed's blocks, so nothing is uploaded and nothing of size N is read back.
+ *   dt_gbdt_bin_feed  ONE launch bins the row-major int32 id block [N][F] (ids may be null with F = 0) and n_blocks <=
+ *     DT_GBDT_FEED_MAX_BLOCKS row-major float32 blocks [N][widths[b]] (blocks / widths: HOST arrays of device pointers / ints)
+ *     into BOTH matrices the grower reads: bins uint8 [P][N] and packed uint8 [N][P8], P = F + sum widths, zero padded.  edges
+ *     float64 [P][DT_GBDT_FEED_EDGES] and n_edges int32 [P] are DEVICE tables (a count is clamped to [0, 255]); the rule is
+ *     dt_gbdt_bin's: the number of edges <= (double)x, n_edges for a NaN.  A block of 256 threads walks row tiles of
+ *     DT_GBDT_FEED_ROWS rows (grid-stride, at most DT_GBDT_FEED_GRID blocks): the edge lists of a group of up to
+ *     DT_GBDT_FEED_GROUP features sit in LDS (loaded once per block and group), the tile of each block is read as one contiguous
+ *     slab, binned by a fixed 8-trip search and staged feature-major in LDS; packed goes out as aligned 8-byte words, bins as
+ *     one contiguous byte run per feature.  No atomics, no block waits on another.
+ *   dt_gbdt_leaves_feed  dt_gbdt_predict_leaves' walk (the tile's packed rows staged in LDS when DT_GBDT_PREDICT_ROWS x P8 fits
+ *     DT_GBDT_FEED_STAGE_BYTES) writing a feed block: DT_GBDT_FEED_EMBEDDING: out int32 [N][F + T], columns 0 .. F-1 copied
+ *     from ids int32 [N][F] in the same launch (ids may be null with F = 0), columns F .. F+T-1 the leaf ids;
+ *     DT_GBDT_FEED_DENSE: out float32 [N][T], the ids as floats (F must be 0).
  * Nothing synchronises with the host or allocates.  Sizes outside the limits below, a null or misaligned pointer, a negative
  * lambda or min_gain are DT_ERR_INVALID_ARG before any launch.                                                                */
 #define DT_GBDT_BINARY 0
@@ -1836,6 +1851,14 @@ int dt_column_order_stats(const void* ws, const int32_t* dtypes, const int32_t* 
 #define DT_GBDT_WS_BYTES 184
 #define DT_GBDT_MAX_CLASSES 64
 #define DT_GBDT_MC_BYTES 272
+#define DT_GBDT_FEED_ROWS 256
+#define DT_GBDT_FEED_GROUP 64
+#define DT_GBDT_FEED_GRID 256
+#define DT_GBDT_FEED_EDGES 255
+#define DT_GBDT_FEED_MAX_BLOCKS 8
+#define DT_GBDT_FEED_STAGE_BYTES 16384
+#define DT_GBDT_FEED_EMBEDDING 0
+#define DT_GBDT_FEED_DENSE 1
 typedef struct dt_gbdt_ws {
     const uint8_t* bins;      /* [P][N] */
     const uint32_t* packed;   /* [N][P8 / 4] */
@@ -1890,6 +1913,11 @@ int dt_gbdt_mc_hist(const dt_gbdt_mc* m, int root, void* stream);
 int dt_gbdt_mc_split(const dt_gbdt_mc* m, int root, void* stream);
 int dt_gbdt_mc_grow(const dt_gbdt_mc* m, void* stream);
 int dt_gbdt_mc_leaf_update(const dt_gbdt_mc* m, float* scores, int32_t* row_leaf, void* stream);
+int dt_gbdt_bin_feed(const int32_t* ids, int F, const void* const* blocks, const int32_t* widths, int n_blocks, int64_t N,
+                     const double* edges, const int32_t* n_edges, void* bins, void* packed, void* stream);
+int dt_gbdt_leaves_feed(const void* packed, int64_t N, int P, int T, int L, const int32_t* node_feat, const int32_t* node_bin,
+                        const int32_t* node_child, const int32_t* n_nodes, const int32_t* ids, int F, int mode, void* out,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,15 @@ A different implementation and not the same trees: both times are recorded, no r
                  give the same scores to the bit (asserted); the median of `--repeats` loops after a warm-up, and a per-role
                  split of each from a loop of its own with the device drained around every call
 scikit-learn's multiclass hessian has no K / (K - 1) factor: its line is informational.
-    python tools/gbm_bench.py [--rows N] [--trees T] [--classes K] [--repeats R] [--no-sklearn] [--out FILE]"""
+--feed: one record of its own ('bench': 'gbm_features_feed') instead — the encoder inside a resident feed against the host
+encoder on the same rows in the same run.  The columns are put on the device once as a feed holds them (the int32 id block
+[N, 26], the float32 block [N, 13]); then, alternating, the median of `--repeats` after a warm-up, with min and max:
+  host           GbmLeavesEncoder.fit_transform / transform on the frame (as above)
+  feed           GbmLeavesEncoder.fit_feed / transform_feed on the blocks (profile and edges, one binning launch, the boosting
+                 loop, one leaf launch; only the fitted trees come back), and `roles`: a fit of its own with the device drained
+                 between profile_edges, bin_launch, boosting_loop, state_readback and leaf_launch
+The frame's continuous columns are float32, so both fits see the same values: the same trees are asserted.
+    python tools/gbm_bench.py [--rows N] [--trees T] [--classes K] [--repeats R] [--feed] [--no-sklearn] [--out FILE]"""
 import argparse
 import json
 import os
@@ -98,6 +106,40 @@ def growth(ops, torch, enc, df, y, a, timed, stats):
     return rec
 
 
+def feed_leg(torch, enc_cls, df, y, a, task, kw, cats, conts, timed, stats, dev):
+    """--feed: the in-feed fit and transform against the host ones, alternating"""
+    from deeptables_amd.utils import consts
+    blocks = [torch.from_numpy(np.ascontiguousarray(df[cats].values, dtype=np.int32)).to(dev),
+              torch.from_numpy(np.ascontiguousarray(df[conts].values, dtype=np.float32)).to(dev)]
+    kinds = ['cat', 'cont']
+    enc_cls(cats, conts, n_estimators=3, num_leaves=a.leaves, **task).fit_transform(df, y)                     # warm-up
+    enc_cls(cats, conts, n_estimators=3, num_leaves=a.leaves, **task).fit_feed(blocks, kinds, y)
+    t = {k: [] for k in ('host_fit', 'feed_fit', 'host_transform', 'feed_transform')}
+    for _ in range(a.repeats):
+        host, feed = enc_cls(cats, conts, **task, **kw), enc_cls(cats, conts, **task, **kw)
+        t['host_fit'].append(timed(lambda: host.fit_transform(df, y))[0])
+        s, (wide, _kinds) = timed(lambda: feed.fit_feed(blocks, kinds, y, consts.GBM_FEATURE_TYPE_EMB))
+        t['feed_fit'].append(s)
+    for k in ('node_feat_', 'node_bin_', 'node_child_', 'n_nodes_', 'leaf_value_'):
+        assert np.array_equal(getattr(host, k), getattr(feed, k)), f'the two fits must grow the same trees: {k}'
+    for i in range(a.repeats + 1):                          # the first transform of each warms up
+        s_host, Xp = timed(lambda: host.transform(df))
+        s_feed, (again, _kinds) = timed(lambda: feed.transform_feed(blocks, kinds, consts.GBM_FEATURE_TYPE_EMB))
+        if i:
+            t['host_transform'].append(s_host)
+            t['feed_transform'].append(s_feed)
+    assert torch.equal(again[0], wide[0]), 'transform_feed must reproduce the blocks of the fit'
+    assert np.array_equal(Xp[host.new_columns].values, wide[0][:, len(cats):].cpu().numpy()), 'feed and host leaves must be equal'
+    roles = {}
+    timed_enc = enc_cls(cats, conts, **task, **kw)
+    timed_enc.timings = roles
+    t_roles, _ = timed(lambda: timed_enc.fit_feed(blocks, kinds, y))
+    return {'host': {'fit_transform': stats(t['host_fit']), 'transform': stats(t['host_transform'])},
+            'feed': {'fit_feed': stats(t['feed_fit']), 'transform_feed': stats(t['feed_transform']),
+                     'roles': dict(roles, total_s=t_roles, note='device drained between roles')},
+            'same_trees': True, 'nodes': int(feed.n_nodes_.sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1 << 20)
@@ -106,6 +148,7 @@ def main():
     ap.add_argument('--classes', type=int, default=0, help='0: the binary target; 3 .. 64: a K-class target, K trees per round')
     ap.add_argument('--repeats', type=int, default=3)
     ap.add_argument('--no-sklearn', action='store_true')
+    ap.add_argument('--feed', action='store_true', help='the in-feed fit / transform against the host ones; a record of its own')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'gbm_features.jsonl'))
     a = ap.parse_args()
     import torch
@@ -129,6 +172,16 @@ def main():
     def stats(ts):
         return {'median_s': statistics.median(ts), 'min_s': min(ts), 'max_s': max(ts), 'repeats': len(ts)}
 
+    if a.feed:
+        rec = dict({'bench': 'gbm_features_feed', 'rows': a.rows, 'columns': {'categorical': 26, 'continuous': 13}, 'trees': a.trees,
+                    'leaves': a.leaves, 'classes': a.classes, 'source_hash': entry.source_hash(),
+                    'device': torch.cuda.get_device_name(0)},
+                   **feed_leg(torch, GbmLeavesEncoder, df, y, a, task, kw, cats, conts, timed, stats, dev))
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'a') as f:
+            f.write(json.dumps(rec) + '\n')
+        print(json.dumps(rec))
+        return
     GbmLeavesEncoder(cats, conts, n_estimators=3, num_leaves=a.leaves, **task).fit_transform(df, y)           # warm-up
     fits = []
     for _ in range(a.repeats):
